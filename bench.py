@@ -1,6 +1,6 @@
 """Benchmark of the hot path: bottom-up UNet 1024x1024 inference (BASELINE.json cfg3).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--mode infer|train]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--mode infer|train] [--full] [--dump-outputs DIR]
 
 One *step* (``--mode infer``, the headline) = one pass of the hot path over one per-GPU batch of synthetic
 frames: uint8 frames -> UNet forward (random-init weights of the cfg3 architecture, every kernel a hand-written
@@ -10,7 +10,13 @@ meaningless peaks, the post-process stage consumes *rendered* heads with 6 anima
 that are equally resident in HBM; forward and post-process both run in full inside every step, back to back on
 one stream.
 
-``value`` is measured with the frames already resident in HBM (the bench contract).  The same number of steps is
+A plain run does what ``value`` needs and nothing else: set-up, warm-up, ``--steps`` timed steps (every timed forward a
+hipGraph replay), the outputs of the last timed step written by ``--dump-outputs DIR`` (``DIR/<name>.npy``, float32: grouped
+keypoints, peak values and instance scores of every frame, the head outputs of a fixed, seeded sample of the frames; their
+batch indices ``head_frame_index`` in float64), the line.  Everything below that is not ``value`` -- per-op sampling and ``roofline``, ``h2d_inclusive``, ``cpu_baseline``, the
+extra legs, and at N > 1 the shard check and ``weak_scaling`` -- runs with ``--full`` only.
+
+``value`` is measured with the frames already resident in HBM (the bench contract).  With ``--full`` the same number of steps is
 then timed a second time with the uint8 frames starting in pinned HOST memory, copied asynchronously on a copy
 stream under the previous step's kernels (double-buffered) -- SURVEY section 8(d)'s H2D-inclusive frame time; it
 is reported as ``h2d_inclusive`` and is never ``value``.
@@ -20,16 +26,16 @@ starts the N ranks ITSELF (a child ``python -m torch.distributed.run``, before t
 and fails if the job ends up with a different number of ranks.  Frames are sharded across ranks, no data-path
 collective (frames are independent).  At N > 1 the default is ``--scaling strong`` = BASELINE cfg3 as written ("batch=32,
 DP across 8xMI355X"): ``--global-batch`` (32) frames per step split into contiguous chunks of 32/G per
-rank; the weak-scaling figure (``--batch`` = 32 frames per GPU per step) is measured in the same launch and reported beside
-it as ``weak_scaling``.  ``--scaling weak`` makes the weak figure ``value`` (at N = 1 the two coincide).
+rank; with ``--full`` the weak-scaling figure (``--batch`` = 32 frames per GPU per step) is measured in the same launch and reported
+beside it as ``weak_scaling``.  ``--scaling weak`` makes the weak figure ``value`` (at N = 1 the two coincide).
 value = total frames / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 with the contract fields plus ``roofline`` (dominant kernel = the MFMA conv3x3,
-HIP-event timed inside the timed region), ``step_ms`` (median / p10 / p90 of the per-step GPU time) and, at N=1,
+Prints ONE JSON line on rank 0 with the contract fields, ``step_ms`` (median / p10 / p90 of the per-step GPU time) and,
+with ``--full``, ``roofline`` (dominant kernel = the MFMA conv3x3, HIP-event timed inside the timed region) and, at N=1,
 ``cpu_baseline`` (the oracle on the host cores at 1 and at all threads, with the parity of the HIP path against it
 on the very frames it timed).
 
-The default N = 1 run also carries three short extra legs, each with its own ``roofline`` (executed / direct FLOP
+The ``--full`` N = 1 run also carries three short extra legs, each with its own ``roofline`` (executed / direct FLOP
 accounting): ``train_cfg3`` (the cfg3 network's training step, 32 frames), ``train_cfg4`` (BASELINE cfg4: ConvNeXt-tiny
 centered-instance, 64 crops of 384x384, forward + MSE + backward + Adam) and ``infer_cfg4`` (the same network's inference
 forward, 64 crops).  They run after the headline's timed regions and never touch ``value``.
@@ -158,6 +164,44 @@ def summarize_op_samples(samples, stack_idx, step_ms_median):
     ok = step_ms_median is None or step_ms_median <= 0 or stack <= 1.03 * step_ms_median
     return {"op_ms": [float(v) for v in med], "n": int(a.shape[0]), "sampling": "ok" if ok else "inflated", "stack_ms": stack,
             "stack_ms_by_sample": [round(float(r[list(stack_idx)].sum()), 4) for r in a]}
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_FRAMES = 8            # frames whose head outputs a dump holds (a fixed, seeded sample of the batch)
+DUMP_SEED = 20251016
+
+
+def dump_frame_sample(batch: int, bytes_per_frame: int, budget: int = DUMP_MAX_BYTES * 3 // 4) -> np.ndarray:
+    """Batch indices (sorted) of the frames whose head outputs go into a dump: the same seeded sample in every run, at most DUMP_FRAMES and
+    no more than `budget` bytes of head outputs (cfg3, 32 frames: 8 frames, 40 MB)."""
+    k = max(1, min(batch, DUMP_FRAMES, budget // max(bytes_per_frame, 1)))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(batch, size=k, replace=False))
+
+
+def last_step_outputs(raw: dict, out) -> dict:
+    """Host copies of what one step of the timed path hands its caller: the grouped keypoints, peak values and instance scores of every frame,
+    and the head outputs of the frames dump_frame_sample picks (`head_frame_index`: their indices in the batch)."""
+    arrays = {k: getattr(out, k).detach().cpu().numpy().astype(np.float32) for k in ("pred_keypoints", "pred_peak_values", "instance_scores")
+              if getattr(out, k, None) is not None}
+    heads = sorted(raw)
+    idx = dump_frame_sample(raw[heads[0]].shape[0], sum(raw[k][0].numel() * 4 for k in heads))
+    for k in heads:
+        arrays[k] = raw[k].index_select(0, torch.as_tensor(idx, device=raw[k].device)).float().cpu().numpy()
+    arrays["head_frame_index"] = idx.astype(np.float64)
+    return arrays
+
+
+def write_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: DIR/<name>.npy per array; float32 / float64 only, at most DUMP_MAX_BYTES in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"bench.py: outputs of {total} bytes exceed the dump bound of {DUMP_MAX_BYTES}")
+    bad = [k for k, a in arrays.items() if a.dtype not in (np.float32, np.float64)]
+    if bad:
+        raise TypeError(f"bench.py: outputs {bad} are not float32 / float64")
+    os.makedirs(path, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _free_port() -> int:
@@ -337,14 +381,14 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None,
                     help="default: strong at N > 1 (BASELINE cfg3: global batch 32 split over the GPUs; the weak figure rides along as "
                          "`weak_scaling`), weak at N = 1 (the same thing there)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the train_cfg3 / train_cfg4 / infer_cfg4 legs of the default N = 1 run")
+    ap.add_argument("--no-extra-legs", action="store_true", help="skip the train_cfg3 / train_cfg4 / infer_cfg4 legs of the --full N = 1 run")
     ap.add_argument("--leg-steps", type=int, default=6, help="timed steps of each extra leg")
     ap.add_argument("--small-legs-only", action="store_true", help="print only the small-batch legs (infer_cfg1 / infer_cfg2 / published_workload) as one JSON object: a development shortcut, not the bench line")
     ap.add_argument("--mode", choices=["infer", "train"], default="infer")
     ap.add_argument("--train-config", choices=["cfg3", "cfg4"], default="cfg3")
     ap.add_argument("--dtype", choices=["f32", "f16x3", "f16"], default="f32",
                     help="arithmetic of the 3x3 convolutions: f32 = exact fp32 MFMA (the headline); f16x3 = split-fp16 (22-bit products, fp32 accumulate); "
-                         "f16 = the reference's autocast mode.  The other two are timed as short extra legs of the default run (alt_precisions)")
+                         "f16 = the reference's autocast mode.  The other two are timed as short extra legs of the --full run (alt_precisions)")
     ap.add_argument("--no-alt-precisions", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="launch the forward kernel by kernel instead of replaying one hipGraph")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -355,7 +399,18 @@ def main():
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="REHEARSAL of the multi-rank code path on a one-GPU box: all ranks share cuda:0 and synchronise over gloo "
                          "(RCCL refuses two ranks on one device).  The line it prints is marked as such and is not a measurement.")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: per-op HIP-event sampling inside the timed region (roofline), the h2d_inclusive timing, "
+                         "the CPU baseline, the other precisions, the extra legs, and at N > 1 the shard check and the weak-scaling figure.  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; head_frame_index float64): the grouped keypoints, peak values and "
+                         "instance scores of every frame, and both head outputs of a fixed, seeded sample of the frames (at most 64 MB in all)")
     args = ap.parse_args()
+    if not args.full and not args.small_legs_only:  # a plain run times the headline only (see --full)
+        args.no_extra_legs = args.no_alt_precisions = args.no_cpu_baseline = args.no_h2d_leg = True
+    if args.dump_outputs and args.mode != "infer":
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the inference headline (--mode infer)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args.gpus))
@@ -548,7 +603,7 @@ def run_infer(args, ctx):
     model.set_profiling(True)
     model.set_profiling(False)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    prof_at = set(profile_steps(args.steps))
+    prof_at = set(profile_steps(args.steps)) if args.full else set()  # (a plain run replays the graph on every step)
     op_samples, sample_pending = [], False
 
     def collect_sample():  # the events of the previous profiled forward completed steps ago: reading them stalls nothing
@@ -580,11 +635,13 @@ def run_infer(args, ctx):
             sample_pending = True
         else:
             model.set_profiling(False, resume=True)
-        step(frames, profiled=prof)
+        raw = step(frames, profiled=prof)[0]
         marks[i + 1].record()
-    drain()
+    outs = drain()
     barrier()
     elapsed = time.perf_counter() - t0
+    # what the last timed step computed, copied to the host before anything else runs on these buffers (--dump-outputs)
+    dumped = last_step_outputs(raw, outs[-1]) if args.dump_outputs and rank == 0 and args.steps > 0 else None
     if sample_pending:
         collect_sample()
     model.set_profiling(False)
@@ -598,7 +655,7 @@ def run_infer(args, ctx):
     # rank's frames through EVERY lane (its copies of the network on their own streams) and the grouped keypoints of its last step, bit for bit; plus the time each rank's
     # enqueue thread spent blocked on its grouping worker -- the first place 8 ranks x 3 lanes x (1 enqueue thread + 1 C++ worker) collide on a host
     shard_check = None
-    if world > 1:
+    if world > 1 and args.full:
         import hashlib
 
         def digest(t):
@@ -635,12 +692,13 @@ def run_infer(args, ctx):
             shard_check = {"result": "equal" if ok else "DIFFERENT", "what": "sha1 of each rank's head outputs (every lane) vs rank 0's kernel-by-kernel forward of the same frames; grouped keypoints of the last step vs rank 0's",
                            "ranks": world, "lanes_per_rank": [len(g_["lanes"]) for g_ in gathered], "mismatches": why[:8],
                            "host_stage_wait_ms_per_step_by_rank": [round(g_["host_wait_ms"], 4) for g_ in gathered]}
-    _tab0 = model.op_table(B, SIZE, SIZE)
-    from sleap_nn_amd import _lib as _L0
+    if args.full:
+        _tab0 = model.op_table(B, SIZE, SIZE)
+        from sleap_nn_amd import _lib as _L0
 
-    op_summary = summarize_op_samples(op_samples, [j for j, r in enumerate(_tab0) if r["kind"] in (_L0.OP_CONV, _L0.OP_STEM, _L0.OP_INPUT_CONV)],
-                                      float(np.median([m for j, m in enumerate(step_ms) if j not in prof_at])) if len(step_ms) > len(prof_at) else None)
-    op_ms, n_fw = (op_summary["op_ms"] or [0.0] * len(_tab0)), 1
+        op_summary = summarize_op_samples(op_samples, [j for j, r in enumerate(_tab0) if r["kind"] in (_L0.OP_CONV, _L0.OP_STEM, _L0.OP_INPUT_CONV)],
+                                          float(np.median([m for j, m in enumerate(step_ms) if j not in prof_at])) if len(step_ms) > len(prof_at) else None)
+        op_ms, n_fw = (op_summary["op_ms"] or [0.0] * len(_tab0)), 1
 
     # ---- timed region 2: the same steps with the uint8 frames coming from pinned host memory (H2D on a copy stream, double
     # buffered, overlapped with the previous step's kernels)
@@ -675,7 +733,7 @@ def run_infer(args, ctx):
     # ---- N > 1, default scaling: `value` above is the strong-scaling figure (BASELINE cfg3: global batch 32 split over the
     # GPUs); the weak-scaling figure (--batch frames per GPU per step) is measured here, in the same launch
     elapsed_weak, weak_B = None, None
-    if world > 1 and args.scaling == "strong" and args.scaling_defaulted:
+    if world > 1 and args.full and args.scaling == "strong" and args.scaling_defaulted:
         weak_B, weak_global, weak_host = shard("weak")
         wframes = weak_host.to(dev)
         wcms, wpafs = rendered_heads(weak_B, dev)
@@ -693,7 +751,7 @@ def run_infer(args, ctx):
         heads_in.update(cms=cms, pafs=pafs, info=info)
         del wframes, wcms, wpafs
 
-    # ---- extra legs (N = 1, default run only): the same steps with the convolution stack on the fp16 matrix pipe
+    # ---- extra legs (N = 1, --full run only): the same steps with the convolution stack on the fp16 matrix pipe
     alt = {}
     if world == 1 and precision == "exact" and not args.no_alt_precisions:
         ref_heads = {k: v.clone() for k, v in eager(frames[:2]).items()}
@@ -717,7 +775,7 @@ def run_infer(args, ctx):
 
     # ---- the local-maxima kernels on their own (north_star's "wavefront-reduction local-maxima kernel ... HBM GB/s"): HIP events around the two launches, on the step's rendered maps
     peaks_us = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from sleap_nn_amd.inference.ops.peaks import find_local_peaks_device
 
         pc = layer.postprocess_config
@@ -733,7 +791,7 @@ def run_infer(args, ctx):
         torch.cuda.synchronize()
         peaks_us = 1e3 * e0.elapsed_time(e1) / 50
 
-    # ---- N = 1 default run: the per-rank batches of the strong-scaling runs (global batch 32 over 8 / 4 GPUs = 4 / 8 frames per rank), measured on this one GPU with the
+    # ---- N = 1 --full run: the per-rank batches of the strong-scaling runs (global batch 32 over 8 / 4 GPUs = 4 / 8 frames per rank), measured on this one GPU with the
     # same pipelined step -- what one rank of the driver's SCALE run does per step, without the other ranks
     shards = {}
     if world == 1 and precision == "exact" and not args.no_extra_legs and args.scaling_defaulted and B >= 8:
@@ -824,103 +882,76 @@ def run_infer(args, ctx):
     elapsed_weak = float(t[2].item()) if elapsed_weak is not None else None
     if rank != 0:
         return None
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
 
-    from sleap_nn_amd import _lib as L
+    roofline = None  # (--full: the per-op samples of the timed region priced against the MFMA peak)
+    if args.full:
+        from sleap_nn_amd import _lib as L
 
-    table = model.op_table(B, SIZE, SIZE)
-    conv_rows = [(r, ms / max(n_fw, 1)) for r, ms in zip(table, op_ms) if r["kind"] == L.OP_CONV]
-    conv_flops = sum(r["flops"] for r, _ in conv_rows)
-    conv_ms = sum(ms for _, ms in conv_rows)
-    # whole conv stack = those launches + the fused stem (conv0 on VALU + conv1 on MFMA 16x16x4 + pool)
-    stack_rows = [(r, ms / max(n_fw, 1)) for r, ms in zip(table, op_ms) if r["kind"] in (L.OP_CONV, L.OP_STEM, L.OP_INPUT_CONV)]
-    stack_flops = sum(r["flops"] for r, _ in stack_rows)
-    stack_ms = sum(ms for _, ms in stack_rows)
-    fwd_ms = sum(op_ms) / max(n_fw, 1)
-    # FLOP accounting.  `direct_tflops` prices a launch at the direct-convolution count 2*Cin*Cout*9*H*W.  The kernels
-    # that run are Winograd forms: conv3x3_wino4_kernel (F(4x4,3x3): 36 multiplications per sixteen outputs instead of 144, 1/4 of those FLOPs go
-    # through the matrix cores) for the N-tile-64 layers from 64 input channels on where its time model prefers it, conv3x3_wino2d_kernel<64> (F(2x2,3x3): 4/9) for the other
-    # N-tile-64 layers (and the conv whose 1x1 head rides in its epilogue), conv3x3_w16_kernel (wave-private F(2x2,3x3): 4/9) for the Cout <= 32 ones; the input / output transforms are VALU work.  `achieved` is
-    # what the MFMA pipe EXECUTES in the launches of the dominant kernel over their duration -- the figure a roofline against the
-    # MFMA peak is about; the direct-equivalent rate is reported next to it and is NOT a roofline fraction.
-    # Which kernel ran each conv launch is read back from the library (ph_model_last_kernels of an eager forward), not re-derived here.
-    eager(frames)
-    kv = model.last_kernels()
-    torch.cuda.synchronize()
-    KSHORT = conv_kernel_short_names()
-    by_kernel = {}
-    prev_key = None
-    for (r, ms), code in zip(conv_rows, [c for row, c in zip(table, kv) if row["kind"] == L.OP_CONV]):
-        if code == L.KV_FUSED and prev_key is not None:  # a conv computed inside the launch of the conv in front of it (block2_c32_f16_kernel): its work belongs to that launch
-            e = by_kernel[prev_key]
+        table = model.op_table(B, SIZE, SIZE)
+        conv_rows = [(r, ms / max(n_fw, 1)) for r, ms in zip(table, op_ms) if r["kind"] == L.OP_CONV]
+        conv_flops = sum(r["flops"] for r, _ in conv_rows)
+        conv_ms = sum(ms for _, ms in conv_rows)
+        # whole conv stack = those launches + the fused stem (conv0 on VALU + conv1 on MFMA 16x16x4 + pool)
+        stack_rows = [(r, ms / max(n_fw, 1)) for r, ms in zip(table, op_ms) if r["kind"] in (L.OP_CONV, L.OP_STEM, L.OP_INPUT_CONV)]
+        stack_flops = sum(r["flops"] for r, _ in stack_rows)
+        stack_ms = sum(ms for _, ms in stack_rows)
+        fwd_ms = sum(op_ms) / max(n_fw, 1)
+        # FLOP accounting.  `direct_tflops` prices a launch at the direct-convolution count 2*Cin*Cout*9*H*W.  The kernels
+        # that run are Winograd forms: conv3x3_wino4_kernel (F(4x4,3x3): 36 multiplications per sixteen outputs instead of 144, 1/4 of those FLOPs go
+        # through the matrix cores) for the N-tile-64 layers from 64 input channels on where its time model prefers it, conv3x3_wino2d_kernel<64> (F(2x2,3x3): 4/9) for the other
+        # N-tile-64 layers (and the conv whose 1x1 head rides in its epilogue), conv3x3_w16_kernel (wave-private F(2x2,3x3): 4/9) for the Cout <= 32 ones; the input / output transforms are VALU work.  `achieved` is
+        # what the MFMA pipe EXECUTES in the launches of the dominant kernel over their duration -- the figure a roofline against the
+        # MFMA peak is about; the direct-equivalent rate is reported next to it and is NOT a roofline fraction.
+        # Which kernel ran each conv launch is read back from the library (ph_model_last_kernels of an eager forward), not re-derived here.
+        eager(frames)
+        kv = model.last_kernels()
+        torch.cuda.synchronize()
+        KSHORT = conv_kernel_short_names()
+        by_kernel = {}
+        prev_key = None
+        for (r, ms), code in zip(conv_rows, [c for row, c in zip(table, kv) if row["kind"] == L.OP_CONV]):
+            if code == L.KV_FUSED and prev_key is not None:  # a conv computed inside the launch of the conv in front of it (block2_c32_f16_kernel): its work belongs to that launch
+                e = by_kernel[prev_key]
+                e["ms"] += ms
+                e["direct_flops"] += r["flops"]
+                e["executed_flops"] += r["flops"]
+                e["bytes"] += r["bytes"]
+                continue
+            share = (3.0 if precision == "split" else 1.0) if code == L.KV_F16 else L.KV_MFMA_SHARE[code]
+            prev_key = KSHORT[code]
+            e = by_kernel.setdefault(KSHORT[code], {"launches": 0, "ms": 0.0, "direct_flops": 0.0, "executed_flops": 0.0, "bytes": 0.0})
+            e["launches"] += 1
             e["ms"] += ms
             e["direct_flops"] += r["flops"]
-            e["executed_flops"] += r["flops"]
+            e["executed_flops"] += r["flops"] * share
             e["bytes"] += r["bytes"]
-            continue
-        share = (3.0 if precision == "split" else 1.0) if code == L.KV_F16 else L.KV_MFMA_SHARE[code]
-        prev_key = KSHORT[code]
-        e = by_kernel.setdefault(KSHORT[code], {"launches": 0, "ms": 0.0, "direct_flops": 0.0, "executed_flops": 0.0, "bytes": 0.0})
-        e["launches"] += 1
-        e["ms"] += ms
-        e["direct_flops"] += r["flops"]
-        e["executed_flops"] += r["flops"] * share
-        e["bytes"] += r["bytes"]
-    dom = max(by_kernel, key=lambda k: by_kernel[k]["ms"]) if by_kernel else "direct"
-    D = by_kernel.get(dom, {"launches": 0, "ms": 0.0, "direct_flops": 0.0, "executed_flops": 0.0, "bytes": 0.0})
-    direct_tflops = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-    achieved = D["executed_flops"] / (D["ms"] * 1e-3) / 1e12 if D["ms"] > 0 else 0.0
-    executed_all = sum(e["executed_flops"] for e in by_kernel.values())
-    peak = MFMA_F16_PEAK_TFLOPS if fp16 else MFMA_F32_PEAK_TFLOPS
-    KERNEL_NAMES = conv_kernel_long_names(precision)
-    # HBM traffic of the conv launches: measured with rocprofv3 PMC passes (FETCH_SIZE x2 gfx950 correction, WRITE_SIZE;
-    # tools/summarize_pmc.py) on this same command and committed under profiles/; bench.py itself cannot read PMCs, so it
-    # reports the newest committed figure whose launch count matches this run.
-    traffic, traffic_src = None, None
-    import glob
+        dom = max(by_kernel, key=lambda k: by_kernel[k]["ms"]) if by_kernel else "direct"
+        D = by_kernel.get(dom, {"launches": 0, "ms": 0.0, "direct_flops": 0.0, "executed_flops": 0.0, "bytes": 0.0})
+        direct_tflops = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+        achieved = D["executed_flops"] / (D["ms"] * 1e-3) / 1e12 if D["ms"] > 0 else 0.0
+        executed_all = sum(e["executed_flops"] for e in by_kernel.values())
+        peak = MFMA_F16_PEAK_TFLOPS if fp16 else MFMA_F32_PEAK_TFLOPS
+        KERNEL_NAMES = conv_kernel_long_names(precision)
+        # HBM traffic of the conv launches: measured with rocprofv3 PMC passes (FETCH_SIZE x2 gfx950 correction, WRITE_SIZE;
+        # tools/summarize_pmc.py) on this same command and committed under profiles/; bench.py itself cannot read PMCs, so it
+        # reports the newest committed figure whose launch count matches this run.
+        traffic, traffic_src = None, None
+        import glob
 
-    cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_conv_traffic.json")))
-    if B == 32 and not fp16:
-        for cand in reversed(cands):  # newest first; files of another leg (the fp16 pipe's cfg5 set) or of another launch count are stepped over, not an error
-            try:
-                tj = json.load(open(cand))["conv3x3_mfma"]
-                if int(round(tj["launches_per_forward"])) == len(conv_rows):
-                    traffic, traffic_src = tj["hbm_bytes_per_launch"], os.path.relpath(cand, ROOT)
-                    break
-            except Exception:
-                continue
-    conv_bytes = sum(r["bytes"] for r, _ in conv_rows)
-    frames_total = global_batch * args.steps
-    res = {
-        "metric": "frames/sec bottom-up UNet 1024x1024 inference",
-        "value": frames_total / elapsed,
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": {"f32": "f32", "f16x3": "f16x3 (split-fp16 operand pairs, f32 accumulate)", "f16": "f16 (f32 accumulate)"}[args.dtype],
-        "data": "synthetic",
-        "config": {
-            "workload": "cfg3: bottom-up UNet f16/r2/max_stride32/output_stride4, 1024x1024x1 uint8 frames, 13 nodes / 12 edges",
-            "frames_per_gpu_per_step": B, "global_batch": global_batch, "parallelism": f"dp{world} (frames sharded, no collective)",
-            "weights": "xavier-uniform seed 1234, head x0.05", "postprocess_input": "rendered heads, 6 instances/frame (BASELINE.md s3)",
-            "params": model.num_parameters(), "conv_gflop_per_frame": sum(r["flops"] for r in model.op_table(1, SIZE, SIZE)) / 1e9,
-            "forward_launch": "hipGraph replay (steps with per-op events launch kernel by kernel)" if use_graph else "kernel by kernel",
-            "inputs": "uint8 frames resident in HBM when the timed region starts",
-            "rccl_ranks_seen": ranks_seen, "frames_per_step_by_rank": per_rank_frames, "streams_per_rank": len(lanes), "shard_check": shard_check,
-            "host_threads": {"cores_visible": (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)), "per_rank": 2, "ranks": world,
-                             "what": "one Python thread that enqueues the GPU work (and the pinned H2D staging of the h2d_inclusive leg) + one C++ grouping worker per rank",
-                             "fits": 2 * world <= (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))},
-        },
-        "step_ms": percentiles(step_ms),
-        "untimed_steps_before_timing": max(args.warmup, 2) + 2,  # --warmup steps + two more (and two bare forwards) right in front of the timed region's synchronisation (the GPU would idle through the host-side checks otherwise and start the region at idle clocks)
-        "step_ms_profiled_vs_replayed": {"profiled_mean": float(np.mean([v for i, v in enumerate(step_ms) if i in prof_at])) if prof_at else None,
-                                         "replayed_mean": float(np.mean([v for i, v in enumerate(step_ms) if i not in prof_at])) if len(prof_at) < len(step_ms) else None,
-                                         "by_step": [round(float(v), 3) for v in step_ms]},
-        "roofline": {
+        cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_conv_traffic.json")))
+        if B == 32 and not fp16:
+            for cand in reversed(cands):  # newest first; files of another leg (the fp16 pipe's cfg5 set) or of another launch count are stepped over, not an error
+                try:
+                    tj = json.load(open(cand))["conv3x3_mfma"]
+                    if int(round(tj["launches_per_forward"])) == len(conv_rows):
+                        traffic, traffic_src = tj["hbm_bytes_per_launch"], os.path.relpath(cand, ROOT)
+                        break
+                except Exception:
+                    continue
+        conv_bytes = sum(r["bytes"] for r, _ in conv_rows)
+        roofline = {
             "bound": "mfma",
             "kernel": KERNEL_NAMES[dom] + f", {D['launches']} of the {len(conv_rows)} conv launches of a forward; the first encoder block runs in the fused stem kernel",
             "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
@@ -945,8 +976,42 @@ def run_infer(args, ctx):
             "profiled_forwards": op_summary["n"], "sampling": op_summary["sampling"], "conv_stack_ms_by_sample": op_summary["stack_ms_by_sample"],
             "sampling_rule": "per-op MEDIAN over the profiled forwards (steps " + ",".join(str(v) for v in sorted(prof_at)) + " of the timed region; never steps 0 / 1); "
                              "'inflated' = the conv stack of the medians exceeds 1.03 x the median un-profiled step, the figure is then not a roofline",
+        }
+
+    frames_total = global_batch * args.steps
+    res = {
+        "metric": "frames/sec bottom-up UNet 1024x1024 inference",
+        "value": frames_total / elapsed,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": {"f32": "f32", "f16x3": "f16x3 (split-fp16 operand pairs, f32 accumulate)", "f16": "f16 (f32 accumulate)"}[args.dtype],
+        "data": "synthetic",
+        "config": {
+            "workload": "cfg3: bottom-up UNet f16/r2/max_stride32/output_stride4, 1024x1024x1 uint8 frames, 13 nodes / 12 edges",
+            "frames_per_gpu_per_step": B, "global_batch": global_batch, "parallelism": f"dp{world} (frames sharded, no collective)",
+            "weights": "xavier-uniform seed 1234, head x0.05", "postprocess_input": "rendered heads, 6 instances/frame (BASELINE.md s3)",
+            "params": model.num_parameters(), "conv_gflop_per_frame": sum(r["flops"] for r in model.op_table(1, SIZE, SIZE)) / 1e9,
+            "forward_launch": ("hipGraph replay (steps with per-op events launch kernel by kernel)" if prof_at else "hipGraph replay") if use_graph else "kernel by kernel",
+            "inputs": "uint8 frames resident in HBM when the timed region starts",
+            "rccl_ranks_seen": ranks_seen, "frames_per_step_by_rank": per_rank_frames, "streams_per_rank": len(lanes), "shard_check": shard_check,
+            "host_threads": {"cores_visible": (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)), "per_rank": 2, "ranks": world,
+                             "what": "one Python thread that enqueues the GPU work (and the pinned H2D staging of the h2d_inclusive leg) + one C++ grouping worker per rank",
+                             "fits": 2 * world <= (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))},
         },
+        "step_ms": percentiles(step_ms),
+        "untimed_steps_before_timing": max(args.warmup, 2) + 2,  # --warmup steps + two more (and two bare forwards) right in front of the timed region's synchronisation (the GPU would idle through the host-side checks otherwise and start the region at idle clocks)
+        "step_ms_profiled_vs_replayed": {"profiled_mean": float(np.mean([v for i, v in enumerate(step_ms) if i in prof_at])) if prof_at else None,
+                                         "replayed_mean": float(np.mean([v for i, v in enumerate(step_ms) if i not in prof_at])) if len(prof_at) < len(step_ms) else None,
+                                         "by_step": [round(float(v), 3) for v in step_ms]},
     }
+    if roofline is not None:
+        res["roofline"] = roofline
     if peaks_us is not None:
         cm_bytes = float(cms.numel() * 4)
         peaks_traffic, peaks_traffic_src = None, None
@@ -986,7 +1051,7 @@ SHARD_LANES_4 = 3     # copies of the cfg3 network a rank with <= 4 frames per s
 
 
 def small_batch_legs(args, ctx):
-    """infer_cfg1 / infer_cfg2 / published_workload of the default N = 1 line (the small-batch regime, driver-timed)."""
+    """infer_cfg1 / infer_cfg2 / published_workload of the --full N = 1 line (the small-batch regime, driver-timed)."""
     dev = ctx["dev"]
     out = {}
     torch.cuda.empty_cache()
@@ -1001,7 +1066,7 @@ def small_batch_legs(args, ctx):
 
 
 def extra_legs(args, ctx):
-    """train_cfg3 / train_cfg4 / infer_cfg4 of the default N = 1 line (driver-timed training and ConvNeXt numbers)."""
+    """train_cfg3 / train_cfg4 / infer_cfg4 of the --full N = 1 line (driver-timed training and ConvNeXt numbers)."""
     dev = ctx["dev"]
     out = {}
     torch.cuda.empty_cache()

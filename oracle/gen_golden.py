@@ -19,6 +19,10 @@ tests).  Contents:
   borders) with the outputs of the reference find_local_peaks / find_global_peaks.
 * ``paf.npz``: randomized PAF/peak sets with the outputs of the reference candidate
   enumeration, line scoring, matching and grouping.
+* ``backend_protocol.npz``: the members of the reference's runtime-checkable ``ModelBackend``
+  protocol and the parameters of its ``warmup``.
+* ``outputs_packaging.json``: what the reference's ``Outputs.to_instances`` / ``to_labels`` hand a
+  recording sleap_io stand-in for the cases of tests/test_host_cpu.py's packaging test.
 """
 
 from __future__ import annotations
@@ -868,6 +872,42 @@ def losses_fixture():
     save("losses.npz", **arrs)
 
 
+def backend_protocol_fixture():
+    """What the reference's layers demand of a backend (isinstance against its runtime-checkable ModelBackend): the protocol's members and warmup's parameters."""
+    import inspect
+
+    from sleap_nn.inference.layers.backends.base import ModelBackend as ref
+
+    members = sorted(n for n, _ in inspect.getmembers(ref) if not n.startswith("_") or n == "__call__")
+    save("backend_protocol.npz", members=np.array(members), warmup_params=np.array(list(inspect.signature(ref.warmup).parameters)),
+         runtime_checkable=np.array(bool(getattr(ref, "_is_runtime_protocol", False))))
+
+
+def outputs_packaging_fixture():
+    """The reference's Outputs.to_instances / to_labels on the cases of tests/test_host_cpu.py::test_outputs_to_instances_and_to_labels, through the
+    test's own recording sleap_io stand-in (the record form is the test's _packaging_run)."""
+    import importlib
+
+    from tests.test_host_cpu import _packaging_run, _recording_sleap_io
+
+    sio = _recording_sleap_io()
+    before = dict(sys.modules)  # every module this fixture imports binds the recording stand-in: all of them go again afterwards
+    try:
+        sys.modules["sleap_io"] = sio  # the harness registers an inert stand-in: the recording one must be what the reference module binds
+        sys.modules.pop("sleap_nn.inference.outputs", None)
+        ref = importlib.import_module("sleap_nn.inference.outputs").Outputs
+        rec = _packaging_run(ref, sio)
+    finally:
+        for name in set(sys.modules) - set(before):
+            del sys.modules[name]
+        sys.modules.update(before)
+    path = os.path.join(OUT, "outputs_packaging.json")
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1, allow_nan=False)
+        f.write("\n")
+    print(f"wrote {path}  ({os.path.getsize(path) / 1024:.0f} KiB)")
+
+
 if __name__ == "__main__":
     only = sys.argv[1:]
     if not only or "losses" in only:
@@ -898,3 +938,7 @@ if __name__ == "__main__":
         multiclass_topdown_fixture()
     if not only or "nms" in only:
         centroid_nms_fixture()
+    if not only or "protocol" in only:
+        backend_protocol_fixture()
+    if not only or "packaging" in only:
+        outputs_packaging_fixture()

@@ -144,3 +144,50 @@ def test_per_op_sampling_takes_medians_never_the_first_steps_and_flags_an_inflat
     assert sum(r[0] for r in samples) / 6 > 1.14
     assert bench.summarize_op_samples(samples, [0, 1, 2], step_ms_median=1.70)["sampling"] == "inflated"
     assert bench.summarize_op_samples([], [0], 1.0)["sampling"] == "none"
+
+
+def test_dump_frame_sample_is_seeded_sorted_and_within_the_bound(bench):
+    """--dump-outputs: the frames whose head outputs are written are the same in every run, distinct and sorted, and their bytes stay within 3/4 of the 64 MB
+    bound (cfg3: 13 x 256 x 256 confidence maps + 24 x 128 x 128 PAFs per frame, fp32)."""
+    per_frame = 4 * (13 * 256 * 256 + 24 * 128 * 128)
+    idx = bench.dump_frame_sample(32, per_frame)
+    assert list(idx) == list(bench.dump_frame_sample(32, per_frame)) and list(idx) == sorted(set(idx.tolist()))
+    assert len(idx) == bench.DUMP_FRAMES and 0 <= idx.min() and idx.max() < 32 and len(idx) * per_frame <= bench.DUMP_MAX_BYTES * 3 // 4
+    assert list(bench.dump_frame_sample(2, per_frame)) == [0, 1] and len(bench.dump_frame_sample(32, 20 << 20)) == 2 and len(bench.dump_frame_sample(32, 1 << 30)) == 1
+
+
+def test_last_step_outputs_are_written_as_float_npy_files_within_the_bound(bench, tmp_path):
+    import types
+
+    import numpy as np
+    import torch
+
+    g = torch.Generator().manual_seed(3)
+    raw = {"MultiInstanceConfmapsHead": torch.rand(16, 3, 8, 8, generator=g), "PartAffinityFieldsHead": torch.rand(16, 4, 4, 4, generator=g)}
+    kp = torch.rand(16, 2, 3, 2, generator=g)
+    kp[0, 1] = float("nan")
+    out = types.SimpleNamespace(pred_keypoints=kp, pred_peak_values=torch.rand(16, 2, 3, generator=g), instance_scores=torch.rand(16, 2, generator=g).double())
+    arrays = bench.last_step_outputs(raw, out)
+    idx = bench.dump_frame_sample(16, 4 * (3 * 8 * 8 + 4 * 4 * 4))
+    assert np.array_equal(arrays["head_frame_index"], idx) and arrays["head_frame_index"].dtype == np.float64
+    assert np.array_equal(arrays["MultiInstanceConfmapsHead"], raw["MultiInstanceConfmapsHead"][torch.as_tensor(idx)].numpy())
+    assert arrays["instance_scores"].dtype == np.float32 and np.array_equal(arrays["pred_keypoints"], kp.numpy(), equal_nan=True)
+    bench.write_outputs(str(tmp_path / "d"), arrays)
+    back = {p.stem: np.load(p) for p in (tmp_path / "d").glob("*.npy")}
+    assert set(back) == set(arrays) and all(np.array_equal(back[k], arrays[k], equal_nan=True) and back[k].dtype == arrays[k].dtype for k in arrays)
+    with pytest.raises(TypeError):
+        bench.write_outputs(str(tmp_path / "e"), {"ids": np.arange(4)})
+    with pytest.raises(RuntimeError):
+        bench.write_outputs(str(tmp_path / "e"), {"big": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, dtype=np.float32)})
+    assert not (tmp_path / "e").exists()
+
+
+def test_plain_run_and_full_run_options():
+    """`--full` (everything beyond the headline) and `--dump-outputs DIR` are options of the bench; --dump-outputs belongs to the inference headline."""
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "train", "--dump-outputs", "x"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr

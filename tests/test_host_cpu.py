@@ -60,29 +60,29 @@ def test_integration_binding_struct_matches_the_library():
 
 
 def test_hip_backend_satisfies_the_reference_protocol():
-    """Container-only: the reference's own runtime-checkable ``ModelBackend`` (inference/layers/backends/base.py:18-79,
-    enforced by isinstance at layers/base.py:56-59) accepts a HipBackend-shaped object and rejects a bare object; the
+    """The reference's own runtime-checkable ``ModelBackend`` (inference/layers/backends/base.py:18-79, enforced by isinstance at
+    layers/base.py:56-59) -- its members and warmup's parameters as tests/golden/backend_protocol.npz records them
+    (oracle/gen_golden.py::backend_protocol_fixture) -- accepts a HipBackend-shaped object and rejects a bare object; the
     product's restated Protocol has the same members."""
-    from oracle import ref_harness as R
-
-    if not R.reference_available():
-        pytest.skip("reference tree not present (GPU box)")
-    R.install()
-    import importlib
     import inspect
 
-    ref = importlib.import_module("sleap_nn.inference.layers.backends.base").ModelBackend
     from sleap_nn_amd.inference.backends import HipBackend, ModelBackend
+
+    z = G.load("backend_protocol.npz")
+    ref_members, ref_warmup = {str(m) for m in z["members"]}, [str(p) for p in z["warmup_params"]]
+    assert bool(z["runtime_checkable"])  # the reference's isinstance check looks for exactly these members
+
+    def satisfies(obj):
+        return all(hasattr(obj, m) for m in ref_members)
 
     hb = HipBackend.__new__(HipBackend)  # no GPU here: the protocol check looks at members, not state
     hb._device = torch.device("cuda", 0)
-    assert isinstance(hb, ref) and isinstance(hb, ModelBackend)
-    assert not isinstance(object(), ref)
+    assert satisfies(hb) and isinstance(hb, ModelBackend)
+    assert not satisfies(object()) and not isinstance(object(), ModelBackend)
     members = lambda p: {n for n, _ in inspect.getmembers(p) if not n.startswith("_") or n == "__call__"}  # noqa: E731
-    assert members(ref) == members(ModelBackend) == {"device", "does_baked_postproc", "warmup", "__call__"}
+    assert ref_members == members(ModelBackend) == {"device", "does_baked_postproc", "warmup", "__call__"}
     assert hb.device == "cuda:0" and hb.does_baked_postproc is False
-    sig_ref, sig_own = inspect.signature(ref.warmup), inspect.signature(HipBackend.warmup)
-    assert list(sig_ref.parameters) == list(sig_own.parameters) == ["self", "input_shape"]
+    assert ref_warmup == list(inspect.signature(HipBackend.warmup).parameters) == ["self", "input_shape"]
 
 
 def test_library_has_no_environment_knobs():
@@ -677,25 +677,8 @@ def _recording_sleap_io():
     return m
 
 
-def _same_instances(a, b):
-    assert len(a) == len(b)
-    for x, y in zip(a, b):
-        assert np.array_equal(x.points, y.points, equal_nan=True) and np.array_equal(x.point_scores, y.point_scores, equal_nan=True)
-        assert x.score == y.score and x.skeleton is y.skeleton and x.track is y.track and x.tracking_score == y.tracking_score
-
-
-def test_outputs_to_instances_and_to_labels(monkeypatch):
-    """`Outputs.to_instances` / `to_labels` (outputs.py:284-477, 612-779) on a recording stand-in for sleap_io: NaN slots dropped,
-    per-instance score = instance_scores or the nansum of the node scores, centroid-only packaging at the anchor node, multi-class
-    tracks by class index (top-down) or by slot (bottom-up), frame / video indices, loud on a missing video -- and, where the
-    reference tree is present, identical to the reference's own methods on the same tensors."""
-    import sys
-
-    from sleap_nn_amd.inference.outputs import Outputs
-
-    sio = _recording_sleap_io()
-    monkeypatch.setitem(sys.modules, "sleap_io", sio)
-    skel = sio.Skeleton(["a", "b", "c"])
+def _outputs_cases():
+    """The Outputs of every packaging case of test_outputs_to_instances_and_to_labels (oracle/gen_golden.py::outputs_packaging_fixture hands the same to the reference)."""
     nan = float("nan")
     kp = torch.tensor([[[[1.0, 2.0], [3.0, 4.0], [nan, nan]], [[nan, nan]] * 3, [[5.0, 6.0], [nan, nan], [7.0, 8.0]]],
                        [[[nan, nan]] * 3] * 3])
@@ -712,17 +695,52 @@ def test_outputs_to_instances_and_to_labels(monkeypatch):
         "centroid_only": dict(pred_centroids=torch.tensor([[[10.0, 20.0], [nan, nan], [30.0, 40.0]], [[nan, nan]] * 3]),
                               pred_centroid_values=torch.tensor([[0.8, nan, nan], [nan] * 3])),
     }
+    return cases
+
+
+def _packaging_record(instances, skel, tracks):
+    """Instances as plain data (NaN as None, the track by its index in `tracks`): the form tests/golden/outputs_packaging.json holds the reference's in."""
+    def num(a):
+        a = np.asarray(a, dtype=np.float64) if a is not None else None
+        return None if a is None else [num(x) for x in a] if a.ndim else (None if np.isnan(a) else float(a))
+
+    return [{"points": num(i.points), "point_scores": num(i.point_scores), "score": num(i.score), "skeleton_given": i.skeleton is skel,
+             "track": None if i.track is None else tracks.index(i.track), "tracking_score": num(i.tracking_score)} for i in instances]
+
+
+def _packaging_run(outputs_cls, sio):
+    """Every case through `outputs_cls` (the product's Outputs or the reference's) with the recording stand-in `sio`: per case the instances of
+    frames 0 and 1 and what to_labels packs (frame indices, videos, track names)."""
+    skel = sio.Skeleton(["a", "b", "c"])
     tracks = [sio.Track("t0"), sio.Track("t1"), sio.Track("t2")]
     videos = ["video0", "video1"]
-    ref_cls = None
-    from oracle import ref_harness as R
+    rec = {}
+    for name, kw in _outputs_cases().items():
+        o = outputs_cls(**kw)
+        tr = tracks if name.startswith("multiclass") else None
+        anchor = 1 if name == "centroid_only" else None
+        lab = o.to_labels(skel, videos=videos if name == "bottomup" else None, anchor_ind=anchor, tracks=tr)
+        rec[name] = {"instances": [_packaging_record(o.to_instances(skel, b, anchor_ind=anchor, tracks=tr), skel, tracks) for b in range(2)],
+                     "labels": {"frame_idx": [f.frame_idx for f in lab.labeled_frames], "video": [f.video for f in lab.labeled_frames], "tracks": [t.name for t in lab.tracks]}}
+    return rec
 
-    if R.reference_available():
-        R.install()
-        monkeypatch.setitem(sys.modules, "sleap_io", sio)  # the harness registers its own inert stand-in: ours must win
-        import importlib
 
-        ref_cls = importlib.import_module("sleap_nn.inference.outputs").Outputs
+def test_outputs_to_instances_and_to_labels(monkeypatch):
+    """`Outputs.to_instances` / `to_labels` (outputs.py:284-477, 612-779) on a recording stand-in for sleap_io: NaN slots dropped,
+    per-instance score = instance_scores or the nansum of the node scores, centroid-only packaging at the anchor node, multi-class
+    tracks by class index (top-down) or by slot (bottom-up), frame / video indices, loud on a missing video -- and identical to what
+    the reference's own methods return on the same tensors (tests/golden/outputs_packaging.json)."""
+    import sys
+
+    from sleap_nn_amd.inference.outputs import Outputs
+
+    sio = _recording_sleap_io()
+    monkeypatch.setitem(sys.modules, "sleap_io", sio)
+    skel = sio.Skeleton(["a", "b", "c"])
+    cases = _outputs_cases()
+    kp, pv = cases["bottomup"]["pred_keypoints"], cases["bottomup"]["pred_peak_values"]
+    tracks = [sio.Track("t0"), sio.Track("t1"), sio.Track("t2")]
+    videos = ["video0", "video1"]
     for name, kw in cases.items():
         o = Outputs(**kw)
         tr = tracks if name.startswith("multiclass") else None
@@ -750,18 +768,13 @@ def test_outputs_to_instances_and_to_labels(monkeypatch):
         if tr is not None:
             assert [t.name for t in lab.tracks] == sorted({i.track.name for i in lab.labeled_frames[0].instances}, key=[i.track.name for i in lab.labeled_frames[0].instances].index)
         assert len(o.to_labels(skel, keep_empty_frames=True).labeled_frames) == 2
-        if ref_cls is not None:
-            r = ref_cls(**kw)
-            for b in range(2):
-                _same_instances(got[b], r.to_instances(skel, b, anchor_ind=1 if name == "centroid_only" else None, tracks=tr))
-            rl = r.to_labels(skel, videos=videos if name == "bottomup" else None, anchor_ind=1 if name == "centroid_only" else None, tracks=tr)
-            assert [f.frame_idx for f in rl.labeled_frames] == [f.frame_idx for f in lab.labeled_frames] and [f.video for f in rl.labeled_frames] == [f.video for f in lab.labeled_frames]
-            assert [t.name for t in rl.tracks] == [t.name for t in lab.tracks]
     with pytest.raises(IndexError):
         Outputs(pred_keypoints=kp, pred_peak_values=pv, video_indices=torch.tensor([2, 0])).to_labels(skel, videos=videos)
     with pytest.raises(ValueError):
         Outputs(**cases["centroid_only"]).to_instances(skel, 0, anchor_ind=5)
     assert Outputs().to_instances(skel) == []
+    with open(os.path.join(G.GOLDEN_DIR, "outputs_packaging.json")) as f:
+        assert _packaging_run(Outputs, sio) == json.load(f)
 
 
 def test_wino4_transform_tables_known_answer():
