@@ -36,6 +36,17 @@ class OpDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kind", "src0", "src1", "dst", "cin0", "cin1", "cout", "ksize", "flags", "weight", "bias", "out_index", "dst2", "weight2", "bias2", "cmid")]
 
 
+class AugSample(C.Structure):
+    """``struct ph_aug_sample`` (include/posehip.h): one sample's augmentation parameters."""
+
+    _fields_ = [("minv", C.c_float * 6), ("m", C.c_float * 6), ("edge", C.c_float * 12), ("flags", C.c_int32), ("uni_lo", C.c_int32), ("uni_hi", C.c_int32),
+                ("gauss_mean", C.c_float), ("gauss_std", C.c_float), ("contrast", C.c_float), ("brightness", C.c_float), ("erase_y", C.c_int32),
+                ("erase_x", C.c_int32), ("erase_h", C.c_int32), ("erase_w", C.c_int32), ("fill", C.c_int32 * 3), ("seed", C.c_uint32), ("pad_", C.c_int32)]
+
+
+AUG_FLIP, AUG_WARP, AUG_UNIFORM, AUG_GAUSS, AUG_CONTRAST, AUG_BRIGHTNESS, AUG_ERASE = 1, 2, 4, 8, 16, 32, 64
+
+
 class PosehipError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libposehip error {code}: {msg}")
@@ -97,6 +108,8 @@ SIGNATURES = {
     "ph_centroid_select": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ph_topdown_scatter": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "ph_group_packed": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _f32, C.c_double, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ph_aug_sample_size": (_i32, []),
+    "ph_augment": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ph_group_batch": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, C.c_double, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
@@ -126,6 +139,8 @@ def lib():
         fn.argtypes = args
     if l.ph_op_desc_size() != C.sizeof(OpDesc):
         raise ImportError(f"{LIB_PATH}: struct ph_op_desc is {l.ph_op_desc_size()} bytes, this binding's OpDesc {C.sizeof(OpDesc)}: rebuild the library")
+    if l.ph_aug_sample_size() != C.sizeof(AugSample):
+        raise ImportError(f"{LIB_PATH}: struct ph_aug_sample is {l.ph_aug_sample_size()} bytes, this binding's AugSample {C.sizeof(AugSample)}: rebuild the library")
     _lib = l
     return l
 
