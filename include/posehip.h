@@ -32,6 +32,9 @@
  *   ph_augment          data/skia_augmentation.py (apply_intensity_augmentation_skia,
  *                       apply_flip_augmentation_skia, apply_geometric_augmentation_skia) as
  *                       called at data/custom_datasets.py:1101-1117.
+ *   ph_tile_extract     inference/layers/tiled.py:62-84 (_extract_square_tile, per tile).
+ *   ph_tile_merge       inference/tile_merger.py:107-179 (TileMerger.integrate per tile + merge) and the
+ *                       crop of inference/layers/tiled.py:262-263.
  */
 #ifndef POSEHIP_H
 #define POSEHIP_H
@@ -43,7 +46,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 109
+#define PH_VERSION 110
 
 /* error codes */
 #define PH_OK 0
@@ -494,6 +497,26 @@ int32_t ph_aug_sample_size(void);
 int ph_augment(const void* src_dev, void* dst_dev, int32_t dtype, int32_t B, int32_t C, int32_t H, int32_t W,
                const float* kp_in_dev, float* kp_out_dev, int32_t I, int32_t N, const ph_aug_sample* params_dev,
                const int32_t* sym_pairs_dev, int32_t n_pairs, int32_t* counters_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Tiled inference (inference/layers/tiled.py)
+ * ---------------------------------------------------------------------------------- */
+
+/* All tiles of all frames of a batch in one launch.  frames_dev: (F, C, H, W), dtype 0 = uint8, 1 = float32, NCHW contiguous.
+ * y_origins_dev int32[ny] / x_origins_dev int32[nx]: tile origins per axis in frame pixels (device memory; the grid is their
+ * Cartesian product).  tiles_dev: (F * ny * nx, C, tile_size, tile_size) of the same dtype; tile iy * nx + ix of frame f is row
+ * f * ny * nx + iy * nx + ix.  Pixels outside the frame are written as zeros.  No alignment of rows or origins is assumed. */
+int ph_tile_extract(const void* frames_dev, int32_t dtype, int32_t F, int32_t C, int32_t H, int32_t W, const int32_t* y_origins_dev, int32_t ny,
+                    const int32_t* x_origins_dev, int32_t nx, int32_t tile_size, void* tiles_dev, void* stream);
+
+/* Stitch per-tile maps into per-frame maps with an importance window, as a gather.  tile_maps_dev: (F * ny * nx, N, th, tw) fp32 in
+ * the row order of ph_tile_extract; window_dev: (th, tw) fp32; origins in OUTPUT pixels (device memory); out_dev: (F, N, h, w) fp32.
+ * Per output pixel, over the covering tiles in ascending tile index (iy outer, ix inner), starting from acc = cnt = +0:
+ * acc = acc + tile * w, cnt = cnt + w as separate round-to-nearest fp32 operations, result acc / cnt -- the sequence
+ * TileMerger.integrate / merge(eps=None) performs, so the output is bit-identical to that canvas cropped to (h, w); pixels no tile
+ * covers are NaN.  Tiles may reach past (h, w): only the cropped region is written. */
+int ph_tile_merge(const float* tile_maps_dev, const float* window_dev, int32_t F, int32_t N, int32_t th, int32_t tw, const int32_t* y_origins_dev,
+                  int32_t ny, const int32_t* x_origins_dev, int32_t nx, int32_t h, int32_t w, float* out_dev, void* stream);
 
 #ifdef __cplusplus
 }

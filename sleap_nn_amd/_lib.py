@@ -110,6 +110,8 @@ SIGNATURES = {
     "ph_group_packed": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _f32, C.c_double, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ph_aug_sample_size": (_i32, []),
     "ph_augment": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "ph_tile_extract": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "ph_tile_merge": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
     "ph_group_batch": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, C.c_double, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 

@@ -17,7 +17,8 @@ import torch
 
 from sleap_nn_amd.inference.backends import HipBackend
 from sleap_nn_amd.inference.layers import (BottomUpLayer, BottomUpMultiClassLayer, CenteredInstanceLayer, CentroidLayer, PostprocessConfig,
-                                           PreprocessConfig, SingleInstanceLayer, TopDownLayer)
+                                           PreprocessConfig, SingleInstanceLayer, TiledLayer, TopDownLayer)
+from sleap_nn_amd.inference.layers.tiled import tiling_block, tiling_kwargs
 from sleap_nn_amd.inference.loaders import LoadedAssets, load_model_assets
 from sleap_nn_amd.inference.ops.paf import PAFScorer
 from sleap_nn_amd.inference.outputs import Outputs
@@ -80,9 +81,16 @@ def _warn_unverified_lanes(n: int, why: str) -> None:
                   "end-to-end throughput from the multi-lane predictor; results are unaffected)", RuntimeWarning, stacklevel=3)
 
 
-def _select_layer(assets: Sequence[LoadedAssets], device: str, post: PostprocessConfig, max_instances: Optional[int], **paf_kw):
-    """predictor.py:600 (``_select_layer``) for the model types of the hot path."""
+def _select_layer(assets: Sequence[LoadedAssets], device: str, post: PostprocessConfig, max_instances: Optional[int], tile_size: Optional[int] = None,
+                  overlap: Optional[int] = None, **paf_kw):
+    """predictor.py:600 (``_select_layer``) for the model types of the hot path.  A single-instance run directory trained with tiling
+    (``data_config.preprocessing.tiling.enabled``) gets a ``TiledLayer`` around its ``SingleInstanceLayer`` (predictor.py:191-246, 600-610);
+    ``tile_size`` / ``overlap`` are checked against the trained geometry, not applied."""
     by_type = {a.model_type: a for a in assets}
+    for a in assets:  # there is no tiled wrapper for the other model types: running them whole-frame at a geometry they were not trained for would be a silent wrong answer
+        if a.model_type != "single_instance" and tiling_block(a.preprocessing) is not None:
+            raise NotImplementedError(f"run directory {a.model_dir} was trained with tiling (data_config.preprocessing.tiling.enabled), but tiled inference "
+                                      f"is only built for single_instance models, not {a.model_type}")
 
     def backend(a):
         return HipBackend(a.build_model(), device)
@@ -99,8 +107,10 @@ def _select_layer(assets: Sequence[LoadedAssets], device: str, post: Postprocess
                              max_instances=max_instances, max_stride=a.backbone_config["max_stride"], preprocess_config=pre(a), postprocess_config=post)
     if "single_instance" in by_type:
         a = by_type["single_instance"]
-        return SingleInstanceLayer(backend(a), a.head_config["confmaps"]["output_stride"], max_stride=a.backbone_config["max_stride"],
-                                   preprocess_config=pre(a), postprocess_config=post)
+        tiling = tiling_kwargs(a.preprocessing, tile_size, overlap)  # (raises on a malformed block or an override that differs, before a model is built)
+        layer = SingleInstanceLayer(backend(a), a.head_config["confmaps"]["output_stride"], max_stride=a.backbone_config["max_stride"],
+                                    preprocess_config=pre(a), postprocess_config=post)
+        return layer if tiling is None else TiledLayer(layer, **tiling)
     if "multi_class_bottomup" in by_type:
         a = by_type["multi_class_bottomup"]
         h = a.head_config
@@ -151,15 +161,17 @@ class Predictor:
     @classmethod
     def from_model_paths(cls, model_paths: Sequence[str], device: str = "cuda", batch_size: int = 4, peak_threshold: float = 0.2,
                          integral_refinement: Optional[str] = "integral", integral_patch_size: int = 5, max_instances: Optional[int] = None,
-                         return_confmaps: bool = False, streams: int = 3, **paf_kw) -> "Predictor":
-        """``streams``: bottom-up and top-down run directories of small networks (<= 16 M parameters) are loaded ``streams`` times; the pipelined ``predict`` keeps that many batches in flight
+                         return_confmaps: bool = False, streams: int = 3, tile_size: Optional[int] = None, overlap: Optional[int] = None, **paf_kw) -> "Predictor":
+        """``tile_size`` / ``overlap``: for run directories trained with tiling, checked against the trained geometry (a different value raises ``ValueError``:
+        the geometry is fixed at training time); ignored otherwise, as in the reference.
+        ``streams``: bottom-up and top-down run directories of small networks (<= 16 M parameters) are loaded ``streams`` times; the pipelined ``predict`` keeps that many batches in flight
         on streams of their own (see ``replicas``).  Measured on the reference's fixture models at batch 4 (``tools/streams_n_probe.py``, frames/s end to end with 1 / 2 / 3 / 4 lanes):
         bottom-up 8 000 / 12 700 / 13 300 / 14 700, top-down 7 100 / 10 700 / 12 800 / 11 300, single instance 32 900 / 43 500 / 42 400 / 47 000 -- three is the default (the runtime has
         four hardware queues: the lanes are chosen so that they do not share one, ``concurrent_streams``)."""
         assets = [load_model_assets(p) for p in model_paths]
         post = PostprocessConfig(peak_threshold=peak_threshold, refinement=integral_refinement or "none", integral_patch_size=integral_patch_size,
                                  max_instances=max_instances, return_confmaps=return_confmaps)
-        layer = _select_layer(assets, device, post, max_instances, **paf_kw)
+        layer = _select_layer(assets, device, post, max_instances, tile_size=tile_size, overlap=overlap, **paf_kw)
         replicas = []
         small = lambda l: l.backend.model.num_parameters() <= _REPLICA_MAX_PARAMS
         if streams > 1 and ((isinstance(layer, (BottomUpLayer, SingleInstanceLayer)) and small(layer)) or
