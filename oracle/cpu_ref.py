@@ -71,6 +71,10 @@ def unet_plan(bb: dict) -> dict:
     cin = int(bb["in_channels"])
     assert stem_blocks <= 1, "stem_stride > 2 does not run in the reference (unet.py:287-288 vs encoder_decoder.py:652-676)"
     assert int(bb.get("stacks", 1)) == 1
+    assert cpb >= 1
+    # unet.py:126-175: with convs_per_block = 1 the expand block is skipped, and with it the local import the contract block
+    # (unet.py:159) relies on: the reference cannot build this model, so there is nothing to restate
+    assert not (middle and cpb == 1), "convs_per_block=1 with middle_block=True does not build in the reference (unet.py:126-175)"
 
     stem = []  # StemBlock (encoder_decoder.py:144-225): 7x7 convs (stem_kernel_size = 7, never configured), pool before convs from block 1 on
     prev = cin
@@ -101,7 +105,10 @@ def unet_plan(bb: dict) -> dict:
             prev = fmid
         mid.append([(f"backbone.middle_blocks.{mb}.blocks.stack0_enc{enc_num}_middle_contract_conv0", fmid, fmid)])
         prev = fmid
-    x_in = fmid  # decoder input channels (unet.py:198-206, block_contraction False)
+    # decoder input channels (unet.py:198-206); block_contraction is never set by the reference's from_config (unet.py:230-253),
+    # so its default of False holds.  Without a middle block the tensor that arrives has ``prev`` channels: for rate != 1 the first
+    # decoder conv's weight (declared with fmid) does not fit it and the forward fails, as the reference's does.
+    x_in = fmid
     dec = []
     cur_stride = 2 ** (down + stem_blocks + (1 if stem_blocks else 0))  # unet.py:178-191: the stem's own final pool counts too
     stride_to_filters = {cur_stride: x_in}
@@ -116,7 +123,7 @@ def unet_plan(bb: dict) -> dict:
             first_in = fout + fout
         else:
             first_in = pin + fout
-        for i in range(cpb):
+        for i in range(2):  # unet.py:203-216 does not forward convs_per_block: Decoder default 2 (encoder_decoder.py:603,687)
             blk["convs"].append((pfx + f"_refine_conv{i}", first_in if i == 0 else fout, fout))
         dec.append(blk)
         stride_to_filters[nxt] = fout

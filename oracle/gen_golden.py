@@ -15,6 +15,9 @@ tests).  Contents:
   reference ``Model`` on them, and the golden keypoints/scores those pickles hold.
 * ``unet_tiny_*.npz``: random-weight tiny UNets (bilinear / transposed-conv / 13-node
   bottom-up) run through the reference ``Model`` incl. selected intermediate activations.
+* ``unet_tiny_cpb{3,3_trans,1}.npz``: the same for ``convs_per_block`` 3 and 1 (the reference's decoder keeps two refine convs).
+* ``unet_config_grid.json.gz``: a 288-point grid of UNet configs walked through the reference ``Model``: builds / runs / fails, and
+  for the points that run the names and shapes of its ``backbone.*`` state.
 * ``peaks.npz``: tests/assets/inference/minimal_cms.pt + randomized maps (ties, negatives,
   borders) with the outputs of the reference find_local_peaks / find_global_peaks.
 * ``paf.npz``: randomized PAF/peak sets with the outputs of the reference candidate
@@ -102,7 +105,8 @@ def ckpt_fixture(kind: str, model_type: str, n_frames: int):
 
 
 # ---------------------------------------------------------------------------------------
-def tiny_unet(name, bb, heads, model_type, hw, batch, seed, in_dtype="uint8"):
+def tiny_unet(name, bb, heads, model_type, hw, batch, seed, in_dtype="uint8", must_save=()):
+    """``must_save``: name endings of activations that have to be among the saved ones (each must match a layer the reference built)."""
     torch.manual_seed(seed)
     m = Model("unet", rh.attrdict(bb), rh.attrdict(heads), model_type).eval()
     with torch.no_grad():
@@ -130,6 +134,10 @@ def tiny_unet(name, bb, heads, model_type, hw, batch, seed, in_dtype="uint8"):
         arrs["out/" + k] = _np(v)
     keep = list(acts.keys())
     pick = [keep[0], keep[1], keep[len(keep) // 2], keep[-1]]
+    for end in must_save:
+        hit = [k for k in keep if k.endswith(end)]
+        assert hit, (end, keep)
+        pick += [k for k in hit[:1] if k not in pick]
     for k in pick:
         arrs["act/" + k] = _np(acts[k])
     arrs["config_json"] = np.array(json.dumps({"backbone": bb, "heads": heads, "model_type": model_type}))
@@ -333,6 +341,62 @@ def winograd_kernel_fixture():
     heads = {"confmaps": {"part_names": ["a", "b", "c", "d"], "sigma": 2.5, "output_stride": 2, "loss_weight": 1.0},
              "pafs": {"edges": [["a", "b"], ["b", "c"], ["c", "d"]], "sigma": 15, "output_stride": 4, "loss_weight": 1.0}}
     tiny_unet("unet_f16_wino.npz", bb, heads, "bottomup", (56, 88), 2, seed=47)
+
+
+CPB_HEADS = {"confmaps": {"part_names": ["a", "b", "c"], "sigma": 2.5, "output_stride": 2, "loss_weight": 1.0},
+             "pafs": {"edges": [["a", "b"], ["b", "c"]], "sigma": 15, "output_stride": 4, "loss_weight": 1.0}}
+
+
+def convs_per_block_fixtures():
+    """UNets with convs_per_block != 2.  The reference forwards the key to its stem, encoder and middle block but not to its Decoder
+    (unet.py:203-216), whose blocks keep two refine convs; the weights are the reference Model's own state_dict, so names and shapes are its.
+    Saved activations include the tensors whose existence is the point: the third conv of an encoder block, middle_expand_conv1 and the
+    last decoder block's _refine_conv1."""
+    bb = {"in_channels": 1, "kernel_size": 3, "filters": 8, "filters_rate": 2, "max_stride": 8, "stem_stride": None, "middle_block": True, "up_interpolate": True,
+          "stacks": 1, "convs_per_block": 3, "output_stride": 2}
+    want3 = ("stack0_enc1_conv2", "_middle_expand_conv1", "stack0_dec1_s4_to_s2_refine_conv1")
+    tiny_unet("unet_tiny_cpb3.npz", bb, CPB_HEADS, "bottomup", (24, 40), 2, seed=51, must_save=want3)
+    tiny_unet("unet_tiny_cpb3_trans.npz", dict(bb, up_interpolate=False, filters_rate=1.5), CPB_HEADS, "bottomup", (24, 40), 2, seed=52, must_save=want3)
+    # the only one-conv family the reference runs: no middle block (with one it fails while building) and rate 1 (else its forward fails)
+    tiny_unet("unet_tiny_cpb1.npz", dict(bb, convs_per_block=1, middle_block=False, filters_rate=1), CPB_HEADS, "bottomup", (24, 40), 2, seed=53,
+              must_save=("stack0_dec1_s4_to_s2_refine_conv1",))
+
+
+def unet_config_grid_fixture():
+    """Walk a grid of documented UNet config keys through the reference ``Model``: does it build, does its forward run, and what are the
+    names and shapes of its ``backbone.*`` state.  Results only (tests/test_host_cpu.py walks every point)."""
+    import gzip
+    import itertools
+
+    heads = {"confmaps": {"part_names": ["a", "b"], "sigma": 2.5, "output_stride": 2, "loss_weight": 1.0}}
+    points = []
+    # (in_channels changes no status, only the first conv's shape: with it the grid has 288 points)
+    for cpb, middle, interp, stem, rate, k, cin in itertools.product((1, 2, 3), (True, False), (True, False), (None, 2), (1, 1.5, 2), (3, 5), (1, 3)):
+        bb = {"in_channels": cin, "kernel_size": k, "filters": 8, "filters_rate": rate, "max_stride": 8, "stem_stride": stem, "middle_block": middle,
+              "up_interpolate": interp, "stacks": 1, "convs_per_block": cpb, "output_stride": 2}
+        rec = {"config": bb}
+        torch.manual_seed(0)
+        try:
+            m = Model("unet", rh.attrdict(bb), rh.attrdict(heads), "single_instance").eval()
+        except Exception as e:
+            rec["status"], rec["error"] = "build_raises", type(e).__name__
+            points.append(rec)
+            continue
+        try:
+            with torch.inference_mode():
+                m(torch.zeros(1, cin, 32, 48))
+            rec["status"] = "ok"
+            rec["backbone_state"] = [[n, list(v.shape)] for n, v in m.state_dict().items() if n.startswith("backbone.")]
+        except Exception as e:
+            rec["status"], rec["error"] = "forward_raises", type(e).__name__
+        points.append(rec)
+    count = {s: sum(p["status"] == s for p in points) for s in ("ok", "build_raises", "forward_raises")}
+    print("unet_config_grid:", len(points), "points", count)
+    path = os.path.join(OUT, "unet_config_grid.json.gz")
+    doc = {"heads": heads, "model_type": "single_instance", "input_hw": [32, 48], "points": points}
+    with open(path, "wb") as raw, gzip.GzipFile(filename="", mode="wb", fileobj=raw, mtime=0) as f:  # mtime 0: regenerating changes no byte
+        f.write(json.dumps(doc, separators=(",", ":")).encode())
+    print(f"wrote {path}  ({os.path.getsize(path) / 1024:.0f} KiB)")
 
 
 def core_fixtures():
@@ -922,6 +986,10 @@ if __name__ == "__main__":
         schedulers_fixture()
     if not only or "core" in only:
         core_fixtures()
+    if not only or "cpb" in only:
+        convs_per_block_fixtures()
+    if not only or "grid" in only:
+        unet_config_grid_fixture()
     if not only or "topdown" in only:
         topdown_fixture()
     if not only or "topdown_sized" in only:

@@ -113,6 +113,17 @@ class UNet:
             raise ValueError("only stacks=1 is supported (the reference's multi-stack path is non-functional, unet.py:120,277)")
         if self.kernel_size % 2 != 1 or not (1 <= self.kernel_size <= 9):
             raise ValueError("kernel_size must be odd and <= 9")
+        if self.convs_per_block < 1:
+            raise ValueError("convs_per_block must be at least 1")
+        if self.middle_block and self.convs_per_block == 1:
+            # unet.py:126-175: SimpleConvBlock is imported inside the ``convs_per_block > 1`` branch that builds the expand block, so
+            # with one conv per block the contract block (unet.py:159) names a local that was never bound and the reference fails
+            # while it builds the model.  There is no network to reproduce, so none is invented here.
+            raise ValueError(
+                "convs_per_block=1 with middle_block=True cannot be built in the reference (unet.py:126-175: the middle expand "
+                "block is skipped and the contract block then fails on an unbound local); use middle_block=False with "
+                "filters_rate=1, the only one-conv UNet the reference runs"
+            )
         f, r, sb = self.filters, self.filters_rate, self.stem_blocks
         cur, cur_c = -1, self.in_channels
         stem_out: Optional[Tuple[int, int]] = None
@@ -161,6 +172,8 @@ class UNet:
                 "(unet.py:196-205); only filters_rate=1 is runnable without a middle block, in the reference as well"
             )
         self.middle_slot = cur
+        # block_contraction is never set by the reference's from_config (unet.py:230-253), so its default of False holds: the
+        # middle block keeps fmid channels and the decoder input is declared with fmid (unet.py:196-205)
         x_in = fmid
         # pools so far: one per encoder block but the very first conv block of the network, plus the final one; a stem adds its own
         # final pool, so with a stem the deepest feature sits at 2 * max_stride (unet.py:178-191)
@@ -185,7 +198,7 @@ class UNet:
                 self.labels[name] = dst
                 up_c = fout
             cur, cur_c = dst, up_c
-            for i in range(self.convs_per_block):
+            for i in range(2):  # unet.py:203-216 does not forward convs_per_block: Decoder default 2 (encoder_decoder.py:603,687)
                 name = pfx + f"_refine_conv{i}"
                 if i == 0 and b < len(skips):
                     sk, sk_c = skips[b]

@@ -1097,7 +1097,9 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           if (fmt == FMT_F16 && m->block_fuse && plan.reuse && d.src1 < 0 && d.ksize == 3 && d.dst2 < 0 && op.bn == 32 && so.cp == 32 && s0.cp == 32 && d.cin0 <= 16 &&
               op_index < m->ops.size()) {
             // inference plans, plain fp16: conv(<= 16 -> 32) + ReLU whose only reader is the next op, a conv(32 -> 32) (+ ReLU, + pool): both in ONE launch, the intermediate
-            // tensor stays in LDS (block2_c32_f16_kernel)
+            // tensor stays in LDS (block2_c32_f16_kernel).  The conditions are on PADDED channel counts, and the pool is optional: with three convs per block the router takes
+            // enc0's second and third conv ((16 -> 16), (16 -> 16) + pool: weights and biases zero-padded to 32) and enc1's first and second ((16 -> 32), (32 -> 32) with NO pool
+            // behind it: dst_pool = nullptr, only the full-resolution tensor is stored) -- both under test in tests/test_gpu_block_structure.py
             const PackedOp& nxo = m->ops[op_index];
             const ph_op_desc& nx = nxo.d;
             bool fuse = nx.kind == PH_OP_CONV && nx.ksize == 3 && nx.src0 == d.dst && nx.src1 < 0 && nxo.bn == 32 && plan.slots[nx.dst].cp == 32 && nx.cin0 == d.cout && nxo.w_f16_dev[1] &&

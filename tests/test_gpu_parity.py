@@ -28,6 +28,19 @@ def _head_close(got, ref, key=None):
     assert err <= HEAD_RTOL * scale, (key, err, scale)
 DEV = "cuda:0"
 
+# convs_per_block 3 (bilinear / transposed-conv at rate 1.5) and 1: the reference's decoder keeps two refine convs per block (unet.py:203-216)
+CPB_GOLDENS = ["unet_tiny_cpb3.npz", "unet_tiny_cpb3_trans.npz", "unet_tiny_cpb1.npz"]
+
+
+def _assert_block_structure_activations_found(name, cfg, found):
+    """The tensors whose existence is the point of the convs_per_block goldens must have been read back and compared, not skipped."""
+    if name not in CPB_GOLDENS:
+        return
+    assert any(k.endswith("_refine_conv1") for k in found), (name, found)
+    if cfg["backbone"]["convs_per_block"] == 3:
+        assert any("encoder_stack" in k and k.endswith("_conv2") for k in found), (name, found)
+        assert any(k.endswith("_middle_expand_conv1") for k in found), (name, found)
+
 
 def _model(cfg, weights):
     from sleap_nn_amd.architectures.model import Model
@@ -38,7 +51,7 @@ def _model(cfg, weights):
 
 
 @pytest.mark.parametrize("name", ["unet_tiny_interp.npz", "unet_tiny_trans.npz", "unet_tiny_bu13.npz", "unet_tiny_rgb.npz", "ckpt_bottomup.npz", "ckpt_single_instance.npz",
-                                  "unet_tiny_stem.npz", "unet_tiny_k5.npz", "unet_f16_wino.npz"])
+                                  "unet_tiny_stem.npz", "unet_tiny_k5.npz", "unet_f16_wino.npz"] + CPB_GOLDENS)
 def test_forward_matches_reference_golden(name):
     z = G.load(name)
     cfg = G.config(z)
@@ -53,6 +66,7 @@ def test_forward_matches_reference_golden(name):
         err = (got - ref).abs().max().item()
         assert err <= CMS_ATOL, (k, err)
     n_act = 0
+    found = []
     for k in [f for f in z.files if f.startswith("act/")]:
         ref = torch.from_numpy(z[k])
         try:
@@ -62,10 +76,16 @@ def test_forward_matches_reference_golden(name):
         err = (got - ref).abs().max().item()
         assert err <= CMS_ATOL, (k, err)
         n_act += 1
+        found.append(k[4:])
     assert n_act >= 2 or not any(f.startswith("act/") for f in z.files)
+    _assert_block_structure_activations_found(name, cfg, found)
+    if name in CPB_GOLDENS:
+        from sleap_nn_amd import _lib as L
+
+        assert m.ops[0].kind != L.OP_STEM and L.KV_STEM not in m.last_kernels()  # neither block shape is the two-conv stem
 
 
-@pytest.mark.parametrize("name", ["unet_tiny_interp.npz", "unet_tiny_rgb.npz", "ckpt_bottomup.npz"])
+@pytest.mark.parametrize("name", ["unet_tiny_interp.npz", "unet_tiny_rgb.npz", "ckpt_bottomup.npz"] + CPB_GOLDENS)
 def test_unfused_program_matches_too(name):
     """The plan-level stem fusion is optional: the op-by-op program must give the same maps."""
     z = G.load(name)
@@ -79,6 +99,7 @@ def test_unfused_program_matches_too(name):
         ref = torch.from_numpy(z[k])
         got = m.read_activation(k[4:], ref.shape[0], ref.shape[-2:]).cpu()
         assert (got - ref).abs().max().item() <= CMS_ATOL, k
+    _assert_block_structure_activations_found(name, cfg, [k[4:] for k in z.files if k.startswith("act/")])  # (every one was read above)
 
 
 def test_stem_fusion_odd_sizes_vs_unfused():
@@ -544,7 +565,8 @@ def test_cfg3_benched_workload_full_size_vs_oracle_and_batch_invariance(precisio
 FP16_ATOL = 5e-3
 
 
-@pytest.mark.parametrize("name", ["unet_tiny_interp.npz", "unet_tiny_trans.npz", "unet_tiny_bu13.npz", "unet_tiny_rgb.npz", "ckpt_bottomup.npz", "ckpt_single_instance.npz", "unet_f16_wino.npz"])
+@pytest.mark.parametrize("name", ["unet_tiny_interp.npz", "unet_tiny_trans.npz", "unet_tiny_bu13.npz", "unet_tiny_rgb.npz", "ckpt_bottomup.npz", "ckpt_single_instance.npz", "unet_f16_wino.npz"]
+                         + CPB_GOLDENS)
 @pytest.mark.parametrize("precision,atol", [("split", CMS_ATOL), ("fp16", FP16_ATOL)])
 def test_forward_matches_reference_golden_on_the_fp16_pipe(name, precision, atol):
     """All six reference goldens (bilinear and transposed-conv decoders, RGB input, the two fixture checkpoints) through the
@@ -560,6 +582,7 @@ def test_forward_matches_reference_golden_on_the_fp16_pipe(name, precision, atol
         err = (out[k[4:]].cpu() - torch.from_numpy(z[k])).abs().max().item()
         assert err <= atol, (k, err)
     n_act = 0
+    found = []
     for k in [f for f in z.files if f.startswith("act/")]:
         ref = torch.from_numpy(z[k])
         try:
@@ -568,7 +591,9 @@ def test_forward_matches_reference_golden_on_the_fp16_pipe(name, precision, atol
             continue
         assert (got - ref).abs().max().item() <= atol * max(1.0, ref.abs().max().item()), k
         n_act += 1
+        found.append(k[4:])
     assert n_act >= 2 or not any(f.startswith("act/") for f in z.files)
+    _assert_block_structure_activations_found(name, cfg, found)
 
 
 def test_split_precision_is_fp32_equivalent_on_the_benched_network():

@@ -330,6 +330,32 @@ def test_backward_randomised_shapes(seed):
         done += 1
 
 
+@pytest.mark.parametrize("case", ["cpb3", "cpb1"])
+def test_backward_with_other_convs_per_block(case):
+    """convs_per_block 3 (three convs per encoder block, two expand convs in the middle block) and 1 (no middle block, rate 1: the only
+    one-conv UNet the reference runs): the backward plan walks the same op list, in which the decoder blocks keep two refine convs whatever
+    the key says (unet.py:203-216 of the reference).  Losses and every gradient against the oracle's autograd step."""
+    bb, heads, mt = _cfg(16, 16, 2)
+    if case == "cpb3":
+        bb.update(convs_per_block=3)
+        hw, B = (48, 80), 2
+    else:
+        bb.update(convs_per_block=1, middle_block=False, filters_rate=1, in_channels=3)
+        hw, B = (48, 112), 3
+    sd, img, targets, lw, tm = _setup(bb, heads, mt, hw, B, seed=23)
+    n_refine = sum(1 for k in sd if "_refine_conv" in k and k.endswith(".weight"))
+    assert n_refine == 2 * 3 and not any("_refine_conv2" in k for k in sd)  # three decoder blocks (stride 16 -> 2), two refine convs each
+    assert any("_conv2.weight" in k for k in sd) == (case == "cpb3")
+    ref_losses, ref_grads = O.training_step(sd, bb, heads, mt, img, targets, lw)
+    loss = tm.forward_backward(img, targets).cpu().numpy()
+    assert np.allclose(loss, np.array(ref_losses, dtype=np.float32), rtol=1e-5, atol=1e-6), (loss, ref_losses)
+    worst = _check_grads(tm, ref_grads)
+    print(f"convs_per_block {case}: loss {loss.tolist()} vs {ref_losses}, worst gradient error {worst:.2e} of its tensor's scale")
+    g1 = tm.grads.clone()
+    tm.forward_backward(img, targets)
+    assert torch.equal(g1, tm.grads)
+
+
 def test_eval_train_round_trip_keeps_trained_weights():
     """After optimizer steps the live parameters exist only in the TrainingModule's device arena.  Wrapping the model in a
     HipBackend for validation switches it to the fused program (handle rebuilt) and train() switches back: both

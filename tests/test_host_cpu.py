@@ -106,6 +106,52 @@ def test_unet_without_middle_block_follows_the_reference_contract():
         UNet.from_config({**base, "filters_rate": 2})
 
 
+def test_unet_wiring_equals_the_reference_over_the_whole_config_grid():
+    """unet_config_grid.json.gz: convs_per_block 1/2/3 x middle_block x up_interpolate x stem_stride None/2 x filters_rate 1/1.5/2 x
+    kernel_size 3/5 x in_channels 1/3 (filters 8, max_stride 8, output_stride 2, one single-instance head, a 32x48 frame), each point
+    walked through the reference Model by oracle/gen_golden.py.  Where the reference builds and runs, product and oracle must have its
+    backbone parameter names and shapes exactly -- the reference forwards convs_per_block to its stem, encoder and middle block but not
+    to its Decoder (unet.py:203-216), whose blocks always hold two refine convs.  Where the reference fails (building: one conv per block
+    with a middle block; in forward: no middle block at rate != 1), the product refuses at construction and the oracle fails as well.
+    Every point is walked; the counts are the reference's own and guard against a fixture that silently shrinks."""
+    import gzip
+    import os
+
+    from sleap_nn_amd.architectures.unet import UNet
+
+    with gzip.open(os.path.join(G.GOLDEN_DIR, "unet_config_grid.json.gz"), "rt") as f:
+        doc = json.load(f)
+    points, heads, mt = doc["points"], doc["heads"], doc["model_type"]
+    count = {s: sum(p["status"] == s for p in points) for s in ("ok", "build_raises", "forward_raises")}
+    assert len(points) == 288 and count == {"ok": 144, "build_raises": 48, "forward_raises": 96}, (len(points), count)
+    assert len({json.dumps(p["config"], sort_keys=True) for p in points}) == 288  # 288 different configs
+    assert {p["config"]["convs_per_block"] for p in points if p["status"] == "ok"} == {1, 2, 3}
+    walked = 0
+    for p in points:
+        bb = p["config"]
+        if p["status"] == "ok":
+            want = {n: tuple(shape) for n, shape in p["backbone_state"]}
+            assert len(want) == len(p["backbone_state"])
+            got = {k: tuple(v) for k, v in UNet.from_config(bb).param_shapes.items()}
+            assert got == want, (bb, sorted(set(got) ^ set(want)))
+            sd = O.init_state(bb, heads, mt)
+            ora = {k: tuple(v.shape) for k, v in sd.items() if k.startswith("backbone.")}
+            assert ora == want, (bb, sorted(set(ora) ^ set(want)))
+            plan = O.unet_plan(bb)
+            named = [n for blk in plan["stem"] + plan["enc"] + plan["dec"] for n, _, _ in blk["convs"]] + [n for convs in plan["mid"] for n, _, _ in convs]
+            named += [blk["trans"][0] for blk in plan["dec"] if not blk["interp"]]
+            assert sorted(named) == sorted({n.rsplit(".", 1)[0] for n in want}), bb
+        else:
+            with pytest.raises(ValueError):
+                UNet.from_config(bb)
+            with pytest.raises((AssertionError, RuntimeError, ValueError, KeyError)):
+                sd = O.init_state(bb, heads, mt)
+                O.model_forward(sd, bb, heads, mt, torch.zeros((1, bb["in_channels"], 32, 48), dtype=torch.uint8))
+        walked += 1
+    assert walked == 288
+    print(f"unet config grid: {walked} points walked, 0 skipped")
+
+
 def test_unet_with_stem_block_and_wide_kernels_follows_the_reference_structure():
     """stem_stride 2 (StemBlock, encoder_decoder.py:144-225): 7x7 stem convs, reference parameter names and shapes (taken from the
     golden the reference Model produced), the deepest feature at 2 x max_stride, the stem output as the last skip; kernel_size 5;
