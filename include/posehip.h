@@ -35,6 +35,8 @@
  *   ph_tile_extract     inference/layers/tiled.py:62-84 (_extract_square_tile, per tile).
  *   ph_tile_merge       inference/tile_merger.py:107-179 (TileMerger.integrate per tile + merge) and the
  *                       crop of inference/layers/tiled.py:262-263.
+ *   ph_seg_*            inference/segmentation.py:12-237 (find_center_peaks, group_instances_from_offsets) as called
+ *                       at inference/layers/segmentation.py:159-266, and the thresholding of :438-503 (semantic).
  */
 #ifndef POSEHIP_H
 #define POSEHIP_H
@@ -46,7 +48,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 110
+#define PH_VERSION 111
 
 /* error codes */
 #define PH_OK 0
@@ -100,6 +102,8 @@ enum ph_op_kind {
 #define PH_FLAG_SCALE_RESIDUAL 8
 #define PH_FLAG_SOFTMAX 16 /* PH_OP_HEAD: softmax over the output channels (ClassVectorsHead, heads.py:536-537) */
 #define PH_FLAG_SILU 32    /* PH_OP_CONVT: SiLU instead of ReLU (the activation is an epilogue parameter of the phase GEMMs) */
+#define PH_FLAG_NO_TRAIN 64 /* PH_OP_HEAD: a head whose loss is not built (BCE + Dice, masked smooth-L1: the segmentation model types);
+                               the forward ignores it, ph_model_backward refuses the program */
 
 typedef struct ph_op_desc {
   int32_t kind;      /* enum ph_op_kind                                              */
@@ -517,6 +521,49 @@ int ph_tile_extract(const void* frames_dev, int32_t dtype, int32_t F, int32_t C,
  * covers are NaN.  Tiles may reach past (h, w): only the cropped region is written. */
 int ph_tile_merge(const float* tile_maps_dev, const float* window_dev, int32_t F, int32_t N, int32_t th, int32_t tw, const int32_t* y_origins_dev,
                   int32_t ny, const int32_t* x_origins_dev, int32_t nx, int32_t h, int32_t w, float* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Bottom-up instance segmentation grouping (inference/segmentation.py)
+ * ---------------------------------------------------------------------------------- */
+
+/* Scratch of ph_seg_center_peaks for B maps of (h, w) and a candidate list of `cap` entries per frame. */
+int64_t ph_seg_scratch_bytes(int32_t B, int32_t h, int32_t w, int32_t cap);
+
+/* Plateau-aware centre peaks of B centre maps (B, h, w) fp32 (find_center_peaks, segmentation.py:12-60).  A pixel is a candidate
+ * when hm > threshold and hm >= every in-image value of its nms_kernel x nms_kernel window (3, 5 or 7); candidates that touch by
+ * 4-connectivity form one component, represented by its maximum (raster-first on ties) and numbered by its raster-first pixel.
+ * max_instances > 0 and more components: the max_instances largest values, descending (torch.topk); otherwise component order.
+ * centers_dev int32 (B, max_centers, 2) = (x, y) in map pixels, scores_dev fp32 (B, max_centers).  counts_dev int32[2 B]:
+ * [b] = centres of frame b, [B + b] = its candidates.  Both are TRUE counts: a frame with more candidates than `cap` reports 0
+ * centres, one with more centres than max_centers has only the first max_centers written -- the caller compares and comes back
+ * with room (the convention of ph_local_peaks).  pix_counts_dev int32 (n_count_bufs, B, max_centers) is zeroed here for
+ * ph_seg_assign / ph_seg_gate.  Two launches, no host synchronisation; scratch must be 8-byte aligned. */
+int ph_seg_center_peaks(const float* center_dev, int32_t B, int32_t h, int32_t w, float threshold, int32_t nms_kernel, int32_t max_instances, int32_t cap,
+                        int32_t max_centers, int32_t* centers_dev, float* scores_dev, int32_t* counts_dev, int32_t* pix_counts_dev, int32_t n_count_bufs,
+                        void* scratch_dev, int64_t scratch_bytes, void* stream);
+
+/* Label map of the foreground pixels (segmentation.py:159-190): for fg > fg_threshold, px = x s + s/2 + dx, py = y s + s/2 + dy,
+ * cx = xc s + s/2, cy = yc s + s/2, d = (px - cx)^2 + (py - cy)^2 in fp32 with every operation rounded on its own (no FMA), label =
+ * first argmin over the frame's centres.  fg_dev (B, 1, h, w), offsets_dev (B, 2, h, w) = (dx, dy); centers_dev / counts_dev from
+ * ph_seg_center_peaks.  labels_dev (B, h, w) of label_bytes-wide signed integers (1: max_centers <= 127, 2: <= 32767, 4), -1 =
+ * background; dist_dev NULL or fp32 (B, h, w) = the chosen d; pix_counts_dev[b][k] += pixels labelled k (buffer 0 of the array
+ * ph_seg_center_peaks zeroed). */
+int ph_seg_assign(const float* fg_dev, const float* offsets_dev, int32_t B, int32_t h, int32_t w, float fg_threshold, int32_t output_stride,
+                  const int32_t* centers_dev, const int32_t* counts_dev, int32_t max_centers, int32_t label_bytes, void* labels_dev, float* dist_dev,
+                  int32_t* pix_counts_dev, void* stream);
+
+/* Adaptive distance gate (segmentation.py:197-211), `iters` passes: r2 = (alpha * sqrt(count / pi) * s)^2 in fp32 from the
+ * kept-pixel counts of the previous pass, keep = d <= r2[label] recomputed over ALL assigned pixels of labels_in_dev each pass, as the reference does.
+ * pix_counts_dev int32 (iters + 1, B, max_centers): buffer 0 = ph_seg_assign's counts, buffer k + 1 = the counts after pass k
+ * (zeroed by ph_seg_center_peaks).  labels_out_dev (its own buffer) = the labels kept by the last pass, -1 elsewhere. */
+int ph_seg_gate(const void* labels_in_dev, const float* dist_dev, int32_t B, int32_t h, int32_t w, float alpha, int32_t output_stride, int32_t iters,
+                const int32_t* counts_dev, int32_t max_centers, int32_t label_bytes, int32_t* pix_counts_dev, void* labels_out_dev, void* stream);
+
+/* Semantic variant (layers/segmentation.py:438-503): mask_dev uint8 (B, h, w) = fg > fg_threshold, count_dev int32[B] its
+ * pixels, sum_dev double[B] the sum of fg over them (fixed summation order: deterministic; the reference's score is sum / count). */
+int64_t ph_seg_semantic_scratch_bytes(int32_t B, int32_t h, int32_t w);
+int ph_seg_semantic(const float* fg_dev, int32_t B, int32_t h, int32_t w, float fg_threshold, uint8_t* mask_dev, int32_t* count_dev, double* sum_dev,
+                    void* scratch_dev, int64_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

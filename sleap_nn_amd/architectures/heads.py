@@ -127,6 +127,52 @@ class ClassVectorsHead(Head):
         return "categorical_crossentropy"
 
 
+class SegmentationHead(Head):
+    """heads.py:610-642 (one channel of foreground logits; the sigmoid belongs to the model's forward, not to the head)."""
+
+    def __init__(self, output_stride: int = 2, loss_weight: float = 1.0) -> None:
+        super().__init__(output_stride, loss_weight)
+
+    @property
+    def channels(self) -> int:
+        return 1
+
+    @property
+    def loss_function(self) -> str:
+        return "bce_dice"
+
+
+class InstanceCenterHead(Head):
+    """heads.py:645-670 (one channel: Gaussian at each instance's mask centroid)."""
+
+    def __init__(self, sigma: float = 4.0, output_stride: int = 2, loss_weight: float = 1.0) -> None:
+        super().__init__(output_stride, loss_weight)
+        self.sigma = sigma
+
+    @property
+    def channels(self) -> int:
+        return 1
+
+
+class CenterOffsetHead(Head):
+    """heads.py:673-700 (two channels: dx then dy, pixel -> its instance's centre, in input pixels)."""
+
+    def __init__(self, output_stride: int = 2, loss_weight: float = 0.1) -> None:
+        super().__init__(output_stride, loss_weight)
+
+    @property
+    def channels(self) -> int:
+        return 2
+
+    @property
+    def loss_function(self) -> str:
+        return "smooth_l1"
+
+
+# model types that are built for inference only: their losses (BCE + Dice, masked smooth-L1) and mask targets are not
+SEGMENTATION_MODEL_TYPES = ("bottomup_segmentation", "semantic_segmentation")
+
+
 def get_head(model_type: str, head_config) -> List[Head]:
     """Head list per model type, in the reference's order (architectures/model.py:70-154)."""
     from sleap_nn_amd.utils import cfg_get, to_plain
@@ -149,7 +195,15 @@ def get_head(model_type: str, head_config) -> List[Head]:
         return [MultiInstanceConfmapsHead(**kw("confmaps")), ClassMapsHead(**kw("class_maps"))]
     if model_type == "multi_class_topdown":
         return [CenteredInstanceConfmapsHead(**kw("confmaps")), ClassVectorsHead(**kw("class_vectors"))]
+    if model_type in SEGMENTATION_MODEL_TYPES:
+        # only output_stride / loss_weight of the segmentation leaf are head arguments; its loss and target knobs are not (model.py:113-124)
+        seg = kw("segmentation")
+        seg_kw = {k: seg[k] for k in ("output_stride", "loss_weight") if k in seg}
+        if model_type == "semantic_segmentation":
+            return [SegmentationHead(**seg_kw)]
+        return [SegmentationHead(**seg_kw), InstanceCenterHead(**kw("center")), CenterOffsetHead(**kw("offsets"))]
     raise Exception(
         f"{model_type} is not a model type of the MI355X hot path. Supported: `single_instance`, "
-        "`centered_instance`, `centroid`, `bottomup`, `multi_class_bottomup`, `multi_class_topdown`."
+        "`centered_instance`, `centroid`, `bottomup`, `multi_class_bottomup`, `multi_class_topdown`, "
+        "`bottomup_segmentation`, `semantic_segmentation`."
     )

@@ -14,7 +14,7 @@ from typing import Dict, List, Optional
 import torch
 
 from sleap_nn_amd import _lib as L
-from sleap_nn_amd.architectures.heads import ClassMapsHead, ClassVectorsHead, Head, get_head
+from sleap_nn_amd.architectures.heads import SEGMENTATION_MODEL_TYPES, ClassMapsHead, ClassVectorsHead, Head, SegmentationHead, get_head
 from sleap_nn_amd.architectures.convnext import ConvNextWrapper
 from sleap_nn_amd.architectures.unet import OpSpec, UNet
 from sleap_nn_amd.utils import cfg_get, cfg_keys
@@ -69,6 +69,10 @@ class Model:
             self.param_shapes[name + ".weight"] = (head.channels, cin, 1, 1)
             self.param_shapes[name + ".bias"] = (head.channels,)
             flags = L.FLAG_SIGMOID if isinstance(head, ClassMapsHead) else 0
+            if model_type in SEGMENTATION_MODEL_TYPES:
+                # the reference applies the foreground sigmoid in the Lightning module's forward (lightning_modules.py:3041-3050): here it is the head op's epilogue,
+                # so the output dict equals that forward's -- probabilities under "SegmentationHead", raw maps under the other keys.  Inference only (PH_FLAG_NO_TRAIN).
+                flags = (L.FLAG_SIGMOID if isinstance(head, SegmentationHead) else 0) | L.FLAG_NO_TRAIN
             self.ops.append(OpSpec(L.OP_HEAD, src, -1, -1, cin, 0, head.channels, 1, flags, name + ".weight", name + ".bias", out_index=i, label=name))
         self.unfused_ops = list(self.ops)
         self.fused_ops = self._fuse_cnblocks(self._fuse_pools(self._fuse_stem(self.ops)))

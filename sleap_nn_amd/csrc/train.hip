@@ -258,6 +258,9 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
              "ph_model_backward: null argument");
   PH_REQUIRE(((uintptr_t)grad_workspace_dev & 255) == 0, "gradient workspace must be 256-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
+  for (const auto& op : m->ops)  // the MSE / cross-entropy gradients below are not these heads' losses
+    PH_REQUIRE(!(op.d.kind == PH_OP_HEAD && (op.d.flags & PH_FLAG_NO_TRAIN)),
+               "ph_model_backward: head %d belongs to a segmentation model type, whose losses (BCE + Dice, masked smooth-L1) are not built: inference only", op.d.out_index);
   PH_REQUIRE(m->last_plan.fmt == FMT_F32, "backward needs the activations of an exact-fp32 forward (handle option conv_precision = 0)");
   PH_REQUIRE(!m->last_plan.reuse, "backward needs every activation of the forward (handle option workspace_reuse = 0)");
   BwdPlan bp;

@@ -16,7 +16,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import yaml
 
-MODEL_TYPES = ("single_instance", "centroid", "centered_instance", "bottomup", "multi_class_bottomup", "multi_class_topdown")
+MODEL_TYPES = ("single_instance", "centroid", "centered_instance", "bottomup", "multi_class_bottomup", "multi_class_topdown", "bottomup_segmentation",
+               "semantic_segmentation")
 
 
 class _Opaque:
@@ -89,8 +90,9 @@ def load_model_assets(model_dir: str, ckpt_name: str = "best.ckpt") -> LoadedAss
     if backbone_type is None:
         raise ValueError(f"no backbone config in {cfg_path}")
     skels = cfg.get("data_config", {}).get("skeletons") or []
-    nodes = [n["name"] for n in skels[0]["nodes"]] if skels else []
-    edges = [(e["source"]["name"], e["destination"]["name"]) for e in skels[0].get("edges", [])] if skels else []
+    skel = skels[0] if isinstance(skels, (list, tuple)) and skels and isinstance(skels[0], dict) else {}  # (segmentation runs may carry no skeleton, or an empty one)
+    nodes = [n["name"] for n in skel.get("nodes") or []]
+    edges = [(e["source"]["name"], e["destination"]["name"]) for e in skel.get("edges") or []]
     sd = load_lightning_state_dict(os.path.join(model_dir, ckpt_name))
     return LoadedAssets(model_type, backbone_type, bb[backbone_type], heads[model_type], cfg.get("data_config", {}).get("preprocessing", {}) or {},
                         sd, model_dir, nodes, edges)

@@ -37,6 +37,9 @@ class Outputs:
     pred_class_probs: Optional[torch.Tensor] = None  # stage 2 of multi-class top-down: (n_crops, 1, n_classes)
     pred_class_vectors: Optional[torch.Tensor] = None  # (B, I, n_classes) when requested
     pred_paf_graph: Optional[Tuple[torch.Tensor, ...]] = None
+    # segmentation layers: per frame a list of {"mask": bool ndarray, "score", "scale": (sx, sy), "offset": (ox, oy)} (image = mask / scale + offset).  Host
+    # objects, not tensors: to() / cpu() / detach() / slim() / numpy() hand the list on as it is
+    pred_masks: Optional[List[List[Dict[str, Any]]]] = None
     preprocess_info: Optional[PreprocInfo] = None
     frame_indices: Optional[torch.Tensor] = None
     video_indices: Optional[torch.Tensor] = None
@@ -93,7 +96,7 @@ class Outputs:
             v = getattr(self, name)
             if v is not None:
                 return int(v.shape[0])
-        return 0
+        return len(self.pred_masks) if self.pred_masks is not None else 0
 
     def _host(self, name: str, b: int) -> Optional[np.ndarray]:
         v = getattr(self, name)
@@ -194,4 +197,6 @@ class Outputs:
             v = getattr(self, f.name)
             if isinstance(v, torch.Tensor):
                 parts.append(f"{f.name}=Tensor{tuple(v.shape)}")
+            elif f.name == "pred_masks" and v is not None:
+                parts.append(f"pred_masks={[len(m) for m in v]}")
         return f"Outputs({', '.join(parts)})" if parts else "Outputs(empty)"

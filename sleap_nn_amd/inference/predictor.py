@@ -17,7 +17,7 @@ import torch
 
 from sleap_nn_amd.inference.backends import HipBackend
 from sleap_nn_amd.inference.layers import (BottomUpLayer, BottomUpMultiClassLayer, CenteredInstanceLayer, CentroidLayer, PostprocessConfig,
-                                           PreprocessConfig, SingleInstanceLayer, TiledLayer, TopDownLayer)
+                                           PreprocessConfig, SegmentationLayer, SemanticSegmentationLayer, SingleInstanceLayer, TiledLayer, TopDownLayer)
 from sleap_nn_amd.inference.layers.tiled import tiling_block, tiling_kwargs
 from sleap_nn_amd.inference.loaders import LoadedAssets, load_model_assets
 from sleap_nn_amd.inference.ops.paf import PAFScorer
@@ -81,11 +81,16 @@ def _warn_unverified_lanes(n: int, why: str) -> None:
                   "end-to-end throughput from the multi-lane predictor; results are unaffected)", RuntimeWarning, stacklevel=3)
 
 
+_SEG_KW = ("fg_threshold", "min_mask_area", "center_nms_kernel", "distance_gate_alpha", "full_res_masks", "mask_cleanup", "mask_cleanup_radius", "merge_fragments",
+           "mask_output")
+
+
 def _select_layer(assets: Sequence[LoadedAssets], device: str, post: PostprocessConfig, max_instances: Optional[int], tile_size: Optional[int] = None,
-                  overlap: Optional[int] = None, **paf_kw):
+                  overlap: Optional[int] = None, seg_kw: Optional[dict] = None, **paf_kw):
     """predictor.py:600 (``_select_layer``) for the model types of the hot path.  A single-instance run directory trained with tiling
     (``data_config.preprocessing.tiling.enabled``) gets a ``TiledLayer`` around its ``SingleInstanceLayer`` (predictor.py:191-246, 600-610);
-    ``tile_size`` / ``overlap`` are checked against the trained geometry, not applied."""
+    ``tile_size`` / ``overlap`` are checked against the trained geometry, not applied.  ``seg_kw``: the segmentation layers' knobs (``_SEG_KW``; the semantic
+    layer takes the subset it has)."""
     by_type = {a.model_type: a for a in assets}
     for a in assets:  # there is no tiled wrapper for the other model types: running them whole-frame at a geometry they were not trained for would be a silent wrong answer
         if a.model_type != "single_instance" and tiling_block(a.preprocessing) is not None:
@@ -100,6 +105,19 @@ def _select_layer(assets: Sequence[LoadedAssets], device: str, post: Postprocess
         return PreprocessConfig(ensure_rgb=p.get("ensure_rgb") or None, ensure_grayscale=p.get("ensure_grayscale") or None,
                                 max_height=p.get("max_height") or None, max_width=p.get("max_width") or None, scale=float(p.get("scale") or 1.0))
 
+    seg_kw = dict(seg_kw or {})
+    unknown = sorted(set(seg_kw) - set(_SEG_KW))
+    if unknown:
+        raise TypeError(f"unknown segmentation keyword(s) {unknown}; known: {list(_SEG_KW)}")
+    if "bottomup_segmentation" in by_type:  # the three heads share one stride: head_configs.bottomup_segmentation.segmentation.output_stride (loaders.py:455-456)
+        a = by_type["bottomup_segmentation"]
+        return SegmentationLayer(backend(a), a.head_config["segmentation"]["output_stride"], max_stride=a.backbone_config["max_stride"], max_instances=max_instances,
+                                 preprocess_config=pre(a), postprocess_config=post, **seg_kw)
+    if "semantic_segmentation" in by_type:
+        a = by_type["semantic_segmentation"]
+        sem_kw = {k: v for k, v in seg_kw.items() if k in ("fg_threshold", "min_mask_area", "full_res_masks", "mask_output")}
+        return SemanticSegmentationLayer(backend(a), a.head_config["segmentation"]["output_stride"], max_stride=a.backbone_config["max_stride"],
+                                         preprocess_config=pre(a), postprocess_config=post, **sem_kw)
     if "bottomup" in by_type:
         a = by_type["bottomup"]
         h = a.head_config
@@ -161,8 +179,14 @@ class Predictor:
     @classmethod
     def from_model_paths(cls, model_paths: Sequence[str], device: str = "cuda", batch_size: int = 4, peak_threshold: float = 0.2,
                          integral_refinement: Optional[str] = "integral", integral_patch_size: int = 5, max_instances: Optional[int] = None,
-                         return_confmaps: bool = False, streams: int = 3, tile_size: Optional[int] = None, overlap: Optional[int] = None, **paf_kw) -> "Predictor":
-        """``tile_size`` / ``overlap``: for run directories trained with tiling, checked against the trained geometry (a different value raises ``ValueError``:
+                         return_confmaps: bool = False, streams: int = 3, tile_size: Optional[int] = None, overlap: Optional[int] = None, fg_threshold: float = 0.5,
+                         min_mask_area: int = 0, center_nms_kernel: int = 3, distance_gate_alpha: Optional[float] = None, full_res_masks: bool = False,
+                         mask_cleanup: bool = False, mask_cleanup_radius: int = 0, merge_fragments: bool = False, mask_output: str = "mask", **paf_kw) -> "Predictor":
+        """``fg_threshold`` / ``min_mask_area`` / ``max_instances`` / ``center_nms_kernel`` / ``distance_gate_alpha`` / ``full_res_masks``: knobs of the segmentation
+        layers (``bottomup_segmentation`` / ``semantic_segmentation`` run directories; defaults as the reference; ``mask_cleanup``, ``mask_cleanup_radius``,
+        ``merge_fragments`` and ``mask_output`` are accepted so that a value the layer does not build raises there).  These layers run the plain per-batch path of
+        ``predict``: the pipelined multi-lane paths are not built for them (their post-process ends in a host read and builds host masks).
+        ``tile_size`` / ``overlap``: for run directories trained with tiling, checked against the trained geometry (a different value raises ``ValueError``:
         the geometry is fixed at training time); ignored otherwise, as in the reference.
         ``streams``: bottom-up and top-down run directories of small networks (<= 16 M parameters) are loaded ``streams`` times; the pipelined ``predict`` keeps that many batches in flight
         on streams of their own (see ``replicas``).  Measured on the reference's fixture models at batch 4 (``tools/streams_n_probe.py``, frames/s end to end with 1 / 2 / 3 / 4 lanes):
@@ -171,7 +195,10 @@ class Predictor:
         assets = [load_model_assets(p) for p in model_paths]
         post = PostprocessConfig(peak_threshold=peak_threshold, refinement=integral_refinement or "none", integral_patch_size=integral_patch_size,
                                  max_instances=max_instances, return_confmaps=return_confmaps)
-        layer = _select_layer(assets, device, post, max_instances, tile_size=tile_size, overlap=overlap, **paf_kw)
+        seg_kw = dict(fg_threshold=fg_threshold, min_mask_area=min_mask_area, center_nms_kernel=center_nms_kernel, distance_gate_alpha=distance_gate_alpha,
+                      full_res_masks=full_res_masks, mask_cleanup=mask_cleanup, mask_cleanup_radius=mask_cleanup_radius, merge_fragments=merge_fragments,
+                      mask_output=mask_output)
+        layer = _select_layer(assets, device, post, max_instances, tile_size=tile_size, overlap=overlap, seg_kw=seg_kw, **paf_kw)
         replicas = []
         small = lambda l: l.backend.model.num_parameters() <= _REPLICA_MAX_PARAMS
         if streams > 1 and ((isinstance(layer, (BottomUpLayer, SingleInstanceLayer)) and small(layer)) or

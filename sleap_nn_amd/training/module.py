@@ -48,6 +48,11 @@ class TrainingModule:
         training plan too (handle option ``conv_wino4 = 2``; gradients within ~1e-5 of their tensor's scale of the F(2x2,3x3) ones).
         ``native_allreduce``: with more than one rank, exchange the gradients through the C ABI's own RCCL communicator (``ph_model_set_comm``: the two buckets are
         enqueued by ``ph_model_backward`` itself) instead of ``torch.distributed``; default: when the process group's backend is nccl (= RCCL on ROCm)."""
+        from sleap_nn_amd.architectures.heads import SEGMENTATION_MODEL_TYPES
+
+        if getattr(model, "model_type", None) in SEGMENTATION_MODEL_TYPES:
+            raise NotImplementedError(f"training a '{model.model_type}' model is not built (BCE + Dice, masked smooth-L1 and mask targets): these model types run "
+                                      "inference only, and are not trained with the MSE loss of the pose heads instead")
         L.lib()
         if not torch.cuda.is_available():
             raise RuntimeError("TrainingModule needs an MI355X; there is no CPU fallback")
