@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 111
+#define PH_VERSION 112
 
 /* error codes */
 #define PH_OK 0
@@ -229,6 +229,19 @@ int ph_render_confmaps(const float* points_dev, int32_t B, int32_t I, int32_t N,
                        int32_t stride, float sigma, float* out_dev, void* stream);
 int ph_render_pafs(const float* points_dev, const int32_t* edges_dev, int32_t B, int32_t I, int32_t N, int32_t E,
                    int32_t img_h, int32_t img_w, int32_t stride, float sigma, float* out_dev, void* stream);
+
+/* Identity class maps of a batch in one launch (reference: data/identity.py:34-137 generate_class_maps).
+ * points_dev: (B, I, N, 2) fp32, NaN = missing; weights_dev: (B, C, I) fp32 class weights (0 / 1: the one-hot class vectors
+ * in the layout the caller's reshape gives them).  Per grid point: M_i = max over nodes of exp(-d^2 / (2 (sigma*stride)^2))
+ * (NaN -> 0), S = sum_i M_i, mask_i = M_i / S where M_i > threshold else 0, out[c] = max_i weights[c][i] * mask_i (0 for I = 0).
+ * out_dev: (B, C, h, w) fp32, h = ceil(img_h / stride).  threshold >= 0; a frame's points and weights must fit 64 KiB. */
+int ph_render_class_maps(const float* points_dev, const float* weights_dev, int32_t B, int32_t I, int32_t N, int32_t C,
+                         int32_t img_h, int32_t img_w, int32_t stride, float sigma, float threshold, float* out_dev,
+                         void* stream);
+/* Instance centroids (reference: data/instance_centroids.py:7-98 generate_centroids).  points_dev: (n, N, 2) fp32; out_dev: (n, 2).
+ * The anchor node when anchor_ind >= 0 and both its coordinates are present; else the NaN-ignoring mean, counted per axis;
+ * NaN when no node has a coordinate.  anchor_ind < 0: always the mean. */
+int ph_instance_centroids(const float* points_dev, int64_t n, int32_t N, int32_t anchor_ind, float* out_dev, void* stream);
 
 /* Diagnostic / test hook (pure host arithmetic, no GPU needed): the split-K plan the 3x3 kernels would take for a layer of this shape on a chip of n_cu CUs
  * under handle option conv_splitk = splitk (padded channel counts; section 4.1d of DESIGN.md).  out[0] = K slices on the F(2x2,3x3) kernel, out[1] = on the
