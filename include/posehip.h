@@ -35,6 +35,8 @@
  *   ph_tile_extract     inference/layers/tiled.py:62-84 (_extract_square_tile, per tile).
  *   ph_tile_merge       inference/tile_merger.py:107-179 (TileMerger.integrate per tile + merge) and the
  *                       crop of inference/layers/tiled.py:262-263.
+ *   ph_loss_* / ph_model_set_head_loss   training/losses.py:64-133 as called at training/lightning_modules.py:3052-3109, 3463-3475.
+ *   ph_render_seg_targets   data/segmentation_maps.py as called at data/custom_datasets.py:3593-3626.
  *   ph_seg_*            inference/segmentation.py:12-237 (find_center_peaks, group_instances_from_offsets) as called
  *                       at inference/layers/segmentation.py:159-266, and the thresholding of :438-503 (semantic).
  */
@@ -48,7 +50,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 112
+#define PH_VERSION 113
 
 /* error codes */
 #define PH_OK 0
@@ -102,8 +104,8 @@ enum ph_op_kind {
 #define PH_FLAG_SCALE_RESIDUAL 8
 #define PH_FLAG_SOFTMAX 16 /* PH_OP_HEAD: softmax over the output channels (ClassVectorsHead, heads.py:536-537) */
 #define PH_FLAG_SILU 32    /* PH_OP_CONVT: SiLU instead of ReLU (the activation is an epilogue parameter of the phase GEMMs) */
-#define PH_FLAG_NO_TRAIN 64 /* PH_OP_HEAD: a head whose loss is not built (BCE + Dice, masked smooth-L1: the segmentation model types);
-                               the forward ignores it, ph_model_backward refuses the program */
+#define PH_FLAG_NO_TRAIN 64 /* PH_OP_HEAD: a head of the segmentation model types, which neither MSE nor cross entropy trains; the forward ignores it,
+                               ph_model_backward refuses the program unless ph_model_set_head_loss chose the head's loss on this handle */
 
 typedef struct ph_op_desc {
   int32_t kind;      /* enum ph_op_kind                                              */
@@ -181,6 +183,33 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
                       int32_t min_hard_keypoints, int32_t max_hard_keypoints, float ohkm_loss_scale,
                       float* loss_dev, float* grads_flat_dev, void* stream);
 
+/* Loss of output `out_index` in ph_model_backward, chosen per handle before a step (reference: training/lightning_modules.py:3052-3109, 3463-3475).
+ *   PH_LOSS_MSE               nn.MSELoss; on a PH_FLAG_NO_TRAIN head (the instance-centre map) without OHKM and sample weights.  n_params = 0.
+ *   PH_LOSS_BCE_DICE          compute_bce_dice_loss (training/losses.py:64-105) on a one-channel head; params = {bce_weight, dice_weight, smooth,
+ *                             pos_weight (negative: none)}, n_params = 4.  In the plans a backward can follow (exact fp32, every activation kept) the head
+ *                             then emits LOGITS -- its PH_FLAG_SIGMOID epilogue is skipped -- and head_out_dev[out_index] of ph_model_backward is those
+ *                             logits; inference plans still return probabilities.  Set it before the forward of the step.
+ *   PH_LOSS_MASKED_SMOOTH_L1  compute_masked_smooth_l1 (losses.py:108-133); target_dev[out_index] is (B, c + 1, h, w): the c target channels, then the
+ *                             binary weight mask.  n_params = 0.
+ * A head whose loss was set is no longer refused for PH_FLAG_NO_TRAIN; a handle on which nothing was set behaves as before. */
+#define PH_LOSS_MSE 1
+#define PH_LOSS_BCE_DICE 2
+#define PH_LOSS_MASKED_SMOOTH_L1 3
+int ph_model_set_head_loss(ph_model* m, int32_t out_index, int32_t kind, const float* params, int32_t n_params);
+
+/* The two losses on their own (deterministic: fixed-order partial sums, no float atomics; three launches on `stream`, no host synchronisation).
+ *   ph_loss_bce_dice: logits / target (B, 1, h, w) fp32, target values in {0, 1}.  BCE = binary_cross_entropy_with_logits (mean, optional pos_weight:
+ *     negative = none) in its stable form; Dice per sample (2 sum(p t) + smooth) / (sum p + sum t + smooth), loss = bce_weight * BCE +
+ *     dice_weight * (1 - mean_b dice_b).  loss_dev[0] = the loss, grad_dev (B, 1, h, w) = loss_weight * d loss / d logit.
+ *   ph_loss_masked_smooth_l1: pred / target (B, C, h, w), mask (B, 1, h, w) binary, broadcast over C.  loss = sum smooth_l1(mask * pred, mask * target;
+ *     beta 1) / (C * sum mask), exactly 0 with an all-zero gradient when the mask is empty.  grad_dev (B, C, h, w) = loss_weight * d loss / d pred.
+ *   scratch_dev: ph_loss_scratch_bytes(B, C) bytes (covers both), 8-byte aligned. */
+int64_t ph_loss_scratch_bytes(int32_t B, int32_t C);
+int ph_loss_bce_dice(const float* logits_dev, const float* target_dev, int32_t B, int32_t h, int32_t w, float bce_weight, float dice_weight, float smooth,
+                     float pos_weight, float loss_weight, float* loss_dev, float* grad_dev, void* scratch_dev, int64_t scratch_bytes, void* stream);
+int ph_loss_masked_smooth_l1(const float* pred_dev, const float* target_dev, const float* mask_dev, int32_t B, int32_t C, int32_t h, int32_t w,
+                             float loss_weight, float* loss_dev, float* grad_dev, void* scratch_dev, int64_t scratch_bytes, void* stream);
+
 /* Two gradient buckets for overlapping the data-parallel all-reduce with the backward sweep (DDP's bucketing,
  * training/model_trainer.py:1751-1813 runs the reference under Lightning's DDP strategy).  The sweep runs heads -> decoder ->
  * middle -> encoder and the arena is in program order, so its tail becomes final first: ph_model_grad_bucket_split returns the
@@ -242,6 +271,23 @@ int ph_render_class_maps(const float* points_dev, const float* weights_dev, int3
  * The anchor node when anchor_ind >= 0 and both its coordinates are present; else the NaN-ignoring mean, counted per axis;
  * NaN when no node has a coordinate.  anchor_ind < 0: always the mean. */
 int ph_instance_centroids(const float* points_dev, int64_t n, int32_t N, int32_t anchor_ind, float* out_dev, void* stream);
+
+/* Targets of the segmentation model types from instance masks (reference: data/segmentation_maps.py).  masks_dev: (B, I, H, W) uint8, non-zero =
+ * foreground, of the image's size; n_instances_dev int32[B]: slots at or beyond n_instances[b] are padding and are never read as masks (a real, empty mask
+ * is different: its centroid is the image centre and it does get a Gaussian).  Output grids are (H / s, W / s) (integer division), cell i of an axis
+ * covering the rows [floor(i H / out), ceil((i + 1) H / out)) -- the windows of adaptive_avg_pool2d, which is what F.interpolate(mode="area") runs.
+ *   centroids_dev float (B, I, 2) = (x, y), areas_dev int64 (B, I): with compute_stats != 0 they are computed first (exact 64-bit sums of x, y and the
+ *     pixel count, one fp64 division each, rounded to fp32; (W / 2, H / 2) for an empty mask; NaN / 0 in padding slots); with compute_stats == 0 they are
+ *     inputs, e.g. what a call for another head's stride has written.  Both are required.
+ *   fg_dev (B, 1, h, w) or NULL: 1 where more than half of the window's pixels lie in the union of the masks (2 count > window; exactly half is
+ *     background), with maxpool != 0 where any does.
+ *   center_dev (B, 1, h, w) or NULL: max over the instances of exp(-((x - cx)^2 + (y - cy)^2) / (2 (sigma s)^2)) on the grid i s + s / 2.
+ *   offsets_dev (B, 2, h, w) / weight_dev (B, 1, h, w), both or neither: among the instances that cover more than half of the cell's window, the one with
+ *     the smallest area wins (equal areas: the higher index); offsets = (cx - x, cy - y), weight 1; zeros elsewhere.  Their batch strides are given in
+ *     floats, so both may be channel ranges of one (B, 3, h, w) tensor (what PH_LOSS_MASKED_SMOOTH_L1 takes as its target). */
+int ph_render_seg_targets(const uint8_t* masks_dev, const int32_t* n_instances_dev, int32_t B, int32_t I, int32_t H, int32_t W, int32_t output_stride,
+                          float sigma, int32_t maxpool, int32_t compute_stats, float* centroids_dev, int64_t* areas_dev, float* fg_dev, float* center_dev,
+                          float* offsets_dev, int64_t offsets_batch_stride, float* weight_dev, int64_t weight_batch_stride, void* stream);
 
 /* Diagnostic / test hook (pure host arithmetic, no GPU needed): the split-K plan the 3x3 kernels would take for a layer of this shape on a chip of n_cu CUs
  * under handle option conv_splitk = splitk (padded channel counts; section 4.1d of DESIGN.md).  out[0] = K slices on the F(2x2,3x3) kernel, out[1] = on the

@@ -17,6 +17,7 @@ PH_E_INVALID, PH_E_HIP, PH_E_CAPACITY, PH_E_INFEASIBLE, PH_E_WORKSPACE = -1, -2,
 OP_INPUT_CONV, OP_CONV, OP_POOL, OP_UPSAMPLE, OP_CONVT, OP_HEAD, OP_STEM = 1, 2, 3, 4, 5, 6, 7
 OP_PATCH_STEM, OP_DWCONV, OP_LAYERNORM, OP_LINEAR, OP_PATCH_CONV, OP_GELU, OP_SCALE_ADD, OP_GLOBAL_MAXPOOL = 8, 9, 10, 11, 12, 13, 14, 15
 FLAG_RELU, FLAG_SIGMOID, FLAG_GELU, FLAG_SCALE_RESIDUAL, FLAG_SOFTMAX, FLAG_SILU, FLAG_NO_TRAIN = 1, 2, 4, 8, 16, 32, 64
+LOSS_MSE, LOSS_BCE_DICE, LOSS_MASKED_SMOOTH_L1 = 1, 2, 3  # PH_LOSS_*: ph_model_set_head_loss
 # PH_KV_*: kernel family an op of the last forward ran (ph_model_last_kernels) and the share of its direct-convolution
 # FLOPs that family puts through the matrix cores
 KV_NONE, KV_DIRECT, KV_WINO1D, KV_WINO2D, KV_W16, KV_C16, KV_ROWGEMM, KV_WINO4, KV_F16, KV_STEM, KV_WINO2D_KS, KV_FUSED, KV_SMALLMAP, KV_F16_ROWS, KV_F16_BLOCK, KV_MLP = range(16)
@@ -84,6 +85,11 @@ SIGNATURES = {
     "ph_model_backward_workspace_bytes": (_i64, [_vp, _i32, _i32, _i32]),
     "ph_model_backward": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_f32), _vp, _i32, _f32,
                                     _i32, _i32, _f32, _vp, _vp, _vp]),
+    "ph_model_set_head_loss": (C.c_int, [_vp, _i32, _i32, C.POINTER(_f32), _i32]),
+    "ph_loss_scratch_bytes": (_i64, [_i32, _i32]),
+    "ph_loss_bce_dice": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _i64, _vp]),
+    "ph_loss_masked_smooth_l1": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i64, _vp]),
+    "ph_render_seg_targets": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "ph_debug_split_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64)]),
     "ph_debug_gemm_bench": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float)]),
     "ph_debug_row_wgrad_bench": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),

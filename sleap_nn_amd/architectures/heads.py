@@ -169,7 +169,8 @@ class CenterOffsetHead(Head):
         return "smooth_l1"
 
 
-# model types that are built for inference only: their losses (BCE + Dice, masked smooth-L1) and mask targets are not
+# model types whose heads neither MSE nor cross entropy trains: their losses (BCE + Dice, masked smooth-L1) and mask targets live in
+# training/segmentation.py and data/segmentation_maps.py; TrainingModule and TargetGenerator refuse them
 SEGMENTATION_MODEL_TYPES = ("bottomup_segmentation", "semantic_segmentation")
 
 

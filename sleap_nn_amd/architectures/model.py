@@ -92,6 +92,8 @@ class Model:
         # re-gathered from it, so eval()/train() round trips never fall back to the host copy in _state
         self._live_params: Optional[torch.Tensor] = None
         self._options["workspace_reuse"] = 1.0  # the model starts in the inference (fused) program
+        # head index -> (PH_LOSS_* kind, parameters): set_head_loss; applied to every training handle, never to an inference one
+        self._head_losses: Dict[int, tuple] = {}
 
     def _add_class_vector_head(self, i: int, head: "ClassVectorsHead") -> None:
         """heads.py:506-539 on the decoder's input feature (architectures/model.py:197-199,253-255)."""
@@ -326,6 +328,21 @@ class Model:
         self._options[str(key)] = float(value)
         return self
 
+    def set_head_loss(self, index: int, kind: int, params=()) -> "Model":
+        """Loss of head ``index`` in ``ph_model_backward`` (``ph_model_set_head_loss``; kinds ``_lib.LOSS_*``).  Remembered across recompiles, like the
+        options, and applied to the handle of the training (unfused) program only: with ``LOSS_BCE_DICE`` that program's head emits logits, while the
+        inference program keeps returning probabilities."""
+        self._head_losses[int(index)] = (int(kind), tuple(float(p) for p in params))
+        if self._handle is not None and self.ops is self.unfused_ops:
+            self._apply_head_losses()
+            self.generation += 1
+        return self
+
+    def _apply_head_losses(self) -> None:
+        for i, (kind, params) in self._head_losses.items():
+            arr = (C.c_float * max(1, len(params)))(*params)
+            L.check(L.lib().ph_model_set_head_loss(self._handle, i, kind, arr, len(params)))
+
     def get_option(self, key: str) -> float:
         if self._handle is None:
             raise RuntimeError("get_option needs a compiled handle (run a forward first)")
@@ -370,6 +387,8 @@ class Model:
         self.generation += 1
         for k, v in self._options.items():
             L.check(lib.ph_model_set_option(self._handle, k.encode(), v))
+        if self.ops is self.unfused_ops:
+            self._apply_head_losses()
         if self._live_params is not None:  # the host copy in _state may be stale during training
             if self._live_params.device != device or self._live_params.numel() != sum(t.numel() for t in tensors):
                 raise RuntimeError("live parameter arena does not match this model / device")

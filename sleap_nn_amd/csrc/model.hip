@@ -1165,7 +1165,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
                 f.head_dst = out_dev[hx.out_index];
                 f.head_cout = hx.cout;
                 f.head_wcp = so.cp;
-                f.head_sigmoid = (hx.flags & PH_FLAG_SIGMOID) ? 1 : 0;
+                f.head_sigmoid = head_sigmoid(m, plan, hx);
                 head_done[j] = 1;
                 if (plan.reuse) {
                   bool other = false;
@@ -1369,7 +1369,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
               a.head_dst = out_dev[hx.out_index];
               a.head_cout = hx.cout;
               a.head_wcp = a.coutp;
-              a.head_sigmoid = (hx.flags & PH_FLAG_SIGMOID) ? 1 : 0;
+              a.head_sigmoid = head_sigmoid(m, plan, hx);
               head_done[j] = 1;
               if (plan.reuse) {  // training keeps every activation
                 bool other = false;
@@ -1515,7 +1515,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
                 f.head_dst = out_dev[hx.out_index];
                 f.head_cout = hx.cout;
                 f.head_wcp = 64;
-                f.head_sigmoid = (hx.flags & PH_FLAG_SIGMOID) ? 1 : 0;
+                f.head_sigmoid = head_sigmoid(m, plan, hx);
                 head_done[j] = 1;
                 if (plan.reuse) {
                   bool other = false;
@@ -1749,7 +1749,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         PH_REQUIRE(s0.c == d.cin0, "head channel mismatch");
         PH_REQUIRE(out_dev[d.out_index] != nullptr, "output %d is null", d.out_index);
         rc = launch_head_fmt(fmt, slot_ptr(d.src0), op.w_dev, op.b_dev, out_dev[d.out_index], batch, s0.h * s0.w, s0.cp, pad16(d.cin0), d.cout,
-                             (d.flags & PH_FLAG_SIGMOID) ? 1 : 0, s);
+                             head_sigmoid(m, plan, d), s);
         if (rc == PH_OK && (d.flags & PH_FLAG_SOFTMAX)) {
           PH_REQUIRE(s0.h == 1 && s0.w == 1, "softmax head expects a pooled (1x1) feature");
           rc = launch_softmax_rows(out_dev[d.out_index], batch, d.cout, s);

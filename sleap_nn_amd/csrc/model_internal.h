@@ -166,6 +166,9 @@ struct ph_model {
   int convt_one_launch = 1;                   // "convt_one_launch": the four output-phase GEMMs of a transposed conv as ONE launch (grid.y = phase) instead of four (four launch floors at small batches)
   int convt_phase = 1;                        // "convt_phase": transposed convs as four phase GEMMs (0: zero-stuffing + 3x3 conv, 4x the FLOPs; A/B)
   int conv_precision = 0;                     // "conv_precision": 0 exact fp32 MFMA; 1 split-fp16 MFMA (22-bit products, fp32 accumulate); 2 plain fp16 (autocast-equivalent)
+  // ph_model_set_head_loss: loss of output i in ph_model_backward (0 = never set: MSE / cross entropy as the flags say, PH_FLAG_NO_TRAIN heads refused)
+  int head_loss_kind[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  float head_loss_params[8][4] = {};          // PH_LOSS_BCE_DICE: bce_weight, dice_weight, smooth, pos_weight (< 0: none)
 };
 
 
@@ -177,4 +180,11 @@ int upload(ph_model* m, const std::vector<float>& host, float** dev);
 int upload_ints(ph_model* m, const std::vector<int>& host, int** dev);
 int choose_bn(int coutp);
 void apply_conv_options(const ph_model* m, ConvArgs& a);
+// Whether head op `d` applies its sigmoid epilogue in `plan`.  A head whose loss is PH_LOSS_BCE_DICE emits LOGITS in the plans a backward can follow
+// (exact fp32, every activation kept): the loss kernel supervises the logit, as the reference's training_step does (lightning_modules.py:3052-3075).
+inline int head_sigmoid(const ph_model* m, const Plan& plan, const ph_op_desc& d) {
+  if (!(d.flags & PH_FLAG_SIGMOID)) return 0;
+  const bool trainable_plan = plan.fmt == FMT_F32 && !plan.reuse;
+  return (trainable_plan && d.out_index >= 0 && d.out_index < 8 && m->head_loss_kind[d.out_index] == PH_LOSS_BCE_DICE) ? 0 : 1;
+}
 }  // namespace ph

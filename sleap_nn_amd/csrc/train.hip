@@ -11,6 +11,8 @@
 
 using namespace ph;
 
+static_assert(PH_MAX_OUTPUTS == sizeof(ph_model::head_loss_kind) / sizeof(int), "ph_model keeps one head loss per possible output");
+
 namespace {
 
 struct BwdPlan {
@@ -71,6 +73,7 @@ int build_bwd_plan(const ph_model* m, int B, int H, int W, BwdPlan& bp) {
       off += align_up((int64_t)B * d.cout * s0.h * s0.w * 4, 256);
       scratch = std::max<int64_t>(scratch, head_bwd_scratch_floats(s0.cp, d.cout, (int64_t)B * s0.h * s0.w));
       scratch = std::max<int64_t>(scratch, loss_scratch_floats(d.cout) + 64);
+      scratch = std::max<int64_t>(scratch, seg_loss_scratch_floats(B, d.cout));
     } else if (d.kind == PH_OP_CONV) {
       const SlotShape& s0 = bp.act.slots[d.src0];
       scratch = std::max<int64_t>(scratch, wgrad_slab_floats(d.cin0, d.cout, B, s0.h, s0.w));
@@ -258,9 +261,12 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
              "ph_model_backward: null argument");
   PH_REQUIRE(((uintptr_t)grad_workspace_dev & 255) == 0, "gradient workspace must be 256-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  for (const auto& op : m->ops)  // the MSE / cross-entropy gradients below are not these heads' losses
-    PH_REQUIRE(!(op.d.kind == PH_OP_HEAD && (op.d.flags & PH_FLAG_NO_TRAIN)),
+  for (const auto& op : m->ops) {  // the MSE / cross-entropy gradients below are not these heads' losses: they train only with a loss chosen by ph_model_set_head_loss
+    if (op.d.kind != PH_OP_HEAD) continue;
+    PH_REQUIRE(op.d.out_index >= 0 && op.d.out_index < PH_MAX_OUTPUTS, "ph_model_backward: head output index %d out of range", op.d.out_index);
+    PH_REQUIRE(!((op.d.flags & PH_FLAG_NO_TRAIN) && m->head_loss_kind[op.d.out_index] == 0),
                "ph_model_backward: head %d belongs to a segmentation model type, whose losses (BCE + Dice, masked smooth-L1) are not built: inference only", op.d.out_index);
+  }
   PH_REQUIRE(m->last_plan.fmt == FMT_F32, "backward needs the activations of an exact-fp32 forward (handle option conv_precision = 0)");
   PH_REQUIRE(!m->last_plan.reuse, "backward needs every activation of the forward (handle option workspace_reuse = 0)");
   BwdPlan bp;
@@ -303,7 +309,22 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
     const SlotShape& s0 = bp.act.slots[d.src0];
     PH_REQUIRE(head_out_dev[d.out_index] && target_dev[d.out_index], "head %d: null output/target", d.out_index);
     float* dy = reinterpret_cast<float*>(gws + bp.head_dy_off[d.out_index]);
-    if (d.flags & PH_FLAG_SOFTMAX)  // class-vector head: cross entropy on the softmax output, gradient wrt the logits
+    const int kind = m->head_loss_kind[d.out_index];
+    const float* hp = m->head_loss_params[d.out_index];
+    const int64_t plane = (int64_t)s0.h * s0.w;
+    if (kind == PH_LOSS_BCE_DICE) {  // head_out_dev holds logits (head_sigmoid, model_internal.h); dy is the gradient wrt the logit
+      PH_REQUIRE(d.cout == 1 && !(d.flags & PH_FLAG_SOFTMAX), "head %d: BCE + Dice needs a one-channel map head", d.out_index);
+      rc = launch_bce_dice(head_out_dev[d.out_index], target_dev[d.out_index], batch, s0.h, s0.w, hp[0], hp[1], hp[2], hp[3], lw[d.out_index], scratch, dy,
+                           loss_dev + 1 + d.out_index, s);
+    } else if (kind == PH_LOSS_MASKED_SMOOTH_L1) {  // target_dev: (B, cout + 1, h, w), the last channel is the weight mask
+      PH_REQUIRE(!(d.flags & (PH_FLAG_SOFTMAX | PH_FLAG_SIGMOID)), "head %d: masked smooth-L1 needs a linear map head", d.out_index);
+      rc = launch_masked_smooth_l1(head_out_dev[d.out_index], target_dev[d.out_index], (d.cout + 1) * plane, target_dev[d.out_index] + d.cout * plane, (d.cout + 1) * plane,
+                                   batch, d.cout, s0.h, s0.w, lw[d.out_index], scratch, dy, loss_dev + 1 + d.out_index, s);
+    } else if (kind == PH_LOSS_MSE && (d.flags & PH_FLAG_NO_TRAIN)) {  // the centre head: plain nn.MSELoss (F.mse_loss, lightning_modules.py:3074)
+      PH_REQUIRE(!(d.flags & (PH_FLAG_SOFTMAX | PH_FLAG_SIGMOID)), "head %d: MSE on a segmentation head needs a linear map head", d.out_index);
+      rc = launch_loss(head_out_dev[d.out_index], target_dev[d.out_index], nullptr, batch, d.cout, s0.h, s0.w, lw[d.out_index], OhkmParams{}, scratch, dy,
+                       loss_dev + 1 + d.out_index, s);
+    } else if (d.flags & PH_FLAG_SOFTMAX)  // class-vector head: cross entropy on the softmax output, gradient wrt the logits
       rc = launch_class_ce(head_out_dev[d.out_index], target_dev[d.out_index], batch, d.cout, lw[d.out_index], dy, loss_dev + 1 + d.out_index, s);
     else
       rc = launch_loss(head_out_dev[d.out_index], target_dev[d.out_index], sample_weights_dev, batch, d.cout, s0.h, s0.w, lw[d.out_index], ok, scratch, dy,
@@ -331,7 +352,7 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
         const bool fold = m->mask_fold && first_consumer[d.src0] == oi && pr >= 0 && m->ops[pr].d.kind == PH_OP_CONV && (m->ops[pr].d.flags & PH_FLAG_RELU) &&
                           head_bwd_can_fold(s0.cp, s0.h * s0.w);
         const bool sum_bias = fold && m->ops[pr].d.bias >= 0;
-        rc = launch_head_bwd(dy, head_out_dev[d.out_index], (d.flags & PH_FLAG_SIGMOID) ? 1 : 0, A(d.src0), op.w_dev, batch, s0.h * s0.w, d.cin0, s0.cp, d.cout,
+        rc = launch_head_bwd(dy, head_out_dev[d.out_index], head_sigmoid(m, m->last_plan, d), A(d.src0), op.w_dev, batch, s0.h * s0.w, d.cin0, s0.cp, d.cout,
                              init[d.src0], G(d.src0), grads_flat_dev + m->weight_offset[d.weight], d.bias >= 0 ? grads_flat_dev + m->weight_offset[d.bias] : nullptr,
                              scratch, s, fold ? A(d.src0) : nullptr, sum_bias ? grads_flat_dev + m->weight_offset[m->ops[pr].d.bias] : nullptr,
                              sum_bias ? m->ops[pr].d.cout : 0);
@@ -764,6 +785,22 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
     PH_HIP_CHECK(hipEventRecord(m->comm_ev[2], m->comm_stream));
     PH_HIP_CHECK(hipStreamWaitEvent(s, m->comm_ev[2], 0));
   }
+  return PH_OK;
+}
+
+int ph_model_set_head_loss(ph_model* m, int32_t out_index, int32_t kind, const float* params, int32_t n_params) {
+  PH_REQUIRE(m, "ph_model_set_head_loss: null model");
+  PH_REQUIRE(out_index >= 0 && out_index < m->n_outputs && out_index < PH_MAX_OUTPUTS, "ph_model_set_head_loss: output %d of %d", out_index, m->n_outputs);
+  PH_REQUIRE(kind == PH_LOSS_MSE || kind == PH_LOSS_BCE_DICE || kind == PH_LOSS_MASKED_SMOOTH_L1, "ph_model_set_head_loss: unknown loss kind %d", kind);
+  PH_REQUIRE(n_params == (kind == PH_LOSS_BCE_DICE ? 4 : 0) && (n_params == 0 || params), "ph_model_set_head_loss: loss kind %d takes %d parameters, got %d", kind,
+             kind == PH_LOSS_BCE_DICE ? 4 : 0, n_params);
+  for (const auto& op : m->ops) {
+    if (op.d.kind != PH_OP_HEAD || op.d.out_index != out_index) continue;
+    PH_REQUIRE(kind != PH_LOSS_BCE_DICE || (op.d.cout == 1 && !(op.d.flags & PH_FLAG_SOFTMAX)), "ph_model_set_head_loss: BCE + Dice needs a one-channel map head");
+    PH_REQUIRE(kind != PH_LOSS_MASKED_SMOOTH_L1 || !(op.d.flags & (PH_FLAG_SOFTMAX | PH_FLAG_SIGMOID)), "ph_model_set_head_loss: masked smooth-L1 needs a linear map head");
+  }
+  m->head_loss_kind[out_index] = kind;
+  for (int i = 0; i < 4; ++i) m->head_loss_params[out_index][i] = i < n_params ? params[i] : 0.f;
   return PH_OK;
 }
 

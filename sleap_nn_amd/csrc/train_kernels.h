@@ -24,6 +24,13 @@ struct WgradArgs {
 int launch_loss(const float* pred, const float* tgt, const float* sample_w, int B, int C, int H, int W, float loss_weight, const OhkmParams& ok, float* scratch,
                 float* dy, float* loss_out, hipStream_t s);
 int64_t loss_scratch_floats(int C);
+// seg_loss_kernels.hip: BCE + Dice on (B, 1, H, W) logits (dz = loss_weight * d loss / d logit) and smooth-L1 (beta 1) under a (B, 1, H, W) mask
+// broadcast over C; the target and the mask may be channel ranges of a wider tensor (batch strides in floats).  pos_weight < 0: none.
+int launch_bce_dice(const float* logits, const float* tgt, int B, int H, int W, float bce_weight, float dice_weight, float smooth, float pos_weight, float loss_weight,
+                    float* scratch, float* dz, float* loss_out, hipStream_t s);
+int launch_masked_smooth_l1(const float* pred, const float* tgt, int64_t tgt_batch_stride, const float* mask, int64_t mask_batch_stride, int B, int C, int H, int W,
+                            float loss_weight, float* scratch, float* dy, float* loss_out, hipStream_t s);
+int64_t seg_loss_scratch_floats(int B, int C);
 constexpr int PH_MAX_OUTPUTS = 8;
 int launch_total_loss(const float* head_loss, const float* w_host, int n, float* out, hipStream_t s);
 int launch_head_bwd(const float* dy, const float* y_out, int sigmoid, const float* x, const float* w_packed, int B, int HW, int cin, int cp, int cout,

@@ -228,7 +228,7 @@ class TargetGenerator:
         from sleap_nn_amd.architectures.heads import get_head
 
         if model_type in _SEGMENTATION_TYPES:
-            raise NotImplementedError(f"'{model_type}' targets (masks, centre maps, offsets) are not rendered here: segmentation models are built for inference only")
+            raise NotImplementedError(f"'{model_type}' targets (masks, centre maps, offsets) are not rendered here: use sleap_nn_amd.data.segmentation_maps.SegmentationTargetGenerator")
         self.model_type = model_type
         self.heads = {h.name: h for h in get_head(model_type, head_config)}
         self.anchor_ind = anchor_ind

@@ -36,6 +36,9 @@ class OHKMConfig:
 class TrainingModule:
     """Owns the device arenas of one model replica and runs training steps."""
 
+    # the segmentation model types train through a subclass that sets their head losses (training/segmentation.py); this class refuses them
+    _trains_segmentation = False
+
     def __init__(self, model: Model, device: str = "cuda", lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, amsgrad: bool = False,
                  optimizer: str = "Adam", weight_decay: Optional[float] = None,
                  loss_weights: Optional[Sequence[float]] = None, ohkm: Optional[OHKMConfig] = None,
@@ -50,9 +53,9 @@ class TrainingModule:
         enqueued by ``ph_model_backward`` itself) instead of ``torch.distributed``; default: when the process group's backend is nccl (= RCCL on ROCm)."""
         from sleap_nn_amd.architectures.heads import SEGMENTATION_MODEL_TYPES
 
-        if getattr(model, "model_type", None) in SEGMENTATION_MODEL_TYPES:
-            raise NotImplementedError(f"training a '{model.model_type}' model is not built (BCE + Dice, masked smooth-L1 and mask targets): these model types run "
-                                      "inference only, and are not trained with the MSE loss of the pose heads instead")
+        if getattr(model, "model_type", None) in SEGMENTATION_MODEL_TYPES and not self._trains_segmentation:
+            raise NotImplementedError(f"training a '{model.model_type}' model is not built here (BCE + Dice, masked smooth-L1 and mask targets): these model types are "
+                                      "not trained with the MSE loss of the pose heads; use sleap_nn_amd.training.segmentation.SegmentationTrainingModule")
         L.lib()
         if not torch.cuda.is_available():
             raise RuntimeError("TrainingModule needs an MI355X; there is no CPU fallback")
@@ -141,9 +144,9 @@ class TrainingModule:
                 self._grad_ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
             outs = [out[h.name].contiguous() for h in m.heads]
             tg = [targets[h.name].to(self.device, torch.float32).contiguous() for h in m.heads]
-            for o, t in zip(outs, tg):
-                if tuple(o.shape) != tuple(t.shape):
-                    raise ValueError(f"target shape {tuple(t.shape)} != prediction shape {tuple(o.shape)}")
+            for i, (o, t) in enumerate(zip(outs, tg)):
+                if tuple(t.shape) != self._target_shape(i, tuple(o.shape)):
+                    raise ValueError(f"target shape {tuple(t.shape)} != {self._target_shape(i, tuple(o.shape))} for a prediction of shape {tuple(o.shape)}")
             optr = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
             tptr = (C.c_void_p * len(tg))(*[t.data_ptr() for t in tg])
             lw = (C.c_float * len(self.loss_weights))(*self.loss_weights)
@@ -176,6 +179,10 @@ class TrainingModule:
             )
         self._last_out = out
         return self._loss
+
+    def _target_shape(self, head_index: int, pred_shape: tuple) -> tuple:
+        """Shape of head ``head_index``'s target for a prediction of ``pred_shape`` (a subclass's loss may take more channels)."""
+        return pred_shape
 
     def all_reduce_grads(self) -> float:
         """Sum the flat gradient arena over the ranks; returns the scale that turns the sum into DDP's mean.
