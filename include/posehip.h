@@ -624,6 +624,33 @@ int64_t ph_seg_semantic_scratch_bytes(int32_t B, int32_t h, int32_t w);
 int ph_seg_semantic(const float* fg_dev, int32_t B, int32_t h, int32_t w, float fg_threshold, uint8_t* mask_dev, int32_t* count_dev, double* sum_dev,
                     void* scratch_dev, int64_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Segmentation evaluation (evaluation.py:339-409 _align_pair / _mask_pair_stats / _mask_to_boundary / _boundary_iou)
+ * ---------------------------------------------------------------------------------- */
+
+/* Contingency table of a predicted and a ground-truth mask set per frame, in one pass over the pixels (_mask_pair_stats,
+ * evaluation.py:352-372, without its P * G image passes).  gt_dev uint8 (B, G, H, W), nonzero = foreground, masks may overlap.
+ * pred_form 0: pred_dev uint8 (B, P, ph, pw), masks may overlap; pred_form 1 / 2 / 4: pred_dev is a label map (B, ph, pw) of signed
+ * integers that many bytes wide, -1 = background, labels in [0, P) (what ph_seg_assign / ph_seg_gate write).  Canvas pixel (y, x)
+ * reads prediction cell (y / pred_stride, x / pred_stride): nearest up-sampling by an exact integer factor.  The canvas is _align_pair's
+ * (evaluation.py:339-349), top-left aligned, max(H, ph * pred_stride) x max(W, pw * pred_stride); a set has no foreground outside its
+ * own extent, and its foreground outside the other set's extent still counts in its area.  n_pred_dev / n_gt_dev int32[B]: slots at or
+ * beyond the count are never read and their outputs are 0 (a label at or beyond n_pred is background).  inter_dev int32 (B, P, G),
+ * pred_area_dev int32 (B, P), gt_area_dev int32 (B, G) are zeroed here on `stream`; integer accumulation only, so the result is exact
+ * and identical from run to run.  1 <= P, G <= 64 (PH_E_INVALID beyond).  One launch, no host synchronisation. */
+int ph_mask_pair_stats(const void* pred_dev, int32_t pred_form, int32_t P, int32_t ph, int32_t pw, int32_t pred_stride, const uint8_t* gt_dev, int32_t G,
+                       int32_t H, int32_t W, int32_t B, const int32_t* n_pred_dev, const int32_t* n_gt_dev, int32_t* inter_dev, int32_t* pred_area_dev,
+                       int32_t* gt_area_dev, void* stream);
+
+/* Boundary region of N masks (_mask_to_boundary, evaluation.py:375-393): masks_dev uint8 (N, H, W), nonzero = foreground; out_dev uint8
+ * (N, H, W) = 1 where mask AND NOT eroded, else 0.  A pixel is eroded exactly when min(y, x, H - 1 - y, W - 1 - x) >= d and every pixel
+ * of its (2d + 1) x (2d + 1) window is foreground: d iterations of a 3x3 erosion behind a one-pixel zero border.  The caller computes
+ * d = max(1, round(0.02 * sqrt(H^2 + W^2))).  Separable (a row pass into scratch_dev, then a column pass); scratch_dev of
+ * ph_mask_boundary_scratch_bytes(N, H, W) bytes, 2-byte aligned; out_dev must not be masks_dev.  Two launches. */
+int64_t ph_mask_boundary_scratch_bytes(int32_t N, int32_t H, int32_t W);
+int ph_mask_boundary(const uint8_t* masks_dev, int32_t N, int32_t H, int32_t W, int32_t d, uint8_t* out_dev, void* scratch_dev, int64_t scratch_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
