@@ -37,6 +37,8 @@
  *                       crop of inference/layers/tiled.py:262-263.
  *   ph_loss_* / ph_model_set_head_loss   training/losses.py:64-133 as called at training/lightning_modules.py:3052-3109, 3463-3475.
  *   ph_render_seg_targets   data/segmentation_maps.py as called at data/custom_datasets.py:3593-3626.
+ *   ph_seg_place_crops  inference/segmentation_convert.py:74-133 (decode_mask_to_image_res) over the entries that
+ *                       inference/layers/topdown_segmentation.py:163-284 emits.
  *   ph_seg_*            inference/segmentation.py:12-237 (find_center_peaks, group_instances_from_offsets) as called
  *                       at inference/layers/segmentation.py:159-266, and the thresholding of :438-503 (semantic).
  */
@@ -50,7 +52,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 113
+#define PH_VERSION 114
 
 /* error codes */
 #define PH_OK 0
@@ -623,6 +625,17 @@ int ph_seg_gate(const void* labels_in_dev, const float* dist_dev, int32_t B, int
 int64_t ph_seg_semantic_scratch_bytes(int32_t B, int32_t h, int32_t w);
 int ph_seg_semantic(const float* fg_dev, int32_t B, int32_t h, int32_t w, float fg_threshold, uint8_t* mask_dev, int32_t* count_dev, double* sum_dev,
                     void* scratch_dev, int64_t scratch_bytes, void* stream);
+
+/* Top-down crop masks into frame space (decode_mask_to_image_res, inference/segmentation_convert.py:74-133, for a batch).
+ * masks_dev uint8 (N, h, w) as ph_seg_semantic writes them; pos_of_slot_dev int32[B * P] as ph_centroid_select writes it (-1 = empty slot, a
+ * value at or beyond N counts as empty); geom_dev int32 (N, 4) = (ox, oy, He, We): the rounded image-space origin and the decoded extent of
+ * each crop.  out_dev uint8 (B, P, H, W), 16-byte aligned -- pred_form 0 of ph_mask_pair_stats at pred_stride 1.  Pixel (y, x) of slot s
+ * with crop k = pos_of_slot[s]: v = y - oy, u = x - ox; inside 0 <= v < He, 0 <= u < We it is masks[k][(v * h) / He][(u * w) / We] (integer
+ * division: the nearest resample to (He, We), then the top-left pad / clip), else 0.  A crop whose He or We is outside [1, 65535] is empty.
+ * Every byte of out_dev is written (no memset needed), nothing is accumulated: identical from run to run.  1 <= P <= 64, h, w <= 32767,
+ * B P H W < 2^32 (PH_E_INVALID beyond).  One launch, no host synchronisation. */
+int ph_seg_place_crops(const uint8_t* masks_dev, int32_t N, int32_t h, int32_t w, const int32_t* pos_of_slot_dev, const int32_t* geom_dev, int32_t B, int32_t P,
+                       int32_t H, int32_t W, uint8_t* out_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Segmentation evaluation (evaluation.py:339-409 _align_pair / _mask_pair_stats / _mask_to_boundary / _boundary_iou)

@@ -23,6 +23,11 @@
 //     keep = d <= r2[label] recomputed over ALL assigned pixels, as the reference does, new counts; the last pass writes the gated label map.
 //   * seg_sem_kernel + seg_sem_final_kernel: pixel count and sum of fg over fg > threshold per frame (fixed-order partial sums,
 //     double accumulation: deterministic) and the 0 / 1 map.
+//   * seg_place_kernel: top-down crop masks into frame space (decode_mask_to_image_res, inference/segmentation_convert.py:74-133, for a whole
+//     batch): the output (B, P, H, W) is walked as one flat array of 16-byte chunks, one chunk per lane per step, stored as one
+//     16-byte vector.  A chunk usually lies in one row; where W is no multiple of 16 it runs on into the next row (or slot) and
+//     the lane re-reads that row's crop record.  Nearest source index (u * w) / We by one division where a lane enters the crop,
+//     then by remainder stepping.  Every byte is written, nothing is accumulated.
 // All of it is HBM-shaped integer / index work: each of the four channels is read once (the centre map a second time only around
 // pixels above the threshold), and what goes back to the host is one small integer per pixel instead of 16 bytes.
 #include <hip/hip_runtime.h>
@@ -440,6 +445,84 @@ __global__ __launch_bounds__(64) void seg_sem_final_kernel(const int* __restrict
   }
 }
 
+// Output pixel (y, x) of slot s with crop k = pos_of_slot[s] >= 0 and record (ox, oy, He, We) = geom[k]:
+//   v = y - oy, u = x - ox;  0 <= v < He and 0 <= u < We  ->  masks[k][(v * h) / He][(u * w) / We], else 0.
+// h, w <= 32767 (checked on the host) and extents outside [1, 65535] make the crop empty, so both products fit 32 bits; coordinate
+// differences are taken in unsigned arithmetic after the sign test, so no origin can overflow them.  `total` = B P H W < 2^32.
+__global__ __launch_bounds__(256) void seg_place_kernel(const uint8_t* __restrict__ masks, const int* __restrict__ pos_of_slot, const int* __restrict__ geom, int N, int h,
+                                                        int w, int slots, int H, int W, uint32_t total, uint8_t* __restrict__ out) {
+  const uint32_t n_chunks = total / 16u + (total % 16u != 0u);
+  const uint32_t step = gridDim.x * 256u;
+  for (uint32_t c = blockIdx.x * 256u + threadIdx.x; c < n_chunks; c += step) {
+    const uint32_t i0 = c * 16u;
+    const uint32_t row0 = i0 / (uint32_t)W;
+    int x = (int)(i0 - row0 * (uint32_t)W);
+    int slot = (int)(row0 / (uint32_t)H);
+    int y = (int)(row0 - (uint32_t)slot * (uint32_t)H);
+    const uint8_t* src = nullptr;  // the crop row that output row (slot, y) reads, or null: the row is zero
+    int ox = 0;
+    uint32_t We = 0u;
+    auto load_row = [&]() {
+      src = nullptr;
+      if (slot >= slots) return;  // (stepping off the end of the last row)
+      const int k = pos_of_slot[slot];
+      if (k < 0 || k >= N) return;
+      const int gx = geom[4 * k], gy = geom[4 * k + 1], He = geom[4 * k + 2], we = geom[4 * k + 3];
+      if (He < 1 || He > 65535 || we < 1 || we > 65535 || gy > y) return;
+      const uint32_t v = (uint32_t)y - (uint32_t)gy;
+      if (v >= (uint32_t)He) return;
+      src = masks + ((size_t)k * h + (v * (uint32_t)h) / (uint32_t)He) * w;
+      ox = gx;
+      We = (uint32_t)we;
+    };
+    load_row();
+    const int n = (int)min(16u, total - i0);
+    uint32_t word[4] = {0u, 0u, 0u, 0u};
+    uint32_t q = 0u, r = 0u;  // source column of the current pixel and the remainder (u * w) % We
+    bool stepping = false;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      if (i < n) {
+        uint32_t px = 0u;
+        if (src && x >= ox) {
+          const uint32_t u = (uint32_t)x - (uint32_t)ox;
+          if (u < We) {
+            if (!stepping) {
+              const uint32_t t = u * (uint32_t)w;
+              q = u ? t / We : 0u;
+              r = t - q * We;
+              stepping = true;
+            }
+            px = src[q];
+            r += (uint32_t)w;
+            while (r >= We) {
+              r -= We;
+              ++q;
+            }
+          }
+        }
+        word[i >> 2] |= px << (8 * (i & 3));
+        if (++x == W) {
+          x = 0;
+          if (++y == H) {
+            y = 0;
+            ++slot;
+          }
+          load_row();
+          stepping = false;
+        }
+      }
+    }
+    if (n == 16) {
+      reinterpret_cast<uint4*>(out)[c] = make_uint4(word[0], word[1], word[2], word[3]);
+    } else {  // the last, short chunk of the array
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (i < n) out[(size_t)i0 + i] = (uint8_t)(word[i >> 2] >> (8 * (i & 3)));
+    }
+  }
+}
+
 static inline int seg_pix_blocks(int hw) { return (hw + 256 * SG_PIX - 1) / (256 * SG_PIX); }
 
 }  // namespace ph
@@ -551,6 +634,23 @@ extern "C" int ph_seg_semantic(const float* fg_dev, int32_t B, int32_t h, int32_
   int* part_cnt = reinterpret_cast<int*>(part_sum + (size_t)B * nb);
   hipLaunchKernelGGL(seg_sem_kernel, dim3(nb, B), dim3(256), 0, s, fg_dev, h * w, fg_threshold, mask_dev, part_cnt, part_sum);
   hipLaunchKernelGGL(seg_sem_final_kernel, dim3(B), dim3(64), 0, s, part_cnt, part_sum, nb, count_dev, sum_dev);
+  PH_HIP_CHECK(hipGetLastError());
+  return PH_OK;
+}
+
+extern "C" int ph_seg_place_crops(const uint8_t* masks_dev, int32_t N, int32_t h, int32_t w, const int32_t* pos_of_slot_dev, const int32_t* geom_dev, int32_t B, int32_t P,
+                                  int32_t H, int32_t W, uint8_t* out_dev, void* stream) {
+  PH_REQUIRE(pos_of_slot_dev && out_dev && (N == 0 || (masks_dev && geom_dev)), "ph_seg_place_crops: null pointer");
+  PH_REQUIRE(P >= 1 && P <= 64, "ph_seg_place_crops: P=%d must lie in [1, 64] (the mask evaluator's limit)", P);
+  PH_REQUIRE(B > 0 && H > 0 && W > 0 && N >= 0, "ph_seg_place_crops: bad shape B=%d H=%d W=%d N=%d", B, H, W, N);
+  PH_REQUIRE(N == 0 || (h >= 1 && h <= 32767 && w >= 1 && w <= 32767), "ph_seg_place_crops: crop masks of %d x %d; each side must lie in [1, 32767]", h, w);
+  const int64_t total = (int64_t)B * P * H * W;
+  PH_REQUIRE(total <= 0xffffffffLL, "ph_seg_place_crops: output of %lld bytes; at most 2^32 - 1 per call", (long long)total);
+  PH_REQUIRE(((uintptr_t)out_dev & 15) == 0, "ph_seg_place_crops: the output must be 16-byte aligned");
+  const int64_t chunks = (total + 15) / 16;
+  const int blocks = (int)std::min<int64_t>((chunks + 255) / 256, 1 << 20);
+  hipLaunchKernelGGL(seg_place_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), masks_dev, pos_of_slot_dev, geom_dev, N, h, w, B * P, H, W,
+                     (uint32_t)total, out_dev);
   PH_HIP_CHECK(hipGetLastError());
   return PH_OK;
 }

@@ -339,13 +339,41 @@ def _pair_tables_device(pred, gt, n_pred: np.ndarray, n_gt: np.ndarray, s: int, 
     return inter, pa, ga
 
 
+def _from_outputs(pred, gt, n_pred, pred_stride: int):
+    """``(pred, n_pred, pred_stride, scores)`` of a prediction batch given as an inference ``Outputs``; anything else passes through with ``scores=None``.
+
+    With ``pred_mask_stack`` / ``pred_mask_counts`` (top-down segmentation, ``place_masks=True``) the device stack is the prediction as it is: stack form,
+    stride 1, no host round trip.  Otherwise the host ``pred_masks`` entries -- any ``offset``, any ``scale`` -- are decoded into a stack at the ground
+    truth's frame size by ``place_crop_masks``' host implementation (``ops.segmentation.stack_pred_masks``) and follow ``gt`` onto its device."""
+    if not hasattr(pred, "pred_masks"):
+        return pred, n_pred, pred_stride, None
+    if pred.pred_masks is None:
+        raise ValueError("these Outputs carry no pred_masks")
+    scores = [np.array([d["score"] for d in frame], dtype=float) for frame in pred.pred_masks]
+    if getattr(pred, "pred_mask_stack", None) is not None:
+        stack = pred.pred_mask_stack
+        if _on_device(gt) and not _on_device(stack):
+            stack = stack.to(gt.device)
+        return stack, pred.pred_mask_counts, 1, scores
+    from sleap_nn_amd.inference.ops.segmentation import stack_pred_masks
+
+    stack, counts = stack_pred_masks(pred.pred_masks, gt.shape[-2:])
+    if hasattr(gt, "device"):
+        import torch
+
+        stack = torch.from_numpy(stack).to(gt.device)
+    return stack, counts, 1, scores
+
+
 def mask_pair_tables(pred, gt, n_pred=None, n_gt=None, pred_stride: int = 1):
     """Integer tables of a batch: ``inter (B, P, G)``, ``pred_area (B, P)``, ``gt_area (B, G)``, int32, slots beyond a frame's counts 0.
 
     ``gt``: ``(B, G, H, W)``, nonzero = foreground.  ``pred``: a stack ``(B, P, ph, pw)`` or a label map ``(B, ph, pw)`` of signed
     integers (``-1`` = background, labels in ``[0, n_pred)``), read at cell ``(y // pred_stride, x // pred_stride)`` on the top-left
     aligned canvas ``max(H, ph * s) x max(W, pw * s)`` (``_align_pair``).  Tensors on the GPU with at most 64 masks per side come back
-    as device tensors from ``ph_mask_pair_stats`` without a host synchronisation; everything else is NumPy on the host."""
+    as device tensors from ``ph_mask_pair_stats`` without a host synchronisation; everything else is NumPy on the host.  ``pred`` may also be an
+    inference ``Outputs`` with masks (``_from_outputs``)."""
+    pred, n_pred, pred_stride, _ = _from_outputs(pred, gt, n_pred, pred_stride)
     s = int(pred_stride)
     if s < 1:
         raise ValueError(f"pred_stride must be >= 1, got {pred_stride}")
@@ -374,6 +402,7 @@ def _iou_from_tables(inter: np.ndarray, pa: np.ndarray, ga: np.ndarray) -> np.nd
 def mask_pair_stats(pred, gt, n_pred=None, n_gt=None, pred_stride: int = 1):
     """Per frame ``(iou (n_pred, n_gt) float64, inter int64, pred_area int64 (n_pred,), gt_area int64 (n_gt,))`` of ``mask_pair_tables``'
     batch: ``iou = inter / (pred_area + gt_area - inter)``, 1.0 where the union is empty (``_mask_pair_stats`` + the areas)."""
+    pred, n_pred, pred_stride, _ = _from_outputs(pred, gt, n_pred, pred_stride)
     is_stack, B, P, _, _ = _pred_layout(pred, n_pred)
     n_pred, n_gt = _counts(n_pred, B, P), _counts(n_gt, B, gt.shape[1])
     inter, pa, ga = (_to_numpy(t) for t in mask_pair_tables(pred, gt, n_pred, n_gt, pred_stride))
@@ -517,7 +546,11 @@ class MaskEvaluator:
         return len(self._frames)
 
     def add_batch(self, pred, pred_scores, gt, n_pred=None, n_gt=None, pred_stride: int = 1) -> None:
-        """``pred`` / ``gt`` / counts / stride as in ``mask_pair_tables``; ``pred_scores (B, P)`` (or one array per frame), ``None`` = 1.0 each."""
+        """``pred`` / ``gt`` / counts / stride as in ``mask_pair_tables``; ``pred_scores (B, P)`` (or one array per frame), ``None`` = 1.0 each (for an
+        ``Outputs``: its entries' scores)."""
+        pred, n_pred, pred_stride, own_scores = _from_outputs(pred, gt, n_pred, pred_stride)
+        if pred_scores is None:
+            pred_scores = own_scores
         is_stack, B, P, _, _ = _pred_layout(pred, n_pred)
         n_pred, n_gt = _counts(n_pred, B, P), _counts(n_gt, B, gt.shape[1])
         s = int(pred_stride)

@@ -9,3 +9,4 @@ from sleap_nn_amd.inference.layers.single_instance import SingleInstanceLayer  #
 from sleap_nn_amd.inference.layers.tiled import TiledLayer  # noqa: F401
 from sleap_nn_amd.inference.layers.topdown import TopDownLayer  # noqa: F401
 from sleap_nn_amd.inference.layers.topdown_multiclass import CenteredInstanceMultiClassLayer, TopDownMultiClassLayer  # noqa: F401
+from sleap_nn_amd.inference.layers.topdown_segmentation import CenteredInstanceMaskLayer, TopDownSegmentationLayer  # noqa: F401

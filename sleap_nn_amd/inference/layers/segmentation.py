@@ -8,8 +8,8 @@ small integer per pixel and a record of centres / scores / counts) and builds ``
 tensors the same contract runs on the host.
 
 Not built (each raises ``NotImplementedError`` naming the knob): ``mask_cleanup`` / ``mask_cleanup_radius`` (SciPy / OpenCV
-morphology), ``merge_fragments`` (the RAG fragment merge), ``mask_output`` other than ``"mask"`` (polygon packaging), the tiled
-segmentation wrappers and ``centered_instance_segmentation``.
+morphology), ``merge_fragments`` (the RAG fragment merge), ``mask_output`` other than ``"mask"`` (polygon packaging) and the tiled
+segmentation wrappers.  Top-down segmentation (``centered_instance_segmentation``) is ``layers/topdown_segmentation.py``.
 """
 from __future__ import annotations
 

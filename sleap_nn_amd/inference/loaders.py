@@ -17,7 +17,7 @@ import torch
 import yaml
 
 MODEL_TYPES = ("single_instance", "centroid", "centered_instance", "bottomup", "multi_class_bottomup", "multi_class_topdown", "bottomup_segmentation",
-               "semantic_segmentation")
+               "semantic_segmentation", "centered_instance_segmentation")
 
 
 class _Opaque:
@@ -70,7 +70,12 @@ class LoadedAssets:
     def build_model(self):
         from sleap_nn_amd.architectures.model import Model
 
-        m = Model(self.backbone_type, self.backbone_config, self.head_config, self.model_type)
+        if self.model_type == "centered_instance_segmentation":
+            # a lone SegmentationHead with the sigmoid in its epilogue: the semantic type's program, built from the same `segmentation` leaf (whose
+            # anchor_part / crop_size are data-pipeline entries, not head arguments); `model_type` here keeps the real name
+            m = Model(self.backbone_type, self.backbone_config, {"segmentation": self.head_config["segmentation"]}, "semantic_segmentation")
+        else:
+            m = Model(self.backbone_type, self.backbone_config, self.head_config, self.model_type)
         m.load_state_dict(self.state_dict, strict=True)
         return m
 

@@ -17,6 +17,9 @@ The contract (what the reference computes, frame by frame):
 * the adaptive distance gate re-estimates ``r^2 = (alpha sqrt(count / pi) s)^2`` for ``distance_gate_iters`` passes from the currently kept pixels and
   keeps ``d <= r^2[label]``, recomputed over all assigned pixels each pass;
 * a frame without foreground or without centres has no instances; instances left without pixels are dropped, the others keep their order.
+
+Also here: the semantic threshold / count / sum (``semantic_masks``) and the geometry and placement of top-down crop masks
+(``crop_mask_geometry``, ``place_crop_masks``: ``ph_seg_place_crops`` on the device, NumPy on the host, one contract).
 """
 from __future__ import annotations
 
@@ -25,7 +28,7 @@ import math
 import threading
 from collections import OrderedDict
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -259,6 +262,47 @@ def group_instances_from_offsets(foreground: torch.Tensor, center_heatmap: torch
     return _group_host(fg, hm, off, fg_threshold, peak_threshold, output_stride, max_instances, center_nms_kernel, distance_gate_alpha, distance_gate_iters)
 
 
+def semantic_enqueue(foreground: torch.Tensor, fg_threshold: float = 0.5, host_masks: bool = True) -> dict:
+    """``ph_seg_semantic`` on the current stream and the asynchronous copies of its record (sums, counts) -- and, with ``host_masks``, of the 0 / 1
+    maps -- into pinned memory; no host synchronisation.  ``mask_dev`` (B, h, w) uint8 stays on the device."""
+    from sleap_nn_amd import _lib as L
+
+    lib = L.lib()
+    fg = L.require_cuda(foreground, "foreground").detach().to(torch.float32).contiguous()
+    B, _c, h, w = fg.shape
+    dev = fg.device
+    with torch.cuda.device(dev):
+        mask = torch.empty((B, h, w), dtype=torch.uint8, device=dev)
+        rec = torch.empty(2 * B, dtype=torch.float64, device=dev)  # [sums B | counts B int32 in the first half of the second B doubles]
+        cnt = rec[B:].view(torch.int32)[:B]
+        need = int(lib.ph_seg_semantic_scratch_bytes(B, h, w))
+        scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        L.check(lib.ph_seg_semantic(p(fg), B, h, w, float(fg_threshold), p(mask), p(cnt), p(rec), p(scratch), need, L.current_stream_ptr()))
+        mask_h = _pinned_take(mask.shape, mask.dtype) if host_masks else None
+        rec_h = _pinned_take(rec.shape, rec.dtype)
+        if host_masks:
+            mask_h.copy_(mask, non_blocking=True)
+        rec_h.copy_(rec, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+    return {"mask_dev": mask, "mask": mask_h, "rec": rec_h, "event": ev, "B": B, "dev": (fg, rec, scratch)}
+
+
+def semantic_finish(hd: dict):
+    """Wait for the record of ``semantic_enqueue`` (the one host read): (masks (B, h, w) bool ndarray or None, pixel counts (B,), scores (B,))."""
+    hd["event"].synchronize()
+    B, rec_h, mask_h = hd["B"], hd["rec"], hd["mask"]
+    sums = rec_h[:B].numpy().copy()
+    counts = rec_h[B:].view(torch.int32)[:B].numpy().astype(np.int64)
+    masks = None
+    if mask_h is not None:
+        masks = mask_h.numpy().astype(bool)
+        _pinned_give(mask_h)
+    _pinned_give(rec_h)
+    return masks, counts, np.where(counts > 0, sums / np.maximum(counts, 1), 0.0)
+
+
 def semantic_masks(foreground: torch.Tensor, fg_threshold: float = 0.5):
     """``foreground`` (B, 1, h, w) -> (masks (B, h, w) bool ndarray, pixel counts (B,), scores (B,) = mean probability over the mask, 0 where it is empty).
     GPU tensors: ``ph_seg_semantic`` (count and sum on the device, one byte per pixel to the host); CPU tensors: torch."""
@@ -269,27 +313,134 @@ def semantic_masks(foreground: torch.Tensor, fg_threshold: float = 0.5):
         cnt = m.flatten(1).sum(1).numpy()
         scores = np.array([float(fg[b, 0][m[b]].mean()) if cnt[b] else 0.0 for b in range(B)], dtype=np.float64)
         return m.numpy(), cnt.astype(np.int64), scores
+    return semantic_finish(semantic_enqueue(fg, fg_threshold))
+
+
+# ---- top-down crop masks: geometry and placement into frame space ---------------------------------------------------------------
+
+class CropGeometry(NamedTuple):
+    """Per crop: ``offset`` (N, 2) float64 (ox, oy) and ``scale`` (N, 2) float64 (sx, sy) as the ``pred_masks`` entries carry them
+    (image = mask / scale + offset), ``origin`` (N, 2) int32 = round(offset) and ``extent`` (N, 2) int32 = (He, We), the decoded size."""
+
+    offset: np.ndarray
+    scale: np.ndarray
+    origin: np.ndarray
+    extent: np.ndarray
+
+
+def mask_extent(mask_hw, scale) -> tuple:
+    """``(He, We) = (round(h / sy), round(w / sx))``: the image extent a mask of ``mask_hw`` decodes to at ``scale = (sx, sy)``."""
+    return int(round(mask_hw[0] / scale[1])), int(round(mask_hw[1] / scale[0]))
+
+
+def crop_mask_geometry(topleft_sized, eff, input_scale: float, stride, crop_hw, mask_hw) -> CropGeometry:
+    """Offset / scale of top-down crop masks in host arithmetic (layers/topdown_segmentation.py:232-271) and what their decoding needs.
+
+    ``topleft_sized`` (N, 2) float32: the crop boxes' top-left corners (x, y) in sized space (``make_centered_bboxes``); the crop was cut at
+    ``trunc(top_left + half) - half`` with ``half = (crop_w // 2, crop_h // 2)``, added in float32 like the gather.  ``eff`` (N,): the
+    sizematcher scale of each crop's frame.  ``offset`` = that integer corner / eff, ``scale`` = eff * input_scale / stride (both axes)."""
+    tl = np.asarray(topleft_sized, dtype=np.float32).reshape(-1, 2)
+    eff = np.asarray(eff, dtype=np.float32).reshape(-1)
+    n = tl.shape[0]
+    ch, cw = int(crop_hw[0]), int(crop_hw[1])
+    half = np.array([cw // 2, ch // 2], dtype=np.float32)
+    corner = np.trunc(tl + half).astype(np.int64) - half.astype(np.int64)
+    stride = float(stride)
+    offset, scale = np.zeros((n, 2), np.float64), np.zeros((n, 2), np.float64)
+    origin, extent = np.zeros((n, 2), np.int32), np.zeros((n, 2), np.int32)
+    for k in range(n):
+        e = float(eff[k])
+        offset[k] = (float(corner[k, 0]) / e, float(corner[k, 1]) / e)
+        scale[k] = ((e * float(input_scale)) / stride, (e * float(input_scale)) / stride)
+        origin[k] = (int(round(offset[k, 0])), int(round(offset[k, 1])))
+        extent[k] = mask_extent(mask_hw, scale[k])
+    return CropGeometry(offset, scale, origin, extent)
+
+
+def _place_host(masks: np.ndarray, pos: np.ndarray, origins: np.ndarray, extents: np.ndarray, H: int, W: int, P: int) -> np.ndarray:
+    B = pos.shape[0] // P
+    out = np.zeros((B, P, H, W), dtype=np.uint8)
+    n, h, w = masks.shape
+    for s in np.nonzero((pos >= 0) & (pos < n))[0]:
+        k = int(pos[s])
+        ox, oy = int(origins[k, 0]), int(origins[k, 1])
+        He, We = int(extents[k, 0]), int(extents[k, 1])
+        if not (1 <= He <= 65535 and 1 <= We <= 65535):
+            continue
+        y0, y1, x0, x1 = max(0, oy), min(H, oy + He), max(0, ox), min(W, ox + We)
+        if y0 >= y1 or x0 >= x1:
+            continue
+        rows = ((np.arange(y0, y1, dtype=np.int64) - oy) * h) // He
+        cols = ((np.arange(x0, x1, dtype=np.int64) - ox) * w) // We
+        out[s // P, s % P, y0:y1, x0:x1] = masks[k][rows[:, None], cols[None, :]]
+    return out
+
+
+def place_crop_masks(masks, pos_of_slot, origins, extents, frame_hw, P: int):
+    """Crop masks into frame space: ``uint8 (B, P, H, W)`` with ``B = len(pos_of_slot) // P`` -- the mask-stack form of ``evaluation.mask_pair_tables`` at stride 1.
+
+    ``masks`` uint8 / bool (N, h, w) (or (N, 1, h, w)); ``pos_of_slot`` int32 (B * P,): the crop of each slot or -1; ``origins`` (N, 2) = (ox, oy) and
+    ``extents`` (N, 2) = (He, We) integers (``crop_mask_geometry``).  Pixel (y, x) of a slot with crop k: ``v = y - oy, u = x - ox``; inside
+    ``0 <= v < He`` and ``0 <= u < We`` it is ``masks[k, (v * h) // He, (u * w) // We]``, else 0 -- the nearest resample to the extent, the rounded
+    origin, the top-left pad with negative rows / columns dropped and the clip to the frame of ``decode_mask_to_image_res``.
+    GPU tensors: ``ph_seg_place_crops``, one launch on the current stream, no host synchronisation, the result stays on the device (``1 <= P <= 64``,
+    fewer than 2^32 output bytes).  CPU tensors and arrays: NumPy, returned as an array (a tensor when ``masks`` is one)."""
+    H, W = int(frame_hw[0]), int(frame_hw[1])
+    P = int(P)
+    on_gpu = torch.is_tensor(masks) and masks.is_cuda
+    if P < 1 or (H < 1 or W < 1):
+        raise ValueError(f"place_crop_masks: P={P} and the frame {H} x {W} must be positive")
+    geom = np.concatenate([_host_int(origins).reshape(-1, 2), _host_int(extents).reshape(-1, 2)], axis=1) if not (torch.is_tensor(origins) and origins.is_cuda) else None
+    if not on_gpu:
+        m = masks.detach().numpy() if torch.is_tensor(masks) else np.asarray(masks)
+        m = m.reshape((m.shape[0],) + tuple(m.shape[-2:])).astype(np.uint8)
+        pos = _host_int(pos_of_slot).reshape(-1)
+        if pos.shape[0] % P:
+            raise ValueError(f"place_crop_masks: {pos.shape[0]} slots are no multiple of P={P}")
+        out = _place_host(m, pos, geom[:, :2], geom[:, 2:], H, W, P)
+        return torch.from_numpy(out) if torch.is_tensor(masks) else out
     from sleap_nn_amd import _lib as L
 
-    lib = L.lib()
-    dev = fg.device
+    dev = masks.device
+    m = (masks.view(torch.uint8) if masks.dtype == torch.bool else masks.to(torch.uint8)).contiguous()
+    n = int(m.shape[0])
+    h, w = (int(m.shape[-2]), int(m.shape[-1])) if n else (1, 1)
     with torch.cuda.device(dev):
-        mask = torch.empty((B, h, w), dtype=torch.uint8, device=dev)
-        rec = torch.empty(2 * B, dtype=torch.float64, device=dev)  # [sums B | counts B int32 in the first half of the second B doubles]
-        cnt = rec[B:].view(torch.int32)[:B]
-        need = int(lib.ph_seg_semantic_scratch_bytes(B, h, w))
-        scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        pos = torch.as_tensor(pos_of_slot).to(dev, torch.int32, non_blocking=True).contiguous().view(-1)
+        if pos.numel() % P:
+            raise ValueError(f"place_crop_masks: {pos.numel()} slots are no multiple of P={P}")
+        if geom is None:
+            g = torch.cat([origins.view(-1, 2), torch.as_tensor(extents).to(dev).view(-1, 2)], dim=1).to(torch.int32).contiguous()
+        else:
+            g = torch.from_numpy(np.ascontiguousarray(geom, dtype=np.int32)).to(dev, non_blocking=True)
+        if int(g.shape[0]) != n:
+            raise ValueError(f"place_crop_masks: {n} masks, {int(g.shape[0])} geometry records")
+        B = pos.numel() // P
+        out = torch.empty((B, P, H, W), dtype=torch.uint8, device=dev)
         p = lambda t: C.c_void_p(t.data_ptr())
-        L.check(lib.ph_seg_semantic(p(fg), B, h, w, float(fg_threshold), p(mask), p(cnt), p(rec), p(scratch), need, L.current_stream_ptr()))
-        mask_h, rec_h = _pinned_take(mask.shape, mask.dtype), _pinned_take(rec.shape, rec.dtype)
-        mask_h.copy_(mask, non_blocking=True)
-        rec_h.copy_(rec, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
-    ev.synchronize()
-    sums = rec_h[:B].numpy().copy()
-    counts = rec_h[B:].view(torch.int32)[:B].numpy().astype(np.int64)
-    masks = mask_h.numpy().astype(bool)
-    _pinned_give(mask_h)
-    _pinned_give(rec_h)
-    return masks, counts, np.where(counts > 0, sums / np.maximum(counts, 1), 0.0)
+        L.check(L.lib().ph_seg_place_crops(p(m) if n else None, n, h, w, p(pos), p(g) if n else None, B, P, H, W, p(out), L.current_stream_ptr()))
+    return out
+
+
+def _host_int(x) -> np.ndarray:
+    return (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(np.int64)
+
+
+def stack_pred_masks(pred_masks, frame_hw, P: Optional[int] = None):
+    """Host ``pred_masks`` entries (any scale / offset) as a frame-space stack: ``(uint8 (B, P, H, W) ndarray, counts int32 (B,))``; slot j of a frame
+    is its j-th entry, ``P`` defaults to the largest count (at least 1).  Every entry is decoded by ``place_crop_masks`` on its own extent."""
+    B = len(pred_masks)
+    counts = np.array([len(f) for f in pred_masks], dtype=np.int32)
+    P = max(1, int(counts.max(initial=0))) if P is None else int(P)
+    if int(counts.max(initial=0)) > P:
+        raise ValueError(f"stack_pred_masks: a frame has {int(counts.max())} masks, P={P}")
+    H, W = int(frame_hw[0]), int(frame_hw[1])
+    out = np.zeros((B, P, H, W), dtype=np.uint8)
+    for b, frame in enumerate(pred_masks):
+        for j, d in enumerate(frame):
+            m = np.asarray(d["mask"])
+            scale, offset = d.get("scale", (1.0, 1.0)), d.get("offset", (0.0, 0.0))
+            origin = np.array([[int(round(offset[0])), int(round(offset[1]))]])
+            extent = np.array([mask_extent(m.shape, scale)])
+            out[b, j] = _place_host(m[None].astype(np.uint8), np.zeros(1, np.int64), origin, extent, H, W, 1)[0, 0]
+    return out, counts

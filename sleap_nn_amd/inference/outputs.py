@@ -40,6 +40,10 @@ class Outputs:
     # segmentation layers: per frame a list of {"mask": bool ndarray, "score", "scale": (sx, sy), "offset": (ox, oy)} (image = mask / scale + offset).  Host
     # objects, not tensors: to() / cpu() / detach() / slim() / numpy() hand the list on as it is
     pred_masks: Optional[List[List[Dict[str, Any]]]] = None
+    # top-down segmentation with place_masks=True: the frame's masks placed at image resolution on the device, uint8 (B, P, H, W), slot j = entry j of
+    # pred_masks, and the entries per frame, int32 (B,) -- the mask-stack form sleap_nn_amd.evaluation reads without a host round trip
+    pred_mask_stack: Optional[torch.Tensor] = None
+    pred_mask_counts: Optional[torch.Tensor] = None
     preprocess_info: Optional[PreprocInfo] = None
     frame_indices: Optional[torch.Tensor] = None
     video_indices: Optional[torch.Tensor] = None

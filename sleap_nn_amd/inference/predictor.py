@@ -109,6 +109,23 @@ def _select_layer(assets: Sequence[LoadedAssets], device: str, post: Postprocess
     unknown = sorted(set(seg_kw) - set(_SEG_KW))
     if unknown:
         raise TypeError(f"unknown segmentation keyword(s) {unknown}; known: {list(_SEG_KW)}")
+    if "centered_instance_segmentation" in by_type:  # (before the plain centroid branch, predictor.py:633-637: a centroid + seg pair is not a centroid-only run)
+        from sleap_nn_amd.inference.layers.topdown_segmentation import CenteredInstanceMaskLayer, TopDownSegmentationLayer
+
+        i = by_type["centered_instance_segmentation"]
+        if "centroid" not in by_type:
+            raise NotImplementedError(f"run directory {i.model_dir} (centered_instance_segmentation) without a centroid run directory is the reference's "
+                                      "ground-truth-centroid path, which is not built: pass the centroid model's directory as well")
+        c = by_type["centroid"]
+        seg = i.head_config["segmentation"]
+        crop = int(seg.get("crop_size") or i.preprocessing.get("crop_size") or 0)
+        if crop <= 0:
+            raise ValueError("centered-instance segmentation run directory has no crop_size (head_configs.centered_instance_segmentation.segmentation or preprocessing)")
+        cl = CentroidLayer(backend(c), c.head_config["confmaps"]["output_stride"], max_instances=max_instances, max_stride=c.backbone_config["max_stride"],
+                           preprocess_config=pre(c), postprocess_config=post)
+        il = CenteredInstanceMaskLayer(backend(i), seg["output_stride"], max_stride=i.backbone_config["max_stride"], fg_threshold=seg_kw.get("fg_threshold", 0.5),
+                                       preprocess_config=PreprocessConfig(scale=float(i.preprocessing.get("scale") or 1.0)), postprocess_config=post)
+        return TopDownSegmentationLayer(cl, il, (crop, crop), mask_output=seg_kw.get("mask_output", "mask"))
     if "bottomup_segmentation" in by_type:  # the three heads share one stride: head_configs.bottomup_segmentation.segmentation.output_stride (loaders.py:455-456)
         a = by_type["bottomup_segmentation"]
         return SegmentationLayer(backend(a), a.head_config["segmentation"]["output_stride"], max_stride=a.backbone_config["max_stride"], max_instances=max_instances,
@@ -185,7 +202,8 @@ class Predictor:
         """``fg_threshold`` / ``min_mask_area`` / ``max_instances`` / ``center_nms_kernel`` / ``distance_gate_alpha`` / ``full_res_masks``: knobs of the segmentation
         layers (``bottomup_segmentation`` / ``semantic_segmentation`` run directories; defaults as the reference; ``mask_cleanup``, ``mask_cleanup_radius``,
         ``merge_fragments`` and ``mask_output`` are accepted so that a value the layer does not build raises there).  These layers run the plain per-batch path of
-        ``predict``: the pipelined multi-lane paths are not built for them (their post-process ends in a host read and builds host masks).
+        ``predict``: the pipelined multi-lane paths are not built for them (their post-process ends in a host read and builds host masks).  A ``centroid`` +
+        ``centered_instance_segmentation`` pair builds ``TopDownSegmentationLayer`` (``fg_threshold`` / ``mask_output`` forwarded), batch by batch as well.
         ``tile_size`` / ``overlap``: for run directories trained with tiling, checked against the trained geometry (a different value raises ``ValueError``:
         the geometry is fixed at training time); ignored otherwise, as in the reference.
         ``streams``: bottom-up and top-down run directories of small networks (<= 16 M parameters) are loaded ``streams`` times; the pipelined ``predict`` keeps that many batches in flight
@@ -202,7 +220,7 @@ class Predictor:
         replicas = []
         small = lambda l: l.backend.model.num_parameters() <= _REPLICA_MAX_PARAMS
         if streams > 1 and ((isinstance(layer, (BottomUpLayer, SingleInstanceLayer)) and small(layer)) or
-                            (isinstance(layer, TopDownLayer) and small(layer.centroid_layer) and small(layer.centered_instance_layer))):
+                            (isinstance(layer, TopDownLayer) and getattr(layer, "_PIPELINED", True) and small(layer.centroid_layer) and small(layer.centered_instance_layer))):
             replicas = [_select_layer(assets, device, post, max_instances, **paf_kw) for _ in range(streams - 1)]
         return cls(layer, batch_size, replicas=replicas)
 
@@ -223,7 +241,7 @@ class Predictor:
             frames = torch.from_numpy(frames)
         if pipelined and isinstance(self.layer, BottomUpLayer):
             return self._predict_streaming_pipelined(frames)
-        if pipelined and hasattr(self.layer, "_enqueue_stage1"):
+        if pipelined and hasattr(self.layer, "_enqueue_stage1") and getattr(self.layer, "_PIPELINED", True):
             return self._predict_two_stage_pipelined(frames)
         if pipelined and hasattr(self.layer, "_enqueue_postprocess"):
             return self._predict_host_stage_pipelined(frames)
