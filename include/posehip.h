@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 114
+#define PH_VERSION 115
 
 /* error codes */
 #define PH_OK 0
@@ -619,6 +619,23 @@ int ph_seg_assign(const float* fg_dev, const float* offsets_dev, int32_t B, int3
  * (zeroed by ph_seg_center_peaks).  labels_out_dev (its own buffer) = the labels kept by the last pass, -1 elsewhere. */
 int ph_seg_gate(const void* labels_in_dev, const float* dist_dev, int32_t B, int32_t h, int32_t w, float alpha, int32_t output_stride, int32_t iters,
                 const int32_t* counts_dev, int32_t max_centers, int32_t label_bytes, int32_t* pix_counts_dev, void* labels_out_dev, void* stream);
+
+/* Mask cleanup of the label map ph_seg_assign / ph_seg_gate wrote (_clean_instance_mask at radius 0, segmentation.py:240-273; DESIGN.md
+ * section 4.2d): per (frame, label) keep the largest 4-connected component -- raster-first on equal areas -- and fill its interior
+ * holes (binary_fill_holes: complement cells that cannot reach the outside of the image by 4-connected steps through the complement;
+ * pixels of other instances count as complement, so masks may overlap afterwards).  labels_out_dev (its own buffer, the input's
+ * type): pixels of dropped components become -1.  record_dev int32 [areas (B, max_centers) | hole counts (B, max_centers) | holes
+ * per frame B | pool words needed per frame B]: area = kept component + its holes, 0 for a label without pixels.  holes_dev int32
+ * (B, hole_cap, 2) = (pixel index y * w + x, label), instance-major, raster order inside an instance, offsets from an exclusive scan
+ * of the hole counts; the per-frame totals are TRUE counts: entries beyond hole_cap are not written and the caller comes back with
+ * room.  Boxes (bounding box + a one-pixel ring) whose two bitmaps exceed the LDS ones are flooded in a pool of pool_words 64-bit
+ * words per frame inside the scratch; a frame that needs more reports its need the same way (instances without room keep their
+ * holes unfilled until then).  h, w <= 32767.  Integer arithmetic only: exact, and identical from run to run.  Eight launches on
+ * `stream`, no host synchronisation; scratch 8-byte aligned, ph_seg_cleanup_scratch_bytes(B, h, w, max_centers, pool_words) bytes. */
+int64_t ph_seg_cleanup_scratch_bytes(int32_t B, int32_t h, int32_t w, int32_t max_centers, int32_t pool_words);
+int ph_seg_cleanup(const void* labels_in_dev, int32_t B, int32_t h, int32_t w, const int32_t* counts_dev, int32_t max_centers, int32_t label_bytes,
+                   void* labels_out_dev, int32_t* record_dev, int32_t* holes_dev, int32_t hole_cap, int32_t pool_words, void* scratch_dev,
+                   int64_t scratch_bytes, void* stream);
 
 /* Semantic variant (layers/segmentation.py:438-503): mask_dev uint8 (B, h, w) = fg > fg_threshold, count_dev int32[B] its
  * pixels, sum_dev double[B] the sum of fg over them (fixed summation order: deterministic; the reference's score is sum / count). */

@@ -7,9 +7,9 @@ device (``inference/ops/segmentation.py``: centre peaks, pixel assignment, dista
 small integer per pixel and a record of centres / scores / counts) and builds ``Outputs.pred_masks`` from the label map; for CPU
 tensors the same contract runs on the host.
 
-Not built (each raises ``NotImplementedError`` naming the knob): ``mask_cleanup`` / ``mask_cleanup_radius`` (SciPy / OpenCV
-morphology), ``merge_fragments`` (the RAG fragment merge), ``mask_output`` other than ``"mask"`` (polygon packaging) and the tiled
-segmentation wrappers.  Top-down segmentation (``centered_instance_segmentation``) is ``layers/topdown_segmentation.py``.
+``mask_cleanup=True`` is ``layers/segmentation_cleanup.py`` (``CleanupSegmentationLayer``; this class keeps refusing the knob).  Not built
+(each raises ``NotImplementedError`` naming the knob): ``mask_cleanup_radius`` (OpenCV morphology), ``merge_fragments`` (the RAG fragment
+merge), ``mask_output`` other than ``"mask"`` (polygon packaging) and the tiled segmentation wrappers.  Top-down segmentation (``centered_instance_segmentation``) is ``layers/topdown_segmentation.py``.
 """
 from __future__ import annotations
 
@@ -130,7 +130,7 @@ class SegmentationLayer(InferenceLayer):
         g = group_instances_from_offsets(raw_out[self._SEG_KEY], raw_out[self._CENTER_KEY], raw_out[self._OFFSET_KEY], fg_threshold=self.fg_threshold,
                                          peak_threshold=pc.peak_threshold, output_stride=self.output_stride, max_instances=max_instances,
                                          center_nms_kernel=self.center_nms_kernel, distance_gate_alpha=self.distance_gate_alpha,
-                                         distance_gate_iters=self.distance_gate_iters)
+                                         distance_gate_iters=self.distance_gate_iters, mask_cleanup=self.mask_cleanup)
         pred_masks: List[List[dict]] = []
         for b in range(g.labels.shape[0]):
             frame = [self._package(inst["mask"], inst["score"], info, b) for inst in g.instances(b, self.output_stride)]

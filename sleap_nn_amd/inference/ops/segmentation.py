@@ -16,7 +16,12 @@ The contract (what the reference computes, frame by frame):
   ``cx = xc s + s/2`` (likewise y);
 * the adaptive distance gate re-estimates ``r^2 = (alpha sqrt(count / pi) s)^2`` for ``distance_gate_iters`` passes from the currently kept pixels and
   keeps ``d <= r^2[label]``, recomputed over all assigned pixels each pass;
-* a frame without foreground or without centres has no instances; instances left without pixels are dropped, the others keep their order.
+* a frame without foreground or without centres has no instances; instances left without pixels are dropped, the others keep their order;
+* ``mask_cleanup=True`` (``_clean_instance_mask`` at radius 0, segmentation.py:240-273), per instance after assignment and gate: of its 4-connected
+  components the one with the most pixels is kept (raster-first on ties), then every complement pixel that cannot reach the outside of the image by
+  4-connected steps through the complement joins the mask (``binary_fill_holes``; other instances' pixels are complement, so masks may overlap).  The label
+  map then holds the kept components and ``Grouping.holes`` the filled pixels; ``ph_seg_cleanup`` (csrc/seg_cleanup_kernels.hip) on the device,
+  ``clean_label_map`` on the host.  Not built: ``mask_cleanup_radius > 0`` (OpenCV's elliptical open / close) and ``merge_fragments``.
 
 Also here: the semantic threshold / count / sum (``semantic_masks``) and the geometry and placement of top-down crop masks
 (``crop_mask_geometry``, ``place_crop_masks``: ``ph_seg_place_crops`` on the device, NumPy on the host, one contract).
@@ -36,17 +41,21 @@ import torch.nn.functional as F
 
 DEFAULT_CAP = 2048  # candidates per frame that the collapse kernel keeps in LDS
 DEFAULT_MAX_CENTERS = 127  # centres per frame that one-byte labels hold
+DEFAULT_HOLE_CAP = 4096  # filled hole pixels per frame that the cleanup's list holds
 
 
 @dataclass
 class Grouping:
     """``labels`` (B, h, w) signed integers, -1 = background, otherwise an index into the frame's centres; per frame ``centers`` (N, 2) int32 (x, y) in map
-    pixels, ``scores`` (N,) float32 (the centre's peak value) and ``counts`` (N,) the pixels each centre kept."""
+    pixels, ``scores`` (N,) float32 (the centre's peak value) and ``counts`` (N,) the pixels each centre kept.  After mask cleanup ``labels`` holds each
+    instance's kept component, ``holes`` per frame the filled pixels as int32 (K, 2) = (pixel index y * w + x, label), instance-major and in raster order
+    inside an instance (they may lie on other instances' pixels), and ``counts`` the cleaned areas (component + holes)."""
 
     labels: np.ndarray
     centers: List[np.ndarray]
     scores: List[np.ndarray]
     counts: List[np.ndarray]
+    holes: Optional[List[np.ndarray]] = None
 
     def instances(self, b: int, output_stride: int) -> List[Dict]:
         """The reference's per-frame list (segmentation.py:213-237): ``{"mask", "center", "score"}`` per non-empty instance, in centre order; ``center`` in input pixels."""
@@ -54,9 +63,13 @@ class Grouping:
         lab = self.labels[b]
         s = np.float32(output_stride)
         half = np.float32(output_stride / 2.0)
+        holes = self.holes[b] if self.holes is not None else None
         for k in np.nonzero(self.counts[b] > 0)[0]:
             cx, cy = self.centers[b][k]
-            out.append({"mask": lab == k, "center": (float(np.float32(cx) * s + half), float(np.float32(cy) * s + half)), "score": float(self.scores[b][k])})
+            mask = lab == k
+            if holes is not None and len(holes):
+                mask.reshape(-1)[holes[holes[:, 1] == k, 0]] = True
+            out.append({"mask": mask, "center": (float(np.float32(cx) * s + half), float(np.float32(cy) * s + half)), "score": float(self.scores[b][k])})
         return out
 
 
@@ -101,10 +114,84 @@ def find_center_peaks_host(hm: torch.Tensor, threshold: float, kernel_size: int 
     return np.stack([xs[reps], ys[reps]], axis=1).astype(np.int32), vals[reps].astype(np.float32)
 
 
-def _group_host(fg, hm, off, fg_threshold, peak_threshold, output_stride, max_instances, center_nms_kernel, distance_gate_alpha, distance_gate_iters) -> Grouping:
+def _components(lab: np.ndarray) -> np.ndarray:
+    """``lab`` (h, w) integers -> int64 (h, w): the raster-first pixel index of each pixel's component, -1 where ``lab < 0``.  Two 4-neighbours are joined
+    when they carry the same non-negative value.  Union-find over the rows' runs of equal values; a root is always the earliest run of its tree."""
+    h, w = lab.shape
+    flat = lab.reshape(-1)
+    start = np.ones(h * w, dtype=bool)
+    start[1:] = flat[1:] != flat[:-1]
+    start[::w] = True
+    run_of = (np.cumsum(start) - 1).reshape(h, w)
+    run_start = np.nonzero(start)[0]
+    parent = list(range(len(run_start)))
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+
+    if h > 1:
+        join = (lab[1:] == lab[:-1]) & (lab[1:] >= 0)
+        pairs = np.unique(np.stack([run_of[1:][join], run_of[:-1][join]], axis=1), axis=0)
+        for a, c in pairs.tolist():
+            a, c = find(a), find(c)
+            if a != c:
+                parent[max(a, c)] = min(a, c)
+    root = np.array([find(i) for i in range(len(parent))], dtype=np.int64)
+    comp = run_start[root][run_of]
+    comp[lab < 0] = -1
+    return comp
+
+
+def clean_label_map(labels: np.ndarray, n_centers: int):
+    """Mask cleanup of one frame's label map (h, w) on the host: ``(cleaned (h, w), holes int32 (K, 2), areas int32 (n_centers,))`` -- the contract of
+    ``ph_seg_cleanup``: per label the largest 4-connected component (raster-first on ties) stays in ``cleaned``, the others become -1; ``holes`` lists the
+    pixels ``binary_fill_holes`` adds to each kept component as (pixel index, label), instance-major, raster order inside an instance; ``areas`` = component +
+    holes.  The flood runs over the component's bounding box grown by a one-pixel ring: everything beyond is connected to the outside."""
+    lab = np.asarray(labels)
+    h, w = lab.shape
+    n = int(n_centers)
+    cleaned = np.full_like(lab, -1)
+    areas = np.zeros(n, dtype=np.int32)
+    holes: List[np.ndarray] = []
+    comp = _components(np.where(lab < n, lab, -1))
+    on = comp >= 0
+    if n and on.any():
+        roots, size = np.unique(comp[on], return_counts=True)  # ascending root = raster order
+        root_lab = lab.reshape(-1)[roots].astype(np.int64)
+        kept = np.full(n, -1, dtype=np.int64)
+        for k in np.unique(root_lab):
+            sel = np.nonzero(root_lab == k)[0]
+            j = sel[np.argmax(size[sel])]  # the first maximum: raster-first on ties
+            kept[k], areas[k] = roots[j], size[j]
+        keep = on & (comp == kept[np.where(on, lab, 0)])
+        cleaned[keep] = lab[keep]
+        ys, xs = np.nonzero(keep)
+        kl = lab[ys, xs].astype(np.int64)
+        y0, x0 = np.full(n, h), np.full(n, w)
+        y1, x1 = np.full(n, -1), np.full(n, -1)
+        np.minimum.at(y0, kl, ys), np.minimum.at(x0, kl, xs), np.maximum.at(y1, kl, ys), np.maximum.at(x1, kl, xs)
+        for k in np.nonzero(kept >= 0)[0]:
+            if y1[k] - y0[k] < 2 or x1[k] - x0[k] < 2:
+                continue
+            free = np.ones((y1[k] - y0[k] + 3, x1[k] - x0[k] + 3), dtype=bool)
+            free[1:-1, 1:-1] = cleaned[y0[k] : y1[k] + 1, x0[k] : x1[k] + 1] != k
+            c = _components(free.astype(np.int8) - 1)
+            hy, hx = np.nonzero(free & (c != c[0, 0]))  # (the ring is free and connected: one component, which holds the corner)
+            if len(hy):
+                holes.append(np.stack([(hy + y0[k] - 1) * w + (hx + x0[k] - 1), np.full(len(hy), k)], axis=1).astype(np.int32))
+                areas[k] += len(hy)
+    return cleaned, (np.concatenate(holes) if holes else np.zeros((0, 2), np.int32)), areas
+
+
+def _group_host(fg, hm, off, fg_threshold, peak_threshold, output_stride, max_instances, center_nms_kernel, distance_gate_alpha, distance_gate_iters,
+                mask_cleanup: bool = False) -> Grouping:
     B, _c, h, w = fg.shape
     labels = np.full((B, h, w), -1, dtype=np.int32)
     centers, scores, counts = [], [], []
+    holes = [] if mask_cleanup else None
     s = output_stride
     for b in range(B):
         cen, val = find_center_peaks_host(hm[b, 0], peak_threshold, center_nms_kernel)
@@ -134,11 +221,14 @@ def _group_host(fg, hm, off, fg_threshold, peak_threshold, output_stride, max_in
             lab = torch.where(keep, assign, torch.full_like(assign, -1))
             labels[b][y.numpy(), x.numpy()] = lab.numpy()
             cnt = torch.bincount(assign[keep], minlength=len(cen)).numpy()
+        if mask_cleanup:
+            labels[b], hol, cnt = clean_label_map(labels[b], len(cen))
+            holes.append(hol)
         centers.append(cen)
         scores.append(val)
         counts.append(cnt.astype(np.int32))
     n_max = max([len(c) for c in centers] + [0])
-    return Grouping(labels.astype(_np_label_dtype(n_max)), centers, scores, counts)
+    return Grouping(labels.astype(_np_label_dtype(n_max)), centers, scores, counts, holes)
 
 
 def _np_label_dtype(n: int):
@@ -176,8 +266,11 @@ def _pinned_give(t: torch.Tensor) -> None:
 
 def group_enqueue(fg: torch.Tensor, hm: torch.Tensor, off: torch.Tensor, fg_threshold: float, peak_threshold: float, output_stride: int,
                   max_instances: Optional[int], center_nms_kernel: int, distance_gate_alpha: Optional[float], distance_gate_iters: int,
-                  cap: int = DEFAULT_CAP, max_centers: int = DEFAULT_MAX_CENTERS) -> dict:
-    """The grouping launches on the current stream and the asynchronous copies of their results into pinned memory; no host synchronisation."""
+                  cap: int = DEFAULT_CAP, max_centers: int = DEFAULT_MAX_CENTERS, mask_cleanup: bool = False, hole_cap: int = DEFAULT_HOLE_CAP,
+                  pool_words: Optional[int] = None) -> dict:
+    """The grouping launches on the current stream and the asynchronous copies of their results into pinned memory; no host synchronisation.  With
+    ``mask_cleanup`` ``ph_seg_cleanup`` follows the assignment / gate on the same stream; its record and hole list (``hole_cap`` pairs per frame,
+    ``pool_words`` 64-bit words per frame for boxes beyond the LDS bitmaps: by default one box of the whole map) are copied with the rest."""
     from sleap_nn_amd import _lib as L
 
     lib = L.lib()
@@ -214,6 +307,22 @@ def group_enqueue(fg: torch.Tensor, hm: torch.Tensor, off: torch.Tensor, fg_thre
             L.check(lib.ph_seg_gate(p(labels), p(dist), B, h, w, float(distance_gate_alpha), int(output_stride), iters, p(counts), mc, labels.element_size(), p(pix),
                                     p(gated), st))
             labels = gated
+        clean = None
+        if mask_cleanup:
+            hole_cap = max(1, int(hole_cap))
+            pool_words = 2 * (h + 2) * ((w + 2 + 63) // 64) if pool_words is None else int(pool_words)
+            rec = torch.empty(2 * B * mc + 2 * B, dtype=torch.int32, device=dev)  # [areas B mc | hole counts B mc | holes per frame B | pool words needed B]
+            holes = torch.empty((B, hole_cap, 2), dtype=torch.int32, device=dev)
+            cneed = int(lib.ph_seg_cleanup_scratch_bytes(B, h, w, mc, pool_words))
+            cscratch = torch.empty((cneed + 7) // 8, dtype=torch.int64, device=dev)
+            cleaned = torch.empty_like(labels)
+            L.check(lib.ph_seg_cleanup(p(labels), B, h, w, p(counts), mc, labels.element_size(), p(cleaned), p(rec), p(holes), hole_cap, pool_words, p(cscratch),
+                                       cneed, st))
+            uncleaned, labels = labels, cleaned
+            rec_h, holes_h = _pinned_take(rec.shape, rec.dtype), _pinned_take(holes.shape, holes.dtype)
+            rec_h.copy_(rec, non_blocking=True)
+            holes_h.copy_(holes, non_blocking=True)
+            clean = {"rec": rec_h, "holes": holes_h, "hole_cap": hole_cap, "pool_words": pool_words, "dev": (rec, holes, cscratch, uncleaned)}
         small_h = _pinned_take(small.shape, small.dtype)
         labels_h = _pinned_take(labels.shape, labels.dtype)
         small_h.copy_(small, non_blocking=True)
@@ -221,45 +330,67 @@ def group_enqueue(fg: torch.Tensor, hm: torch.Tensor, off: torch.Tensor, fg_thre
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
     args = (fg, hm, off, fg_threshold, peak_threshold, output_stride, max_instances, center_nms_kernel, distance_gate_alpha, distance_gate_iters)
-    return {"small": small_h, "labels": labels_h, "event": ev, "B": B, "mc": mc, "cap": int(cap), "iters": iters, "args": args, "dev": (small, labels, scratch, dist)}
+    return {"small": small_h, "labels": labels_h, "event": ev, "B": B, "mc": mc, "cap": int(cap), "iters": iters, "args": args, "dev": (small, labels, scratch, dist),
+            "clean": clean}
 
 
 def group_finish(hd: dict) -> Grouping:
-    """Wait for the batch's record (the one host read), come back with room when a frame had more candidates than ``cap`` or more centres than ``max_centers``."""
+    """Wait for the batch's record (the one host read), come back with room when a frame had more candidates than ``cap`` or more centres than ``max_centers`` --
+    or, with mask cleanup, more holes than ``hole_cap`` or large boxes beyond ``pool_words``."""
     hd["event"].synchronize()
     B, mc, iters = hd["B"], hd["mc"], hd["iters"]
     small = hd["small"].numpy()
     n_cen, n_cand = small[:B], small[B : 2 * B]
     most_cand, most_cen = int(n_cand.max(initial=0)), int(n_cen.max(initial=0))
+    cl = hd.get("clean")
+    give = [hd["small"], hd["labels"]] + ([cl["rec"], cl["holes"]] if cl else [])
     if most_cand > hd["cap"] or most_cen > mc:  # rare (a frame that overflowed its candidate list reported no centres: it may come back once more for those)
         cap, mc2 = max(hd["cap"], most_cand), max(mc, most_cen)
-        _pinned_give(hd["small"])
-        _pinned_give(hd["labels"])
-        return group_finish(group_enqueue(*hd["args"], cap=cap, max_centers=mc2))
+        for t in give:
+            _pinned_give(t)
+        more = dict(mask_cleanup=True, hole_cap=cl["hole_cap"], pool_words=cl["pool_words"]) if cl else {}
+        return group_finish(group_enqueue(*hd["args"], cap=cap, max_centers=mc2, **more))
+    if cl:
+        rec = cl["rec"].numpy()
+        n_holes, pool_need = rec[2 * B * mc : 2 * B * mc + B], rec[2 * B * mc + B :]
+        most_holes, most_pool = int(n_holes.max(initial=0)), int(pool_need.max(initial=0))
+        if most_holes > cl["hole_cap"] or most_pool > cl["pool_words"]:  # (an instance without pool room reported no holes: it may come back once more for those)
+            for t in give:
+                _pinned_give(t)
+            return group_finish(group_enqueue(*hd["args"], cap=hd["cap"], max_centers=mc, mask_cleanup=True, hole_cap=max(cl["hole_cap"], most_holes),
+                                              pool_words=max(cl["pool_words"], most_pool)))
     cen = small[2 * B : 2 * B + 2 * B * mc].reshape(B, mc, 2)
     sc = small[2 * B + 2 * B * mc : 2 * B + 3 * B * mc].view(np.float32).reshape(B, mc)
     pix = small[2 * B + 3 * B * mc :].reshape(iters + 1, B, mc)[iters]
+    holes = None
+    if cl:
+        pix = rec[: B * mc].reshape(B, mc)  # the cleaned areas
+        holes = [cl["holes"][b, : n_holes[b]].numpy().copy() for b in range(B)]
     out = Grouping(hd["labels"].numpy().copy(), [cen[b, : n_cen[b]].copy() for b in range(B)], [sc[b, : n_cen[b]].copy() for b in range(B)],
-                   [pix[b, : n_cen[b]].copy() for b in range(B)])
-    _pinned_give(hd["small"])
-    _pinned_give(hd["labels"])
+                   [pix[b, : n_cen[b]].copy() for b in range(B)], holes)
+    for t in give:
+        _pinned_give(t)
     return out
 
 
 def group_instances_from_offsets(foreground: torch.Tensor, center_heatmap: torch.Tensor, offsets: torch.Tensor, fg_threshold: float = 0.5, peak_threshold: float = 0.2,
                                  output_stride: int = 2, max_instances: Optional[int] = None, center_nms_kernel: int = 3, distance_gate_alpha: Optional[float] = None,
-                                 distance_gate_iters: int = 3, device=None, cap: int = DEFAULT_CAP, max_centers: int = DEFAULT_MAX_CENTERS) -> Grouping:
-    """``foreground`` (B, 1, h, w) probabilities, ``center_heatmap`` (B, 1, h, w), ``offsets`` (B, 2, h, w) = (dx, dy) -> ``Grouping``.  ``device=None``: where the
+                                 distance_gate_iters: int = 3, device=None, cap: int = DEFAULT_CAP, max_centers: int = DEFAULT_MAX_CENTERS, mask_cleanup: bool = False,
+                                 hole_cap: int = DEFAULT_HOLE_CAP, pool_words: Optional[int] = None) -> Grouping:
+    """``foreground`` (B, 1, h, w) probabilities, ``center_heatmap`` (B, 1, h, w), ``offsets`` (B, 2, h, w) = (dx, dy) -> ``Grouping``.  ``mask_cleanup``: keep each
+    instance's largest component and fill its holes (``hole_cap`` / ``pool_words``: the device path's first capacities).  ``device=None``: where the
     tensors are -- the HIP kernels for GPU tensors, the host implementation for CPU tensors; ``device="cuda..."`` moves CPU tensors to the GPU first, ``"cpu"`` the other way."""
     if center_nms_kernel not in (3, 5, 7):
         raise ValueError(f"center_nms_kernel must be 3, 5 or 7, got {center_nms_kernel}")
     dev = torch.device(device) if device is not None else foreground.device
     if dev.type == "cuda":
         fg, hm, off = (t.to(dev) for t in (foreground, center_heatmap, offsets))
+        more = dict(mask_cleanup=True, hole_cap=hole_cap, pool_words=pool_words) if mask_cleanup else {}
         return group_finish(group_enqueue(fg, hm, off, fg_threshold, peak_threshold, output_stride, max_instances, center_nms_kernel, distance_gate_alpha,
-                                          distance_gate_iters, cap=cap, max_centers=max_centers))
+                                          distance_gate_iters, cap=cap, max_centers=max_centers, **more))
     fg, hm, off = (t.detach().to("cpu", torch.float32) for t in (foreground, center_heatmap, offsets))
-    return _group_host(fg, hm, off, fg_threshold, peak_threshold, output_stride, max_instances, center_nms_kernel, distance_gate_alpha, distance_gate_iters)
+    return _group_host(fg, hm, off, fg_threshold, peak_threshold, output_stride, max_instances, center_nms_kernel, distance_gate_alpha, distance_gate_iters,
+                       mask_cleanup=bool(mask_cleanup))
 
 
 def semantic_enqueue(foreground: torch.Tensor, fg_threshold: float = 0.5, host_masks: bool = True) -> dict:

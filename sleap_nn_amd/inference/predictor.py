@@ -128,7 +128,9 @@ def _select_layer(assets: Sequence[LoadedAssets], device: str, post: Postprocess
         return TopDownSegmentationLayer(cl, il, (crop, crop), mask_output=seg_kw.get("mask_output", "mask"))
     if "bottomup_segmentation" in by_type:  # the three heads share one stride: head_configs.bottomup_segmentation.segmentation.output_stride (loaders.py:455-456)
         a = by_type["bottomup_segmentation"]
-        return SegmentationLayer(backend(a), a.head_config["segmentation"]["output_stride"], max_stride=a.backbone_config["max_stride"], max_instances=max_instances,
+        from sleap_nn_amd.inference.layers.segmentation_cleanup import CleanupSegmentationLayer
+
+        return (CleanupSegmentationLayer if seg_kw.get("mask_cleanup") else SegmentationLayer)(backend(a), a.head_config["segmentation"]["output_stride"], max_stride=a.backbone_config["max_stride"], max_instances=max_instances,
                                  preprocess_config=pre(a), postprocess_config=post, **seg_kw)
     if "semantic_segmentation" in by_type:
         a = by_type["semantic_segmentation"]
@@ -200,8 +202,9 @@ class Predictor:
                          min_mask_area: int = 0, center_nms_kernel: int = 3, distance_gate_alpha: Optional[float] = None, full_res_masks: bool = False,
                          mask_cleanup: bool = False, mask_cleanup_radius: int = 0, merge_fragments: bool = False, mask_output: str = "mask", **paf_kw) -> "Predictor":
         """``fg_threshold`` / ``min_mask_area`` / ``max_instances`` / ``center_nms_kernel`` / ``distance_gate_alpha`` / ``full_res_masks``: knobs of the segmentation
-        layers (``bottomup_segmentation`` / ``semantic_segmentation`` run directories; defaults as the reference; ``mask_cleanup``, ``mask_cleanup_radius``,
-        ``merge_fragments`` and ``mask_output`` are accepted so that a value the layer does not build raises there).  These layers run the plain per-batch path of
+        layers (``bottomup_segmentation`` / ``semantic_segmentation`` run directories; defaults as the reference; ``mask_cleanup=True`` builds ``CleanupSegmentationLayer``:
+        largest component + hole fill per instance on the device; ``mask_cleanup_radius``, ``merge_fragments`` and ``mask_output`` are accepted so that a value
+        the layer does not build raises there).  These layers run the plain per-batch path of
         ``predict``: the pipelined multi-lane paths are not built for them (their post-process ends in a host read and builds host masks).  A ``centroid`` +
         ``centered_instance_segmentation`` pair builds ``TopDownSegmentationLayer`` (``fg_threshold`` / ``mask_output`` forwarded), batch by batch as well.
         ``tile_size`` / ``overlap``: for run directories trained with tiling, checked against the trained geometry (a different value raises ``ValueError``:
