@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 115
+#define PH_VERSION 116
 
 /* error codes */
 #define PH_OK 0
@@ -636,6 +636,25 @@ int64_t ph_seg_cleanup_scratch_bytes(int32_t B, int32_t h, int32_t w, int32_t ma
 int ph_seg_cleanup(const void* labels_in_dev, int32_t B, int32_t h, int32_t w, const int32_t* counts_dev, int32_t max_centers, int32_t label_bytes,
                    void* labels_out_dev, int32_t* record_dev, int32_t* holes_dev, int32_t hole_cap, int32_t pool_words, void* scratch_dev,
                    int64_t scratch_bytes, void* stream);
+
+/* Pair tables for the fragment merge (merge_instances' region-adjacency graph, inference/segmentation.py:424-579) from
+ * the label map ph_seg_assign / ph_seg_gate (or ph_seg_cleanup) wrote; center_dev (B, 1, h, w), offsets_dev (B, 2, h, w), centers_dev /
+ * counts_dev from ph_seg_center_peaks.  With n = min(counts[b], max_centers) and d = dilate in [1, 4]:
+ *   contact T[a][b] (a != b) = pixels labelled b with at least one pixel labelled a within L1 distance <= d inside the image (SciPy's cross
+ *     iterated d times, border value 0); a pixel counts once per a.  Exact integers; _contact_fraction's overlap(i, j) = T[i][j] + T[j][i].
+ *   moments_dev double (B, max_centers, 4) = sums over the label's pixels of (rx, ry, rx^2, ry^2), rx = (x - xc) s + dx, ry = (y - yc) s + dy:
+ *     the offset-predicted centre relative to the instance's own; float64 sums of the fp32 offsets in a fixed order (bit-identical from run
+ *     to run and on any stream; no floating-point atomics); zeros for a label without pixels or at and beyond n.
+ *   edges_dev int32 (B, edge_cap, 5) = (i, j, T[i][j], T[j][i], fp32 bits of the ridge minimum) for the pairs i < j with T[i][j] + T[j][i] > 0,
+ *     in (i, j) order; edge_counts_dev[b] is the TRUE count: entries beyond edge_cap are not written and the caller comes back with room.
+ *     Ridge minimum: min of the centre map over the cells round(c_i + (c_j - c_i) k / 47), k = 7..39, clipped to the map
+ *     (_center_valley_ridge's 33 interior samples of 48; computed in integers, no sample is a rounding tie); NaN if a sample is NaN.
+ * max_centers <= 4096 and B * max_centers^2 <= 2^29 (a dense table in the scratch); h, w <= 32767.  Four launches on `stream`, no host
+ * synchronisation; scratch 8-byte aligned, ph_seg_merge_scratch_bytes(B, h, w, max_centers) bytes (0 for arguments out of range). */
+int64_t ph_seg_merge_scratch_bytes(int32_t B, int32_t h, int32_t w, int32_t max_centers);
+int ph_seg_merge_tables(const void* labels_dev, const float* center_dev, const float* offsets_dev, int32_t B, int32_t h, int32_t w, int32_t output_stride,
+                        int32_t dilate, const int32_t* centers_dev, const int32_t* counts_dev, int32_t max_centers, int32_t label_bytes, double* moments_dev,
+                        int32_t* edge_counts_dev, int32_t* edges_dev, int32_t edge_cap, void* scratch_dev, int64_t scratch_bytes, void* stream);
 
 /* Semantic variant (layers/segmentation.py:438-503): mask_dev uint8 (B, h, w) = fg > fg_threshold, count_dev int32[B] its
  * pixels, sum_dev double[B] the sum of fg over them (fixed summation order: deterministic; the reference's score is sum / count). */

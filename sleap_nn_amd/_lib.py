@@ -126,6 +126,8 @@ SIGNATURES = {
     "ph_seg_gate": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "ph_seg_cleanup_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "ph_seg_cleanup": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
+    "ph_seg_merge_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "ph_seg_merge_tables": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     "ph_seg_semantic_scratch_bytes": (_i64, [_i32, _i32, _i32]),
     "ph_seg_semantic": (C.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ph_seg_place_crops": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),

@@ -6,6 +6,7 @@ from sleap_nn_amd.inference.layers.centroid import CentroidLayer  # noqa: F401
 from sleap_nn_amd.inference.layers.configs import PostprocessConfig, PreprocessConfig  # noqa: F401
 from sleap_nn_amd.inference.layers.segmentation import SegmentationLayer, SemanticSegmentationLayer  # noqa: F401
 from sleap_nn_amd.inference.layers.segmentation_cleanup import CleanupSegmentationLayer  # noqa: F401
+from sleap_nn_amd.inference.layers.segmentation_merge import MergeSegmentationLayer  # noqa: F401
 from sleap_nn_amd.inference.layers.single_instance import SingleInstanceLayer  # noqa: F401
 from sleap_nn_amd.inference.layers.tiled import TiledLayer  # noqa: F401
 from sleap_nn_amd.inference.layers.topdown import TopDownLayer  # noqa: F401

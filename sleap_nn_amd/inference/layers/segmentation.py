@@ -7,9 +7,10 @@ device (``inference/ops/segmentation.py``: centre peaks, pixel assignment, dista
 small integer per pixel and a record of centres / scores / counts) and builds ``Outputs.pred_masks`` from the label map; for CPU
 tensors the same contract runs on the host.
 
-``mask_cleanup=True`` is ``layers/segmentation_cleanup.py`` (``CleanupSegmentationLayer``; this class keeps refusing the knob).  Not built
-(each raises ``NotImplementedError`` naming the knob): ``mask_cleanup_radius`` (OpenCV morphology), ``merge_fragments`` (the RAG fragment
-merge), ``mask_output`` other than ``"mask"`` (polygon packaging) and the tiled segmentation wrappers.  Top-down segmentation (``centered_instance_segmentation``) is ``layers/topdown_segmentation.py``.
+``mask_cleanup=True`` is ``layers/segmentation_cleanup.py`` (``CleanupSegmentationLayer``) and ``merge_fragments=True`` (the RAG fragment merge)
+``layers/segmentation_merge.py`` (``MergeSegmentationLayer``); this class keeps refusing both knobs.  Not built (each raises ``NotImplementedError``
+naming the knob): ``mask_cleanup_radius`` (OpenCV morphology), ``merge_fragments`` together with ``mask_cleanup``, ``mask_output`` other than ``"mask"``
+(polygon packaging) and the tiled segmentation wrappers.  Top-down segmentation (``centered_instance_segmentation``) is ``layers/topdown_segmentation.py``.
 """
 from __future__ import annotations
 
@@ -35,7 +36,7 @@ def _refuse(**knobs) -> None:
 
 
 class SegmentationLayer(InferenceLayer):
-    """Constructor arguments and defaults of layers/segmentation.py:102-152.  ``merge_*`` and ``polygon_epsilon`` are stored only (their features are refused)."""
+    """Constructor arguments and defaults of layers/segmentation.py:102-152.  ``polygon_epsilon`` is stored only (its feature is refused); the ``merge_*`` knobs are stored for ``MergeSegmentationLayer``."""
 
     _SEG_KEY = "SegmentationHead"
     _CENTER_KEY = "InstanceCenterHead"
@@ -122,6 +123,10 @@ class SegmentationLayer(InferenceLayer):
             return None
         return {"mask": out, "score": float(score), "scale": scale, "offset": offset}
 
+    def _grouping_kw(self) -> dict:
+        """Further keywords of the grouping (the fragment merge's, in ``MergeSegmentationLayer``)."""
+        return {}
+
     def postprocess(self, raw_out: dict, info: PreprocInfo) -> Outputs:
         pc = self.postprocess_config
         max_instances = getattr(pc, "max_instances", None)
@@ -130,7 +135,7 @@ class SegmentationLayer(InferenceLayer):
         g = group_instances_from_offsets(raw_out[self._SEG_KEY], raw_out[self._CENTER_KEY], raw_out[self._OFFSET_KEY], fg_threshold=self.fg_threshold,
                                          peak_threshold=pc.peak_threshold, output_stride=self.output_stride, max_instances=max_instances,
                                          center_nms_kernel=self.center_nms_kernel, distance_gate_alpha=self.distance_gate_alpha,
-                                         distance_gate_iters=self.distance_gate_iters, mask_cleanup=self.mask_cleanup)
+                                         distance_gate_iters=self.distance_gate_iters, mask_cleanup=self.mask_cleanup, **self._grouping_kw())
         pred_masks: List[List[dict]] = []
         for b in range(g.labels.shape[0]):
             frame = [self._package(inst["mask"], inst["score"], info, b) for inst in g.instances(b, self.output_stride)]

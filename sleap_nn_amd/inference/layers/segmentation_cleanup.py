@@ -8,7 +8,8 @@ csrc/seg_cleanup_kernels.hip) and its results come down with the grouping's one 
 this class when ``mask_cleanup`` is asked for.
 
 Not built (each raises ``NotImplementedError`` naming the knob): ``mask_cleanup_radius > 0`` (OpenCV's elliptical open / close),
-``merge_fragments``, ``mask_output`` other than ``"mask"`` and the tiled segmentation wrappers.
+``merge_fragments`` together with ``mask_cleanup`` (``merge_fragments`` alone is ``layers/segmentation_merge.py``), ``mask_output`` other than
+``"mask"`` and the tiled segmentation wrappers.
 """
 from __future__ import annotations
 

@@ -21,7 +21,13 @@ The contract (what the reference computes, frame by frame):
   components the one with the most pixels is kept (raster-first on ties), then every complement pixel that cannot reach the outside of the image by
   4-connected steps through the complement joins the mask (``binary_fill_holes``; other instances' pixels are complement, so masks may overlap).  The label
   map then holds the kept components and ``Grouping.holes`` the filled pixels; ``ph_seg_cleanup`` (csrc/seg_cleanup_kernels.hip) on the device,
-  ``clean_label_map`` on the host.  Not built: ``mask_cleanup_radius > 0`` (OpenCV's elliptical open / close) and ``merge_fragments``.
+  ``clean_label_map`` on the host;
+* ``merge_fragments=True`` (``merge_instances``, segmentation.py:424-782), per frame after assignment and gate: a region-adjacency graph over the candidate
+  masks (contact by dilation, centre-map ridge, offset agreement), agglomerated by ``"greedy"`` or ``"multicut"``.  The per-pixel tables come from
+  ``ph_seg_merge_tables`` (csrc/seg_merge_kernels.hip) on the device label map with the same host read, or from ``merge_tables_host``; the graph is host work
+  (``inference/ops/segmentation_merge.py``).  The label map is then relabelled: label k is the k-th group, ``Grouping.members`` names each group's centres.
+  Not built: ``mask_cleanup_radius > 0`` (OpenCV's elliptical open / close) and ``merge_fragments`` together with ``mask_cleanup`` (cleaned masks overlap
+  through their filled holes: the label map no longer carries membership).
 
 Also here: the semantic threshold / count / sum (``semantic_masks``) and the geometry and placement of top-down crop masks
 (``crop_mask_geometry``, ``place_crop_masks``: ``ph_seg_place_crops`` on the device, NumPy on the host, one contract).
@@ -39,6 +45,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from sleap_nn_amd.inference.ops.segmentation_merge import DEFAULT_EDGE_CAP, MERGE_DEFAULTS, check_merge_args, merge_frame, merge_tables_host
+
 DEFAULT_CAP = 2048  # candidates per frame that the collapse kernel keeps in LDS
 DEFAULT_MAX_CENTERS = 127  # centres per frame that one-byte labels hold
 DEFAULT_HOLE_CAP = 4096  # filled hole pixels per frame that the cleanup's list holds
@@ -49,13 +57,16 @@ class Grouping:
     """``labels`` (B, h, w) signed integers, -1 = background, otherwise an index into the frame's centres; per frame ``centers`` (N, 2) int32 (x, y) in map
     pixels, ``scores`` (N,) float32 (the centre's peak value) and ``counts`` (N,) the pixels each centre kept.  After mask cleanup ``labels`` holds each
     instance's kept component, ``holes`` per frame the filled pixels as int32 (K, 2) = (pixel index y * w + x, label), instance-major and in raster order
-    inside an instance (they may lie on other instances' pixels), and ``counts`` the cleaned areas (component + holes)."""
+    inside an instance (they may lie on other instances' pixels), and ``counts`` the cleaned areas (component + holes).  After the fragment merge an entry
+    is a group: ``labels`` index the groups, ``centers`` / ``scores`` are the representative's, ``counts`` the members' sum, and ``members`` per frame lists
+    each group's original centre indices."""
 
     labels: np.ndarray
     centers: List[np.ndarray]
     scores: List[np.ndarray]
     counts: List[np.ndarray]
     holes: Optional[List[np.ndarray]] = None
+    members: Optional[List[List[List[int]]]] = None
 
     def instances(self, b: int, output_stride: int) -> List[Dict]:
         """The reference's per-frame list (segmentation.py:213-237): ``{"mask", "center", "score"}`` per non-empty instance, in centre order; ``center`` in input pixels."""
@@ -187,7 +198,7 @@ def clean_label_map(labels: np.ndarray, n_centers: int):
 
 
 def _group_host(fg, hm, off, fg_threshold, peak_threshold, output_stride, max_instances, center_nms_kernel, distance_gate_alpha, distance_gate_iters,
-                mask_cleanup: bool = False) -> Grouping:
+                mask_cleanup: bool = False, merge: Optional[dict] = None, merge_trace: Optional[list] = None) -> Grouping:
     B, _c, h, w = fg.shape
     labels = np.full((B, h, w), -1, dtype=np.int32)
     centers, scores, counts = [], [], []
@@ -228,7 +239,36 @@ def _group_host(fg, hm, off, fg_threshold, peak_threshold, output_stride, max_in
         scores.append(val)
         counts.append(cnt.astype(np.int32))
     n_max = max([len(c) for c in centers] + [0])
-    return Grouping(labels.astype(_np_label_dtype(n_max)), centers, scores, counts, holes)
+    g = Grouping(labels.astype(_np_label_dtype(n_max)), centers, scores, counts, holes)
+    if merge is not None:
+        tables = []
+        for b in range(B):
+            _T, mom, edges, ridge = merge_tables_host(g.labels[b], hm[b, 0].numpy(), off[b].numpy(), centers[b], len(centers[b]), output_stride, merge["merge_dilate"])
+            tables.append((edges, ridge, mom))
+        g = merge_grouping(g, tables, output_stride, merge, trace=merge_trace)
+    return g
+
+
+def _merge_kw(merge_method, merge_thresholds, merge_w_valley, merge_w_offset, merge_dilate, join_bias) -> dict:
+    return dict(merge_method=str(merge_method), merge_thresholds=tuple(float(t) for t in merge_thresholds), merge_w_valley=float(merge_w_valley),
+                merge_w_offset=float(merge_w_offset), merge_dilate=int(merge_dilate), join_bias=float(join_bias))
+
+
+def merge_grouping(g: Grouping, tables, output_stride: int, merge: dict, trace: Optional[list] = None) -> Grouping:
+    """The fragment merge applied to a ``Grouping``: ``tables[b] = (edges (E, 4), ridge (E,), moments (n, 4))`` of frame b (``merge_tables_host`` or the
+    device record), ``merge`` the ``merge_*`` knobs and ``join_bias``.  ``trace`` (a list) receives one dict per frame (``segmentation_merge.merge_frame``)."""
+    labels = g.labels.copy()
+    centers, scores, counts, members = [], [], [], []
+    for b in range(labels.shape[0]):
+        edges, ridge, mom = tables[b]
+        tr = {} if trace is not None else None
+        labels[b], c, s, n, m = merge_frame(labels[b], g.centers[b], g.scores[b], g.counts[b], edges, ridge, mom, output_stride, method=merge["merge_method"],
+                                            thresholds=merge["merge_thresholds"], w_valley=merge["merge_w_valley"], w_offset=merge["merge_w_offset"],
+                                            join_bias=merge["join_bias"], trace=tr)
+        centers.append(c), scores.append(s), counts.append(n), members.append(m)
+        if trace is not None:
+            trace.append(tr)
+    return Grouping(labels, centers, scores, counts, None, members)
 
 
 def _np_label_dtype(n: int):
@@ -267,11 +307,22 @@ def _pinned_give(t: torch.Tensor) -> None:
 def group_enqueue(fg: torch.Tensor, hm: torch.Tensor, off: torch.Tensor, fg_threshold: float, peak_threshold: float, output_stride: int,
                   max_instances: Optional[int], center_nms_kernel: int, distance_gate_alpha: Optional[float], distance_gate_iters: int,
                   cap: int = DEFAULT_CAP, max_centers: int = DEFAULT_MAX_CENTERS, mask_cleanup: bool = False, hole_cap: int = DEFAULT_HOLE_CAP,
-                  pool_words: Optional[int] = None) -> dict:
+                  pool_words: Optional[int] = None, merge_fragments: bool = False, merge_method: str = "greedy", merge_thresholds: tuple = (0.85, 0.6, 0.4),
+                  merge_w_valley: float = 1.0, merge_w_offset: float = 0.25, merge_dilate: int = 1, join_bias: float = 0.5,
+                  edge_cap: int = DEFAULT_EDGE_CAP, merge_trace: Optional[list] = None) -> dict:
     """The grouping launches on the current stream and the asynchronous copies of their results into pinned memory; no host synchronisation.  With
     ``mask_cleanup`` ``ph_seg_cleanup`` follows the assignment / gate on the same stream; its record and hole list (``hole_cap`` pairs per frame,
-    ``pool_words`` 64-bit words per frame for boxes beyond the LDS bitmaps: by default one box of the whole map) are copied with the rest."""
+    ``pool_words`` 64-bit words per frame for boxes beyond the LDS bitmaps: by default one box of the whole map) are copied with the rest.  With
+    ``merge_fragments`` ``ph_seg_merge_tables`` follows the assignment / gate instead: its moments and edge list (``edge_cap`` pairs per frame) are copied
+    with the rest as well -- still one event and one host read; without it the launches and copies are exactly those above."""
     from sleap_nn_amd import _lib as L
+
+    merge = None
+    if merge_fragments:
+        if mask_cleanup:
+            raise NotImplementedError("merge_fragments=True together with mask_cleanup=True is not built: see inference/ops/segmentation_merge.py")
+        check_merge_args(merge_method, merge_dilate, device=True, max_centers=max_centers)
+        merge = _merge_kw(merge_method, merge_thresholds, merge_w_valley, merge_w_offset, merge_dilate, join_bias)
 
     lib = L.lib()
     L.require_cuda(fg, "foreground")
@@ -323,6 +374,18 @@ def group_enqueue(fg: torch.Tensor, hm: torch.Tensor, off: torch.Tensor, fg_thre
             rec_h.copy_(rec, non_blocking=True)
             holes_h.copy_(holes, non_blocking=True)
             clean = {"rec": rec_h, "holes": holes_h, "hole_cap": hole_cap, "pool_words": pool_words, "dev": (rec, holes, cscratch, uncleaned)}
+        if merge is not None:
+            edge_cap = max(1, int(edge_cap))
+            mom = torch.empty((B, mc, 4), dtype=torch.float64, device=dev)
+            erec = torch.empty(B + B * edge_cap * 5, dtype=torch.int32, device=dev)  # [edges per frame B | edges (B, edge_cap, 5)]
+            mneed = int(lib.ph_seg_merge_scratch_bytes(B, h, w, mc))
+            mscratch = torch.empty((mneed + 7) // 8, dtype=torch.int64, device=dev)
+            L.check(lib.ph_seg_merge_tables(p(labels), p(hm), p(off), B, h, w, int(output_stride), max(1, merge["merge_dilate"]), p(cen), p(counts), mc,
+                                            labels.element_size(), p(mom), p(erec[:B]), p(erec[B:]), edge_cap, p(mscratch), mneed, st))
+            mom_h, erec_h = _pinned_take(mom.shape, mom.dtype), _pinned_take(erec.shape, erec.dtype)
+            mom_h.copy_(mom, non_blocking=True)
+            erec_h.copy_(erec, non_blocking=True)
+            merge = dict(merge, mom=mom_h, erec=erec_h, edge_cap=edge_cap, trace=merge_trace, dev=(mom, erec, mscratch))
         small_h = _pinned_take(small.shape, small.dtype)
         labels_h = _pinned_take(labels.shape, labels.dtype)
         small_h.copy_(small, non_blocking=True)
@@ -331,24 +394,27 @@ def group_enqueue(fg: torch.Tensor, hm: torch.Tensor, off: torch.Tensor, fg_thre
         ev.record(torch.cuda.current_stream(dev))
     args = (fg, hm, off, fg_threshold, peak_threshold, output_stride, max_instances, center_nms_kernel, distance_gate_alpha, distance_gate_iters)
     return {"small": small_h, "labels": labels_h, "event": ev, "B": B, "mc": mc, "cap": int(cap), "iters": iters, "args": args, "dev": (small, labels, scratch, dist),
-            "clean": clean}
+            "clean": clean, "merge": merge}
 
 
 def group_finish(hd: dict) -> Grouping:
     """Wait for the batch's record (the one host read), come back with room when a frame had more candidates than ``cap`` or more centres than ``max_centers`` --
-    or, with mask cleanup, more holes than ``hole_cap`` or large boxes beyond ``pool_words``."""
+    or, with mask cleanup, more holes than ``hole_cap`` or large boxes beyond ``pool_words``, or, with the fragment merge, more touching pairs than ``edge_cap``.
+    The merge's graph part runs here, on the host, from the record."""
     hd["event"].synchronize()
     B, mc, iters = hd["B"], hd["mc"], hd["iters"]
     small = hd["small"].numpy()
     n_cen, n_cand = small[:B], small[B : 2 * B]
     most_cand, most_cen = int(n_cand.max(initial=0)), int(n_cen.max(initial=0))
     cl = hd.get("clean")
-    give = [hd["small"], hd["labels"]] + ([cl["rec"], cl["holes"]] if cl else [])
+    mg = hd.get("merge")
+    give = [hd["small"], hd["labels"]] + ([cl["rec"], cl["holes"]] if cl else []) + ([mg["mom"], mg["erec"]] if mg else [])
+    again = dict(merge_fragments=True, edge_cap=mg["edge_cap"], merge_trace=mg["trace"], **{k: mg[k] for k in MERGE_DEFAULTS}) if mg else {}
     if most_cand > hd["cap"] or most_cen > mc:  # rare (a frame that overflowed its candidate list reported no centres: it may come back once more for those)
         cap, mc2 = max(hd["cap"], most_cand), max(mc, most_cen)
         for t in give:
             _pinned_give(t)
-        more = dict(mask_cleanup=True, hole_cap=cl["hole_cap"], pool_words=cl["pool_words"]) if cl else {}
+        more = dict(mask_cleanup=True, hole_cap=cl["hole_cap"], pool_words=cl["pool_words"]) if cl else again
         return group_finish(group_enqueue(*hd["args"], cap=cap, max_centers=mc2, **more))
     if cl:
         rec = cl["rec"].numpy()
@@ -359,6 +425,13 @@ def group_finish(hd: dict) -> Grouping:
                 _pinned_give(t)
             return group_finish(group_enqueue(*hd["args"], cap=hd["cap"], max_centers=mc, mask_cleanup=True, hole_cap=max(cl["hole_cap"], most_holes),
                                               pool_words=max(cl["pool_words"], most_pool)))
+    if mg:
+        n_edges = mg["erec"].numpy()[:B]
+        most_edges = int(n_edges.max(initial=0))
+        if most_edges > mg["edge_cap"]:
+            for t in give:
+                _pinned_give(t)
+            return group_finish(group_enqueue(*hd["args"], cap=hd["cap"], max_centers=mc, **dict(again, edge_cap=most_edges)))
     cen = small[2 * B : 2 * B + 2 * B * mc].reshape(B, mc, 2)
     sc = small[2 * B + 2 * B * mc : 2 * B + 3 * B * mc].view(np.float32).reshape(B, mc)
     pix = small[2 * B + 3 * B * mc :].reshape(iters + 1, B, mc)[iters]
@@ -368,6 +441,11 @@ def group_finish(hd: dict) -> Grouping:
         holes = [cl["holes"][b, : n_holes[b]].numpy().copy() for b in range(B)]
     out = Grouping(hd["labels"].numpy().copy(), [cen[b, : n_cen[b]].copy() for b in range(B)], [sc[b, : n_cen[b]].copy() for b in range(B)],
                    [pix[b, : n_cen[b]].copy() for b in range(B)], holes)
+    if mg:
+        er = mg["erec"].numpy()[B:].reshape(B, mg["edge_cap"], 5)
+        mom = mg["mom"].numpy()
+        tables = [(er[b, : n_edges[b], :4].astype(np.int64), er[b, : n_edges[b], 4].copy().view(np.float32), mom[b, : n_cen[b]].copy()) for b in range(B)]
+        out = merge_grouping(out, tables, hd["args"][5], mg, trace=mg["trace"])
     for t in give:
         _pinned_give(t)
     return out
@@ -376,21 +454,34 @@ def group_finish(hd: dict) -> Grouping:
 def group_instances_from_offsets(foreground: torch.Tensor, center_heatmap: torch.Tensor, offsets: torch.Tensor, fg_threshold: float = 0.5, peak_threshold: float = 0.2,
                                  output_stride: int = 2, max_instances: Optional[int] = None, center_nms_kernel: int = 3, distance_gate_alpha: Optional[float] = None,
                                  distance_gate_iters: int = 3, device=None, cap: int = DEFAULT_CAP, max_centers: int = DEFAULT_MAX_CENTERS, mask_cleanup: bool = False,
-                                 hole_cap: int = DEFAULT_HOLE_CAP, pool_words: Optional[int] = None) -> Grouping:
+                                 hole_cap: int = DEFAULT_HOLE_CAP, pool_words: Optional[int] = None, merge_fragments: bool = False, merge_method: str = "greedy",
+                                 merge_thresholds: tuple = (0.85, 0.6, 0.4), merge_w_valley: float = 1.0, merge_w_offset: float = 0.25, merge_dilate: int = 1,
+                                 join_bias: float = 0.5, edge_cap: int = DEFAULT_EDGE_CAP, merge_trace: Optional[list] = None) -> Grouping:
     """``foreground`` (B, 1, h, w) probabilities, ``center_heatmap`` (B, 1, h, w), ``offsets`` (B, 2, h, w) = (dx, dy) -> ``Grouping``.  ``mask_cleanup``: keep each
-    instance's largest component and fill its holes (``hole_cap`` / ``pool_words``: the device path's first capacities).  ``device=None``: where the
+    instance's largest component and fill its holes (``hole_cap`` / ``pool_words``: the device path's first capacities).  ``merge_fragments``: fuse
+    touching fragments (``merge_instances`` with ``merge_method`` ``"greedy"`` / ``"multicut"`` / ``"none"``, the ``merge_*`` knobs and ``join_bias`` as there;
+    ``edge_cap``: the device path's first capacity of touching pairs per frame; ``merge_dilate`` above 4 is a ``ValueError`` on the device; ``merge_trace``: a list that receives one dict per frame with the graph's ``"edges"``
+    ``(i, j, affinity)``, their ``"detail"`` and the agglomeration's ``"decisions"``, centres numbered as before the merge).  ``device=None``: where the
     tensors are -- the HIP kernels for GPU tensors, the host implementation for CPU tensors; ``device="cuda..."`` moves CPU tensors to the GPU first, ``"cpu"`` the other way."""
     if center_nms_kernel not in (3, 5, 7):
         raise ValueError(f"center_nms_kernel must be 3, 5 or 7, got {center_nms_kernel}")
     dev = torch.device(device) if device is not None else foreground.device
+    merge = None
+    if merge_fragments:
+        if mask_cleanup:
+            raise NotImplementedError("merge_fragments=True together with mask_cleanup=True is not built: see inference/ops/segmentation_merge.py")
+        check_merge_args(merge_method, merge_dilate, device=dev.type == "cuda", max_centers=max_centers)
+        merge = _merge_kw(merge_method, merge_thresholds, merge_w_valley, merge_w_offset, merge_dilate, join_bias)
     if dev.type == "cuda":
         fg, hm, off = (t.to(dev) for t in (foreground, center_heatmap, offsets))
         more = dict(mask_cleanup=True, hole_cap=hole_cap, pool_words=pool_words) if mask_cleanup else {}
+        if merge is not None:
+            more = dict(merge_fragments=True, edge_cap=edge_cap, merge_trace=merge_trace, **merge)
         return group_finish(group_enqueue(fg, hm, off, fg_threshold, peak_threshold, output_stride, max_instances, center_nms_kernel, distance_gate_alpha,
                                           distance_gate_iters, cap=cap, max_centers=max_centers, **more))
     fg, hm, off = (t.detach().to("cpu", torch.float32) for t in (foreground, center_heatmap, offsets))
     return _group_host(fg, hm, off, fg_threshold, peak_threshold, output_stride, max_instances, center_nms_kernel, distance_gate_alpha, distance_gate_iters,
-                       mask_cleanup=bool(mask_cleanup))
+                       mask_cleanup=bool(mask_cleanup), merge=merge, merge_trace=merge_trace)
 
 
 def semantic_enqueue(foreground: torch.Tensor, fg_threshold: float = 0.5, host_masks: bool = True) -> dict:

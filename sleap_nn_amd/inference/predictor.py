@@ -82,7 +82,7 @@ def _warn_unverified_lanes(n: int, why: str) -> None:
 
 
 _SEG_KW = ("fg_threshold", "min_mask_area", "center_nms_kernel", "distance_gate_alpha", "full_res_masks", "mask_cleanup", "mask_cleanup_radius", "merge_fragments",
-           "mask_output")
+           "merge_method", "merge_thresholds", "merge_w_valley", "merge_w_offset", "merge_dilate", "mask_output")
 
 
 def _select_layer(assets: Sequence[LoadedAssets], device: str, post: PostprocessConfig, max_instances: Optional[int], tile_size: Optional[int] = None,
@@ -129,8 +129,10 @@ def _select_layer(assets: Sequence[LoadedAssets], device: str, post: Postprocess
     if "bottomup_segmentation" in by_type:  # the three heads share one stride: head_configs.bottomup_segmentation.segmentation.output_stride (loaders.py:455-456)
         a = by_type["bottomup_segmentation"]
         from sleap_nn_amd.inference.layers.segmentation_cleanup import CleanupSegmentationLayer
+        from sleap_nn_amd.inference.layers.segmentation_merge import MergeSegmentationLayer
 
-        return (CleanupSegmentationLayer if seg_kw.get("mask_cleanup") else SegmentationLayer)(backend(a), a.head_config["segmentation"]["output_stride"], max_stride=a.backbone_config["max_stride"], max_instances=max_instances,
+        cls = MergeSegmentationLayer if seg_kw.get("merge_fragments") else (CleanupSegmentationLayer if seg_kw.get("mask_cleanup") else SegmentationLayer)
+        return cls(backend(a), a.head_config["segmentation"]["output_stride"], max_stride=a.backbone_config["max_stride"], max_instances=max_instances,
                                  preprocess_config=pre(a), postprocess_config=post, **seg_kw)
     if "semantic_segmentation" in by_type:
         a = by_type["semantic_segmentation"]
@@ -200,10 +202,13 @@ class Predictor:
                          integral_refinement: Optional[str] = "integral", integral_patch_size: int = 5, max_instances: Optional[int] = None,
                          return_confmaps: bool = False, streams: int = 3, tile_size: Optional[int] = None, overlap: Optional[int] = None, fg_threshold: float = 0.5,
                          min_mask_area: int = 0, center_nms_kernel: int = 3, distance_gate_alpha: Optional[float] = None, full_res_masks: bool = False,
-                         mask_cleanup: bool = False, mask_cleanup_radius: int = 0, merge_fragments: bool = False, mask_output: str = "mask", **paf_kw) -> "Predictor":
+                         mask_cleanup: bool = False, mask_cleanup_radius: int = 0, merge_fragments: bool = False, merge_method: str = "greedy",
+                         merge_thresholds: tuple = (0.85, 0.6, 0.4), merge_w_valley: float = 1.0, merge_w_offset: float = 0.25, merge_dilate: int = 1,
+                         mask_output: str = "mask", **paf_kw) -> "Predictor":
         """``fg_threshold`` / ``min_mask_area`` / ``max_instances`` / ``center_nms_kernel`` / ``distance_gate_alpha`` / ``full_res_masks``: knobs of the segmentation
         layers (``bottomup_segmentation`` / ``semantic_segmentation`` run directories; defaults as the reference; ``mask_cleanup=True`` builds ``CleanupSegmentationLayer``:
-        largest component + hole fill per instance on the device; ``mask_cleanup_radius``, ``merge_fragments`` and ``mask_output`` are accepted so that a value
+        largest component + hole fill per instance on the device; ``merge_fragments=True`` builds ``MergeSegmentationLayer``: touching fragments fused by the
+        RAG merge with the ``merge_*`` knobs, its pair tables on the device; both together, ``mask_cleanup_radius`` and ``mask_output`` are accepted so that a value
         the layer does not build raises there).  These layers run the plain per-batch path of
         ``predict``: the pipelined multi-lane paths are not built for them (their post-process ends in a host read and builds host masks).  A ``centroid`` +
         ``centered_instance_segmentation`` pair builds ``TopDownSegmentationLayer`` (``fg_threshold`` / ``mask_output`` forwarded), batch by batch as well.
@@ -218,7 +223,8 @@ class Predictor:
                                  max_instances=max_instances, return_confmaps=return_confmaps)
         seg_kw = dict(fg_threshold=fg_threshold, min_mask_area=min_mask_area, center_nms_kernel=center_nms_kernel, distance_gate_alpha=distance_gate_alpha,
                       full_res_masks=full_res_masks, mask_cleanup=mask_cleanup, mask_cleanup_radius=mask_cleanup_radius, merge_fragments=merge_fragments,
-                      mask_output=mask_output)
+                      merge_method=merge_method, merge_thresholds=merge_thresholds, merge_w_valley=merge_w_valley, merge_w_offset=merge_w_offset,
+                      merge_dilate=merge_dilate, mask_output=mask_output)
         layer = _select_layer(assets, device, post, max_instances, tile_size=tile_size, overlap=overlap, seg_kw=seg_kw, **paf_kw)
         replicas = []
         small = lambda l: l.backend.model.num_parameters() <= _REPLICA_MAX_PARAMS
