@@ -41,6 +41,10 @@
  *                       inference/layers/topdown_segmentation.py:163-284 emits.
  *   ph_seg_*            inference/segmentation.py:12-237 (find_center_peaks, group_instances_from_offsets) as called
  *                       at inference/layers/segmentation.py:159-266, and the thresholding of :438-503 (semantic).
+ *   ph_track_pose_scores   tracking/tracker.py:513-586 (get_scores' loop over instance / candidate pairs) with evaluation.py:644-760
+ *                       (compute_oks) and tracking/utils.py:184-252 (compute_iou, compute_euclidean_distance, compute_cosine_sim).
+ *   ph_track_mask_pairs    tracking/utils.py:127-244 (get_mask, compute_mask_iou: masks decoded to the image grid by
+ *                       inference/segmentation_convert.py:74-133 and ANDed pair by pair), on the device label maps.
  */
 #ifndef POSEHIP_H
 #define POSEHIP_H
@@ -52,7 +56,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 116
+#define PH_VERSION 117
 
 /* error codes */
 #define PH_OK 0
@@ -699,6 +703,37 @@ int ph_mask_pair_stats(const void* pred_dev, int32_t pred_form, int32_t P, int32
 int64_t ph_mask_boundary_scratch_bytes(int32_t N, int32_t H, int32_t W);
 int ph_mask_boundary(const uint8_t* masks_dev, int32_t N, int32_t H, int32_t W, int32_t d, uint8_t* out_dev, void* scratch_dev, int64_t scratch_bytes,
                      void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Cross-frame tracking (tracking/tracker.py:513-586 get_scores, tracking/utils.py:127-252)
+ * ---------------------------------------------------------------------------------- */
+
+enum ph_track_method { PH_TRACK_OKS = 0, PH_TRACK_IOU = 1, PH_TRACK_EUCLID = 2, PH_TRACK_COSINE = 3 };
+
+/* Every pose pair score of a batch in one call (host code, float64, the reference's operation order).  cur (B, I, N, 2): the features of the
+ * batch's frames, instance-major, N pairs of doubles per instance (keypoints (x, y) with NaN for a missing node for PH_TRACK_OKS; any
+ * feature of 2 N numbers for PH_TRACK_EUCLID / PH_TRACK_COSINE; N = 2, [xmin, ymin, xmax, ymax], for PH_TRACK_IOU).  hist (L, I, N, 2):
+ * the features of earlier frames, newest LAST, the last n_hist slots valid.  counts int32 (B + L): the instances of each cur frame, then
+ * of each hist slot; rows at or beyond a count are never read.  out double (B, L, I, I): [b][k - 1][i][j] = the score of instance i of
+ * frame b against instance j of the frame k calls earlier, which is cur[b - k] if b >= k and hist[L - (k - b)] otherwise; NaN where i or
+ * j is beyond its frame's count or the lag reaches beyond n_hist.  PH_TRACK_OKS: compute_oks with the current instance as points_gt, its
+ * bounding-box area as the scale, np.spacing(1) and oks_stddev; PH_TRACK_IOU: compute_iou with its + 1s; PH_TRACK_EUCLID: minus the
+ * Euclidean norm; PH_TRACK_COSINE: the cosine.  A NaN stays NaN where NumPy gives NaN.  1 <= L <= 32. */
+int ph_track_pose_scores(const double* cur, int32_t B, const double* hist, int32_t L, int32_t n_hist, int32_t I, int32_t N, const int32_t* counts,
+                         int32_t method, double oks_stddev, double* out);
+
+/* Weighted contingency tables of a batch of label maps against earlier label maps.  labels_dev (B, h, w) and hist_dev (L, h, w): signed
+ * integers label_bytes (1, 2 or 4) wide, -1 = background, as ph_seg_assign / ph_seg_gate write them; a label at or beyond P is treated as
+ * BACKGROUND.  hist_dev holds earlier frames, newest LAST, the last n_hist slots valid.  row_weight_dev int32[h], col_weight_dev int32[w]:
+ * the image rows / columns a cell row / column stands for (0 in the padding); image_pixels = sum(row_weight) * sum(col_weight), stated
+ * by the caller, must be below 2^31 (the counters are int32).  inter_dev int32 (B, L, P, P): [b][k - 1][a][c] = the sum over cells (v, u)
+ * of row_weight[v] * col_weight[u] where frame b has label a and the frame k calls earlier has label c -- that frame is labels[b - k] if
+ * b >= k and hist[L - (k - b)] otherwise; a lag that reaches beyond n_hist is written as zeros.  area_dev int32 (B, P): [b][a] = the same
+ * weighted count of label a alone.  Both are zeroed here on `stream`; integer accumulation only, so the result is exact and identical
+ * from run to run and on any stream.  1 <= P <= 64, 1 <= L <= 32 (PH_E_INVALID beyond).  One launch, no host synchronisation. */
+int ph_track_mask_pairs(const void* labels_dev, int32_t label_bytes, int32_t B, int32_t h, int32_t w, const void* hist_dev, int32_t L, int32_t n_hist,
+                        const int32_t* row_weight_dev, const int32_t* col_weight_dev, int64_t image_pixels, int32_t P, int32_t* inter_dev, int32_t* area_dev,
+                        void* stream);
 
 #ifdef __cplusplus
 }

@@ -134,6 +134,8 @@ SIGNATURES = {
     "ph_mask_pair_stats": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ph_mask_boundary_scratch_bytes": (_i64, [_i32, _i32, _i32]),
     "ph_mask_boundary": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "ph_track_pose_scores": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, C.c_double, _vp]),
+    "ph_track_mask_pairs": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "ph_group_batch": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, C.c_double, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 

@@ -36,8 +36,14 @@ def _refuse(**knobs) -> None:
 
 
 class SegmentationLayer(InferenceLayer):
-    """Constructor arguments and defaults of layers/segmentation.py:102-152.  ``polygon_epsilon`` is stored only (its feature is refused); the ``merge_*`` knobs are stored for ``MergeSegmentationLayer``."""
+    """Constructor arguments and defaults of layers/segmentation.py:102-152.  ``polygon_epsilon`` is stored only (its feature is refused); the ``merge_*`` knobs are stored for ``MergeSegmentationLayer``.
 
+    ``keep_label_map=True`` (not in the reference; the mask tracker's device path, ``sleap_nn_amd/tracking``): ``postprocess`` also returns ``Outputs.pred_label_map``
+    (the device label map as ``ph_seg_assign`` / ``ph_seg_gate`` wrote it), ``Outputs.pred_mask_labels`` (per frame the label of each ``pred_masks`` entry; entries
+    dropped by the area floor have no slot) and ``Outputs.pred_label_weights`` (per frame the image rows / columns each cell row / column stands for).  Only where
+    the label map carries membership: the cleanup / merge subclasses and CPU tensors leave the three fields unset."""
+
+    _KEEPS_LABEL_MAP = True  # the label map of the grouping IS the masks' membership (not after mask cleanup or the fragment merge)
     _SEG_KEY = "SegmentationHead"
     _CENTER_KEY = "InstanceCenterHead"
     _OFFSET_KEY = "CenterOffsetHead"
@@ -47,8 +53,10 @@ class SegmentationLayer(InferenceLayer):
                  distance_gate_alpha: Optional[float] = None, merge_fragments: bool = False, merge_method: str = "greedy",
                  merge_thresholds: tuple = (0.85, 0.6, 0.4), merge_w_valley: float = 1.0, merge_w_offset: float = 0.25, merge_dilate: int = 1,
                  full_res_masks: bool = False, mask_output: str = "mask", polygon_epsilon: float = 0.01,
-                 preprocess_config: Optional[PreprocessConfig] = None, postprocess_config: Optional[PostprocessConfig] = None) -> None:
+                 preprocess_config: Optional[PreprocessConfig] = None, postprocess_config: Optional[PostprocessConfig] = None, keep_label_map: bool = False) -> None:
         super().__init__(backend, preprocess_config or PreprocessConfig(), postprocess_config or PostprocessConfig(peak_threshold=0.2), output_stride, max_stride)
+        self.keep_label_map = bool(keep_label_map)
+        self._axis_cache: dict = {}
         _refuse(mask_cleanup=(bool(mask_cleanup), False), mask_cleanup_radius=(int(mask_cleanup_radius) if int(mask_cleanup_radius) > 0 else 0, 0),
                 merge_fragments=(bool(merge_fragments), False), mask_output=(str(mask_output), "mask"))
         self.fg_threshold = fg_threshold
@@ -90,6 +98,10 @@ class SegmentationLayer(InferenceLayer):
     def _mask_to_original(self, mask: np.ndarray, info: PreprocInfo, b: int) -> np.ndarray:
         """Output-stride mask -> original resolution: nearest upsample to the processed size, crop the bottom / right pad, nearest resize back
         (layers/segmentation.py:327-364)."""
+        return self._map_to_original(mask, info, b).numpy() > 0.5
+
+    def _map_to_original(self, mask: np.ndarray, info: PreprocInfo, b: int) -> torch.Tensor:
+        """The resample of ``_mask_to_original`` on any (h, w) map of small numbers, as float32 (nearest: the values come through unchanged)."""
         proc_h, proc_w = info.processed_size
         orig_h, orig_w = info.original_size
         if proc_h == 0 or proc_w == 0:
@@ -104,7 +116,30 @@ class SegmentationLayer(InferenceLayer):
         t = t[:, :, :scaled_h, :scaled_w]
         if (scaled_h, scaled_w) != (orig_h, orig_w):
             t = F.interpolate(t, size=(orig_h, orig_w), mode="nearest")
-        return t[0, 0].numpy() > 0.5
+        return t[0, 0]
+
+    def axis_index_maps(self, info: PreprocInfo, b: int, map_hw) -> tuple:
+        """``(row_index, col_index)``: the label-map row each IMAGE row reads, and the column each image column reads, when a ``pred_masks`` entry of this layer
+        is decoded to the image grid (``decode_mask_to_image_res``).  The resample is separable.  Stride-resolution entries: the integer rule
+        ``(Y * valid_h) // He`` over the extent ``He = round(valid_h / sy)`` (``place_crop_masks``); ``full_res_masks``: the composition in ``_mask_to_original``,
+        run on an index map.  Cached per geometry."""
+        h, w = int(map_hw[0]), int(map_hw[1])
+        key = (h, w, tuple(info.original_size), tuple(info.processed_size), self._eff(info, b), float(info.input_scale), int(info.output_stride), self.full_res_masks)
+        hit = self._axis_cache.get(key)
+        if hit is not None:
+            return hit
+        if self.full_res_masks:
+            rows = self._map_to_original(np.broadcast_to(np.arange(h, dtype=np.float32)[:, None], (h, w)), info, b)[:, 0].numpy().astype(np.int64)
+            cols = self._map_to_original(np.broadcast_to(np.arange(w, dtype=np.float32)[None, :], (h, w)), info, b)[0, :].numpy().astype(np.int64)
+        else:
+            m, scale, _off = self._mask_to_stride(np.zeros((h, w), dtype=bool), info, b)
+            He, We = int(round(m.shape[0] / scale[1])), int(round(m.shape[1] / scale[0]))
+            rows = (np.arange(He, dtype=np.int64) * m.shape[0]) // max(He, 1)
+            cols = (np.arange(We, dtype=np.int64) * m.shape[1]) // max(We, 1)
+        if len(self._axis_cache) >= 16:
+            self._axis_cache.clear()
+        self._axis_cache[key] = (rows, cols)
+        return rows, cols
 
     @staticmethod
     def _eff(info: PreprocInfo, b: int) -> float:
@@ -137,9 +172,17 @@ class SegmentationLayer(InferenceLayer):
                                          center_nms_kernel=self.center_nms_kernel, distance_gate_alpha=self.distance_gate_alpha,
                                          distance_gate_iters=self.distance_gate_iters, mask_cleanup=self.mask_cleanup, **self._grouping_kw())
         pred_masks: List[List[dict]] = []
+        kept: List[List[int]] = []
         for b in range(g.labels.shape[0]):
             frame = [self._package(inst["mask"], inst["score"], info, b) for inst in g.instances(b, self.output_stride)]
             pred_masks.append([m for m in frame if m is not None])
+            kept.append([int(k) for k, m in zip(np.nonzero(g.counts[b] > 0)[0], frame) if m is not None])  # (``Grouping.instances`` walks the same labels in this order)
+        if self.keep_label_map and self._KEEPS_LABEL_MAP and g.labels_dev is not None:
+            from sleap_nn_amd.tracking.scoring import axis_weights
+
+            h, w = g.labels.shape[1:]
+            weights = [axis_weights(*self.axis_index_maps(info, b, (h, w)), h, w) for b in range(g.labels.shape[0])]
+            return Outputs(pred_masks=pred_masks, preprocess_info=info, pred_label_map=g.labels_dev, pred_mask_labels=kept, pred_label_weights=weights)
         return Outputs(pred_masks=pred_masks, preprocess_info=info)
 
 

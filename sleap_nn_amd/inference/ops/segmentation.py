@@ -59,7 +59,8 @@ class Grouping:
     instance's kept component, ``holes`` per frame the filled pixels as int32 (K, 2) = (pixel index y * w + x, label), instance-major and in raster order
     inside an instance (they may lie on other instances' pixels), and ``counts`` the cleaned areas (component + holes).  After the fragment merge an entry
     is a group: ``labels`` index the groups, ``centers`` / ``scores`` are the representative's, ``counts`` the members' sum, and ``members`` per frame lists
-    each group's original centre indices."""
+    each group's original centre indices.  ``labels_dev``: on the device path without cleanup or merge, the device tensor ``labels`` was read from (the mask
+    tracker's tables read it in place)."""
 
     labels: np.ndarray
     centers: List[np.ndarray]
@@ -67,6 +68,7 @@ class Grouping:
     counts: List[np.ndarray]
     holes: Optional[List[np.ndarray]] = None
     members: Optional[List[List[List[int]]]] = None
+    labels_dev: Optional[torch.Tensor] = None
 
     def instances(self, b: int, output_stride: int) -> List[Dict]:
         """The reference's per-frame list (segmentation.py:213-237): ``{"mask", "center", "score"}`` per non-empty instance, in centre order; ``center`` in input pixels."""
@@ -441,6 +443,8 @@ def group_finish(hd: dict) -> Grouping:
         holes = [cl["holes"][b, : n_holes[b]].numpy().copy() for b in range(B)]
     out = Grouping(hd["labels"].numpy().copy(), [cen[b, : n_cen[b]].copy() for b in range(B)], [sc[b, : n_cen[b]].copy() for b in range(B)],
                    [pix[b, : n_cen[b]].copy() for b in range(B)], holes)
+    if not cl and not mg:
+        out.labels_dev = hd["dev"][1]
     if mg:
         er = mg["erec"].numpy()[B:].reshape(B, mg["edge_cap"], 5)
         mom = mg["mom"].numpy()

@@ -11,7 +11,7 @@ import torch
 
 from sleap_nn_amd.inference.preprocess_info import PreprocInfo
 
-_HEAVY = ("original_image", "processed_image", "crops", "pred_confmaps", "pred_pafs", "pred_class_maps", "pred_paf_graph")
+_HEAVY = ("original_image", "processed_image", "crops", "pred_confmaps", "pred_pafs", "pred_class_maps", "pred_paf_graph", "pred_label_map")
 
 
 @dataclass(eq=False, repr=False)
@@ -44,6 +44,15 @@ class Outputs:
     # pred_masks, and the entries per frame, int32 (B,) -- the mask-stack form sleap_nn_amd.evaluation reads without a host round trip
     pred_mask_stack: Optional[torch.Tensor] = None
     pred_mask_counts: Optional[torch.Tensor] = None
+    # tracking (sleap_nn_amd/tracking): the track id of every instance slot, int64 (B, I), -1 = no track (instance_tracking_scores holds the scores); for masks the
+    # tracker writes "track_id" / "tracking_score" into the pred_masks entries instead.  track_objects: id -> sio.Track, shared by the batches of one run
+    instance_track_ids: Optional[torch.Tensor] = None
+    track_objects: Optional[Dict[int, Any]] = None
+    # SegmentationLayer(keep_label_map=True): the device label map (B, h, w) the pred_masks entries were cut from (-1 = background), per frame the label of each
+    # entry, and per frame (row_weight int32 (h,), col_weight int32 (w,)): the image rows / columns a cell row / column stands for on the image grid
+    pred_label_map: Optional[torch.Tensor] = None
+    pred_mask_labels: Optional[List[List[int]]] = None
+    pred_label_weights: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None
     preprocess_info: Optional[PreprocInfo] = None
     frame_indices: Optional[torch.Tensor] = None
     video_indices: Optional[torch.Tensor] = None
@@ -135,6 +144,7 @@ class Outputs:
         iscore = self._host("instance_scores", b)
         tscore = self._host("instance_tracking_scores", b)
         cls = self._host("pred_class_inds", b)
+        tids = self._host("instance_track_ids", b)
         for i in range(kp.shape[0]):
             if np.isnan(kp[i]).all():
                 continue  # NaN-padded slot
@@ -145,6 +155,10 @@ class Outputs:
                 c = int(cls[i, 0]) if cls is not None else i
                 if 0 <= c < n_tracks:
                     row["track_index"] = c
+                if tscore is not None:
+                    row["tracking_score"] = float(tscore[i])
+            elif tids is not None and tids[i] >= 0:  # the tracker's identity: one track per id, ``track_<id>``
+                row["track_id"] = int(tids[i])
                 if tscore is not None:
                     row["tracking_score"] = float(tscore[i])
             yield row
@@ -163,6 +177,12 @@ class Outputs:
             kw = {}
             if "track_index" in row:
                 kw["track"] = tracks[row["track_index"]]
+            if "track_id" in row:
+                if self.track_objects is None:
+                    self.track_objects = {}
+                if row["track_id"] not in self.track_objects:
+                    self.track_objects[row["track_id"]] = sio.Track(f"track_{row['track_id']}")
+                kw["track"] = self.track_objects[row["track_id"]]
             if "tracking_score" in row:
                 kw["tracking_score"] = row["tracking_score"]
             out.append(sio.PredictedInstance.from_numpy(points_data=row["points"], point_scores=row["point_scores"], score=row["score"], skeleton=skeleton, **kw))

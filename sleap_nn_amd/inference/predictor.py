@@ -2,8 +2,10 @@
 
 Surface mirror of ``sleap_nn/inference/predictor.py`` (``from_model_paths`` :925, ``predict`` :1582,
 ``_batch_iter`` :1948, ``_predict_streaming_pipelined`` :2009-2074) for in-memory frame arrays
-(the reference's ``NumpyProvider`` case); video decoding, ``.slp`` writing, filters and tracking
-are outside the hot path.  The bottom-up pipeline overlaps the C++ grouping of batch *i* (a
+(the reference's ``NumpyProvider`` case); video decoding, ``.slp`` writing and filters
+are outside the hot path.  Tracking: ``from_model_paths(..., tracker_config=TrackerConfig(...))`` applies ``sleap_nn_amd.tracking.apply_tracking``
+to the batches of a ``predict`` call in order (pair scores native, mask pair tables on the device); with ``tracker_config=None`` nothing is tracked
+and nothing changes.  The bottom-up pipeline overlaps the C++ grouping of batch *i* (a
 worker thread; the ctypes call releases the GIL) with the GPU work of batch *i+1*.
 """
 from __future__ import annotations
@@ -187,7 +189,8 @@ _REPLICA_MAX_PARAMS = 16_000_000
 
 
 class Predictor:
-    def __init__(self, layer, batch_size: int = 4, use_graph: bool = True, window: int = 3, replicas: Sequence = ()) -> None:
+    def __init__(self, layer, batch_size: int = 4, use_graph: bool = True, window: int = 3, replicas: Sequence = (), tracker_config=None) -> None:
+        self.tracker_config = tracker_config  # a sleap_nn_amd.tracking.TrackerConfig: predict() tracks its batches with a fresh Tracker per call
         self.layer = layer  # any object exposing predict(image) -> Outputs (predictor.py:852-853)
         self.batch_size = batch_size
         self.use_graph = use_graph  # pipelined paths replay the GPU stage of a batch as one hipGraph per input shape
@@ -204,8 +207,11 @@ class Predictor:
                          min_mask_area: int = 0, center_nms_kernel: int = 3, distance_gate_alpha: Optional[float] = None, full_res_masks: bool = False,
                          mask_cleanup: bool = False, mask_cleanup_radius: int = 0, merge_fragments: bool = False, merge_method: str = "greedy",
                          merge_thresholds: tuple = (0.85, 0.6, 0.4), merge_w_valley: float = 1.0, merge_w_offset: float = 0.25, merge_dilate: int = 1,
-                         mask_output: str = "mask", **paf_kw) -> "Predictor":
-        """``fg_threshold`` / ``min_mask_area`` / ``max_instances`` / ``center_nms_kernel`` / ``distance_gate_alpha`` / ``full_res_masks``: knobs of the segmentation
+                         mask_output: str = "mask", tracker_config=None, **paf_kw) -> "Predictor":
+        """``tracker_config``: a ``sleap_nn_amd.tracking.TrackerConfig``; ``predict`` then assigns track ids across its frames (``Outputs.instance_track_ids`` /
+        ``instance_tracking_scores``, or ``"track_id"`` / ``"tracking_score"`` in the ``pred_masks`` entries); a bottom-up segmentation layer is told to keep its
+        device label map for the tracker's tables.  ``None``: no tracking, every output as without this argument.
+        ``fg_threshold`` / ``min_mask_area`` / ``max_instances`` / ``center_nms_kernel`` / ``distance_gate_alpha`` / ``full_res_masks``: knobs of the segmentation
         layers (``bottomup_segmentation`` / ``semantic_segmentation`` run directories; defaults as the reference; ``mask_cleanup=True`` builds ``CleanupSegmentationLayer``:
         largest component + hole fill per instance on the device; ``merge_fragments=True`` builds ``MergeSegmentationLayer``: touching fragments fused by the
         RAG merge with the ``merge_*`` knobs, its pair tables on the device; both together, ``mask_cleanup_radius`` and ``mask_output`` are accepted so that a value
@@ -231,7 +237,9 @@ class Predictor:
         if streams > 1 and ((isinstance(layer, (BottomUpLayer, SingleInstanceLayer)) and small(layer)) or
                             (isinstance(layer, TopDownLayer) and getattr(layer, "_PIPELINED", True) and small(layer.centroid_layer) and small(layer.centered_instance_layer))):
             replicas = [_select_layer(assets, device, post, max_instances, **paf_kw) for _ in range(streams - 1)]
-        return cls(layer, batch_size, replicas=replicas)
+        if tracker_config is not None and isinstance(layer, SegmentationLayer):
+            layer.keep_label_map = True
+        return cls(layer, batch_size, replicas=replicas, tracker_config=tracker_config)
 
     def _staging(self) -> "_PinnedRing":
         ring = self.__dict__.get("_ring")
@@ -245,7 +253,15 @@ class Predictor:
             yield s, frames[s : s + self.batch_size]
 
     def predict(self, frames, pipelined: bool = True) -> List[Outputs]:
-        """``frames``: (N, H, W[, C]) or (N, C, H, W) uint8/float array or tensor. One ``Outputs`` per batch."""
+        """``frames``: (N, H, W[, C]) or (N, C, H, W) uint8/float array or tensor. One ``Outputs`` per batch; tracked when a ``tracker_config`` is set."""
+        outs = self._predict(frames, pipelined)
+        if self.tracker_config is not None:
+            from sleap_nn_amd.tracking import apply_tracking
+
+            outs = apply_tracking(outs, self.tracker_config)
+        return outs
+
+    def _predict(self, frames, pipelined: bool = True) -> List[Outputs]:
         if isinstance(frames, np.ndarray):
             frames = torch.from_numpy(frames)
         if pipelined and isinstance(self.layer, BottomUpLayer):
