@@ -56,7 +56,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 117
+#define PH_VERSION 118
 
 /* error codes */
 #define PH_OK 0
@@ -360,6 +360,16 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_MLP 15      /* cnblock_mlp_kernel: Linear(C, 4C) + GELU + Linear(4C, C) + layer scale + residual of a CNBlock in one launch (both Linear ops report it; the second has no launch of its own) */
 #define PH_KV_FUSED 11    /* no launch of its own: a 1x1 head computed in the epilogue of the conv that produces its input */
 int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
+
+/* Which workspace byte ranges every launch of the LAST ph_model_forward was handed, as the run-time routing decided them (tests of the
+ * planner / router agreement: no launch may write a range it, or a later launch, still reads).  One row of six int64 per range:
+ * {op index, launch ordinal within the op, 0 = source | 1 = destination, activation slot (-1: the scratch region), byte offset into
+ * the workspace, bytes}.  A range is recorded
+ * where its pointer goes into the launcher's arguments; an op without a launch of its own (PH_KV_FUSED, the second PH_KV_MLP op, a
+ * folded bilinear, a LayerNorm applied by the depthwise kernel, a pool written by a conv epilogue) has no rows: its ranges appear under
+ * the op that did the work.  The scratch region behind the slots is a destination of the launches that are handed it.  Host-side
+ * bookkeeping of the forward: no launch, no device access.  Writes min(*n_rows, max_rows) rows; rows may be NULL when max_rows is 0. */
+int ph_model_last_ranges(const ph_model* m, int64_t* rows, int32_t max_rows, int32_t* n_rows);
 
 /* Diagnostic: when buf_dev != NULL the conv3x3 kernels that carry a probe write into the record block of
  * their op -- 32768 x uint64 per op of the program, op i at buf_dev + 32768 i words (the buffer must hold

@@ -477,6 +477,17 @@ class Model:
         L.check(L.lib().ph_model_last_kernels(self._handle, arr, n))
         return list(arr)
 
+    def last_ranges(self):
+        """Workspace byte ranges every launch of the LAST forward was handed (``ph_model_last_ranges``), as the run-time routing
+        decided them: a list of ``(op index, launch ordinal within the op, is_dst, slot, byte offset, bytes)``.  An op without a
+        launch of its own has no entry; the scratch region behind the slots (slot -1) counts as a destination of the launches that
+        use it."""
+        n = C.c_int32()
+        L.check(L.lib().ph_model_last_ranges(self._handle, None, 0, C.byref(n)))
+        arr = (C.c_int64 * (6 * max(1, n.value)))()
+        L.check(L.lib().ph_model_last_ranges(self._handle, arr, n.value, C.byref(n)))
+        return [(int(arr[6 * i]), int(arr[6 * i + 1]), bool(arr[6 * i + 2]), int(arr[6 * i + 3]), int(arr[6 * i + 4]), int(arr[6 * i + 5])) for i in range(n.value)]
+
     def op_table(self, batch: int, height: int, width: int):
         """Per op: label, kind, algorithmic FLOPs (2*Cin*Cout*k*k*Hout*Wout*B for convolutions, SURVEY
         section 8d) and algorithmic HBM bytes (input read once + output written once, logical channels)."""

@@ -263,6 +263,43 @@ int forward_format(const ph_model* m) {
   return m->conv_precision == 1 ? FMT_SPLIT : FMT_F16;
 }
 
+static bool only_reader_is_next(const ph_model* m, size_t i) {  // nothing but op i + 1 reads op i's dst
+  const int slot = m->ops[i].d.dst;
+  for (size_t k = 0; k < m->ops.size(); ++k)
+    if (k != i + 1 && (m->ops[k].d.src0 == slot || m->ops[k].d.src1 == slot)) return false;
+  return true;
+}
+
+// inference plans, plain fp16: conv(<= 16 -> 32) + ReLU whose only reader is the next op, a conv(32 -> 32) (+ ReLU, + pool): both in ONE launch, the intermediate
+// tensor stays in LDS (block2_c32_f16_kernel).  The conditions are on PADDED channel counts, and the pool is optional: with three convs per block the router takes
+// enc0's second and third conv ((16 -> 16), (16 -> 16) + pool: weights and biases zero-padded to 32) and enc1's first and second ((16 -> 32), (32 -> 32) with NO pool
+// behind it: dst_pool = nullptr, only the full-resolution tensor is stored) -- both under test in tests/test_gpu_block_structure.py
+bool fuses_block2(const ph_model* m, size_t i, int fmt, bool reuse) {
+  if (fmt != FMT_F16 || !m->block_fuse || !reuse || i + 1 >= m->ops.size()) return false;
+  const PackedOp& op = m->ops[i];
+  const PackedOp& nxo = m->ops[i + 1];
+  const ph_op_desc& d = op.d;
+  const ph_op_desc& nx = nxo.d;
+  if (!(d.kind == PH_OP_CONV && d.src0 >= 0 && d.src1 < 0 && d.ksize == 3 && d.dst2 < 0 && op.bn == 32 && fmt_cpad(fmt, d.cout) == 32 && fmt_cpad(fmt, d.cin0) == 32 && d.cin0 <= 16)) return false;
+  if (!(nx.kind == PH_OP_CONV && nx.ksize == 3 && nx.src0 == d.dst && nx.src1 < 0 && nxo.bn == 32 && fmt_cpad(fmt, nx.cout) == 32 && nx.cin0 == d.cout)) return false;
+  return only_reader_is_next(m, i);
+}
+
+// CNBlock's MLP in one launch (inference plans that recycle slots: the 4C-wide hidden tensor is nobody else's business): Linear + GELU whose only reader is a
+// Linear with layer scale + residual, both at a width cnblock_mlp_kernel takes
+bool fuses_mlp(const ph_model* m, size_t i, int fmt, bool reuse) {
+  if (!m->mlp_fuse || !reuse || i + 1 >= m->ops.size()) return false;
+  const PackedOp& op = m->ops[i];
+  const PackedOp& nxo = m->ops[i + 1];
+  const ph_op_desc& d = op.d;
+  const ph_op_desc& nx = nxo.d;
+  if (!(d.kind == PH_OP_LINEAR && (d.flags & PH_FLAG_GELU) && op.w_mlp_dev && d.src0 >= 0 && fmt_cpad(fmt, d.cin0) == d.cin0)) return false;
+  if (!(nx.kind == PH_OP_LINEAR && (nx.flags & PH_FLAG_SCALE_RESIDUAL) && nxo.w_mlp_dev && nx.src0 == d.dst && nx.src1 >= 0 && nx.src1 != d.dst && nx.cin0 == d.cout && nx.cout == d.cin0 &&
+        fmt_cpad(fmt, nx.cout) == nx.cout))
+    return false;
+  return only_reader_is_next(m, i);
+}
+
 int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
   plan.slots.assign(m->n_slots, SlotShape());
   plan.fmt = fmt;
@@ -335,8 +372,13 @@ int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
     ++op_i;
     // Run-time fusions let op i write op i + 1's dst one op early (pool_peephole: a conv's epilogue writes the pool that follows it;
     // fuse_gelu_fwd: a Linear writes its GELU or its layer-scale + residual; dw_ln_fuse: a depthwise / stem conv writes its LayerNorm).  Such a dst must not land on
-    // a range op i is still reading, so the releases due before a pool / GELU / LayerNorm of the previous op's output wait one op.
-    const bool forwarded = op_i > 0 && (d.kind == PH_OP_POOL || d.kind == PH_OP_GELU || d.kind == PH_OP_LAYERNORM || d.kind == PH_OP_SCALE_ADD) && d.src0 >= 0 && d.src0 == m->ops[op_i - 1].d.dst;
+    // a range op i is still reading, so the releases due before a pool / GELU / LayerNorm of the previous op's output wait one op.  The same for the second conv of a pair
+    // block2_c32_f16_kernel takes (fuses_block2, the router's own predicate): its dst and pooled dst are stored by the launch that DMA-loads the first conv's src0, halo
+    // pixels of other workgroups' tiles included, tile rounds apart -- that src0 (released here: its last reader is the first conv) must stay out of the free list.
+    // (cnblock_mlp_kernel's pair is NOT held: a row tile reads all of its x and residual rows before it stores them and no other tile reads them, so y exactly on x
+    // is safe; ph_model_forward refuses the fusion for any other overlap.)
+    const bool forwarded = op_i > 0 && (((d.kind == PH_OP_POOL || d.kind == PH_OP_GELU || d.kind == PH_OP_LAYERNORM || d.kind == PH_OP_SCALE_ADD) && d.src0 >= 0 && d.src0 == m->ops[op_i - 1].d.dst) ||
+                                        fuses_block2(m, (size_t)op_i - 1, fmt, reuse));
     if (reuse && !forwarded)  // slots whose last reader ran before this op (a slot nobody reads is released right after the op that wrote it)
       for (int sl = 0; sl < m->n_slots; ++sl)
         if (!released[sl] && plan.slots[sl].offset >= 0 && slot_bytes[sl] > 0 && std::max(last_use[sl], plan.slots[sl].def_op) < op_i) release(sl);
@@ -1014,7 +1056,28 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
     return PH_E_WORKSPACE;
   }
   char* ws = static_cast<char*>(workspace_dev);
-  auto slot_ptr = [&](int sidx) { return reinterpret_cast<float*>(ws + plan.slots[sidx].offset); };
+  // Every slot pointer that goes into a launcher's arguments is taken through rd() (a source) or wr() (a destination), which note the slot's byte range under the
+  // current op and launch (ph_model_last_ranges): the record follows the routing below, whatever it decides.  Host bookkeeping only.
+  size_t op_index = 0;
+  int launch_no = 0;  // launch ordinal within the current op
+  std::vector<RangeRec>& rr = m->last_ranges;
+  rr.clear();
+  auto note = [&](int is_dst, int slot, int64_t offset, int64_t bytes) { rr.push_back(RangeRec{(int)op_index - 1, launch_no, is_dst, slot, offset, bytes}); };
+  auto slot_bytes = [&](int sidx) { const SlotShape& q = plan.slots[sidx]; return (int64_t)batch * q.h * q.w * q.cp * plan.bpc; };
+  auto rd = [&](int sidx) { note(0, sidx, plan.slots[sidx].offset, slot_bytes(sidx)); return reinterpret_cast<float*>(ws + plan.slots[sidx].offset); };
+  auto wr = [&](int sidx) { note(1, sidx, plan.slots[sidx].offset, slot_bytes(sidx)); return reinterpret_cast<float*>(ws + plan.slots[sidx].offset); };
+  auto note_tmp = [&](int is_dst) { note(is_dst, -1, plan.tmp_offset, plan.tmp_bytes); };  // the scratch region behind the slots
+  auto unnote = [&](int is_dst, int sidx) {  // a pointer of the current launch that was replaced before the launch
+    for (size_t k = rr.size(); k-- > 0 && rr[k].op == (int)op_index - 1;)
+      if (rr[k].launch == launch_no && rr[k].is_dst == is_dst && rr[k].slot == sidx) {
+        rr.erase(rr.begin() + k);
+        return;
+      }
+  };
+  auto launch_before = [&]() {  // the ranges noted so far belong to a launch that runs AFTER the one about to be made (a deferred bilinear produced after all)
+    for (size_t k = rr.size(); k-- > 0 && rr[k].op == (int)op_index - 1;)
+      if (rr[k].launch == launch_no) rr[k].launch += 1;
+  };
   if (m->profiling) {
     rc = drain_events(m);
     if (rc != PH_OK) return rc;
@@ -1027,7 +1090,6 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
       }
     m->wino4_stale = false;
   }
-  size_t op_index = 0;
   m->last_variant.assign(m->ops.size(), PH_KV_NONE);
   int* const kv = m->last_variant.data();
   bool skip_next_gelu = false, skip_next_scale_add = false, skip_next_linear = false;
@@ -1040,6 +1102,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
     const ph_op_desc& d = op.d;
     if (m->profiling) PH_HIP_CHECK(hipEventRecord(m->ev[op_index], s));
     ++op_index;
+    launch_no = 0;
     switch (d.kind) {
       case PH_OP_INPUT_CONV: {
         PH_REQUIRE(d.cin0 == in_channels, "input has %d channels, network expects %d", in_channels, d.cin0);
@@ -1047,7 +1110,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         a.src = input_dev;
         a.w = op.w_dev;
         a.bias = op.b_dev;
-        a.dst = slot_ptr(d.dst);
+        a.dst = wr(d.dst);
         a.dtype = in_dtype;
         a.cin = d.cin0;
         a.coutp = pad16(d.cout);
@@ -1071,8 +1134,8 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         a.w1w = op.w_wino_dev;
         a.w1w2 = op.w_stem2_dev;
         a.b1 = op.b2_dev;
-        a.dst_full = d.dst >= 0 ? slot_ptr(d.dst) : nullptr;
-        a.dst_pool = slot_ptr(d.dst2);
+        a.dst_full = d.dst >= 0 ? wr(d.dst) : nullptr;
+        a.dst_pool = wr(d.dst2);
         a.dtype = in_dtype;
         a.cin = d.cin0;
         a.B = batch;
@@ -1094,28 +1157,19 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         if (fmt != FMT_F32) {
           PH_REQUIRE(s0.c == d.cin0 && (d.src1 < 0 || plan.slots[d.src1].c == d.cin1), "conv channel mismatch");
           const SlotShape& so = plan.slots[d.dst];
-          if (fmt == FMT_F16 && m->block_fuse && plan.reuse && d.src1 < 0 && d.ksize == 3 && d.dst2 < 0 && op.bn == 32 && so.cp == 32 && s0.cp == 32 && d.cin0 <= 16 &&
-              op_index < m->ops.size()) {
-            // inference plans, plain fp16: conv(<= 16 -> 32) + ReLU whose only reader is the next op, a conv(32 -> 32) (+ ReLU, + pool): both in ONE launch, the intermediate
-            // tensor stays in LDS (block2_c32_f16_kernel).  The conditions are on PADDED channel counts, and the pool is optional: with three convs per block the router takes
-            // enc0's second and third conv ((16 -> 16), (16 -> 16) + pool: weights and biases zero-padded to 32) and enc1's first and second ((16 -> 32), (32 -> 32) with NO pool
-            // behind it: dst_pool = nullptr, only the full-resolution tensor is stored) -- both under test in tests/test_gpu_block_structure.py
+          if (fuses_block2(m, op_index - 1, fmt, plan.reuse)) {  // (the predicate build_plan holds this pair's releases on)
             const PackedOp& nxo = m->ops[op_index];
             const ph_op_desc& nx = nxo.d;
-            bool fuse = nx.kind == PH_OP_CONV && nx.ksize == 3 && nx.src0 == d.dst && nx.src1 < 0 && nxo.bn == 32 && plan.slots[nx.dst].cp == 32 && nx.cin0 == d.cout && nxo.w_f16_dev[1] &&
-                        op.w_f16_dev[1];
-            for (size_t k = 0; fuse && k < m->ops.size(); ++k)
-              if (k != op_index && (m->ops[k].d.src0 == d.dst || m->ops[k].d.src1 == d.dst)) fuse = false;
-            if (fuse) {
+            if (nxo.w_f16_dev[1] && op.w_f16_dev[1] && so.cp == 32 && s0.cp == 32 && plan.slots[nx.dst].cp == 32) {
               Block2Args b2{};
-              b2.src = slot_ptr(d.src0);
+              b2.src = rd(d.src0);
               b2.wa = op.w_f16_dev[1];
               b2.wb = nxo.w_f16_dev[1];
               b2.ba = op.b_dev;
               b2.bb = nxo.b_dev;
               const bool full_unread = nx.dst2 >= 0 && !plan.unread.empty() && plan.unread[nx.dst];
-              b2.dst_full = full_unread ? nullptr : slot_ptr(nx.dst);
-              b2.dst_pool = nx.dst2 >= 0 ? slot_ptr(nx.dst2) : nullptr;
+              b2.dst_full = full_unread ? nullptr : wr(nx.dst);
+              b2.dst_pool = nx.dst2 >= 0 ? wr(nx.dst2) : nullptr;
               b2.B = batch;
               b2.H = s0.h;
               b2.W = s0.w;
@@ -1130,18 +1184,18 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           }
           const int cdiv = fmt == FMT_F16 ? 32 : 16;
           ConvF16Args f{};
-          f.src0 = slot_ptr(d.src0);
+          f.src0 = rd(d.src0);
           f.rs0 = s0.cp / rs_div;
           f.chunks0 = s0.cp / cdiv;
           if (d.src1 >= 0) {
-            f.src1 = slot_ptr(d.src1);
+            f.src1 = rd(d.src1);
             f.rs1 = plan.slots[d.src1].cp / rs_div;
             f.chunks1 = plan.slots[d.src1].cp / cdiv;
           }
           f.wpack = op.w_f16_dev[fmt == FMT_F16 ? 1 : 0];
           f.bias = op.b_dev;
-          f.dst = slot_ptr(d.dst);
-          f.dst_pool = d.dst2 >= 0 ? slot_ptr(d.dst2) : nullptr;
+          f.dst = wr(d.dst);
+          f.dst_pool = d.dst2 >= 0 ? wr(d.dst2) : nullptr;
           f.skip_dst = (f.dst_pool && plan.reuse && !plan.unread.empty() && plan.unread[d.dst]) ? 1 : 0;
           f.rs_dst = so.cp / rs_div;
           f.coutp = so.cp;
@@ -1186,9 +1240,10 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
             bool on_rows = false;
             if (fmt == FMT_F16 && m->conv_f16_rows) {
               ConvF16Args r = f;
+              const size_t mark = rr.size();
               if (deferred_up >= 0) {
                 const ph_op_desc& up = m->ops[deferred_up].d;
-                r.src1 = slot_ptr(up.src0);
+                r.src1 = rd(up.src0);
                 r.rs1 = plan.slots[up.src0].cp / rs_div;
                 r.src1_lowres = 1;
                 r.rows_blend16 = m->upsample_f16math ? 1 : 0;
@@ -1201,13 +1256,18 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
               if (c_rows >= 0 && (m->conv_f16_rows >= 2 || c_rows < 0.95 * c_old)) {  // (the estimates are good to a few per cent: a tie stays with the round-2 kernel, measured 6 - 8 % faster on the 2-chunk 192 x 192 layers of cfg5)
                 f = r;
                 on_rows = true;
+                if (deferred_up >= 0) unnote(0, d.src1);  // (the half-resolution tensor took the up-sampled one's place)
+              } else {
+                rr.resize(mark);
               }
             }
             if (deferred_up >= 0 && !on_rows) {
               const ph_op_desc& up = m->ops[deferred_up].d;
               const SlotShape& sl = plan.slots[up.src0];
-              rc = launch_upsample_fmt(fmt, slot_ptr(up.src0), slot_ptr(up.dst), batch, sl.h, sl.w, sl.cp, s, (fmt == FMT_F16 && m->upsample_f16math) ? 1 : 0);
+              launch_before();
+              rc = launch_upsample_fmt(fmt, rd(up.src0), wr(up.dst), batch, sl.h, sl.w, sl.cp, s, (fmt == FMT_F16 && m->upsample_f16math) ? 1 : 0);
               if (rc != PH_OK) return rc;
+              ++launch_no;
             }
             deferred_up = -1;
             if (on_rows) {
@@ -1229,13 +1289,13 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         if (d.ksize != 3) {  // k x k "same" conv: k^2-tap row GEMM
           PH_REQUIRE(s0.c == d.cin0 && (d.src1 < 0 || plan.slots[d.src1].c == d.cin1), "conv channel mismatch");
           GemmArgs g{};
-          g.src0 = slot_ptr(d.src0);
+          g.src0 = rd(d.src0);
           g.c0p = s0.cp;
-          g.src1 = d.src1 >= 0 ? slot_ptr(d.src1) : nullptr;
+          g.src1 = d.src1 >= 0 ? rd(d.src1) : nullptr;
           g.c1p = d.src1 >= 0 ? plan.slots[d.src1].cp : 0;
           g.wpack = op.w_gemm_dev;
           g.bias = op.b_gemm_dev;
-          g.dst = slot_ptr(d.dst);
+          g.dst = wr(d.dst);
           g.zeros = m->zeros_dev;
           g.coutp = pad16(d.cout);
           g.bn = op.bn_g;
@@ -1248,18 +1308,21 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           g.late_split = m->gemm_late_split;
           kv[op_index - 1] = PH_KV_ROWGEMM;
           rc = launch_gemm(g, s);
-          if (rc == PH_OK && d.dst2 >= 0) rc = launch_pool(slot_ptr(d.dst), slot_ptr(d.dst2), batch, s0.h, s0.w, g.coutp, s);  // the fused-pool flag of the plan, unfused here
+          if (rc == PH_OK && d.dst2 >= 0) {  // the fused-pool flag of the plan, unfused here
+            ++launch_no;
+            rc = launch_pool(rd(d.dst), wr(d.dst2), batch, s0.h, s0.w, g.coutp, s);
+          }
           break;
         }
         ConvArgs a{};
-        a.src0 = slot_ptr(d.src0);
+        a.src0 = rd(d.src0);
         a.c0p = s0.cp;
-        a.src1 = d.src1 >= 0 ? slot_ptr(d.src1) : nullptr;
+        a.src1 = d.src1 >= 0 ? rd(d.src1) : nullptr;
         a.c1p = d.src1 >= 0 ? plan.slots[d.src1].cp : 0;
         PH_REQUIRE(s0.c == d.cin0 && (d.src1 < 0 || plan.slots[d.src1].c == d.cin1), "conv channel mismatch");
         a.wpack = op.w_dev;
         a.bias = op.b_dev;
-        a.dst = slot_ptr(d.dst);
+        a.dst = wr(d.dst);
         a.coutp = pad16(d.cout);
         a.B = batch;
         a.H = s0.h;
@@ -1267,7 +1330,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         a.relu = (d.flags & PH_FLAG_RELU) ? 1 : 0;
         a.bn = op.bn;
         a.clock_probe = m->clock_probe ? m->clock_probe + PH_PROBE_WORDS_PER_OP * (op_index - 1) : nullptr;  // one record block per op (diagnostic builds / kernels that stamp)
-        a.dst_pool = d.dst2 >= 0 ? slot_ptr(d.dst2) : nullptr;
+        a.dst_pool = d.dst2 >= 0 ? wr(d.dst2) : nullptr;
         a.skip_dst = (a.dst_pool && plan.reuse && !plan.unread.empty() && plan.unread[d.dst]) ? 1 : 0;  // e.g. cfg3's second encoder block: 1 GiB per 32 frames nobody reads
         a.wpack_dma = op.w_dma_dev;
         a.wpack_wino = op.w_wino_dev;
@@ -1302,13 +1365,18 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           const ph_op_desc& up = m->ops[deferred_up].d;
           const SlotShape& sl = plan.slots[up.src0];
           ConvArgs f = a;
-          f.src1 = slot_ptr(up.src0);
+          const size_t mark = rr.size();
+          f.src1 = rd(up.src0);
           f.src1_lowres = 1;
           if ((m->use_dma && conv3x3_dma_is_wino4(f)) || conv3x3_takes_sm(f)) {
             a = f;
+            unnote(0, d.src1);  // (the half-resolution tensor took the up-sampled one's place)
           } else {
-            rc = launch_upsample(slot_ptr(up.src0), slot_ptr(up.dst), batch, sl.h, sl.w, sl.cp, s);
+            rr.resize(mark);
+            launch_before();
+            rc = launch_upsample(rd(up.src0), wr(up.dst), batch, sl.h, sl.w, sl.cp, s);
             if (rc != PH_OK) return rc;
+            ++launch_no;
           }
           deferred_up = -1;
         }
@@ -1386,13 +1454,16 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           // 2x2 max pool: when the next op is the pool of this conv's output, the epilogue writes both tensors and the pool op is skipped.
           const ph_op_desc& nx = m->ops[op_index].d;
           if (nx.kind == PH_OP_POOL && nx.src0 == d.dst) {
-            a.dst_pool = slot_ptr(nx.dst);
-            if (conv3x3_dma_is_f2x2(a))  // the F(2x2,3x3) kernels (a Winograd tile is a pool window); other kernels keep the separate pool
+            a.dst_pool = wr(nx.dst);
+            if (conv3x3_dma_is_f2x2(a)) {  // the F(2x2,3x3) kernels (a Winograd tile is a pool window); other kernels keep the separate pool
               pooled_by_conv = d.dst;
-            else
+            } else {
               a.dst_pool = nullptr;
+              unnote(1, nx.dst);
+            }
           }
         }
+        if (a.split_scratch) note_tmp(1);  // (partial-sum planes of a split-K launch)
         if (on_sm) {
           kv[op_index - 1] = PH_KV_SMALLMAP;
           rc = launch_conv3x3_sm(a, s);
@@ -1408,8 +1479,9 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           break;
         }
         const SlotShape& s0 = plan.slots[d.src0];
-        rc = fmt == FMT_F32 ? launch_pool(slot_ptr(d.src0), slot_ptr(d.dst), batch, s0.h, s0.w, s0.cp, s)
-                            : launch_pool_fmt(fmt, slot_ptr(d.src0), slot_ptr(d.dst), batch, s0.h, s0.w, s0.cp, s);
+        float* const src = rd(d.src0);
+        float* const dst = wr(d.dst);
+        rc = fmt == FMT_F32 ? launch_pool(src, dst, batch, s0.h, s0.w, s0.cp, s) : launch_pool_fmt(fmt, src, dst, batch, s0.h, s0.w, s0.cp, s);
         break;
       }
       case PH_OP_UPSAMPLE: {
@@ -1439,8 +1511,10 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
             break;
           }
         }
-        rc = fmt == FMT_F32 ? launch_upsample(slot_ptr(d.src0), slot_ptr(d.dst), batch, s0.h, s0.w, s0.cp, s)
-                            : launch_upsample_fmt(fmt, slot_ptr(d.src0), slot_ptr(d.dst), batch, s0.h, s0.w, s0.cp, s, (fmt == FMT_F16 && m->upsample_f16math) ? 1 : 0);
+        float* const src = rd(d.src0);
+        float* const dst = wr(d.dst);
+        rc = fmt == FMT_F32 ? launch_upsample(src, dst, batch, s0.h, s0.w, s0.cp, s)
+                            : launch_upsample_fmt(fmt, src, dst, batch, s0.h, s0.w, s0.cp, s, (fmt == FMT_F16 && m->upsample_f16math) ? 1 : 0);
         break;
       }
       case PH_OP_CONVT: {
@@ -1450,11 +1524,12 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           const SlotShape& so = plan.slots[d.dst];
           for (int ph = 0; ph < (m->convt_one_launch ? 1 : 4) && rc == PH_OK; ++ph) {  // one launch for the four phases (grid.y), or four launches
             GemmArgs g{};
-            g.src0 = slot_ptr(d.src0);
+            launch_no = ph;
+            g.src0 = rd(d.src0);
             g.c0p = s0.cp;
             g.wpack = op.wt_phase_dev[ph];
             g.bias = op.bt_dev;
-            g.dst = slot_ptr(d.dst);
+            g.dst = wr(d.dst);
             g.zeros = m->zeros_dev;
             g.coutp = so.cp;
             g.bn = op.bn_t;
@@ -1483,8 +1558,11 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         }
         PH_REQUIRE(!op.wt_scale_dev && !(d.flags & PH_FLAG_SILU), "folded BatchNorm / SiLU on a transposed conv need the phase GEMMs (exact precision, convt_phase = 1)");
         float* tmp = reinterpret_cast<float*>(ws + plan.tmp_offset);
-        rc = launch_zero_stuff(slot_ptr(d.src0), tmp, batch, s0.h, s0.w, s0.cp / rs_div, s);  // 16-B quads: format-agnostic
+        note_tmp(1);
+        rc = launch_zero_stuff(rd(d.src0), tmp, batch, s0.h, s0.w, s0.cp / rs_div, s);  // 16-B quads: format-agnostic
         if (rc != PH_OK) break;
+        ++launch_no;
+        note_tmp(0);  // (the conv below reads the zero-stuffed tensor)
         if (fmt != FMT_F32) {
           const SlotShape& so = plan.slots[d.dst];
           ConvF16Args f{};
@@ -1493,7 +1571,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           f.chunks0 = s0.cp / (fmt == FMT_F16 ? 32 : 16);
           f.wpack = op.w_f16_dev[fmt == FMT_F16 ? 1 : 0];
           f.bias = op.b_dev;
-          f.dst = slot_ptr(d.dst);
+          f.dst = wr(d.dst);
           f.rs_dst = so.cp / rs_div;
           f.coutp = so.cp;
           f.B = batch;
@@ -1538,7 +1616,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         a.c1p = 0;
         a.wpack = op.w_dev;
         a.bias = op.b_dev;
-        a.dst = slot_ptr(d.dst);
+        a.dst = wr(d.dst);
         a.coutp = pad16(d.cout);
         a.B = batch;
         a.H = 2 * s0.h;
@@ -1561,7 +1639,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         a.src = input_dev;
         a.w = op.w_dev;
         a.bias = op.b_dev;
-        a.dst = slot_ptr(d.dst);
+        a.dst = wr(d.dst);
         a.dtype = in_dtype;
         a.cin = d.cin0;
         a.coutp = so.cp;
@@ -1583,7 +1661,8 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
               a.ln_gamma = m->ops[op_index].w_dev;
               a.ln_beta = m->ops[op_index].b_dev;
               a.ln_c = d.cout;
-              a.dst = slot_ptr(nx.dst);
+              unnote(1, d.dst);
+              a.dst = wr(nx.dst);
               fused_ln = (int)op_index;
             }
           }
@@ -1595,10 +1674,10 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         const SlotShape& s0 = plan.slots[d.src0];
         PH_REQUIRE(s0.c == d.cin0, "depthwise conv channel mismatch");
         DwConvArgs a{};
-        a.src = slot_ptr(d.src0);
+        a.src = rd(d.src0);
         a.w = op.w_dev;
         a.bias = op.b_dev;
-        a.dst = slot_ptr(d.dst);
+        a.dst = wr(d.dst);
         a.cp = s0.cp;
         a.B = batch;
         a.H = s0.h;
@@ -1614,7 +1693,8 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
               a.ln_gamma = m->ops[op_index].w_dev;
               a.ln_beta = m->ops[op_index].b_dev;
               a.ln_c = d.cout;
-              a.dst = slot_ptr(nx.dst);
+              unnote(1, d.dst);
+              a.dst = wr(nx.dst);
               fused_ln = (int)op_index;
             }
           }
@@ -1629,7 +1709,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         }
         const SlotShape& s0 = plan.slots[d.src0];
         PH_REQUIRE(s0.c == d.cin0, "LayerNorm channel mismatch");
-        rc = launch_layernorm(slot_ptr(d.src0), op.w_dev, op.b_dev, slot_ptr(d.dst), s0.c, s0.cp, (size_t)batch * s0.h * s0.w, s);
+        rc = launch_layernorm(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), s0.c, s0.cp, (size_t)batch * s0.h * s0.w, s);
         break;
       }
       case PH_OP_LINEAR:
@@ -1642,25 +1722,27 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         const SlotShape& s0 = plan.slots[d.src0];
         const SlotShape& so = plan.slots[d.dst];
         PH_REQUIRE(s0.c == d.cin0, "GEMM channel mismatch");
-        // CNBlock's MLP in one launch (inference plans that recycle slots: the 4C-wide hidden tensor is nobody else's business): Linear + GELU whose only reader is a
-        // Linear with layer scale + residual, both at a width cnblock_mlp_kernel takes
-        if (m->mlp_fuse && d.kind == PH_OP_LINEAR && (d.flags & PH_FLAG_GELU) && op.w_mlp_dev && plan.reuse && op_index < m->ops.size()) {
+        if (fuses_mlp(m, op_index - 1, fmt, plan.reuse)) {
           const PackedOp& nxo = m->ops[op_index];
           const ph_op_desc& nx = nxo.d;
-          bool pair = nx.kind == PH_OP_LINEAR && (nx.flags & PH_FLAG_SCALE_RESIDUAL) && nxo.w_mlp_dev && nx.src0 == d.dst && nx.src1 >= 0 && nx.src1 != d.dst && nx.cin0 == d.cout && nx.cout == d.cin0 &&
-                      s0.cp == d.cin0 && plan.slots[nx.dst].cp == nx.cout && plan.slots[nx.src1].cp == nx.cout;
-          for (size_t k = 0; pair && k < m->ops.size(); ++k)
-            if (k != op_index && (m->ops[k].d.src0 == d.dst || m->ops[k].d.src1 == d.dst)) pair = false;
+          bool pair = s0.cp == d.cin0 && plan.slots[nx.dst].cp == nx.cout && plan.slots[nx.src1].cp == nx.cout;
+          // build_plan releases x (d.src0) before it places y (nx.dst): y may come to lie on x's range, or across it where free blocks have coalesced.  cnblock_mlp_kernel is
+          // safe for y EXACTLY on x (or on the residual) -- a row tile reads all of its x rows at its start and its residual elements in the epilogue, each before the store of
+          // the same elements, and no other tile reads those rows -- and for nothing else: y shifted against x would overwrite rows another tile has yet to read.  Then: two GEMMs.
+          for (int src : {d.src0, nx.src1}) {
+            const int64_t ys = plan.slots[nx.dst].offset, ye = ys + slot_bytes(nx.dst), xs = plan.slots[src].offset, xe = xs + slot_bytes(src);
+            if (ys < xe && xs < ye && !(ys == xs && ye == xe)) pair = false;
+          }
           if (pair) {
             MlpArgs f{};
-            f.x = slot_ptr(d.src0);
+            f.x = rd(d.src0);
             f.w1img = op.w_mlp_dev;
             f.w2img = nxo.w_mlp_dev;
             f.b1 = op.b_dev;
             f.b2 = nxo.b_dev;
             f.scale = nxo.w2_dev;
-            f.residual = slot_ptr(nx.src1);
-            f.dst = slot_ptr(nx.dst);
+            f.residual = rd(nx.src1);
+            f.dst = wr(nx.dst);
             f.M = batch * so.h * so.w;
             f.C = d.cin0;
             kv[op_index - 1] = PH_KV_MLP;
@@ -1670,10 +1752,10 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           }
         }
         GemmArgs a{};
-        a.src0 = slot_ptr(d.src0);
+        a.src0 = rd(d.src0);
         a.wpack = op.w_dma_dev;
         a.bias = op.b_dev;
-        a.dst = slot_ptr(d.dst);
+        a.dst = wr(d.dst);
         a.zeros = m->zeros_dev;
         a.c0p = s0.cp;
         a.coutp = so.cp;
@@ -1685,7 +1767,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         a.act = (d.flags & PH_FLAG_GELU) ? 2 : ((d.flags & PH_FLAG_RELU) ? 1 : 0);
         if (d.flags & PH_FLAG_SCALE_RESIDUAL) {
           a.scale = op.w2_dev;
-          a.residual = slot_ptr(d.src1);
+          a.residual = rd(d.src1);
         }
         a.late_split = m->gemm_late_split;
         // training program (Linear and GELU as separate ops, the pre-activation is kept for the backward pass): the
@@ -1695,7 +1777,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           if (nx.kind == PH_OP_GELU && nx.src0 == d.dst && nx.dst != d.dst) {
             a.act = 2;
             a.dst_pre = a.dst;
-            a.dst = slot_ptr(nx.dst);
+            a.dst = wr(nx.dst);
             skip_next_gelu = true;
           }
         }
@@ -1705,9 +1787,9 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           const ph_op_desc& nx = m->ops[op_index].d;
           if (nx.kind == PH_OP_SCALE_ADD && nx.src0 == d.dst && nx.dst != d.dst && nx.src1 != d.dst && nx.src1 >= 0 && nx.cin0 == d.cout) {
             a.scale = m->ops[op_index].w_dev;
-            a.residual = slot_ptr(nx.src1);
+            a.residual = rd(nx.src1);
             a.dst_pre = a.dst;
-            a.dst = slot_ptr(nx.dst);
+            a.dst = wr(nx.dst);
             skip_next_scale_add = true;
           }
         }
@@ -1718,7 +1800,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
       case PH_OP_GLOBAL_MAXPOOL: {
         const SlotShape& s0 = plan.slots[d.src0];
         PH_REQUIRE(s0.c == d.cin0, "global pool channel mismatch");
-        rc = launch_global_maxpool(slot_ptr(d.src0), slot_ptr(d.dst), batch, s0.h * s0.w, s0.cp, s);
+        rc = launch_global_maxpool(rd(d.src0), wr(d.dst), batch, s0.h * s0.w, s0.cp, s);
         break;
       }
       case PH_OP_GELU: {
@@ -1727,7 +1809,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           break;
         }
         const SlotShape& s0 = plan.slots[d.src0];
-        rc = launch_gelu_fwd(slot_ptr(d.src0), slot_ptr(d.dst), (size_t)batch * s0.h * s0.w * s0.cp, s);
+        rc = launch_gelu_fwd(rd(d.src0), wr(d.dst), (size_t)batch * s0.h * s0.w * s0.cp, s);
         break;
       }
       case PH_OP_SCALE_ADD: {
@@ -1737,7 +1819,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         }
         const SlotShape& s0 = plan.slots[d.src0];
         PH_REQUIRE(s0.c == d.cin0, "scale-add channel mismatch");
-        rc = launch_scale_add_fwd(slot_ptr(d.src0), slot_ptr(d.src1), op.w_dev, slot_ptr(d.dst), s0.cp, (size_t)batch * s0.h * s0.w * s0.cp, s);
+        rc = launch_scale_add_fwd(rd(d.src0), rd(d.src1), op.w_dev, wr(d.dst), s0.cp, (size_t)batch * s0.h * s0.w * s0.cp, s);
         break;
       }
       case PH_OP_HEAD: {
@@ -1748,7 +1830,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         const SlotShape& s0 = plan.slots[d.src0];
         PH_REQUIRE(s0.c == d.cin0, "head channel mismatch");
         PH_REQUIRE(out_dev[d.out_index] != nullptr, "output %d is null", d.out_index);
-        rc = launch_head_fmt(fmt, slot_ptr(d.src0), op.w_dev, op.b_dev, out_dev[d.out_index], batch, s0.h * s0.w, s0.cp, pad16(d.cin0), d.cout,
+        rc = launch_head_fmt(fmt, rd(d.src0), op.w_dev, op.b_dev, out_dev[d.out_index], batch, s0.h * s0.w, s0.cp, pad16(d.cin0), d.cout,
                              head_sigmoid(m, plan, d), s);
         if (rc == PH_OK && (d.flags & PH_FLAG_SOFTMAX)) {
           PH_REQUIRE(s0.h == 1 && s0.w == 1, "softmax head expects a pooled (1x1) feature");
@@ -1887,6 +1969,21 @@ int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops) {
   PH_REQUIRE(m && codes, "ph_model_last_kernels: null argument");
   PH_REQUIRE(n_ops == (int32_t)m->ops.size(), "ph_model_last_kernels: model has %d ops", (int)m->ops.size());
   for (int i = 0; i < n_ops; ++i) codes[i] = i < (int)m->last_variant.size() ? m->last_variant[i] : PH_KV_NONE;
+  return PH_OK;
+}
+
+int ph_model_last_ranges(const ph_model* m, int64_t* rows, int32_t max_rows, int32_t* n_rows) {
+  PH_REQUIRE(m && n_rows && max_rows >= 0 && (rows || max_rows == 0), "ph_model_last_ranges: bad arguments");
+  *n_rows = (int32_t)m->last_ranges.size();
+  for (int i = 0; i < max_rows && i < *n_rows; ++i) {
+    const RangeRec& r = m->last_ranges[i];
+    rows[6 * i] = r.op;
+    rows[6 * i + 1] = r.launch;
+    rows[6 * i + 2] = r.is_dst;
+    rows[6 * i + 3] = r.slot;
+    rows[6 * i + 4] = r.offset;
+    rows[6 * i + 5] = r.bytes;
+  }
   return PH_OK;
 }
 

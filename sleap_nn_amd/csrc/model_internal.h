@@ -79,6 +79,13 @@ struct SlotShape {
   int def_op = -1;                  // index of the op that writes the slot
 };
 
+// One workspace byte range a launch of the last forward was handed (ph_model_last_ranges).
+struct RangeRec {
+  int op = 0, launch = 0, is_dst = 0;  // op index in the program, launch ordinal within that op, 0 = source | 1 = destination
+  int slot = -1;                       // activation slot the range belongs to (-1: the scratch region behind the slots)
+  int64_t offset = 0, bytes = 0;
+};
+
 struct Plan {
   std::vector<SlotShape> slots;
   int64_t tmp_offset = 0, tmp_bytes = 0, total = 0;
@@ -106,6 +113,7 @@ struct ph_model {
   char* last_ws = nullptr;
   int last_batch = 0;
   std::vector<int> last_variant;  // PH_KV_* code of the kernel each op of the last forward ran (ph_model_last_kernels)
+  std::vector<ph::RangeRec> last_ranges;  // workspace ranges each launch of the last forward read / wrote (ph_model_last_ranges)
   // optional per-op HIP-event timing (ph_model_set_profiling)
   bool profiling = false;
   bool events_pending = false;
@@ -175,6 +183,12 @@ struct ph_model {
 namespace ph {
 int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt = FMT_F32);
 int forward_format(const ph_model* m);
+// Run-time fusions in which the launch of op i also computes op i + 1, so that op i + 1's dst is written while op i's sources are still being read.  Conditions on the
+// program, the handle options and the plan's format only -- what is known before any weight form is derived.  fuses_block2 is called by BOTH ph_model_forward (which fuses)
+// and build_plan (which holds the releases due at op i + 1, so that its dst stays off the ranges op i reads): the two cannot drift apart.  fuses_mlp is the router's alone:
+// cnblock_mlp_kernel is safe with y exactly on x, build_plan does not hold that pair, and ph_model_forward refuses the fusion for any other overlap of the plan's ranges.
+bool fuses_block2(const ph_model* m, size_t i, int fmt, bool reuse);  // block2_c32_f16_kernel: conv(<= 16 -> 32) + conv(32 -> 32) (+ pool)
+bool fuses_mlp(const ph_model* m, size_t i, int fmt, bool reuse);     // cnblock_mlp_kernel: Linear + GELU + Linear + layer scale + residual
 int ensure_f16_weights(ph_model* m, int plain, hipStream_t s);  // format the forward of this program runs in under the handle's conv_precision
 int upload(ph_model* m, const std::vector<float>& host, float** dev);
 int upload_ints(ph_model* m, const std::vector<int>& host, int** dev);
