@@ -35,6 +35,7 @@
  *   ph_tile_extract     inference/layers/tiled.py:62-84 (_extract_square_tile, per tile).
  *   ph_tile_merge       inference/tile_merger.py:107-179 (TileMerger.integrate per tile + merge) and the
  *                       crop of inference/layers/tiled.py:262-263.
+ *   ph_tile_merge_heads the same stitch for the heads of inference/layers/tiled.py:353-668 in one launch.
  *   ph_loss_* / ph_model_set_head_loss   training/losses.py:64-133 as called at training/lightning_modules.py:3052-3109, 3463-3475.
  *   ph_render_seg_targets   data/segmentation_maps.py as called at data/custom_datasets.py:3593-3626.
  *   ph_seg_place_crops  inference/segmentation_convert.py:74-133 (decode_mask_to_image_res) over the entries that
@@ -56,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 118
+#define PH_VERSION 119
 
 /* error codes */
 #define PH_OK 0
@@ -596,6 +597,18 @@ int ph_tile_extract(const void* frames_dev, int32_t dtype, int32_t F, int32_t C,
  * covers are NaN.  Tiles may reach past (h, w): only the cropped region is written. */
 int ph_tile_merge(const float* tile_maps_dev, const float* window_dev, int32_t F, int32_t N, int32_t th, int32_t tw, const int32_t* y_origins_dev,
                   int32_t ny, const int32_t* x_origins_dev, int32_t nx, int32_t h, int32_t w, float* out_dev, void* stream);
+
+/* ph_tile_merge for K heads (1 <= K <= 4) in ONE launch (the tiled segmentation wrappers: foreground 1, centre 1, offset 2 channels;
+ * DESIGN.md section 10a).  arenas_dev / outs_dev / channels are HOST arrays of K entries: arenas_dev[k] is a device pointer to
+ * (F * ny * nx, channels[k], th, tw) fp32 in the row order of ph_tile_extract, outs_dev[k] one to a contiguous (F, channels[k], h, w)
+ * fp32 map; channels[k] >= 1 and at most 8 channels in total.  Window, origins, (h, w) and the arithmetic are ph_tile_merge's and shared
+ * by the heads; per pixel the covering tiles are walked once, the window loaded once per tile, cnt and every channel's accumulator
+ * kept in registers.  Channels are independent, so each output is bit-identical to ph_tile_merge on its arena and to the matching
+ * channels of a TileMerger canvas of sum(channels).  Pointers and channel counts go to the kernel by value (no device pointer
+ * table, no host synchronisation).  No output may overlap an arena or another output. */
+int ph_tile_merge_heads(const float* const* arenas_dev, const int32_t* channels, int32_t K, const float* window_dev, int32_t F, int32_t th, int32_t tw,
+                        const int32_t* y_origins_dev, int32_t ny, const int32_t* x_origins_dev, int32_t nx, int32_t h, int32_t w, float* const* outs_dev,
+                        void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Bottom-up instance segmentation grouping (inference/segmentation.py)

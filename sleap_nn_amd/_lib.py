@@ -121,6 +121,7 @@ SIGNATURES = {
     "ph_augment": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ph_tile_extract": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
     "ph_tile_merge": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "ph_tile_merge_heads": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
     "ph_seg_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "ph_seg_center_peaks": (C.c_int, [_vp, _i32, _i32, _i32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp]),
     "ph_seg_assign": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),

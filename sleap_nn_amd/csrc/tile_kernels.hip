@@ -242,3 +242,175 @@ extern "C" int ph_tile_merge(const float* tile_maps_dev, const float* window_dev
   PH_HIP_CHECK(hipGetLastError());
   return PH_OK;
 }
+
+// ---- merge, several heads in one launch ---------------------------------------------------------------------------
+
+namespace ph {
+
+constexpr int kMergeMaxHeads = 4;
+constexpr int kMergeMaxChannels = 8;
+
+// Kernel argument, by value: one entry per CHANNEL of the concatenated heads (the host flattens head k, channel n to slot j).
+// src[j] = arena_k + n * th * tw with tile stride cs[j] * th * tw; dst[j] = out_k + n * h * w with frame stride cs[j] * h * w; cs[j] = c_k.
+struct MergeHeadsArgs {
+  const float* src[kMergeMaxChannels];
+  float* dst[kMergeMaxChannels];
+  int32_t cs[kMergeMaxChannels];
+};
+
+// As merge_pixels, but the window row segment of a covering tile is loaded once and feeds cnt and all CT accumulators (registers:
+// CT * V + V floats).  Per channel the sequence of roundings is merge_pixels' own: acc = acc + tile * w, cnt = cnt + w, acc / cnt.
+template <int CT, int V>
+__device__ __forceinline__ void merge_heads_pixels(const MergeHeadsArgs& a, const float* __restrict__ win, const int32_t* __restrict__ yo,
+                                                   const int32_t* __restrict__ xo, int f, int th, int tw, int ny, int nx, int h, int w, int y, int x,
+                                                   int iy0, int iy1, int ix0, int ix1) {
+  const size_t plane = (size_t)th * tw;
+  const size_t T_ = (size_t)ny * nx;
+  float cnt[V], acc[CT][V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) cnt[j] = 0.0f;
+#pragma unroll
+  for (int c = 0; c < CT; ++c)
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc[c][j] = 0.0f;
+  for (int iy = iy0; iy <= iy1; ++iy) {
+    const int dy = y - yo[iy];
+    if (dy < 0 || dy >= th) continue;
+    for (int ix = ix0; ix <= ix1; ++ix) {
+      const int dx = x - xo[ix];
+      if (dx < 0 || dx + V > tw) continue;
+      const size_t off = (size_t)dy * tw + dx;
+      const size_t t = (size_t)f * T_ + (size_t)iy * nx + ix;
+      float wv[V];
+      load_row<V>(win + off, wv);
+#pragma unroll
+      for (int j = 0; j < V; ++j) cnt[j] = cnt[j] + wv[j];
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {
+        float tv[V];
+        load_row<V>(a.src[c] + t * (size_t)a.cs[c] * plane + off, tv);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const float p = tv[j] * wv[j];  // (its own rounding: see the pragma above)
+          acc[c][j] = acc[c][j] + p;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < CT; ++c) {
+    float* o = a.dst[c] + ((size_t)f * a.cs[c] * h + y) * (size_t)w + x;
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(o) = make_float4(acc[c][0] / cnt[0], acc[c][1] / cnt[1], acc[c][2] / cnt[2], acc[c][3] / cnt[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) o[j] = acc[c][j] / cnt[j];
+    }
+  }
+}
+
+// Thread mapping and coverage search of tile_merge_kernel.  V = 4: w % 4 == 0, tw >= 4 and every output 16-byte aligned.
+template <int CT, int V>
+__global__ __launch_bounds__(256) void tile_merge_heads_kernel(const MergeHeadsArgs a, const float* __restrict__ win, const int32_t* __restrict__ yo,
+                                                               const int32_t* __restrict__ xo, int F, int th, int tw, int ny, int nx, int h, int w) {
+  const int wv = w / V;
+  const size_t groups = (size_t)F * h * wv;
+  for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (size_t)gridDim.x * 256) {
+    const int x = (int)(g % wv) * V;
+    const size_t r = g / wv;
+    const int y = (int)(r % h);
+    const int f = (int)(r / h);
+    int iy0 = ny, iy1 = -1;
+    for (int i = 0; i < ny; ++i) {
+      const int d = y - yo[i];
+      if (d >= 0 && d < th) {
+        iy0 = min(iy0, i);
+        iy1 = i;
+      }
+    }
+    int ix0 = nx, ix1 = -1;
+    bool same = true;  // every tile covers all V pixels of the group or none of them
+    for (int i = 0; i < nx; ++i) {
+      const int d = x - xo[i];
+      const bool first = d >= 0 && d < tw, last = d + V - 1 >= 0 && d + V - 1 < tw;
+      if (first || last) {
+        ix0 = min(ix0, i);
+        ix1 = i;
+      }
+      same = same && (first == last);
+    }
+    if (V == 1 || same) {
+      merge_heads_pixels<CT, V>(a, win, yo, xo, f, th, tw, ny, nx, h, w, y, x, iy0, iy1, ix0, ix1);
+    } else {
+      for (int j = 0; j < V; ++j) merge_heads_pixels<CT, 1>(a, win, yo, xo, f, th, tw, ny, nx, h, w, y, x + j, iy0, iy1, ix0, ix1);
+    }
+  }
+}
+
+template <int CT>
+static void launch_merge_heads(bool vec, unsigned grid, hipStream_t s, const MergeHeadsArgs& a, const float* win, const int32_t* yo, const int32_t* xo, int F,
+                               int th, int tw, int ny, int nx, int h, int w) {
+  if (vec)
+    hipLaunchKernelGGL((tile_merge_heads_kernel<CT, 4>), dim3(grid), dim3(256), 0, s, a, win, yo, xo, F, th, tw, ny, nx, h, w);
+  else
+    hipLaunchKernelGGL((tile_merge_heads_kernel<CT, 1>), dim3(grid), dim3(256), 0, s, a, win, yo, xo, F, th, tw, ny, nx, h, w);
+}
+
+}  // namespace ph
+
+extern "C" int ph_tile_merge_heads(const float* const* arenas_dev, const int32_t* channels, int32_t K, const float* window_dev, int32_t F, int32_t th, int32_t tw,
+                                   const int32_t* y_origins_dev, int32_t ny, const int32_t* x_origins_dev, int32_t nx, int32_t h, int32_t w, float* const* outs_dev,
+                                   void* stream) {
+  using namespace ph;
+  PH_REQUIRE(arenas_dev && channels && window_dev && y_origins_dev && x_origins_dev && outs_dev, "ph_tile_merge_heads: null pointer");
+  PH_REQUIRE(K >= 1 && K <= kMergeMaxHeads, "ph_tile_merge_heads: K must be 1..%d, got %d", kMergeMaxHeads, K);
+  int total = 0;
+  for (int k = 0; k < K; ++k) {
+    PH_REQUIRE(arenas_dev[k] && outs_dev[k], "ph_tile_merge_heads: null pointer (head %d)", k);
+    PH_REQUIRE(channels[k] >= 1 && channels[k] <= kMergeMaxChannels, "ph_tile_merge_heads: head %d has %d channels (1..%d)", k, channels[k], kMergeMaxChannels);
+    total += channels[k];
+  }
+  PH_REQUIRE(total <= kMergeMaxChannels, "ph_tile_merge_heads: %d channels in total (at most %d)", total, kMergeMaxChannels);
+  PH_REQUIRE(F > 0 && th > 0 && tw > 0, "ph_tile_merge_heads: bad tile-map shape F=%d th=%d tw=%d", F, th, tw);
+  PH_REQUIRE(ny > 0 && nx > 0 && h > 0 && w > 0, "ph_tile_merge_heads: bad grid / output ny=%d nx=%d h=%d w=%d", ny, nx, h, w);
+  PH_REQUIRE((int64_t)ny * nx <= 0x7fffffffLL / F, "ph_tile_merge_heads: too many tiles (%d x %d x %d)", F, ny, nx);
+  // byte ranges: no output may overlap an arena or another output
+  const uint64_t tiles = (uint64_t)F * ny * nx, plane = (uint64_t)th * tw * sizeof(float), frame = (uint64_t)h * w * sizeof(float);
+  auto overlap = [](uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) { return a < b + nb && b < a + na; };
+  for (int k = 0; k < K; ++k) {
+    const uintptr_t o = (uintptr_t)outs_dev[k];
+    const uint64_t no = (uint64_t)F * channels[k] * frame;
+    for (int j = 0; j < K; ++j) {
+      PH_REQUIRE(!overlap(o, no, (uintptr_t)arenas_dev[j], tiles * channels[j] * plane), "ph_tile_merge_heads: output %d aliases arena %d", k, j);
+      PH_REQUIRE(j == k || !overlap(o, no, (uintptr_t)outs_dev[j], (uint64_t)F * channels[j] * frame), "ph_tile_merge_heads: output %d aliases output %d", k, j);
+    }
+  }
+  MergeHeadsArgs a{};
+  bool vec = w % 4 == 0 && tw >= 4;
+  int c = 0;
+  for (int k = 0; k < K; ++k) {
+    vec = vec && ((uintptr_t)outs_dev[k] & 15) == 0;
+    for (int n = 0; n < channels[k]; ++n, ++c) {
+      a.src[c] = arenas_dev[k] + (size_t)n * th * tw;
+      a.dst[c] = outs_dev[k] + (size_t)n * h * w;
+      a.cs[c] = channels[k];
+    }
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t groups = (size_t)F * h * (vec ? w / 4 : w);
+  int cus = 0;
+  if (int rc = device_cu_count(&cus); rc != PH_OK) return rc;
+  const unsigned grid = (unsigned)std::min<size_t>((groups + 255) / 256, (size_t)cus * 8);  // 8 workgroups of 4 waves per CU, grid-stride beyond
+  switch (total) {
+    case 1: launch_merge_heads<1>(vec, grid, s, a, window_dev, y_origins_dev, x_origins_dev, F, th, tw, ny, nx, h, w); break;
+    case 2: launch_merge_heads<2>(vec, grid, s, a, window_dev, y_origins_dev, x_origins_dev, F, th, tw, ny, nx, h, w); break;
+    case 3: launch_merge_heads<3>(vec, grid, s, a, window_dev, y_origins_dev, x_origins_dev, F, th, tw, ny, nx, h, w); break;
+    case 4: launch_merge_heads<4>(vec, grid, s, a, window_dev, y_origins_dev, x_origins_dev, F, th, tw, ny, nx, h, w); break;
+    case 5: launch_merge_heads<5>(vec, grid, s, a, window_dev, y_origins_dev, x_origins_dev, F, th, tw, ny, nx, h, w); break;
+    case 6: launch_merge_heads<6>(vec, grid, s, a, window_dev, y_origins_dev, x_origins_dev, F, th, tw, ny, nx, h, w); break;
+    case 7: launch_merge_heads<7>(vec, grid, s, a, window_dev, y_origins_dev, x_origins_dev, F, th, tw, ny, nx, h, w); break;
+    default: launch_merge_heads<8>(vec, grid, s, a, window_dev, y_origins_dev, x_origins_dev, F, th, tw, ny, nx, h, w); break;
+  }
+  PH_HIP_CHECK(hipGetLastError());
+  return PH_OK;
+}

@@ -8,7 +8,7 @@ from sleap_nn_amd.inference.layers.segmentation import SegmentationLayer, Semant
 from sleap_nn_amd.inference.layers.segmentation_cleanup import CleanupSegmentationLayer  # noqa: F401
 from sleap_nn_amd.inference.layers.segmentation_merge import MergeSegmentationLayer  # noqa: F401
 from sleap_nn_amd.inference.layers.single_instance import SingleInstanceLayer  # noqa: F401
-from sleap_nn_amd.inference.layers.tiled import TiledLayer  # noqa: F401
+from sleap_nn_amd.inference.layers.tiled import TiledLayer, TiledSegmentationLayer, TiledSemanticSegmentationLayer  # noqa: F401
 from sleap_nn_amd.inference.layers.topdown import TopDownLayer  # noqa: F401
 from sleap_nn_amd.inference.layers.topdown_multiclass import CenteredInstanceMultiClassLayer, TopDownMultiClassLayer  # noqa: F401
 from sleap_nn_amd.inference.layers.topdown_segmentation import CenteredInstanceMaskLayer, TopDownSegmentationLayer  # noqa: F401

@@ -10,7 +10,7 @@ tensors the same contract runs on the host.
 ``mask_cleanup=True`` is ``layers/segmentation_cleanup.py`` (``CleanupSegmentationLayer``) and ``merge_fragments=True`` (the RAG fragment merge)
 ``layers/segmentation_merge.py`` (``MergeSegmentationLayer``); this class keeps refusing both knobs.  Not built (each raises ``NotImplementedError``
 naming the knob): ``mask_cleanup_radius`` (OpenCV morphology), ``merge_fragments`` together with ``mask_cleanup``, ``mask_output`` other than ``"mask"``
-(polygon packaging) and the tiled segmentation wrappers.  Top-down segmentation (``centered_instance_segmentation``) is ``layers/topdown_segmentation.py``.
+(polygon packaging).  The tiled wrappers are ``layers/tiled.py`` (``TiledSegmentationLayer`` / ``TiledSemanticSegmentationLayer``).  Top-down segmentation (``centered_instance_segmentation``) is ``layers/topdown_segmentation.py``.
 """
 from __future__ import annotations
 

@@ -9,7 +9,7 @@ this class when ``mask_cleanup`` is asked for.
 
 Not built (each raises ``NotImplementedError`` naming the knob): ``mask_cleanup_radius > 0`` (OpenCV's elliptical open / close),
 ``merge_fragments`` together with ``mask_cleanup`` (``merge_fragments`` alone is ``layers/segmentation_merge.py``), ``mask_output`` other than
-``"mask"`` and the tiled segmentation wrappers.
+``"mask"``.  Tiled inference wraps this layer in ``TiledSegmentationLayer`` (``layers/tiled.py``).
 """
 from __future__ import annotations
 

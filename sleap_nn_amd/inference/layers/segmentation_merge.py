@@ -10,8 +10,8 @@ graph (tens of nodes) is host work (``inference/ops/segmentation_merge.py``).  F
 ``SegmentationLayer`` itself keeps refusing the knob; ``predictor._select_layer`` builds this class when ``merge_fragments`` is asked for.
 
 Not built (each raises ``NotImplementedError`` naming the knobs): ``merge_fragments`` together with ``mask_cleanup`` (cleaned masks overlap through their
-filled holes, so the label map no longer carries membership), ``mask_cleanup_radius > 0``, ``mask_output`` other than ``"mask"`` and the tiled
-segmentation wrappers.
+filled holes, so the label map no longer carries membership), ``mask_cleanup_radius > 0``, ``mask_output`` other than ``"mask"``.  Tiled inference wraps
+this layer in ``TiledSegmentationLayer`` (``layers/tiled.py``).
 """
 from __future__ import annotations
 

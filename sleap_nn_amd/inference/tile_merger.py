@@ -5,12 +5,12 @@ canvas: ``ACC += tile * w``, ``CNT += w`` per tile, ``ACC / CNT`` at the end.  E
 
 ``TileMerger`` is the public class of the reference, the ``accumulator_device="cpu"`` path of ``TiledLayer`` and the statement
 of the arithmetic that ``ph_tile_merge`` (``csrc/tile_kernels.hip``) reproduces bit for bit as a gather; ``merge_tiles`` is
-that kernel's wrapper.
+that kernel's wrapper, ``merge_tile_heads`` the wrapper of ``ph_tile_merge_heads`` (several heads sharing one grid, one launch).
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence, Tuple, Union
+from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -98,6 +98,63 @@ def merge_tiles(tile_maps: torch.Tensor, window: torch.Tensor, y_origins: Union[
         L.check(L.lib().ph_tile_merge(C.c_void_p(tile_maps.data_ptr()), C.c_void_p(window.data_ptr()), frames, N, th, tw, C.c_void_p(yo.data_ptr()), ny,
                                       C.c_void_p(xo.data_ptr()), nx, h, w, C.c_void_p(out.data_ptr()), L.current_stream_ptr()))
     return out
+
+
+MERGE_MAX_HEADS = 4  # ``ph_tile_merge_heads``: the pointers travel in the kernel argument
+MERGE_MAX_CHANNELS = 8
+
+
+def merge_tile_heads(arenas: Sequence[torch.Tensor], window: torch.Tensor, y_origins: Union[torch.Tensor, Sequence[int]], x_origins: Union[torch.Tensor, Sequence[int]],
+                     out_hw: Tuple[int, int], frames: int = 1) -> List[torch.Tensor]:
+    """``ph_tile_merge_heads``: ``K`` arenas ``(frames * ny * nx, c_k, th, tw)`` fp32 on one GPU (1 <= K <= 4, at most 8 channels in total, one window, one
+    grid) -> ``K`` contiguous maps ``(frames, c_k, h, w)`` in ONE launch on the current stream; each is bit-identical to ``merge_tiles`` on its arena and to
+    the matching channels of one ``TileMerger`` canvas of ``sum c_k`` channels."""
+    arenas = list(arenas)
+    if not 1 <= len(arenas) <= MERGE_MAX_HEADS:
+        raise ValueError(f"merge_tile_heads takes 1 to {MERGE_MAX_HEADS} arenas, got {len(arenas)}")
+    for k, a in enumerate(arenas):
+        L.require_cuda(a, f"arenas[{k}]")
+        if a.dim() != 4 or a.dtype != torch.float32:
+            raise ValueError(f"arenas[{k}] must be a float32 (tiles, c, th, tw) tensor, got {a.dtype} {tuple(a.shape)}")
+    dev = arenas[0].device
+    n_tiles, _c, th, tw = arenas[0].shape
+    for k, a in enumerate(arenas):
+        if a.device != dev or a.shape[0] != n_tiles or tuple(a.shape[-2:]) != (th, tw):
+            raise ValueError(f"arenas[{k}] {tuple(a.shape)} on {a.device} does not match arenas[0] {tuple(arenas[0].shape)} on {dev}")
+        if a.shape[1] < 1:
+            raise ValueError(f"arenas[{k}] has no channels")
+    total = sum(int(a.shape[1]) for a in arenas)
+    if total > MERGE_MAX_CHANNELS:
+        raise ValueError(f"{total} channels in total, ph_tile_merge_heads takes at most {MERGE_MAX_CHANNELS}")
+    arenas = [a.contiguous() for a in arenas]
+    yo, xo = origins_tensor(y_origins, dev), origins_tensor(x_origins, dev)
+    ny, nx = int(yo.numel()), int(xo.numel())
+    if n_tiles != frames * ny * nx:
+        raise ValueError(f"{n_tiles} tile maps for {frames} frames of {ny} x {nx} tiles")
+    if tuple(window.shape) != (th, tw):
+        raise ValueError(f"window {tuple(window.shape)} does not match the tile maps ({th}, {tw})")
+    window = window.to(device=dev, dtype=torch.float32).contiguous()
+    h, w = int(out_hw[0]), int(out_hw[1])
+    outs = [torch.empty((frames, int(a.shape[1]), h, w), dtype=torch.float32, device=dev) for a in arenas]
+    merge_tile_heads_into(arenas, window, yo, xo, outs)
+    return outs
+
+
+def merge_tile_heads_into(arenas: Sequence[torch.Tensor], window: torch.Tensor, yo: torch.Tensor, xo: torch.Tensor, outs: Sequence[torch.Tensor]) -> None:
+    """The launch of ``merge_tile_heads`` into caller-owned contiguous ``outs (frames, c_k, h, w)`` (views at any 4-byte-aligned address); arguments are taken as
+    validated: contiguous fp32 arenas, an fp32 device window, int32 device origins."""
+    K = len(arenas)
+    frames, _c, h, w = outs[0].shape
+    th, tw = arenas[0].shape[-2:]
+    for a, o in zip(arenas, outs):
+        if not o.is_contiguous() or o.dtype != torch.float32 or tuple(o.shape) != (frames, a.shape[1], h, w) or o.device != a.device:
+            raise ValueError(f"output {tuple(o.shape)} {o.dtype} does not match its arena {tuple(a.shape)} (contiguous float32 (frames, c, h, w) expected)")
+    ptrs = (C.c_void_p * K)(*[a.data_ptr() for a in arenas])
+    optrs = (C.c_void_p * K)(*[o.data_ptr() for o in outs])
+    chans = (C.c_int32 * K)(*[int(a.shape[1]) for a in arenas])
+    with torch.cuda.device(arenas[0].device):
+        L.check(L.lib().ph_tile_merge_heads(ptrs, chans, K, C.c_void_p(window.data_ptr()), int(frames), int(th), int(tw), C.c_void_p(yo.data_ptr()), int(yo.numel()),
+                                            C.c_void_p(xo.data_ptr()), int(xo.numel()), int(h), int(w), optrs, L.current_stream_ptr()))
 
 
 def extract_tiles(frames: torch.Tensor, y_origins: Union[torch.Tensor, Sequence[int]], x_origins: Union[torch.Tensor, Sequence[int]], tile_size: int) -> torch.Tensor:
