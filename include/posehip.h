@@ -316,6 +316,8 @@ int ph_debug_row_wgrad_bench(int32_t M, int32_t n, int32_t k, int32_t iters, flo
  * N-tile-64 layers | 0 direct 9-tap kernels), "stem_wino", "dgrad_wino" (0: direct kernels for the backward's data-gradient convs), "conv_dma", "conv_dma32",
  * "conv_persist", "conv_c16", "conv_dma_stagger", "fuse_gelu_fwd", "fuse_gelu_bwd", "wgrad_rows", "convt_phase", "workspace_reuse" (1: activation slots of an inference forward share memory by lifetime),
  * "conv_precision" (0 exact fp32 MFMA | 1 split-fp16 MFMA, 22-bit products | 2 plain fp16, the reference's autocast mode),
+ * "convnext_f16" (1: under "conv_precision" 2 a program with ConvNeXt encoder ops runs whole on fp16 activations -- patch stem, depthwise 7x7 + LayerNorm,
+ * Linear / 2x2-stride-2 convs as fp16 MFMA row GEMMs, then the fp16 decoder; 0, the default: such a program runs exact fp32 under every precision),
  * "gemm_late_split", "gemm_persist2", "conv_gemm_fill", "conv_gemm_fill_wino", "conv_gemm_fill_wino2d",
  * "conv_wino2d" / "conv_w16" (the Winograd F(2x2,3x3) kernels), "conv_wino4" (K-heavy 3x3 convs on the Winograd F(4x4,3x3) kernel: 1 inference
  * plans | 2 every plan | 0 never), "conv_wino4_min_cin", "upsample_fold" (a bilinear x2 read only by the next conv's second source rides in that kernel's input transform), "head_fuse" (a 1x1 head computed in its producer conv's epilogue),
@@ -359,6 +361,11 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_F16_ROWS 13 /* conv3x3_f16_rows_kernel: plain fp16 on v_mfma_f32_16x16x32_f16, row tiles, loader waves, folded bilinear x2 */
 #define PH_KV_F16_BLOCK 14 /* block2_c32_f16_kernel: conv(<= 16 -> 32) + conv(32 -> 32) (+ pool) of an encoder block in one launch (plain fp16); the second conv reports PH_KV_FUSED */
 #define PH_KV_MLP 15      /* cnblock_mlp_kernel: Linear(C, 4C) + GELU + Linear(4C, C) + layer scale + residual of a CNBlock in one launch (both Linear ops report it; the second has no launch of its own) */
+#define PH_KV_CNX_F16_STEM 16 /* patch_stem_f16_kernel: ConvNeXt patch stem, fp16 output (plain fp16 precision)                                    */
+#define PH_KV_CNX_F16_DW 17   /* dwconv7_f16_kernel / dwconv7_ln_f16_kernel: depthwise 7x7 on fp16 activations (with the LayerNorm behind it in inference plans: that op reports PH_KV_FUSED) */
+#define PH_KV_CNX_F16_LN 18   /* layernorm_f16_kernel: LayerNorm over the channels of an fp16 tensor, fp32 moments                                  */
+#define PH_KV_CNX_F16_GEMM 19 /* gemm_f16_kernel: Linear / 2x2-stride-2 conv as a row GEMM on v_mfma_f32_32x32x16_f16 (bias, GELU, layer scale + residual epilogues) */
+#define PH_KV_CNX_F16_ELTWISE 20 /* gelu_fmt_kernel / scale_add_fmt_kernel on fp16 activations (unfused programs)                                    */
 #define PH_KV_FUSED 11    /* no launch of its own: a 1x1 head computed in the epilogue of the conv that produces its input */
 int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
 

@@ -278,16 +278,27 @@ class Model:
             self.set_option("workspace_reuse", 0 if self.keep_activations else 1)
         return self
 
-    def set_precision(self, precision: str) -> "Model":
-        """Arithmetic of the inference forward's 3x3 convolutions (UNet programs; ConvNeXt programs always run exact):
+    def set_precision(self, precision: str, convnext_f16: Optional[bool] = None) -> "Model":
+        """Arithmetic of the inference forward:
         ``"exact"``: fp32 products on the fp32 matrix pipe (bit-for-bit a k-ordered fmaf chain);
         ``"split"``: every operand as a (hi, lo) pair of fp16 numbers, three fp16 MFMAs per product with fp32 accumulation --
-        22-bit products, ~1e-6 relative on the head outputs, 16/3 of the fp32 matrix rate;
+        22-bit products, ~1e-6 relative on the head outputs, 16/3 of the fp32 matrix rate.  UNet programs only: a ConvNeXt
+        program set to ``"split"`` runs exact;
         ``"fp16"``: plain fp16 operands and storage, fp32 accumulation -- the reference's autocast mode
-        (torch_backend.py:113-143; its tolerance is 5e-3)."""
+        (torch_backend.py:113-143; its tolerance is 5e-3).  UNet programs run their 3x3 convolutions on the fp16 matrix pipe.
+        ConvNeXt programs run whole in fp16 storage when the handle option ``convnext_f16`` is 1 as well: patch stem,
+        depthwise 7x7 + LayerNorm, both Linear layers of a CNBlock and the 2x2 downsampling convs as fp16 MFMA row GEMMs
+        with fp32 accumulators, fp32 LayerNorm moments and fp32 erf-GELU, the residual stream stored in fp16,
+        then the fp16 decoder.  ``convnext_f16=True`` / ``False`` sets that option here (``None`` leaves it as it is; a
+        ``set_option("convnext_f16", 1)`` before a ``HipBackend(model, use_fp16=True)`` does the same).  It is 0 by default,
+        and a ConvNeXt program then runs exact under every precision, as it always did: tests/test_gpu_plan_hazards.py pins the
+        fp32 plan of ConvNeXt programs (its one-launch CNBlock MLP included) under ``"split"`` and ``"fp16"``.
+        Programs with a class-vector head (global max pool, softmax) and every training program run exact whatever is set."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
         self.precision = precision
+        if convnext_f16 is not None:
+            self.set_option("convnext_f16", 1 if convnext_f16 else 0)
         if self.ops is self.fused_ops:
             self.set_option("conv_precision", PRECISIONS[precision])
         return self

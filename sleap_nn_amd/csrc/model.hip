@@ -237,8 +237,10 @@ void apply_conv_options(const ph_model* m, ConvArgs& a) {
   a.use_sm = 0;  // (ph_model_forward: the kind of plan decides)
 }
 
-// Programs made only of the UNet-style ops can run on the fp16 matrix pipe (handle option "conv_precision"); anything
-// else (ConvNeXt blocks, class-vector heads, non-3x3 kernels) and every training program stays in exact fp32.
+// Programs made only of the UNet-style ops can run on the fp16 matrix pipe (handle option "conv_precision"); so can, in the
+// plain fp16 precision and with the handle option "convnext_f16" set, programs with the ConvNeXt encoder ops (convnext_f16_kernels.hip).  Anything else (class-vector heads
+// and the global max pool in front of them, non-3x3 kernels, ConvNeXt programs in the split precision) and every training program
+// (conv_precision 0) stays in exact fp32.
 int forward_format(const ph_model* m) {
   if (m->conv_precision != 1 && m->conv_precision != 2) return FMT_F32;
   for (const PackedOp& op : m->ops) {
@@ -248,6 +250,17 @@ int forward_format(const ph_model* m) {
       case PH_OP_INPUT_CONV:
       case PH_OP_POOL:
       case PH_OP_UPSAMPLE:
+        break;
+      case PH_OP_PATCH_STEM:
+      case PH_OP_DWCONV:
+      case PH_OP_LAYERNORM:
+      case PH_OP_PATCH_CONV:
+      case PH_OP_GELU:
+      case PH_OP_SCALE_ADD:
+        if (m->conv_precision != 2 || !m->convnext_f16) return FMT_F32;
+        break;
+      case PH_OP_LINEAR:  // (a Linear with a ReLU is a class-vector head's: exact)
+        if (m->conv_precision != 2 || !m->convnext_f16 || (d.flags & ~(PH_FLAG_GELU | PH_FLAG_SCALE_RESIDUAL)) || !op.w_cnx_f16_dev) return FMT_F32;
         break;
       case PH_OP_CONV:
       case PH_OP_CONVT:
@@ -288,7 +301,7 @@ bool fuses_block2(const ph_model* m, size_t i, int fmt, bool reuse) {
 // CNBlock's MLP in one launch (inference plans that recycle slots: the 4C-wide hidden tensor is nobody else's business): Linear + GELU whose only reader is a
 // Linear with layer scale + residual, both at a width cnblock_mlp_kernel takes
 bool fuses_mlp(const ph_model* m, size_t i, int fmt, bool reuse) {
-  if (!m->mlp_fuse || !reuse || i + 1 >= m->ops.size()) return false;
+  if (!m->mlp_fuse || !reuse || fmt != FMT_F32 || i + 1 >= m->ops.size()) return false;  // (fp32 only: the fp16 pipe runs the pair as two row GEMMs)
   const PackedOp& op = m->ops[i];
   const PackedOp& nxo = m->ops[i + 1];
   const ph_op_desc& d = op.d;
@@ -978,6 +991,25 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
             ok = upload(m, zb, &op.zero_bias_dev) == PH_OK;
           }
         }
+        if (ok) {  // fp16 image for gemm_f16_kernel (plain fp16 precision), derived on the device; refreshed by ph_model_set_params
+          const int coutp32 = fmt_cpad(FMT_F16, d.cout), cinp32 = fmt_cpad(FMT_F16, d.cin0);
+          void* w = nullptr;
+          ok = hipMalloc(&w, (size_t)gemm_f16_weight_image_halves(coutp32, cinp32, segs) * 2) == hipSuccess;
+          if (ok) {
+            m->allocs.push_back(w);
+            ok = launch_gemm_f16_weight_image(op.w_dma_dev, w, d.cout, d.cin0, coutp32, cinp32, segs, op.bn, nullptr) == PH_OK;
+            DerivedBuffer db;
+            db.src = op.w_dma_dev;
+            db.dst = static_cast<float*>(w);
+            db.panels = d.cout;
+            db.n_tiles = d.cin0;
+            db.chunks0 = segs;
+            db.bn = op.bn;
+            db.kind = 7;
+            m->derived.push_back(db);
+            op.w_cnx_f16_dev = w;
+          }
+        }
         if (ok && (d.flags & PH_FLAG_SCALE_RESIDUAL)) {
           if (!widx_ok(d.weight2) || weight_numel[d.weight2] != d.cout || d.src1 < 0) return fail("layer-scale epilogue needs weight2 (C) and a residual source", i);
           ok = pack_upload(m, pad_vec(npad, d.cout), weights[d.weight2], index_array(d.weight2), &op.w2_dev) == PH_OK;
@@ -1089,6 +1121,14 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         if (rc != PH_OK) return rc;
       }
     m->wino4_stale = false;
+  }
+  if (m->cnx_f16_stale && fmt == FMT_F16) {  // (the fp16 row-GEMM images ph_model_set_params left for the first forward that reads them)
+    for (const DerivedBuffer& db : m->derived)
+      if (db.kind == 7) {
+        rc = launch_gemm_f16_weight_image(db.src, db.dst, db.panels, db.n_tiles, fmt_cpad(FMT_F16, db.panels), fmt_cpad(FMT_F16, db.n_tiles), db.chunks0, db.bn, s);
+        if (rc != PH_OK) return rc;
+      }
+    m->cnx_f16_stale = false;
   }
   m->last_variant.assign(m->ops.size(), PH_KV_NONE);
   int* const kv = m->last_variant.data();
@@ -1635,6 +1675,27 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
       case PH_OP_PATCH_STEM: {
         PH_REQUIRE(d.cin0 == in_channels, "input has %d channels, network expects %d", in_channels, d.cin0);
         const SlotShape& so = plan.slots[d.dst];
+        if (fmt == FMT_F16) {
+          PatchStemF16Args f{};
+          f.src = input_dev;
+          f.w = op.w_dev;
+          f.bias = op.b_dev;
+          f.dst = wr(d.dst);
+          f.dtype = in_dtype;
+          f.cin = d.cin0;
+          f.wcp = pad16(d.cout);
+          f.cp = so.cp;
+          f.B = batch;
+          f.H = height;
+          f.W = width;
+          f.OH = so.h;
+          f.OW = so.w;
+          f.k = d.ksize;
+          f.stride = d.cmid;
+          kv[op_index - 1] = PH_KV_CNX_F16_STEM;
+          rc = launch_patch_stem_f16(f, s);
+          break;
+        }
         PatchStemArgs a{};
         a.src = input_dev;
         a.w = op.w_dev;
@@ -1673,6 +1734,37 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
       case PH_OP_DWCONV: {
         const SlotShape& s0 = plan.slots[d.src0];
         PH_REQUIRE(s0.c == d.cin0, "depthwise conv channel mismatch");
+        if (fmt == FMT_F16) {
+          DwConvF16Args f{};
+          f.src = rd(d.src0);
+          f.w = op.w_dev;
+          f.bias = op.b_dev;
+          f.dst = wr(d.dst);
+          f.wcp = pad16(d.cout);
+          f.cp = s0.cp;
+          f.B = batch;
+          f.H = s0.h;
+          f.W = s0.w;
+          if (m->dw_ln_fuse && plan.reuse && f.cp <= 1024 && op_index < m->ops.size()) {  // as below: the LayerNorm rides in the depthwise kernel
+            const ph_op_desc& nx = m->ops[op_index].d;
+            if (nx.kind == PH_OP_LAYERNORM && nx.src0 == d.dst && nx.cin0 == d.cout) {
+              bool other = false;
+              for (size_t k = 0; k < m->ops.size(); ++k)
+                if (k != op_index && (m->ops[k].d.src0 == d.dst || m->ops[k].d.src1 == d.dst)) other = true;
+              if (!other) {
+                f.ln_gamma = m->ops[op_index].w_dev;
+                f.ln_beta = m->ops[op_index].b_dev;
+                f.ln_c = d.cout;
+                unnote(1, d.dst);
+                f.dst = wr(nx.dst);
+                fused_ln = (int)op_index;
+              }
+            }
+          }
+          kv[op_index - 1] = PH_KV_CNX_F16_DW;
+          rc = launch_dwconv7_f16(f, s);
+          break;
+        }
         DwConvArgs a{};
         a.src = rd(d.src0);
         a.w = op.w_dev;
@@ -1705,10 +1797,16 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
       case PH_OP_LAYERNORM: {
         if (fused_ln == (int)op_index - 1) {  // applied by the depthwise conv before it
           fused_ln = -1;
+          if (fmt == FMT_F16) kv[op_index - 1] = PH_KV_FUSED;
           break;
         }
         const SlotShape& s0 = plan.slots[d.src0];
         PH_REQUIRE(s0.c == d.cin0, "LayerNorm channel mismatch");
+        if (fmt == FMT_F16) {
+          kv[op_index - 1] = PH_KV_CNX_F16_LN;
+          rc = launch_layernorm_f16(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), s0.c, pad16(s0.c), s0.cp, (size_t)batch * s0.h * s0.w, s);
+          break;
+        }
         rc = launch_layernorm(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), s0.c, s0.cp, (size_t)batch * s0.h * s0.w, s);
         break;
       }
@@ -1722,6 +1820,28 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         const SlotShape& s0 = plan.slots[d.src0];
         const SlotShape& so = plan.slots[d.dst];
         PH_REQUIRE(s0.c == d.cin0, "GEMM channel mismatch");
+        if (fmt == FMT_F16) {
+          PH_REQUIRE(op.w_cnx_f16_dev && !(d.flags & ~(PH_FLAG_GELU | PH_FLAG_SCALE_RESIDUAL)), "op has no fp16 row-GEMM form");
+          GemmF16Args f{};
+          f.src = rd(d.src0);
+          f.wimg = op.w_cnx_f16_dev;
+          f.bias = op.b_dev;
+          f.dst = wr(d.dst);
+          f.cinp = s0.cp;
+          f.coutp = so.cp;
+          f.M = batch * so.h * so.w;
+          f.taps = d.kind == PH_OP_PATCH_CONV ? 4 : 1;
+          f.H = s0.h;
+          f.W = s0.w;
+          f.gelu = (d.flags & PH_FLAG_GELU) ? 1 : 0;
+          if (d.flags & PH_FLAG_SCALE_RESIDUAL) {
+            f.scale = op.w2_dev;
+            f.residual = rd(d.src1);
+          }
+          kv[op_index - 1] = PH_KV_CNX_F16_GEMM;
+          rc = launch_gemm_f16(f, s);
+          break;
+        }
         if (fuses_mlp(m, op_index - 1, fmt, plan.reuse)) {
           const PackedOp& nxo = m->ops[op_index];
           const ph_op_desc& nx = nxo.d;
@@ -1809,6 +1929,11 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           break;
         }
         const SlotShape& s0 = plan.slots[d.src0];
+        if (fmt == FMT_F16) {
+          kv[op_index - 1] = PH_KV_CNX_F16_ELTWISE;
+          rc = launch_gelu_fmt(fmt, rd(d.src0), wr(d.dst), (size_t)batch * s0.h * s0.w, s0.cp, s);
+          break;
+        }
         rc = launch_gelu_fwd(rd(d.src0), wr(d.dst), (size_t)batch * s0.h * s0.w * s0.cp, s);
         break;
       }
@@ -1819,6 +1944,11 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         }
         const SlotShape& s0 = plan.slots[d.src0];
         PH_REQUIRE(s0.c == d.cin0, "scale-add channel mismatch");
+        if (fmt == FMT_F16) {
+          kv[op_index - 1] = PH_KV_CNX_F16_ELTWISE;
+          rc = launch_scale_add_fmt(fmt, rd(d.src0), rd(d.src1), op.w_dev, wr(d.dst), (size_t)batch * s0.h * s0.w, pad16(d.cout), s0.cp, s);
+          break;
+        }
         rc = launch_scale_add_fwd(rd(d.src0), rd(d.src1), op.w_dev, wr(d.dst), s0.cp, (size_t)batch * s0.h * s0.w * s0.cp, s);
         break;
       }
@@ -1907,6 +2037,7 @@ std::vector<OptionRef> option_table(ph_model* m) {
       {"workspace_reuse", &m->workspace_reuse, nullptr},  // 1: activation slots share memory once their last reader has run (inference programs only)
       {"convt_one_launch", &m->convt_one_launch, nullptr},  // 1: the four output-phase GEMMs of a transposed conv in one launch (grid.y = phase); 0: four launches
       {"convt_phase", &m->convt_phase, nullptr},        // 0: transposed convs by zero-stuffing + 3x3 conv (4x the FLOPs; A/B reference)
+      {"convnext_f16", &m->convnext_f16, nullptr},      // 1: under conv_precision 2 a ConvNeXt program runs whole in plain fp16 (0: exact fp32 whatever the precision)
       {"conv_precision", &m->conv_precision, nullptr},  // 0 exact fp32 MFMA, 1 split-fp16 MFMA (22-bit products), 2 plain fp16 (autocast-equivalent)
       {"gemm_late_split", &m->gemm_late_split, nullptr},
       {"gemm_persist2", &m->gemm_persist2, nullptr},

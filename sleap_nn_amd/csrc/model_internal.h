@@ -5,6 +5,7 @@
 
 #include "act_format.h"
 #include "common.h"
+#include "convnext_f16_kernels.h"
 #include "f16_kernels.h"
 #include "net_kernels.h"
 
@@ -52,6 +53,7 @@ struct PackedOp {
   float* wt_shift_dev = nullptr;
   int bn_t = 0, bn_td = 0;
   float* w_f16_dev[2] = {nullptr, nullptr};  // 3x3 conv / transposed conv on the fp16 matrix pipe: [0] split-fp16, [1] plain fp16 weights (derived lazily from w_dma_dev)
+  void* w_cnx_f16_dev = nullptr;  // Linear / 2x2-stride-2 conv on the fp16 matrix pipe: gemm_f16_kernel's weight image (derived from w_dma_dev at ph_model_create)
   float* w16_dev = nullptr;   // 16 -> 16 channel 3x3 conv: [tap][ci][co] for conv3x3_c16_kernel
   float* wd16_dev = nullptr;  // ... and of its data gradient
 };
@@ -69,7 +71,7 @@ struct DerivedBuffer {
   const float* src = nullptr;
   float* dst = nullptr;
   int panels = 0, bn = 0;  // bn == 0: the fused stem's second conv (launch_stem_wino_pack)
-  int kind = 0;            // 0: Winograd transform of src; 1: fp16 weight pack of the LDS-DMA panels (launch_f16_weight_pack); 2: F(2x2,3x3) transform; 3: wave-private F(2x2,3x3) transform (panels = chunks); 4: the fused stem's F(2x2,3x3) transform; 5: F(4x4,3x3) transform (panels = N tiles, bn = 16-channel chunks); 6: small-map F(2x2,3x3) transform (panels = N blocks of 16, bn = 16-channel chunks, n_tiles = the source packing's N tile)
+  int kind = 0;            // 0: Winograd transform of src; 1: fp16 weight pack of the LDS-DMA panels (launch_f16_weight_pack); 2: F(2x2,3x3) transform; 3: wave-private F(2x2,3x3) transform (panels = chunks); 4: the fused stem's F(2x2,3x3) transform; 5: F(4x4,3x3) transform (panels = N tiles, bn = 16-channel chunks); 6: small-map F(2x2,3x3) transform (panels = N blocks of 16, bn = 16-channel chunks, n_tiles = the source packing's N tile); 7: fp16 row-GEMM weight image of a Linear / 2x2-stride-2 conv (launch_gemm_f16_weight_image: panels = cout, n_tiles = cin, chunks0 = taps, bn = the source packing's N tile)
   int n_tiles = 0, chunks0 = 0, chunks1 = 0, plain = 0;  // kind 1
 };
 
@@ -133,6 +135,7 @@ struct ph_model {
   std::vector<int64_t> weight_numel;
   int64_t n_params = 0;
   bool wino4_stale = false;                    // ph_model_set_params skipped the F(4x4,3x3) weights (training handle): refresh before their next use
+  bool cnx_f16_stale = false;                  // ph_model_set_params skipped the fp16 row-GEMM weight images (conv_precision != 2): refresh before their next use
   std::vector<ph::DerivedBuffer> derived;      // refreshed after the gathers of ph_model_set_params
   std::vector<ph::PackedBuffer> packed;        // every packed weight buffer, for ph_model_set_params
   // ---- per-handle options (ph_model_set_option); the library reads no environment variables
@@ -173,6 +176,7 @@ struct ph_model {
   int workspace_reuse = 0;                    // "workspace_reuse": 1 = slots of an inference program share memory by lifetime (no read-back, no backward)
   int convt_one_launch = 1;                   // "convt_one_launch": the four output-phase GEMMs of a transposed conv as ONE launch (grid.y = phase) instead of four (four launch floors at small batches)
   int convt_phase = 1;                        // "convt_phase": transposed convs as four phase GEMMs (0: zero-stuffing + 3x3 conv, 4x the FLOPs; A/B)
+  int convnext_f16 = 0;                       // "convnext_f16": 1 = a ConvNeXt program under conv_precision 2 runs whole on fp16 activations (convnext_f16_kernels.hip); 0 (default) = it runs exact fp32, as before the fp16 ConvNeXt kernels existed
   int conv_precision = 0;                     // "conv_precision": 0 exact fp32 MFMA; 1 split-fp16 MFMA (22-bit products, fp32 accumulate); 2 plain fp16 (autocast-equivalent)
   // ph_model_set_head_loss: loss of output i in ph_model_backward (0 = never set: MSE / cross entropy as the flags say, PH_FLAG_NO_TRAIN heads refused)
   int head_loss_kind[8] = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -167,6 +167,15 @@ int ph_model_set_params(ph_model* m, const float* params_flat_dev, void* stream)
       if (rc5 != PH_OK) return rc5;
       continue;
     }
+    if (db.kind == 7) {  // fp16 row-GEMM images: only a plain-fp16 forward reads them -- a training step does not pay for them, the next such forward refreshes them (ph_model_forward)
+      if (m->conv_precision != 2 || !m->convnext_f16) {
+        m->cnx_f16_stale = true;
+        continue;
+      }
+      const int rc7 = launch_gemm_f16_weight_image(db.src, db.dst, db.panels, db.n_tiles, fmt_cpad(FMT_F16, db.panels), fmt_cpad(FMT_F16, db.n_tiles), db.chunks0, db.bn, static_cast<hipStream_t>(stream));
+      if (rc7 != PH_OK) return rc7;
+      continue;
+    }
     int rc = db.kind == 1 ? launch_f16_weight_pack(db.src, db.dst, db.n_tiles, db.chunks0, db.chunks1, db.bn, db.plain, static_cast<hipStream_t>(stream))
              : db.kind == 3 ? launch_w16_pack(db.src, db.dst, db.panels, db.bn, static_cast<hipStream_t>(stream))
              : db.kind == 4 ? launch_stem_wino2d_pack(db.src, db.dst, static_cast<hipStream_t>(stream))
