@@ -23,7 +23,10 @@
 //     rule is FEW vector instructions, and every other kind -- LDS, global memory, scalar -- written between the MFMAs of one wave's stream:
 //       - weights come straight from L2 into registers, one quarter ahead (five buffer loads per wave and quarter, each into the registers the
 //         MFMAs before it just read): no LDS ring, no LDS traffic, no LDS-DMA issue cost (~150 cycles per transfer beside MFMAs);
-//       - the halo goes through registers too (buffer load in one quarter, ds_write_b128 in the next): two loads per wave and quarter;
+//       - the halo goes through registers too (buffer load in one quarter, ds_write_b32 in the next): one or two loads per wave and quarter.  The raw slot is channel-planar,
+//         [channel 4][halo row][column]: a transform thread is one (tile, channel) and tile origins are multiples of four columns, so the six patch columns of a row are 24 contiguous,
+//         16-byte-aligned bytes -- one ds_read_b128 + one 8-byte read per patch row (8 reads per thread of an xi pair, 6 of xi 0 / 5) instead of six ds_read_b32; the price is the loader's
+//         four ds_write_b32 per pixel (one per plane) instead of one ds_write_b128;
 //       - the transform is dealt as (16 tiles) x (xi group): waves 0..3 take an xi pair ({1, 2} or {3, 4}: the pair shares its two row
 //         differences), waves 4..7 one of xi 0 / 5, a SIMD one of each; LDS reads are issued one MFMA group ahead of their use;
 //       - the MFMAs of positions 6..8 of a quarter are issued at the top of the NEXT quarter, behind the barrier (their operands wait in
@@ -32,7 +35,7 @@
 //   * Second source at half resolution (ConvArgs::src1_lowres): its slot holds the 18 x 10 LOW-resolution halo (index-clamped by the
 //     loader like the bilinear kernel clamps), the row pass applies B^T U (U = the 6 x 4 bilinear matrix of the patch rows, rows
 //     outside the image zeroed: the conv's padding) as four per-lane coefficients, the column pass forms the six up-sampled column
-//     samples first: 16 instead of 24 LDS reads per thread.
+//     samples first; the four low-resolution columns of a row start at an even column of the plane: two ds_read_b64 per row, 8 reads per thread.
 //   * Epilogue: two rounds through LDS (144 KiB each), every wave with half of its registers per round (channel quads 0, 1, then 2, 3, of both N
 //     halves); all eight waves apply A^T . A: one thread per (tile, channel quad, row half) reads the 36 positions and stores two rows of the 4 x 4
 //     tile: bias, ReLU, the backward pass' ReLU mask, the fused 2 x 2 max pool (its windows are inside a thread's rows), 16-byte stores, eight lanes =
@@ -55,7 +58,12 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int W4_TX = 8, W4_TY = 4;             // Winograd tiles per workgroup tile
 constexpr int W4_PW = 4 * W4_TX;                // 32 output columns
 constexpr int W4_PH = 4 * W4_TY;                // 16 output rows
-constexpr int W4_RAW_FLOATS = 12 * 256;         // one raw halo slot: 12 pieces of 64 entries x 16 B (648 entries used: [hy 18][x & 3][x >> 2: 9]; 11 pieces are moved)
+constexpr int W4_RAW_PITCH = 36;                // a halo row in a raw slot: 34 columns + 2 (row offsets stay multiples of 16 bytes)
+constexpr int W4_RAW_PLANE = 688;               // one channel of a raw slot: 19 rows (18 + the row the second loader piece overshoots into) = 684 floats, rounded up to 48 mod 64 banks
+constexpr int W4_RAW_FLOATS = 3072;             // one raw halo slot (12 KiB), channel-planar: [channel 4][hy 18 + 1][W4_RAW_PITCH] = 4 x 688 = 2752 floats used; 10 pieces of 64 pixels are moved
+static_assert(W4_RAW_PITCH >= W4_PW + 2 && W4_RAW_PITCH % 4 == 0, "a halo row fits its pitch and starts 16-byte aligned");
+static_assert(W4_RAW_PLANE >= (W4_PH + 3) * W4_RAW_PITCH && W4_RAW_PLANE % 64 % 32 == 16, "a plane holds 18 halo rows + the overshoot row; planes 16 banks apart (mod 32): conflict-free ds_read_b128");
+static_assert(4 * W4_RAW_PLANE <= W4_RAW_FLOATS, "four planes fit a raw slot");
 constexpr int W4_V_FLOATS = 36 * 128;           // one V slot: [pg 4][four 16-byte fragment slots + one 8-byte slot][lane 64]
 constexpr int W4_LDS_FLOATS = 36 * 1024;        // the epilogue's exchange: 36 positions x 32 tiles x 8 channel quads x 4 = 144 KiB (the loop uses the first 60 KiB)
 constexpr int W4_Q_FLOATS = 36 * 64 * 4;        // transformed weights of one (N tile, quarter): 36 positions x 64 channels x 4 input channels
@@ -189,8 +197,11 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
 
   // ---- producer constants (t[c] = fma(beta, fma(alpha, d1, d3), fma(alpha, d2, d4)) for xi 1..4, fma(4, P, fma(-5, R, S)) for xi 0 and 5)
   const float alpha = xg == 0 ? -4.f : -1.f, beta = xg == 0 ? 1.f : 2.f, nbeta = -beta;
-  const int pbase_f = ((4 * typ + (xg == 2 ? 0 : 1)) * 36 + txp) * 4 + cp;  // first patch row this thread reads: 1 (xi 1..4: rows 1..4; xi 5: rows 1, 3, 5) or 0 (xi 0: rows 0, 2, 4)
-  const int pbase_l = ((2 * typ) * 18 + txp) * 4 + cp;
+  const int pbase_f = cp * W4_RAW_PLANE + (4 * typ + (xg == 2 ? 0 : 1)) * W4_RAW_PITCH + 4 * txp;  // first patch row this thread reads: 1 (xi 1..4: rows 1..4; xi 5: rows 1, 3, 5) or 0 (xi 0: rows 0, 2, 4)
+  const int pbase_l = cp * W4_RAW_PLANE + (2 * typ) * W4_RAW_PITCH + 2 * txp;
+  // loader role: pixel (lhy, lhx) = entry pw * 64 + lane of the row-major 34-wide halo (rows 0..14 and two pixels of row 15); waves 0 and 1 also move the pixel 15 rows below
+  const int lhy = (pw * 64 + lane) / (W4_PW + 2), lhx = (pw * 64 + lane) - lhy * (W4_PW + 2);
+  const int lwr = lhy * W4_RAW_PITCH + lhx;
   const int vwq = ((cp >> 1) * 32 + typ * 8 + txp) * 4 + (cp & 1) * 2;  // V write: 16-byte slots [lane (c >> 1, tile)][ks = c & 1][position parity]
   const int vwd = 1024 + ((cp >> 1) * 32 + typ * 8 + txp) * 2 + (cp & 1);
   const int vrq = pg * P4_WAVE_FLOATS + lane * 4, vrd = pg * P4_WAVE_FLOATS + 1024 + lane * 2;
@@ -225,33 +236,29 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
     const int qbeg = KS ? ksl * Q / a.ksplit : 0;
     const int qend = KS ? (ksl + 1) * Q / a.ksplit : Q;
     setup(KS ? vid - ksl * units : vid, P);
-    // ---- loader state: this wave moves pieces pw and pw + 8 of a raw slot (pieces 0..10 hold the 648 halo entries; the transfers aimed at piece 11 are out of range = zeros)
+    // ---- loader state: this wave moves piece pw of a raw slot and, waves 0 and 1, the rows 15 below it (rows 15..17; what lands beyond, in row 18, is never read).  The low-resolution
+    // halo (18 x 10) sits at the same (row, column) places, so a lane has ONE LDS address: lanes outside it move zeros.  Row 15, columns 0 and 1 are written twice (lanes 62, 63 of wave 7 and,
+    // as second piece, lanes 0, 1 of wave 0): both lanes load the same pixel, so the two stores carry the same value; no other address is written twice
     unsigned off0[2], off1[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const int e = (pw + 8 * i) * 64 + lane;
-      const int hy = e / 36, rem = e - hy * 36;
-      const int pl = rem / 9, k = rem - pl * 9;
-      const int hx = 4 * k + pl;
+      const int hy = lhy + 15 * i, hx = lhx;
       const int gy = P.y0 + hy - 1, gx = P.x0 + hx - 1;
-      const bool in = pw + 8 * i < 11 && hy < W4_PH + 2 && hx < W4_PW + 2 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+      const bool in = (i == 0 || pw < 2) && hy < W4_PH + 2 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
       off0[i] = in ? (unsigned)((P.b * a.H + gy) * a.W + gx) * (unsigned)(a.c0p * 4) : 0xFFFFFF00u;
       if (!lowres) {
         off1[i] = (in && a.c1p > 0) ? (unsigned)((P.b * a.H + gy) * a.W + gx) * (unsigned)(a.c1p * 4) : 0xFFFFFF00u;
       } else {
-        const int ly = e / 18, rem2 = e - ly * 18;
-        const int par = rem2 / 9, kk = rem2 - par * 9;
-        const int lc = 2 * kk + par;
-        const int sy = min(max((P.y0 >> 1) - 1 + ly, 0), Hl - 1), sx = min(max((P.x0 >> 1) - 1 + lc, 0), Wl - 1);
-        off1[i] = (ly < W4_PH / 2 + 2) ? (unsigned)((P.b * Hl + sy) * Wl + sx) * (unsigned)(a.c1p * 4) : 0xFFFFFF00u;
+        const int sy = min(max((P.y0 >> 1) - 1 + hy, 0), Hl - 1), sx = min(max((P.x0 >> 1) - 1 + hx, 0), Wl - 1);
+        off1[i] = (hy < W4_PH / 2 + 2 && hx < W4_PW / 2 + 2) ? (unsigned)((P.b * Hl + sy) * Wl + sx) * (unsigned)(a.c1p * 4) : 0xFFFFFF00u;
       }
     }
     const __amdgpu_buffer_rsrc_t rsrc0 = __builtin_amdgcn_make_buffer_rsrc((void*)a.src0, 0, (int)((unsigned)(a.B * a.H * a.W) * (unsigned)(a.c0p * 4)), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsrc1 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.src1 ? a.src1 : a.src0), 0,
                                                                            (int)((unsigned)(lowres ? a.B * Hl * Wl : a.B * a.H * a.W) * (unsigned)(a.c1p * 4)), 0x00020000);
-    // The halo goes through registers (buffer load one quarter, ds_write the next): an LDS-DMA transfer costs its wave ~150 cycles of issue beside MFMAs, a register load + ds_write_b128 ~30
+    // The halo goes through registers (buffer load one quarter, four ds_write_b32 the next, one per channel plane): an LDS-DMA transfer costs its wave ~150 cycles of issue beside MFMAs
     f32x4 hreg[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};  // (initialised: left undefined, the register allocator spills 144 registers of the folded-bilinear instantiation instead of 20)
-    const bool has1 = pw + 8 < 11;  // (wave-uniform) this wave owns a second piece of the full-resolution layout
+    const bool has1 = pw < 2;  // (wave-uniform) this wave owns a second piece of the full-resolution layout
     auto load_raw = [&](int k) {  // halo of quarter k into this wave's registers
       const bool s1 = k >= Q0;
       const int so = k < qend ? ((W4_EXP & 64) ? 0 : (s1 ? (k - Q0) * 16 : k * 16)) : 0;
@@ -267,10 +274,14 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
       }
     };
     auto store_raw = [&](int k) {  // ... and from there into raw slot k & 1
-      float* slot = rawbuf + (k & 1) * W4_RAW_FLOATS + lane * 4;
+      float* slot = rawbuf + (k & 1) * W4_RAW_FLOATS + lwr;
       if (W4_EXP & 8) return;
-      *reinterpret_cast<f32x4*>(slot + pw * 256) = hreg[0];
-      if (has1) *reinterpret_cast<f32x4*>(slot + (pw + 8) * 256) = hreg[1];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) slot[c * W4_RAW_PLANE] = hreg[0][c];
+      if (has1) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) slot[15 * W4_RAW_PITCH + c * W4_RAW_PLANE] = hreg[1][c];
+      }
     };
     const int w_tile = P.ntile * Q * (W4_Q_FLOATS * 4);
     f32x4 wf[4];
@@ -319,72 +330,86 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
       zx5 = (P.x0 + 4 * txp + 4 >= a.W) ? 0.f : 1.f;
     }
 
-    // ---- the input transform of quarter k (raw slot k % 3 -> V slot k & 1) in pieces: reads of patch columns [c0, c1), their row pass, then per xi the column pass + stores
+    // ---- the input transform of quarter k (raw slot k & 1 -> V slot k & 1) in pieces: the reads of one half of the patch rows and the part of the row pass they feed, twice (first
+    // the rows of the inner sums), then per xi the column pass + stores.  A thread's patch columns of one row are contiguous in its channel's plane and start at a multiple of four
+    // columns: one ds_read_b128 (columns 0..3) + one ds_read_b64 (4, 5) per row; the four low-resolution columns start at an even column: two ds_read_b64
     float dd[6][4];   // raw values: [patch column][row]
     float ta[6], tb[6];
-    auto t_read = [&](auto xg_tag, auto lr_tag, const float* raw, int c0, int c1) __attribute__((always_inline)) {
+    auto t_read = [&](auto xg_tag, auto lr_tag, const float* raw, int h) __attribute__((always_inline)) {
       constexpr int XG = decltype(xg_tag)::value;
       constexpr bool LR = decltype(lr_tag)::value;
       if (W4_EXP & 2) return;
-      if constexpr (LR) {  // (columns = the four low-resolution columns; rows = the four low-resolution rows)
+      if constexpr (LR) {  // (columns = the four low-resolution columns; rows = the four low-resolution rows: 2 and 3 first)
         const float* p = raw + pbase_l;
 #pragma unroll
-        for (int n = 0; n < 4; ++n)
-          if (n >= c0 && n < c1) {
-            const int co = ((n & 1) * 9 + (n >> 1)) * 4;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dd[n][r] = p[co + r * 18 * 4];
+        for (int r = 0; r < 4; ++r)
+          if ((r >= 2) == (h == 0)) {
+            const f32x2 lo = *reinterpret_cast<const f32x2*>(p + r * W4_RAW_PITCH), hi = *reinterpret_cast<const f32x2*>(p + r * W4_RAW_PITCH + 2);
+            dd[0][r] = lo[0];
+            dd[1][r] = lo[1];
+            dd[2][r] = hi[0];
+            dd[3][r] = hi[1];
           }
-      } else {
+      } else {  // (rows r = patch rows 1..4 of an xi pair: 1 and 3 first; every second patch row of xi 0 / 5: the last two first)
         const float* p = raw + pbase_f;
+        constexpr int NR = XG < 2 ? 4 : 3, RS = XG < 2 ? 1 : 2;
 #pragma unroll
-        for (int c = 0; c < 6; ++c)
-          if (c >= c0 && c < c1) {
-            const int co = ((c & 3) * 9 + (c >> 2)) * 4;
-            if constexpr (XG < 2) {
+        for (int r = 0; r < NR; ++r)
+          if ((XG < 2 ? (r & 1) == 1 : r >= 1) == (h == 0)) {
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(p + r * RS * W4_RAW_PITCH);
+            const f32x2 hi = *reinterpret_cast<const f32x2*>(p + r * RS * W4_RAW_PITCH + 4);
 #pragma unroll
-              for (int r = 0; r < 4; ++r) dd[c][r] = p[co + r * 144];
-            } else {
-#pragma unroll
-              for (int r = 0; r < 3; ++r) dd[c][r] = p[co + 2 * r * 144];
-            }
+            for (int c = 0; c < 4; ++c) dd[c][r] = lo[c];
+            dd[4][r] = hi[0];
+            dd[5][r] = hi[1];
           }
       }
     };
     float tla[4], tlb[4];
-    auto t_rows = [&](auto xg_tag, auto lr_tag, int c0, int c1) __attribute__((always_inline)) {
+    auto t_rows = [&](auto xg_tag, auto lr_tag, int h) __attribute__((always_inline)) {  // h = 0: the inner sums (of the rows read first), 1: the rest
       constexpr int XG = decltype(xg_tag)::value;
       constexpr bool LR = decltype(lr_tag)::value;
       if (W4_EXP & 2) return;
       if constexpr (LR) {
 #pragma unroll
-        for (int n = 0; n < 4; ++n)
-          if (n >= c0 && n < c1) {
-            tla[n] = fmaf(cl[0][0], dd[n][0], fmaf(cl[0][1], dd[n][1], fmaf(cl[0][2], dd[n][2], cl[0][3] * dd[n][3])));
-            asm volatile("" : "+v"(tla[n]));
-            if constexpr (XG < 2) {
-              tlb[n] = fmaf(cl[1][0], dd[n][0], fmaf(cl[1][1], dd[n][1], fmaf(cl[1][2], dd[n][2], cl[1][3] * dd[n][3])));
-              asm volatile("" : "+v"(tlb[n]));
-            }
+        for (int n = 0; n < 4; ++n) {
+          if (h == 0) {
+            tla[n] = fmaf(cl[0][2], dd[n][2], cl[0][3] * dd[n][3]);
+            if constexpr (XG < 2) tlb[n] = fmaf(cl[1][2], dd[n][2], cl[1][3] * dd[n][3]);
+          } else {
+            tla[n] = fmaf(cl[0][0], dd[n][0], fmaf(cl[0][1], dd[n][1], tla[n]));
+            if constexpr (XG < 2) tlb[n] = fmaf(cl[1][0], dd[n][0], fmaf(cl[1][1], dd[n][1], tlb[n]));
           }
+          asm volatile("" : "+v"(tla[n]));
+          if constexpr (XG < 2) asm volatile("" : "+v"(tlb[n]));
+        }
       } else {
 #pragma unroll
-        for (int c = 0; c < 6; ++c)
-          if (c >= c0 && c < c1) {
-            if (W4_EXP & 128) {
-              ta[c] = dd[c][0];
+        for (int c = 0; c < 6; ++c) {
+          if (W4_EXP & 128) {
+            if (h == 0)
               tb[c] = dd[c][1];
-            } else if constexpr (XG < 2) {
-              const float A = fmaf(alpha, dd[c][1], dd[c][3]);
+            else
+              ta[c] = dd[c][0];
+          } else if constexpr (XG < 2) {
+            if (h == 0) {
+              ta[c] = fmaf(alpha, dd[c][1], dd[c][3]);
+              asm volatile("" : "+v"(ta[c]));
+            } else {
+              const float A = ta[c];
               const float Bv = fmaf(alpha, dd[c][0], dd[c][2]);
               ta[c] = fmaf(beta, Bv, A);
               tb[c] = fmaf(nbeta, Bv, A);
               asm volatile("" : "+v"(ta[c]), "+v"(tb[c]));  // scalar chains: packed-fp32 VALU (and the moves that feed it) is a loss beside MFMAs
-            } else {
-              ta[c] = fmaf(4.f, dd[c][0], fmaf(-5.f, dd[c][1], dd[c][2]));
-              asm volatile("" : "+v"(ta[c]));
             }
+          } else {
+            if (h == 0)
+              ta[c] = fmaf(-5.f, dd[c][1], dd[c][2]);
+            else
+              ta[c] = fmaf(4.f, dd[c][0], ta[c]);
+            asm volatile("" : "+v"(ta[c]));
           }
+        }
       }
     };
     auto t_mix = [&](const float (&tl)[4], float (&tt)[6]) __attribute__((always_inline)) {  // low resolution: the six up-sampled column samples of a row-transformed patch
@@ -429,13 +454,17 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
       float* vslot = vbuf + (k & 1) * W4_V_FLOATS;
       constexpr int XG = decltype(xg_tag)::value;
       if (lowres && k >= Q0) {
-        t_read(xg_tag, std::true_type{}, raw, 0, 4);
-        t_rows(xg_tag, std::true_type{}, 0, 4);
+        t_read(xg_tag, std::true_type{}, raw, 0);
+        t_read(xg_tag, std::true_type{}, raw, 1);
+        t_rows(xg_tag, std::true_type{}, 0);
+        t_rows(xg_tag, std::true_type{}, 1);
         t_cols(xg_tag, std::true_type{}, std::integral_constant<int, 0>{}, vslot);
         if constexpr (XG < 2) t_cols(xg_tag, std::true_type{}, std::integral_constant<int, 1>{}, vslot);
       } else {
-        t_read(xg_tag, std::false_type{}, raw, 0, 6);
-        t_rows(xg_tag, std::false_type{}, 0, 6);
+        t_read(xg_tag, std::false_type{}, raw, 0);
+        t_read(xg_tag, std::false_type{}, raw, 1);
+        t_rows(xg_tag, std::false_type{}, 0);
+        t_rows(xg_tag, std::false_type{}, 1);
         t_cols(xg_tag, std::false_type{}, std::integral_constant<int, 0>{}, vslot);
         if constexpr (XG < 2) t_cols(xg_tag, std::false_type{}, std::integral_constant<int, 1>{}, vslot);
       }
@@ -489,7 +518,6 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
       constexpr bool MM = decltype(mm_tag)::value;
       constexpr bool LR = decltype(lr_tag)::value;
       constexpr bool PAIR = XG < 2;
-      constexpr int NC = LR ? 4 : 6, H1 = NC / 2;  // raw columns, read in two halves
       const std::integral_constant<int, 0> first{};
       const std::integral_constant<int, 1> second{};
       for (int q = q0; q < q1; ++q) {
@@ -506,7 +534,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
         }
         P4_SB
         store_raw(q + 2);  // (loaded during quarter q - 1; slot q & 1 was transformed during quarter q - 1)
-        t_read(xg_tag, lr_tag, raw, 0, H1);
+        t_read(xg_tag, lr_tag, raw, 0);
         P4_SB
         P4_ST(1)
         if constexpr (MM) {
@@ -526,8 +554,8 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
           acc[8] = P4_MFMA(wf9[1], vf9.y, acc[8]);
           load_w(q, 4);
         }
-        t_rows(xg_tag, lr_tag, 0, H1);
-        t_read(xg_tag, lr_tag, raw, H1, NC);
+        t_rows(xg_tag, lr_tag, 0);
+        t_read(xg_tag, lr_tag, raw, 1);
         P4_SB
         P4_ST(4)
         if constexpr (MM) {
@@ -538,7 +566,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
           acc[1] = P4_MFMA(wf[0][3], vf0[3], acc[1]);
           load_w(q + 1, 0);
         }
-        t_rows(xg_tag, lr_tag, H1, NC);
+        t_rows(xg_tag, lr_tag, 1);
         P4_SB
         P4_ST(5)
         if constexpr (MM) {
