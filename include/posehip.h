@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 119
+#define PH_VERSION 120
 
 /* error codes */
 #define PH_OK 0
@@ -93,16 +93,25 @@ enum ph_op_kind {
   PH_OP_PATCH_STEM = 8, /* image -> /255 -> Conv2d(k = ksize, stride = cmid, padding 1) + bias -> NHWC slot
                            (convnext.py:73-84; the LayerNorm2d that follows is a PH_OP_LAYERNORM)       */
   PH_OP_DWCONV = 9,     /* depthwise 7x7 "same" conv + bias, weight (C,1,7,7)  (CNBlock.block[0])       */
-  PH_OP_LAYERNORM = 10, /* LayerNorm over channels, eps 1e-6, weight/bias = affine (LayerNorm2d, block[2]) */
+  PH_OP_LAYERNORM = 10, /* LayerNorm over channels, eps 1e-6 (1e-5 with PH_FLAG_LN_EPS_1EM5), weight/bias = affine (LayerNorm2d, block[2]; the Swin norms) */
   PH_OP_LINEAR = 11,    /* per-pixel Linear(cin0 -> cout), weight (cout, cin0) + bias; PH_FLAG_GELU: erf-GELU
                            epilogue (block[3..4]); PH_FLAG_SCALE_RESIDUAL: dst = weight2[c] * (acc + bias) +
-                           src1 (block[5], layer_scale, residual add)                                    */
+                           src1 (block[5], layer_scale, residual add); PH_FLAG_RESIDUAL: dst = acc + bias + src1;
+                           bias = -1: Linear(bias=False)                                                 */
   PH_OP_PATCH_CONV = 12, /* Conv2d(k2, s2) + bias, weight (cout, cin0, 2, 2)  (convnext.py:101-110)     */
   /* the two epilogues of PH_OP_LINEAR as ops of their own: the training program keeps the
      pre-activation tensors that autograd needs (GELU input, un-scaled block output)              */
   PH_OP_GELU = 13,      /* dst = GELU_erf(src0)                                                          */
   PH_OP_SCALE_ADD = 14, /* dst = weight[c] * src0 + src1   (layer_scale * block(x) + x)                  */
-  PH_OP_GLOBAL_MAXPOOL = 15 /* dst (1x1) = max over H x W of src0 (nn.AdaptiveMaxPool2d(1), heads.py:519-520) */
+  PH_OP_GLOBAL_MAXPOOL = 15, /* dst (1x1) = max over H x W of src0 (nn.AdaptiveMaxPool2d(1), heads.py:519-520) */
+  /* Swin Transformer encoder (architectures/swint.py; the blocks are torchvision's SwinTransformerBlock / PatchMerging).  Exact fp32, inference only. */
+  PH_OP_PATCH_MERGE = 16, /* (B, H, W, C) -> (B, ceil(H/2), ceil(W/2), 4C): concat of x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2] (zeros past an odd
+                             edge) + LayerNorm over the 4C channels (weight / bias = its affine), one launch; the bias-less PH_OP_LINEAR `reduction` follows */
+  PH_OP_WINDOW_ATTN = 17  /* shifted-window multi-head attention core: src0 = qkv slot (B, H, W, 3C) of the un-padded, un-rolled map (q | k | v, head a owns
+                             channels 32 a .. 32 a + 31 of each), weight = relative_position_bias_table ((2 ksize - 1)^2, heads), bias = qkv.bias (3C; the q, k, v
+                             of a padded token), ksize = window side (2..8), cin1 = heads (cout = 32 heads), cmid = nominal shift (an axis whose padded size the
+                             window covers is not shifted).  dst (B, H, W, C) = softmax(q k^T / sqrt(32) + bias [- 100 across the shift's bands]) v at each
+                             token's own pixel: pad, roll, window partition, reverse and crop are index arithmetic of the one launch */
 };
 
 #define PH_FLAG_RELU 1
@@ -113,6 +122,8 @@ enum ph_op_kind {
 #define PH_FLAG_SILU 32    /* PH_OP_CONVT: SiLU instead of ReLU (the activation is an epilogue parameter of the phase GEMMs) */
 #define PH_FLAG_NO_TRAIN 64 /* PH_OP_HEAD: a head of the segmentation model types, which neither MSE nor cross entropy trains; the forward ignores it,
                                ph_model_backward refuses the program unless ph_model_set_head_loss chose the head's loss on this handle */
+#define PH_FLAG_LN_EPS_1EM5 128 /* PH_OP_LAYERNORM / PH_OP_PATCH_MERGE: eps 1e-5 (nn.LayerNorm's default: the Swin norms) instead of 1e-6 */
+#define PH_FLAG_RESIDUAL 256    /* PH_OP_LINEAR: dst = acc + bias + src1 (a residual add without a layer scale: Swin's attn.proj and mlp.3) */
 
 typedef struct ph_op_desc {
   int32_t kind;      /* enum ph_op_kind                                              */
@@ -125,12 +136,12 @@ typedef struct ph_op_desc {
   int32_t ksize;     /* kernel size (PH_OP_CONV / INPUT_CONV: odd, <= 7)             */
   int32_t flags;     /* PH_FLAG_*                                                    */
   int32_t weight;    /* index into the weights[] array of ph_model_create, or -1     */
-  int32_t bias;      /* index into the weights[] array, or -1                        */
+  int32_t bias;      /* index into the weights[] array, or -1 (PH_OP_LINEAR: -1 = Linear(bias=False)) */
   int32_t out_index; /* PH_OP_HEAD: which output pointer receives the result         */
   int32_t dst2;      /* PH_OP_STEM: pooled output slot; PH_OP_CONV (ReLU): optional fused 2x2 max-pool slot, -1 = none */
   int32_t weight2;   /* PH_OP_STEM: second conv weight index; PH_OP_LINEAR: layer_scale index; PH_OP_CONVT: folded-BN scale or -1 */
   int32_t bias2;     /* PH_OP_STEM: second conv bias index; PH_OP_CONVT: folded-BN shift or -1 */
-  int32_t cmid;      /* PH_OP_STEM: channels between the two convs (<= 16); PH_OP_PATCH_STEM: stride */
+  int32_t cmid;      /* PH_OP_STEM: channels between the two convs (<= 16); PH_OP_PATCH_STEM: stride; PH_OP_WINDOW_ATTN: nominal shift */
 } ph_op_desc;
 
 /* sizeof(ph_op_desc) as the library was compiled: a binding checks its own struct against it
@@ -366,6 +377,7 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_CNX_F16_LN 18   /* layernorm_f16_kernel: LayerNorm over the channels of an fp16 tensor, fp32 moments                                  */
 #define PH_KV_CNX_F16_GEMM 19 /* gemm_f16_kernel: Linear / 2x2-stride-2 conv as a row GEMM on v_mfma_f32_32x32x16_f16 (bias, GELU, layer scale + residual epilogues) */
 #define PH_KV_CNX_F16_ELTWISE 20 /* gelu_fmt_kernel / scale_add_fmt_kernel on fp16 activations (unfused programs)                                    */
+#define PH_KV_WINDOW_ATTN 21 /* window_attn_kernel: one wave per (window, head), q k^T and p v on v_mfma_f32_32x32x2_f32, softmax in registers */
 #define PH_KV_FUSED 11    /* no launch of its own: a 1x1 head computed in the epilogue of the conv that produces its input */
 int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
 

@@ -16,11 +16,14 @@ PH_E_INVALID, PH_E_HIP, PH_E_CAPACITY, PH_E_INFEASIBLE, PH_E_WORKSPACE = -1, -2,
 
 OP_INPUT_CONV, OP_CONV, OP_POOL, OP_UPSAMPLE, OP_CONVT, OP_HEAD, OP_STEM = 1, 2, 3, 4, 5, 6, 7
 OP_PATCH_STEM, OP_DWCONV, OP_LAYERNORM, OP_LINEAR, OP_PATCH_CONV, OP_GELU, OP_SCALE_ADD, OP_GLOBAL_MAXPOOL = 8, 9, 10, 11, 12, 13, 14, 15
+OP_PATCH_MERGE, OP_WINDOW_ATTN = 16, 17  # Swin Transformer encoder (swin_kernels.hip)
 FLAG_RELU, FLAG_SIGMOID, FLAG_GELU, FLAG_SCALE_RESIDUAL, FLAG_SOFTMAX, FLAG_SILU, FLAG_NO_TRAIN = 1, 2, 4, 8, 16, 32, 64
+FLAG_LN_EPS_1EM5, FLAG_RESIDUAL = 128, 256
 LOSS_MSE, LOSS_BCE_DICE, LOSS_MASKED_SMOOTH_L1 = 1, 2, 3  # PH_LOSS_*: ph_model_set_head_loss
 # PH_KV_*: kernel family an op of the last forward ran (ph_model_last_kernels) and the share of its direct-convolution
 # FLOPs that family puts through the matrix cores
 KV_NONE, KV_DIRECT, KV_WINO1D, KV_WINO2D, KV_W16, KV_C16, KV_ROWGEMM, KV_WINO4, KV_F16, KV_STEM, KV_WINO2D_KS, KV_FUSED, KV_SMALLMAP, KV_F16_ROWS, KV_F16_BLOCK, KV_MLP = range(16)
+SWIN_KV_WINDOW_ATTN = 21  # PH_KV_WINDOW_ATTN (swin_kernels.hip); not named KV_* either, for the reason below
 CNX_KV_F16_STEM, CNX_KV_F16_DW, CNX_KV_F16_LN, CNX_KV_F16_GEMM, CNX_KV_F16_ELTWISE = 16, 17, 18, 19, 20  # PH_KV_CNX_F16_*: the ConvNeXt encoder ops on fp16 activations (convnext_f16_kernels.hip); not named KV_*: that prefix lists the families a 3x3 conv can come back with (benchlegs.common.conv_kernel_short_names)
 KV_NAMES = {KV_NONE: "none", KV_DIRECT: "conv3x3_mfma_dma_persist_kernel (direct)", KV_WINO1D: "conv3x3_wino_persist_kernel (Winograd F(2,3) along x)",
             KV_WINO2D: "conv3x3_wino2d_kernel<64> (Winograd F(2x2,3x3))", KV_W16: "conv3x3_w16_kernel (wave-private Winograd F(2x2,3x3), 16x16x4 MFMA)",
@@ -35,8 +38,9 @@ KV_NAMES = {KV_NONE: "none", KV_DIRECT: "conv3x3_mfma_dma_persist_kernel (direct
             CNX_KV_F16_DW: "dwconv7_f16_kernel / dwconv7_ln_f16_kernel (depthwise 7x7 on fp16 activations, LayerNorm fused in inference plans)",
             CNX_KV_F16_LN: "layernorm_f16_kernel (LayerNorm over channels, fp16 storage, fp32 moments)",
             CNX_KV_F16_GEMM: "gemm_f16_kernel (row GEMM on v_mfma_f32_32x32x16_f16: Linear / 2x2-stride-2 conv)",
-            CNX_KV_F16_ELTWISE: "gelu_fmt_kernel / scale_add_fmt_kernel (fp16 activations)"}
-KV_MFMA_SHARE = {KV_NONE: 0.0, KV_DIRECT: 1.0, KV_WINO1D: 2.0 / 3.0, KV_WINO2D: 4.0 / 9.0, KV_W16: 4.0 / 9.0, KV_C16: 1.0, KV_ROWGEMM: 1.0, KV_WINO4: 0.25, KV_F16: 1.0, KV_STEM: 4.0 / 9.0, KV_WINO2D_KS: 4.0 / 9.0, KV_FUSED: 0.0, KV_SMALLMAP: 4.0 / 9.0, KV_F16_ROWS: 1.0, KV_F16_BLOCK: 1.0, KV_MLP: 1.0, CNX_KV_F16_STEM: 0.0, CNX_KV_F16_DW: 0.0, CNX_KV_F16_LN: 0.0, CNX_KV_F16_GEMM: 1.0, CNX_KV_F16_ELTWISE: 0.0}
+            CNX_KV_F16_ELTWISE: "gelu_fmt_kernel / scale_add_fmt_kernel (fp16 activations)",
+            SWIN_KV_WINDOW_ATTN: "window_attn_kernel (shifted-window attention, one wave per window and head, v_mfma_f32_32x32x2_f32)"}
+KV_MFMA_SHARE = {KV_NONE: 0.0, KV_DIRECT: 1.0, KV_WINO1D: 2.0 / 3.0, KV_WINO2D: 4.0 / 9.0, KV_W16: 4.0 / 9.0, KV_C16: 1.0, KV_ROWGEMM: 1.0, KV_WINO4: 0.25, KV_F16: 1.0, KV_STEM: 4.0 / 9.0, KV_WINO2D_KS: 4.0 / 9.0, KV_FUSED: 0.0, KV_SMALLMAP: 4.0 / 9.0, KV_F16_ROWS: 1.0, KV_F16_BLOCK: 1.0, KV_MLP: 1.0, CNX_KV_F16_STEM: 0.0, CNX_KV_F16_DW: 0.0, CNX_KV_F16_LN: 0.0, CNX_KV_F16_GEMM: 1.0, CNX_KV_F16_ELTWISE: 0.0, SWIN_KV_WINDOW_ATTN: 1.0}
 
 
 class OpDesc(C.Structure):

@@ -162,6 +162,11 @@ class ConvNextWrapper:
                 self.labels[f"{pfx}.{fi}"] = x
                 skips.append((x, ch[si + 1]))
                 fi += 1
+        self._build_tail(x, skips)
+
+    def _build_tail(self, x: int, skips: List[Tuple[int, int]]) -> None:
+        """Additional pool, middle blocks and decoder behind the encoder (shared with the Swin wrapper, whose tail is the same code in the reference)."""
+        ch = self.channels
         cur, cur_c = x, ch[-1]
         # additional pool + middle blocks (convnext.py:219-270, 352-358)
         cur = self._emit(OpSpec(L.OP_POOL, cur, -1, self._new_slot(), cur_c, label="additional_pool"))

@@ -16,6 +16,7 @@ import torch
 from sleap_nn_amd import _lib as L
 from sleap_nn_amd.architectures.heads import SEGMENTATION_MODEL_TYPES, ClassMapsHead, ClassVectorsHead, Head, SegmentationHead, get_head
 from sleap_nn_amd.architectures.convnext import ConvNextWrapper
+from sleap_nn_amd.architectures.swint import SwinTWrapper
 from sleap_nn_amd.architectures.unet import OpSpec, UNet
 from sleap_nn_amd.utils import cfg_get, cfg_keys
 
@@ -24,14 +25,16 @@ PRECISIONS = {"exact": 0, "split": 1, "fp16": 2}
 
 
 def get_backbone(backbone: str, backbone_config):
-    """architectures/model.py:36-67.  ``unet`` and ``convnext`` are built natively."""
+    """architectures/model.py:36-67.  ``unet``, ``convnext`` and ``swint`` (inference) are built natively."""
     if backbone == "unet":
         return UNet.from_config(backbone_config)
     if backbone == "convnext":
         return ConvNextWrapper.from_config(backbone_config)
-    if backbone in ("swint", "pretrained"):
+    if backbone == "swint":
+        return SwinTWrapper.from_config(backbone_config)
+    if backbone == "pretrained":
         raise NotImplementedError(f"backbone '{backbone}' is not implemented on the MI355X path yet")
-    raise KeyError(f"Unsupported backbone: {backbone}. Supported backbones are: unet, convnext")
+    raise KeyError(f"Unsupported backbone: {backbone}. Supported backbones are: unet, convnext, swint")
 
 
 class Model:
@@ -48,6 +51,8 @@ class Model:
 
         self.ops: List[OpSpec] = list(self.backbone.ops)
         self.param_shapes = dict(self.backbone.param_shapes)
+        # checkpoint entries that are not parameters (Swin's relative_position_index): checked at load, kept out of the parameter arena
+        self.buffers: Dict[str, torch.Tensor] = dict(getattr(self.backbone, "buffers", {}))
         self._head_ops_start = len(self.ops)
         for i, head in enumerate(self.heads):
             if isinstance(head, ClassVectorsHead):
@@ -200,7 +205,7 @@ class Model:
 
     # -- parameters -----------------------------------------------------------------------
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        return dict(self._state)
+        return {**self._state, **self.buffers}
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
         """Accepts ``Model`` keys or LightningModule keys (``model.`` prefix, loaders.py:144-176)."""
@@ -209,9 +214,15 @@ class Model:
             k = k[len("model.") :] if k.startswith("model.") else k
             sd[k] = v
         missing = [k for k in self.param_shapes if k not in sd]
-        unexpected = [k for k in sd if k not in self.param_shapes]
+        missing += [k for k in self.buffers if k not in sd]
+        unexpected = [k for k in sd if k not in self.param_shapes and k not in self.buffers]
         if strict and (missing or unexpected):
             raise RuntimeError(f"Error(s) in loading state_dict: missing {missing}, unexpected {unexpected}")
+        for k, want in self.buffers.items():  # the kernels compute these from coordinates: a checkpoint that disagrees was written by another definition
+            if k in sd:
+                got = torch.as_tensor(sd[k]).detach().to("cpu")
+                if tuple(got.shape) != tuple(want.shape) or not torch.equal(got.to(want.dtype), want):
+                    raise RuntimeError(f"buffer {k} of the checkpoint differs from the canonical relative position index of a {self.backbone.window_size}x{self.backbone.window_size} window")
         for k, shape in self.param_shapes.items():
             if k in sd:
                 t = torch.as_tensor(sd[k]).detach().to("cpu", torch.float32).contiguous()
@@ -236,7 +247,7 @@ class Model:
             if k.endswith(".layer_scale"):
                 sd[k] = torch.full(shape, 1e-6)
             elif len(shape) == 1:
-                ln = k.endswith(".weight") and any(o.kind == L.OP_LAYERNORM and o.weight == k for o in self.unfused_ops)
+                ln = k.endswith(".weight") and any(o.kind in (L.OP_LAYERNORM, L.OP_PATCH_MERGE) and o.weight == k for o in self.unfused_ops)
                 sd[k] = torch.ones(shape) if ln else torch.zeros(shape)
             else:
                 rf = 1
@@ -246,6 +257,7 @@ class Model:
                 bound = math.sqrt(6.0 / (fan_in + fan_out))
                 w = (torch.rand(shape, generator=g) * 2 - 1) * bound
                 sd[k] = w * head_scale if k.startswith("head_layers.") else w
+        sd.update(self.buffers)
         self.load_state_dict(sd, strict=True)
         return self
 
@@ -257,6 +269,8 @@ class Model:
 
     def train(self, mode: bool = True) -> "Model":
         """Training keeps every activation: the op-by-op (unfused) program runs."""
+        if mode and self.backbone_type == "swint":
+            raise NotImplementedError("training a 'swint' backbone is not implemented on the MI355X path (inference only)")
         return self.set_fusion(not mode)
 
     def set_fusion(self, fused: bool) -> "Model":
@@ -522,6 +536,14 @@ class Model:
                 oh, ow = (h + 2 - op.ksize) // op.cmid + 1, (w + 2 - op.ksize) // op.cmid + 1
             elif op.kind == L.OP_PATCH_CONV:
                 oh, ow = h // 2, w // 2
+            elif op.kind == L.OP_PATCH_MERGE:
+                oh, ow = (h + 1) // 2, (w + 1) // 2
+            if op.kind == L.OP_WINDOW_ATTN:
+                # q k^T and p v: 2 * N * d multiply-adds each per token and head (cin1 = heads, ksize = window side, head dimension cout / heads)
+                rows.append({"label": op.label.split(".")[-1], "kind": op.kind, "flops": 4.0 * op.ksize * op.ksize * op.cout * h * w * batch,
+                             "bytes": float(4 * (op.cin0 + op.cout) * h * w * batch), "cin0": op.cin0, "cin1": 0, "cout": op.cout, "ksize": op.ksize, "out_hw": (h, w)})
+                hw[op.dst] = (h, w)
+                continue
             if op.kind == L.OP_POOL:
                 oh, ow = (h + 1) // 2, (w + 1) // 2
             elif op.kind in (L.OP_UPSAMPLE, L.OP_CONVT):

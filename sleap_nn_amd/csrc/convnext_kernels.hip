@@ -403,7 +403,7 @@ int launch_dwconv7(const DwConvArgs& a, hipStream_t s) {
 // variance, and are written as zeros (gamma / beta are zero-padded).
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ src, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        float* __restrict__ dst, int c, int cp, size_t npix) {
+                                                        float* __restrict__ dst, int c, int cp, size_t npix, float eps) {
   const int sub = threadIdx.x & 15;
   const int quads = cp >> 2;
   const float inv_c = 1.0f / (float)c;
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     ss += __shfl_xor(ss, 4, 16);
     ss += __shfl_xor(ss, 2, 16);
     ss += __shfl_xor(ss, 1, 16);
-    const float rstd = 1.0f / sqrtf(ss * inv_c + LN_EPS);
+    const float rstd = 1.0f / sqrtf(ss * inv_c + eps);
     if (live) {
       float* o = dst + pix * cp;
       for (int q = sub; q < quads; q += 16) {
@@ -452,9 +452,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   }
 }
 
-int launch_layernorm(const float* src, const float* gamma, const float* beta, float* dst, int c, int cp, size_t npix, hipStream_t s) {
+int launch_layernorm(const float* src, const float* gamma, const float* beta, float* dst, int c, int cp, size_t npix, hipStream_t s, float eps) {
   const int blocks = (int)std::min<size_t>((npix + 15) / 16, 256 * 32);
-  hipLaunchKernelGGL(layernorm_kernel, dim3(blocks), dim3(256), 0, s, src, gamma, beta, dst, c, cp, npix);
+  hipLaunchKernelGGL(layernorm_kernel, dim3(blocks), dim3(256), 0, s, src, gamma, beta, dst, c, cp, npix, eps);
   PH_HIP_CHECK(hipGetLastError());
   return PH_OK;
 }

@@ -21,6 +21,9 @@ __device__ __forceinline__ float erf_as(float x) {
   return copysignf(r, x);
 }
 
+// exp on the hardware v_exp_f32 (1 ulp on 2^y; the rounding of y = x log2(e) adds |x| * 6e-8 relative): softmax arguments are <= 0 after the row maximum is subtracted
+__device__ __forceinline__ float exp_hw(float x) { return __builtin_amdgcn_exp2f(1.4426950408889634f * x); }
+
 // GELU (erf form, nn.GELU default) and its derivative  d/dx [x * Phi(x)] = Phi(x) + x * phi(x).
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erf_as(x * 0.70710678118654752440f)); }
 // Two values at a time on the packed fp32 instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: two results per lane and issue slot): the same operations in the same

@@ -428,7 +428,13 @@ int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
       oh = h / 2;
       ow = w / 2;
       PH_REQUIRE(oh > 0 && ow > 0, "input of a 2x2/stride-2 convolution is smaller than 2x2");
-    } else if ((d.kind == PH_OP_LINEAR && (d.flags & PH_FLAG_SCALE_RESIDUAL)) || d.kind == PH_OP_SCALE_ADD) {
+    } else if (d.kind == PH_OP_PATCH_MERGE) {  // pad to even, four phases on the channels
+      oh = (h + 1) / 2;
+      ow = (w + 1) / 2;
+      PH_REQUIRE(plan.slots[d.src0].c == d.cin0 && d.cout == 4 * d.cin0, "patch merge channel mismatch");
+    } else if (d.kind == PH_OP_WINDOW_ATTN) {
+      PH_REQUIRE(d.src0 >= 0 && plan.slots[d.src0].c == d.cin0 && d.cin0 == 3 * d.cout, "window attention reads a (3C)-channel qkv slot");
+    } else if ((d.kind == PH_OP_LINEAR && (d.flags & (PH_FLAG_SCALE_RESIDUAL | PH_FLAG_RESIDUAL))) || d.kind == PH_OP_SCALE_ADD) {
       PH_REQUIRE(d.src1 >= 0 && d.src1 < m->n_slots && plan.slots[d.src1].offset >= 0, "residual slot %d is not written yet", d.src1);
       const SlotShape& s1 = plan.slots[d.src1];
       PH_REQUIRE(s1.h == h && s1.w == w && s1.c == d.cout, "residual shape mismatch");
@@ -955,18 +961,50 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
              pack_upload(m, pad_vec(cp, d.cout), weights[d.bias], index_array(d.bias), &op.b_dev) == PH_OK;
         break;
       }
+      case PH_OP_PATCH_MERGE: {
+        if (!widx_ok(d.weight) || !widx_ok(d.bias)) return fail("weight index out of range", i);
+        if (d.cout != 4 * d.cin0 || (d.cin0 & 15) || weight_numel[d.weight] != d.cout || weight_numel[d.bias] != d.cout)
+          return fail("patch merge needs a channel count that is a multiple of 16 and a (4C) LayerNorm affine", i);
+        ok = pack_upload(m, pad_vec(d.cout, d.cout), weights[d.weight], index_array(d.weight), &op.w_dev) == PH_OK &&
+             pack_upload(m, pad_vec(d.cout, d.cout), weights[d.bias], index_array(d.bias), &op.b_dev) == PH_OK;
+        break;
+      }
+      case PH_OP_WINDOW_ATTN: {
+        // weight = relative_position_bias_table ((2w - 1)^2, heads) -> head-major; bias = qkv.bias (3C): the q, k, v of a padded token
+        if (!widx_ok(d.weight) || !widx_ok(d.bias)) return fail("weight index out of range", i);
+        const int heads = d.cin1, rel = (2 * d.ksize - 1) * (2 * d.ksize - 1);
+        if (d.ksize < 2 || d.ksize > 8) return fail("window attention needs 2 <= window_size <= 8", i);
+        if (heads < 1 || d.cout != heads * 32 || d.cin0 != 3 * d.cout) return fail("window attention needs head dimension 32 and a (3C) qkv source", i);
+        if (d.cmid < 0 || d.cmid >= d.ksize) return fail("window attention shift must be smaller than the window", i);
+        if (weight_numel[d.weight] != (int64_t)rel * heads || weight_numel[d.bias] != d.cin0) return fail("weight size mismatch", i);
+        auto pack_tbl = [&](const auto* w, auto& out) {
+          out.assign((size_t)rel * heads, 0);
+          for (int r = 0; r < rel; ++r)
+            for (int a = 0; a < heads; ++a) out[(size_t)a * rel + r] = w[(size_t)r * heads + a];
+        };
+        ok = pack_upload(m, pack_tbl, weights[d.weight], index_array(d.weight), &op.w_dev) == PH_OK &&
+             pack_upload(m, pad_vec(d.cin0, d.cin0), weights[d.bias], index_array(d.bias), &op.b_dev) == PH_OK;
+        break;
+      }
       case PH_OP_LINEAR:
       case PH_OP_PATCH_CONV: {
-        if (!widx_ok(d.weight) || !widx_ok(d.bias)) return fail("weight index out of range", i);
+        const bool no_bias = d.kind == PH_OP_LINEAR && d.bias == -1;  // Linear(bias=False): Swin's patch-merging reduction
+        if (!widx_ok(d.weight) || !(widx_ok(d.bias) || no_bias)) return fail("weight index out of range", i);
         const int segs = d.kind == PH_OP_PATCH_CONV ? 4 : 1;
         if (d.kind == PH_OP_PATCH_CONV && d.ksize != 2) return fail("patch conv must be 2x2 stride 2", i);
-        if (weight_numel[d.weight] != (int64_t)d.cin0 * d.cout * segs || weight_numel[d.bias] != d.cout) return fail("weight size mismatch", i);
+        if (weight_numel[d.weight] != (int64_t)d.cin0 * d.cout * segs || (!no_bias && weight_numel[d.bias] != d.cout)) return fail("weight size mismatch", i);
+        if ((d.flags & PH_FLAG_RESIDUAL) && ((d.flags & PH_FLAG_SCALE_RESIDUAL) || d.src1 < 0)) return fail("residual epilogue needs a residual source and no layer scale", i);
         const int coutp = pad16(d.cout);
         op.bn = gemm_choose_bn(coutp);
         const size_t npad = (size_t)((coutp + op.bn - 1) / op.bn) * op.bn;
         auto pack_g = [&](const auto* w, auto& out) { pack_gemm(w, d.cout, d.cin0, 0, segs, op.bn, out); };
-        ok = pack_upload(m, pack_g, weights[d.weight], index_array(d.weight), &op.w_dma_dev) == PH_OK &&
-             pack_upload(m, pad_vec(npad, d.cout), weights[d.bias], index_array(d.bias), &op.b_dev) == PH_OK;
+        ok = pack_upload(m, pack_g, weights[d.weight], index_array(d.weight), &op.w_dma_dev) == PH_OK;
+        if (ok && no_bias) {
+          std::vector<float> zb(npad, 0.f);  // (not a parameter: nothing in the arena maps onto it)
+          ok = upload(m, zb, &op.b_dev) == PH_OK;
+        } else if (ok) {
+          ok = pack_upload(m, pad_vec(npad, d.cout), weights[d.bias], index_array(d.bias), &op.b_dev) == PH_OK;
+        }
         if (ok && d.kind == PH_OP_LINEAR && (d.flags & PH_FLAG_GELU) && cnblock_mlp_fits(d.cin0, pad16(d.cin0), d.cout)) {  // inference programs: the first Linear of a CNBlock MLP ...
           auto pack_1 = [&](const auto* w, auto& out) { pack_mlp_w1(w, d.cin0, out); };
           ok = pack_upload(m, pack_1, weights[d.weight], index_array(d.weight), &op.w_mlp_dev) == PH_OK;
@@ -1714,7 +1752,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         if (m->dw_ln_fuse && plan.reuse && fmt == FMT_F32 && op_index < m->ops.size() && a.cin == 1 && a.coutp <= 128 && a.k >= 2 && a.k <= 4 && a.stride >= 1 && a.stride <= 4) {
           // the stem's LayerNorm2d rides in the patch kernel (inference plans: nothing else reads the un-normalised tensor)
           const ph_op_desc& nx = m->ops[op_index].d;
-          if (nx.kind == PH_OP_LAYERNORM && nx.src0 == d.dst && nx.cin0 == d.cout) {
+          if (nx.kind == PH_OP_LAYERNORM && !(nx.flags & PH_FLAG_LN_EPS_1EM5) && nx.src0 == d.dst && nx.cin0 == d.cout) {  // (the fused form has eps 1e-6 built in)
             bool other = false;
             for (size_t k = 0; k < m->ops.size(); ++k)
               if (k != op_index && (m->ops[k].d.src0 == d.dst || m->ops[k].d.src1 == d.dst)) other = true;
@@ -1807,7 +1845,36 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           rc = launch_layernorm_f16(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), s0.c, pad16(s0.c), s0.cp, (size_t)batch * s0.h * s0.w, s);
           break;
         }
-        rc = launch_layernorm(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), s0.c, s0.cp, (size_t)batch * s0.h * s0.w, s);
+        rc = launch_layernorm(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), s0.c, s0.cp, (size_t)batch * s0.h * s0.w, s, (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f);
+        break;
+      }
+      case PH_OP_PATCH_MERGE: {
+        const SlotShape& s0 = plan.slots[d.src0];
+        const SlotShape& so = plan.slots[d.dst];
+        PH_REQUIRE(fmt == FMT_F32 && s0.c == d.cin0 && s0.cp == d.cin0 && so.cp == d.cout, "patch merge channel mismatch");
+        rc = launch_patch_merge_ln(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), batch, s0.h, s0.w, d.cin0, (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f, s);
+        break;
+      }
+      case PH_OP_WINDOW_ATTN: {
+        const SlotShape& s0 = plan.slots[d.src0];
+        const SlotShape& so = plan.slots[d.dst];
+        PH_REQUIRE(fmt == FMT_F32 && s0.c == d.cin0 && s0.cp == d.cin0 && so.cp == d.cout, "window attention channel mismatch");
+        WindowAttnArgs a{};
+        a.qkv = rd(d.src0);
+        a.table = op.w_dev;
+        a.qkv_bias = op.b_dev;
+        a.dst = wr(d.dst);
+        a.B = batch;
+        a.H = s0.h;
+        a.W = s0.w;
+        a.C = d.cout;
+        a.heads = d.cin1;
+        a.w = d.ksize;
+        // an axis the window covers whole (window >= padded size) is not shifted: decided per axis, from this launch's map
+        a.sh = d.ksize >= (s0.h + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;
+        a.sw = d.ksize >= (s0.w + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;
+        kv[op_index - 1] = PH_KV_WINDOW_ATTN;
+        rc = launch_window_attn(a, s);
         break;
       }
       case PH_OP_LINEAR:
@@ -1887,6 +1954,8 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         a.act = (d.flags & PH_FLAG_GELU) ? 2 : ((d.flags & PH_FLAG_RELU) ? 1 : 0);
         if (d.flags & PH_FLAG_SCALE_RESIDUAL) {
           a.scale = op.w2_dev;
+          a.residual = rd(d.src1);
+        } else if (d.flags & PH_FLAG_RESIDUAL) {  // dst = acc + bias + src1
           a.residual = rd(d.src1);
         }
         a.late_split = m->gemm_late_split;

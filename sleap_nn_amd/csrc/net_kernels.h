@@ -148,7 +148,20 @@ struct GemmArgs {
 
 int launch_patch_stem(const PatchStemArgs& a, hipStream_t s);
 int launch_dwconv7(const DwConvArgs& a, hipStream_t s);
-int launch_layernorm(const float* src, const float* gamma, const float* beta, float* dst, int c, int cp, size_t npix, hipStream_t s);
+int launch_layernorm(const float* src, const float* gamma, const float* beta, float* dst, int c, int cp, size_t npix, hipStream_t s, float eps = 1e-6f);
+// Swin Transformer encoder (swin_kernels.hip)
+struct WindowAttnArgs {
+  const float* qkv = nullptr;       // (B, H, W, 3C): q | k | v of the un-padded, un-rolled map; head a owns channels 32 a .. 32 a + 31 of each
+  const float* table = nullptr;     // relative-position bias table, head-major: [heads][(2w - 1)^2]
+  const float* qkv_bias = nullptr;  // (3C): what a padded token's q, k, v are
+  float* dst = nullptr;             // (B, H, W, C)
+  int B = 0, H = 0, W = 0, C = 0, heads = 0;
+  int w = 0;                        // window side, 2..8
+  int sh = 0, sw = 0;               // per-axis shift (0 where the window covers the padded axis)
+};
+int launch_window_attn(const WindowAttnArgs& a, hipStream_t s);
+// 2x2 phase gather (zero fill past an odd edge) + LayerNorm over the 4C gathered channels: (B, H, W, C) -> (B, ceil(H/2), ceil(W/2), 4C)
+int launch_patch_merge_ln(const float* src, const float* gamma, const float* beta, float* dst, int B, int H, int W, int c, float eps, hipStream_t s);
 int launch_gemm(const GemmArgs& a, hipStream_t s);
 // CNBlock's MLP in one launch (cnblock_mlp_kernels.hip): dst = residual + scale * (W2 gelu(W1 x + b1) + b2) over (M, C) rows
 struct MlpArgs {

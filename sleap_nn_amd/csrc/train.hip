@@ -270,6 +270,9 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
              "ph_model_backward: null argument");
   PH_REQUIRE(((uintptr_t)grad_workspace_dev & 255) == 0, "gradient workspace must be 256-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
+  for (const auto& op : m->ops)  // refused before any launch: the sweep would otherwise run the decoder's gradients first
+    PH_REQUIRE(op.d.kind != PH_OP_WINDOW_ATTN && op.d.kind != PH_OP_PATCH_MERGE && !(op.d.kind == PH_OP_LINEAR && (op.d.flags & PH_FLAG_RESIDUAL)),
+               "ph_model_backward: the Swin Transformer encoder ops have no backward pass: inference only");
   for (const auto& op : m->ops) {  // the MSE / cross-entropy gradients below are not these heads' losses: they train only with a loss chosen by ph_model_set_head_loss
     if (op.d.kind != PH_OP_HEAD) continue;
     PH_REQUIRE(op.d.out_index >= 0 && op.d.out_index < PH_MAX_OUTPUTS, "ph_model_backward: head output index %d out of range", op.d.out_index);
