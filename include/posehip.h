@@ -329,6 +329,9 @@ int ph_debug_row_wgrad_bench(int32_t M, int32_t n, int32_t k, int32_t iters, flo
  * "conv_precision" (0 exact fp32 MFMA | 1 split-fp16 MFMA, 22-bit products | 2 plain fp16, the reference's autocast mode),
  * "convnext_f16" (1: under "conv_precision" 2 a program with ConvNeXt encoder ops runs whole on fp16 activations -- patch stem, depthwise 7x7 + LayerNorm,
  * Linear / 2x2-stride-2 convs as fp16 MFMA row GEMMs, then the fp16 decoder; 0, the default: such a program runs exact fp32 under every precision),
+ * "swint_f16" (1: under "conv_precision" 2 a program with the Swin ops runs whole on fp16 activations -- patch stem, LayerNorms, qkv / proj / MLP / reduction Linears as
+ * fp16 MFMA row GEMMs, window attention on the fp16 matrix pipe with fp32 logits, patch-merge norm, then the fp16 decoder; 0, the default: exact fp32 under every precision;
+ * independent of "convnext_f16"),
  * "gemm_late_split", "gemm_persist2", "conv_gemm_fill", "conv_gemm_fill_wino", "conv_gemm_fill_wino2d",
  * "conv_wino2d" / "conv_w16" (the Winograd F(2x2,3x3) kernels), "conv_wino4" (K-heavy 3x3 convs on the Winograd F(4x4,3x3) kernel: 1 inference
  * plans | 2 every plan | 0 never), "conv_wino4_min_cin", "upsample_fold" (a bilinear x2 read only by the next conv's second source rides in that kernel's input transform), "head_fuse" (a 1x1 head computed in its producer conv's epilogue),
@@ -378,7 +381,9 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_CNX_F16_GEMM 19 /* gemm_f16_kernel: Linear / 2x2-stride-2 conv as a row GEMM on v_mfma_f32_32x32x16_f16 (bias, GELU, layer scale + residual epilogues) */
 #define PH_KV_CNX_F16_ELTWISE 20 /* gelu_fmt_kernel / scale_add_fmt_kernel on fp16 activations (unfused programs)                                    */
 #define PH_KV_WINDOW_ATTN 21 /* window_attn_kernel: one wave per (window, head), q k^T and p v on v_mfma_f32_32x32x2_f32, softmax in registers */
-#define PH_KV_FUSED 11    /* no launch of its own: a 1x1 head computed in the epilogue of the conv that produces its input */
+#define PH_KV_WINDOW_ATTN_F16 22 /* window_attn_f16_kernel: the same plan on v_mfma_f32_32x32x16_f16, fp16 q / k / v / p, fp32 logits and softmax statistics ("swint_f16") */
+#define PH_KV_SWIN_F16_MERGE_LN 23 /* patch_merge_ln_f16_kernel: four-phase gather + LayerNorm(4C) on fp16 activations, fp32 moments ("swint_f16") */
+#define PH_KV_FUSED 11   /* no launch of its own: a 1x1 head computed in the epilogue of the conv that produces its input */
 int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
 
 /* Which workspace byte ranges every launch of the LAST ph_model_forward was handed, as the run-time routing decided them (tests of the

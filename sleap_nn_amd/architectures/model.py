@@ -292,7 +292,7 @@ class Model:
             self.set_option("workspace_reuse", 0 if self.keep_activations else 1)
         return self
 
-    def set_precision(self, precision: str, convnext_f16: Optional[bool] = None) -> "Model":
+    def set_precision(self, precision: str, convnext_f16: Optional[bool] = None, swint_f16: Optional[bool] = None) -> "Model":
         """Arithmetic of the inference forward:
         ``"exact"``: fp32 products on the fp32 matrix pipe (bit-for-bit a k-ordered fmaf chain);
         ``"split"``: every operand as a (hi, lo) pair of fp16 numbers, three fp16 MFMAs per product with fp32 accumulation --
@@ -307,12 +307,21 @@ class Model:
         ``set_option("convnext_f16", 1)`` before a ``HipBackend(model, use_fp16=True)`` does the same).  It is 0 by default,
         and a ConvNeXt program then runs exact under every precision, as it always did: tests/test_gpu_plan_hazards.py pins the
         fp32 plan of ConvNeXt programs (its one-launch CNBlock MLP included) under ``"split"`` and ``"fp16"``.
+        Swin programs have a switch of their own, the handle option ``swint_f16`` (``swint_f16=True`` / ``False`` here, or
+        ``set_option("swint_f16", 1)`` before a ``HipBackend(model, use_fp16=True)``; 0 by default, independent of
+        ``convnext_f16``): with it ``"fp16"`` runs the whole program in fp16 storage -- patch stem, LayerNorms (fp32 moments),
+        the qkv / proj / MLP / reduction Linears as fp16 MFMA row GEMMs with fp32 accumulators and epilogues, window attention
+        on the fp16 matrix pipe with fp32 logits and softmax statistics, the patch-merge norm, the residual stream stored in
+        fp16, then the fp16 decoder.  Without it a Swin program runs exact under every precision
+        (tests/test_gpu_swint.py pins that); ``"split"`` is exact for it either way.
         Programs with a class-vector head (global max pool, softmax) and every training program run exact whatever is set."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
         self.precision = precision
         if convnext_f16 is not None:
             self.set_option("convnext_f16", 1 if convnext_f16 else 0)
+        if swint_f16 is not None:
+            self.set_option("swint_f16", 1 if swint_f16 else 0)
         if self.ops is self.fused_ops:
             self.set_option("conv_precision", PRECISIONS[precision])
         return self

@@ -12,7 +12,8 @@ un-rolled map) -> window attention (pad, roll, partition, bias, band mask, softm
 kernel) -> row GEMM C->C whose epilogue adds the block input -> LayerNorm -> row GEMM C->4C with the erf-GELU in
 its epilogue -> row GEMM 4C->C whose epilogue adds the residual.  Patch merging is the four-phase gather with its
 LayerNorm in one launch, then a bias-less row GEMM.  All norms have eps 1e-5.  Stochastic depth and dropout are
-the identity at inference; training a Swin program is not implemented.
+the identity at inference; training a Swin program is not implemented.  The same program runs in exact fp32 (the default) or,
+with ``Model.set_precision("fp16", swint_f16=True)``, whole on fp16 activations (``csrc/swin_f16_kernels.hip``).
 
 The pool / middle / decoder half is the ConvNeXt wrapper's, as in the reference (swint.py:266-339).
 """

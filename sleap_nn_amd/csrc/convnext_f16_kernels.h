@@ -32,15 +32,16 @@ struct DwConvF16Args {
 };
 int launch_dwconv7_f16(const DwConvF16Args& a, hipStream_t s);
 
-int launch_layernorm_f16(const void* src, const float* gamma, const float* beta, void* dst, int c, int wcp, int cp, size_t npix, hipStream_t s);
+// eps: 1e-6 for LayerNorm2d / CNBlock's norm (convnext.py:67), 1e-5 for the Swin norms (PH_FLAG_LN_EPS_1EM5)
+int launch_layernorm_f16(const void* src, const float* gamma, const float* beta, void* dst, int c, int wcp, int cp, size_t npix, hipStream_t s, float eps = 1e-6f);
 
 // Row GEMM on v_mfma_f32_32x32x16_f16: dst[m][n] = epilogue(sum_k A[m][k] W[n][k] + bias[n]), fp32 accumulators.
 struct GemmF16Args {
   const void* src = nullptr;        // FMT_F16 activations, cinp channels per pixel
   const void* wimg = nullptr;       // launch_gemm_f16_weight_image output
-  const float* bias = nullptr;      // fp32, >= coutp entries, zero-padded
-  const float* scale = nullptr;     // layer scale (fp32, >= coutp, zero-padded) or nullptr
-  const void* residual = nullptr;   // FMT_F16 (M, coutp) or nullptr: dst = scale * (acc + bias) + residual
+  const float* bias = nullptr;      // fp32, >= coutp entries, zero-padded; nullptr: no bias
+  const float* scale = nullptr;     // layer scale (fp32, >= coutp, zero-padded) or nullptr; needs a residual
+  const void* residual = nullptr;   // FMT_F16 (M, coutp) or nullptr: dst = scale * (acc + bias) + residual, without a scale dst = acc + bias + residual
   void* dst = nullptr;              // FMT_F16 (M, coutp)
   int cinp = 0, coutp = 0;          // padded channels (multiples of 32)
   int M = 0;                        // output rows (pixels)

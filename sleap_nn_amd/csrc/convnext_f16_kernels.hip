@@ -277,7 +277,7 @@ int launch_dwconv7_f16(const DwConvF16Args& a, hipStream_t s) {
 // storage.  16 lanes per pixel, 8 channels per load; mean and biased variance in fp32 over the TRUE channel count.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void layernorm_f16_kernel(const void* __restrict__ src, const float* __restrict__ gamma, const float* __restrict__ beta, void* __restrict__ dst,
-                                                            int c, int wcp, int cp, size_t npix) {
+                                                            int c, int wcp, int cp, size_t npix, float eps) {
   const int sub = threadIdx.x & 15;
   const int groups = cp >> 3;
   const float inv_c = 1.0f / (float)c;
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(256) void layernorm_f16_kernel(const void* __restri
     ss += __shfl_xor(ss, 4, 16);
     ss += __shfl_xor(ss, 2, 16);
     ss += __shfl_xor(ss, 1, 16);
-    const float rstd = 1.0f / sqrtf(ss * inv_c + LN_EPS_F16);
+    const float rstd = 1.0f / sqrtf(ss * inv_c + eps);
     if (live) {
       for (int g = sub; g < groups; g += 16) {
         load8<FMT_F16>(src, p, cp, g, v);
@@ -334,10 +334,10 @@ __global__ __launch_bounds__(256) void layernorm_f16_kernel(const void* __restri
   }
 }
 
-int launch_layernorm_f16(const void* src, const float* gamma, const float* beta, void* dst, int c, int wcp, int cp, size_t npix, hipStream_t s) {
+int launch_layernorm_f16(const void* src, const float* gamma, const float* beta, void* dst, int c, int wcp, int cp, size_t npix, hipStream_t s, float eps) {
   PH_REQUIRE(src && gamma && beta && dst && c > 0 && c <= wcp && wcp % 16 == 0 && wcp <= cp && cp % 32 == 0 && npix > 0, "layernorm_f16: bad arguments");
   const int blocks = (int)std::min<size_t>((npix + 15) / 16, 256 * 32);
-  hipLaunchKernelGGL(layernorm_f16_kernel, dim3(blocks), dim3(256), 0, s, src, gamma, beta, dst, c, wcp, cp, npix);
+  hipLaunchKernelGGL(layernorm_f16_kernel, dim3(blocks), dim3(256), 0, s, src, gamma, beta, dst, c, wcp, cp, npix, eps);
   PH_HIP_CHECK(hipGetLastError());
   return PH_OK;
 }
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(GemmF16Args a) {
     multiply(f1);
     load(f1, ks + 3);
   }
-  // epilogue on the fp32 accumulators: + bias, erf-GELU, layer scale + residual; four consecutive channels per 8-byte store
+  // epilogue on the fp32 accumulators: + bias (if any), erf-GELU, (layer scale +) residual; four consecutive channels per 8-byte store
   const _Float16* res = reinterpret_cast<const _Float16*>(a.residual);
 #pragma unroll
   for (int n = 0; n < NB; ++n) {
@@ -440,8 +440,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(GemmF16Args a) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int c0 = (nb0 + n) * 32 + 8 * q + 4 * lh;
-      const f32x4 bias = *reinterpret_cast<const f32x4*>(a.bias + c0);
-      f32x4 sc = {1.f, 1.f, 1.f, 1.f};
+      f32x4 bias = {0.f, 0.f, 0.f, 0.f};  // (no bias: Swin's patch-merging reduction)
+      if (a.bias) bias = *reinterpret_cast<const f32x4*>(a.bias + c0);
+      f32x4 sc = {1.f, 1.f, 1.f, 1.f};  // (a residual without a layer scale: Swin's attn.proj and mlp.3 -- 1 * v + r is v + r exactly)
       if (a.scale) sc = *reinterpret_cast<const f32x4*>(a.scale + c0);
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
@@ -464,9 +465,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(GemmF16Args a) {
 }
 
 int launch_gemm_f16(const GemmF16Args& a, hipStream_t s) {
-  PH_REQUIRE(a.src && a.wimg && a.bias && a.dst && a.M > 0 && a.cinp > 0 && a.cinp % 32 == 0 && a.coutp > 0 && a.coutp % 32 == 0, "gemm_f16: bad arguments");
+  PH_REQUIRE(a.src && a.wimg && a.dst && a.M > 0 && a.cinp > 0 && a.cinp % 32 == 0 && a.coutp > 0 && a.coutp % 32 == 0, "gemm_f16: bad arguments");
   PH_REQUIRE(a.taps == 1 || (a.taps == 4 && a.H >= 2 && a.W >= 2 && a.M % ((a.H / 2) * (a.W / 2)) == 0), "gemm_f16: 1 tap (Linear) or 4 taps (2x2/stride-2 conv over an H x W input)");
-  PH_REQUIRE(!a.residual == !a.scale, "gemm_f16: layer scale and residual come together");
+  PH_REQUIRE(!a.scale || a.residual, "gemm_f16: a layer scale needs a residual");
   const int nblks = a.coutp / 32, nb = nblks % 3 == 0 ? 3 : 2;
   const size_t blocks = (size_t)((a.M + 255) / 256) * ((nblks + nb - 1) / nb);
   PH_REQUIRE(blocks < ((size_t)1 << 31), "gemm_f16: too many workgroups");

@@ -240,9 +240,13 @@ void apply_conv_options(const ph_model* m, ConvArgs& a) {
 // Programs made only of the UNet-style ops can run on the fp16 matrix pipe (handle option "conv_precision"); so can, in the
 // plain fp16 precision and with the handle option "convnext_f16" set, programs with the ConvNeXt encoder ops (convnext_f16_kernels.hip).  Anything else (class-vector heads
 // and the global max pool in front of them, non-3x3 kernels, ConvNeXt programs in the split precision) and every training program
-// (conv_precision 0) stays in exact fp32.
+// (conv_precision 0) stays in exact fp32.  A program with the Swin ops (window attention, patch merging) answers to the handle option
+// "swint_f16" instead of "convnext_f16" (swin_f16_kernels.hip): the two options are independent, neither changes the other's programs.
 int forward_format(const ph_model* m) {
   if (m->conv_precision != 1 && m->conv_precision != 2) return FMT_F32;
+  bool swin = false;
+  for (const PackedOp& op : m->ops) swin = swin || op.d.kind == PH_OP_WINDOW_ATTN || op.d.kind == PH_OP_PATCH_MERGE;
+  const bool enc_f16 = m->conv_precision == 2 && (swin ? m->swint_f16 : m->convnext_f16) != 0;  // the encoder ops have an fp16 form and may use it
   for (const PackedOp& op : m->ops) {
     const ph_op_desc& d = op.d;
     switch (d.kind) {
@@ -257,10 +261,14 @@ int forward_format(const ph_model* m) {
       case PH_OP_PATCH_CONV:
       case PH_OP_GELU:
       case PH_OP_SCALE_ADD:
-        if (m->conv_precision != 2 || !m->convnext_f16) return FMT_F32;
+        if (!enc_f16) return FMT_F32;
         break;
-      case PH_OP_LINEAR:  // (a Linear with a ReLU is a class-vector head's: exact)
-        if (m->conv_precision != 2 || !m->convnext_f16 || (d.flags & ~(PH_FLAG_GELU | PH_FLAG_SCALE_RESIDUAL)) || !op.w_cnx_f16_dev) return FMT_F32;
+      case PH_OP_WINDOW_ATTN:
+      case PH_OP_PATCH_MERGE:
+        if (!enc_f16) return FMT_F32;
+        break;
+      case PH_OP_LINEAR:  // (a Linear with a ReLU is a class-vector head's: exact; PH_FLAG_RESIDUAL is a Swin block's, with or without a bias)
+        if (!enc_f16 || (d.flags & ~(PH_FLAG_GELU | PH_FLAG_SCALE_RESIDUAL | (swin ? PH_FLAG_RESIDUAL : 0))) || !op.w_cnx_f16_dev) return FMT_F32;
         break;
       case PH_OP_CONV:
       case PH_OP_CONVT:
@@ -1842,7 +1850,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         PH_REQUIRE(s0.c == d.cin0, "LayerNorm channel mismatch");
         if (fmt == FMT_F16) {
           kv[op_index - 1] = PH_KV_CNX_F16_LN;
-          rc = launch_layernorm_f16(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), s0.c, pad16(s0.c), s0.cp, (size_t)batch * s0.h * s0.w, s);
+          rc = launch_layernorm_f16(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), s0.c, pad16(s0.c), s0.cp, (size_t)batch * s0.h * s0.w, s, (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f);
           break;
         }
         rc = launch_layernorm(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), s0.c, s0.cp, (size_t)batch * s0.h * s0.w, s, (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f);
@@ -1851,14 +1859,37 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
       case PH_OP_PATCH_MERGE: {
         const SlotShape& s0 = plan.slots[d.src0];
         const SlotShape& so = plan.slots[d.dst];
-        PH_REQUIRE(fmt == FMT_F32 && s0.c == d.cin0 && s0.cp == d.cin0 && so.cp == d.cout, "patch merge channel mismatch");
+        PH_REQUIRE((fmt == FMT_F32 || fmt == FMT_F16) && s0.c == d.cin0 && s0.cp == d.cin0 && so.cp == d.cout, "patch merge channel mismatch");
+        if (fmt == FMT_F16) {
+          kv[op_index - 1] = PH_KV_SWIN_F16_MERGE_LN;
+          rc = launch_patch_merge_ln_f16(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), batch, s0.h, s0.w, d.cin0, (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f, s);
+          break;
+        }
         rc = launch_patch_merge_ln(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), batch, s0.h, s0.w, d.cin0, (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f, s);
         break;
       }
       case PH_OP_WINDOW_ATTN: {
         const SlotShape& s0 = plan.slots[d.src0];
         const SlotShape& so = plan.slots[d.dst];
-        PH_REQUIRE(fmt == FMT_F32 && s0.c == d.cin0 && s0.cp == d.cin0 && so.cp == d.cout, "window attention channel mismatch");
+        PH_REQUIRE((fmt == FMT_F32 || fmt == FMT_F16) && s0.c == d.cin0 && s0.cp == d.cin0 && so.cp == d.cout, "window attention channel mismatch");
+        if (fmt == FMT_F16) {
+          WindowAttnF16Args f{};
+          f.qkv = rd(d.src0);
+          f.table = op.w_dev;
+          f.qkv_bias = op.b_dev;
+          f.dst = wr(d.dst);
+          f.B = batch;
+          f.H = s0.h;
+          f.W = s0.w;
+          f.C = d.cout;
+          f.heads = d.cin1;
+          f.w = d.ksize;
+          f.sh = d.ksize >= (s0.h + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;  // (per axis, as below)
+          f.sw = d.ksize >= (s0.w + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;
+          kv[op_index - 1] = PH_KV_WINDOW_ATTN_F16;
+          rc = launch_window_attn_f16(f, s);
+          break;
+        }
         WindowAttnArgs a{};
         a.qkv = rd(d.src0);
         a.table = op.w_dev;
@@ -1888,11 +1919,11 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         const SlotShape& so = plan.slots[d.dst];
         PH_REQUIRE(s0.c == d.cin0, "GEMM channel mismatch");
         if (fmt == FMT_F16) {
-          PH_REQUIRE(op.w_cnx_f16_dev && !(d.flags & ~(PH_FLAG_GELU | PH_FLAG_SCALE_RESIDUAL)), "op has no fp16 row-GEMM form");
+          PH_REQUIRE(op.w_cnx_f16_dev && !(d.flags & ~(PH_FLAG_GELU | PH_FLAG_SCALE_RESIDUAL | PH_FLAG_RESIDUAL)), "op has no fp16 row-GEMM form");
           GemmF16Args f{};
           f.src = rd(d.src0);
           f.wimg = op.w_cnx_f16_dev;
-          f.bias = op.b_dev;
+          f.bias = (d.kind == PH_OP_LINEAR && d.bias == -1) ? nullptr : op.b_dev;  // Linear(bias=False): the patch-merging reduction
           f.dst = wr(d.dst);
           f.cinp = s0.cp;
           f.coutp = so.cp;
@@ -1903,6 +1934,8 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           f.gelu = (d.flags & PH_FLAG_GELU) ? 1 : 0;
           if (d.flags & PH_FLAG_SCALE_RESIDUAL) {
             f.scale = op.w2_dev;
+            f.residual = rd(d.src1);
+          } else if (d.flags & PH_FLAG_RESIDUAL) {  // dst = acc + bias + src1
             f.residual = rd(d.src1);
           }
           kv[op_index - 1] = PH_KV_CNX_F16_GEMM;
@@ -2107,6 +2140,7 @@ std::vector<OptionRef> option_table(ph_model* m) {
       {"convt_one_launch", &m->convt_one_launch, nullptr},  // 1: the four output-phase GEMMs of a transposed conv in one launch (grid.y = phase); 0: four launches
       {"convt_phase", &m->convt_phase, nullptr},        // 0: transposed convs by zero-stuffing + 3x3 conv (4x the FLOPs; A/B reference)
       {"convnext_f16", &m->convnext_f16, nullptr},      // 1: under conv_precision 2 a ConvNeXt program runs whole in plain fp16 (0: exact fp32 whatever the precision)
+      {"swint_f16", &m->swint_f16, nullptr},            // 1: under conv_precision 2 a Swin program runs whole in plain fp16 (0: exact fp32 whatever the precision); independent of convnext_f16
       {"conv_precision", &m->conv_precision, nullptr},  // 0 exact fp32 MFMA, 1 split-fp16 MFMA (22-bit products), 2 plain fp16 (autocast-equivalent)
       {"gemm_late_split", &m->gemm_late_split, nullptr},
       {"gemm_persist2", &m->gemm_persist2, nullptr},

@@ -176,6 +176,7 @@ struct ph_model {
   int workspace_reuse = 0;                    // "workspace_reuse": 1 = slots of an inference program share memory by lifetime (no read-back, no backward)
   int convt_one_launch = 1;                   // "convt_one_launch": the four output-phase GEMMs of a transposed conv as ONE launch (grid.y = phase) instead of four (four launch floors at small batches)
   int convt_phase = 1;                        // "convt_phase": transposed convs as four phase GEMMs (0: zero-stuffing + 3x3 conv, 4x the FLOPs; A/B)
+  int swint_f16 = 0;                          // "swint_f16": 1 = a Swin program under conv_precision 2 runs whole on fp16 activations (swin_f16_kernels.hip + the fp16 row GEMM / LayerNorm); 0 (default) = exact fp32
   int convnext_f16 = 0;                       // "convnext_f16": 1 = a ConvNeXt program under conv_precision 2 runs whole on fp16 activations (convnext_f16_kernels.hip); 0 (default) = it runs exact fp32, as before the fp16 ConvNeXt kernels existed
   int conv_precision = 0;                     // "conv_precision": 0 exact fp32 MFMA; 1 split-fp16 MFMA (22-bit products, fp32 accumulate); 2 plain fp16 (autocast-equivalent)
   // ph_model_set_head_loss: loss of output i in ph_model_backward (0 = never set: MSE / cross entropy as the flags say, PH_FLAG_NO_TRAIN heads refused)

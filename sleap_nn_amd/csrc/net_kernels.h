@@ -162,6 +162,18 @@ struct WindowAttnArgs {
 int launch_window_attn(const WindowAttnArgs& a, hipStream_t s);
 // 2x2 phase gather (zero fill past an odd edge) + LayerNorm over the 4C gathered channels: (B, H, W, C) -> (B, ceil(H/2), ceil(W/2), 4C)
 int launch_patch_merge_ln(const float* src, const float* gamma, const float* beta, float* dst, int B, int H, int W, int c, float eps, hipStream_t s);
+// ... on plain-fp16 activations (swin_f16_kernels.hip; FMT_F16, C a multiple of 32: no pad channels)
+struct WindowAttnF16Args {
+  const void* qkv = nullptr;        // FMT_F16 (B, H, W, 3C)
+  const float* table = nullptr;     // as WindowAttnArgs: fp32
+  const float* qkv_bias = nullptr;  // (3C) fp32: converted where a padded token reads it
+  void* dst = nullptr;              // FMT_F16 (B, H, W, C)
+  int B = 0, H = 0, W = 0, C = 0, heads = 0;
+  int w = 0;
+  int sh = 0, sw = 0;
+};
+int launch_window_attn_f16(const WindowAttnF16Args& a, hipStream_t s);
+int launch_patch_merge_ln_f16(const void* src, const float* gamma, const float* beta, void* dst, int B, int H, int W, int c, float eps, hipStream_t s);
 int launch_gemm(const GemmArgs& a, hipStream_t s);
 // CNBlock's MLP in one launch (cnblock_mlp_kernels.hip): dst = residual + scale * (W2 gelu(W1 x + b1) + b2) over (M, C) rows
 struct MlpArgs {

@@ -168,7 +168,7 @@ int ph_model_set_params(ph_model* m, const float* params_flat_dev, void* stream)
       continue;
     }
     if (db.kind == 7) {  // fp16 row-GEMM images: only a plain-fp16 forward reads them -- a training step does not pay for them, the next such forward refreshes them (ph_model_forward)
-      if (m->conv_precision != 2 || !m->convnext_f16) {
+      if (m->conv_precision != 2 || !(m->convnext_f16 || m->swint_f16)) {
         m->cnx_f16_stale = true;
         continue;
       }
