@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 120
+#define PH_VERSION 121
 
 /* error codes */
 #define PH_OK 0
@@ -104,14 +104,18 @@ enum ph_op_kind {
   PH_OP_GELU = 13,      /* dst = GELU_erf(src0)                                                          */
   PH_OP_SCALE_ADD = 14, /* dst = weight[c] * src0 + src1   (layer_scale * block(x) + x)                  */
   PH_OP_GLOBAL_MAXPOOL = 15, /* dst (1x1) = max over H x W of src0 (nn.AdaptiveMaxPool2d(1), heads.py:519-520) */
-  /* Swin Transformer encoder (architectures/swint.py; the blocks are torchvision's SwinTransformerBlock / PatchMerging).  Exact fp32, inference only. */
+  /* Swin Transformer encoder (architectures/swint.py; the blocks are torchvision's SwinTransformerBlock / PatchMerging).  Exact fp32 or, under
+     "swint_f16", fp16 storage at inference; ph_model_backward runs their backward on the exact-fp32 program (swin_train_kernels.hip). */
   PH_OP_PATCH_MERGE = 16, /* (B, H, W, C) -> (B, ceil(H/2), ceil(W/2), 4C): concat of x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2] (zeros past an odd
-                             edge) + LayerNorm over the 4C channels (weight / bias = its affine), one launch; the bias-less PH_OP_LINEAR `reduction` follows */
+                             edge) + LayerNorm over the 4C channels (weight / bias = its affine), one launch; the bias-less PH_OP_LINEAR `reduction` follows.
+                             Backward: the gather is rebuilt in scratch, LayerNorm backward over it, scatter to the four phases (the padding receives nothing) */
   PH_OP_WINDOW_ATTN = 17  /* shifted-window multi-head attention core: src0 = qkv slot (B, H, W, 3C) of the un-padded, un-rolled map (q | k | v, head a owns
                              channels 32 a .. 32 a + 31 of each), weight = relative_position_bias_table ((2 ksize - 1)^2, heads), bias = qkv.bias (3C; the q, k, v
                              of a padded token), ksize = window side (2..8), cin1 = heads (cout = 32 heads), cmid = nominal shift (an axis whose padded size the
                              window covers is not shifted).  dst (B, H, W, C) = softmax(q k^T / sqrt(32) + bias [- 100 across the shift's bands]) v at each
-                             token's own pixel: pad, roll, window partition, reverse and crop are index arithmetic of the one launch */
+                             token's own pixel: pad, roll, window partition, reverse and crop are index arithmetic of the one launch.
+                             Backward (window_attn_bwd_kernel): S and P are recomputed from the qkv slot; gradients of the slot, of the table and -- through the
+                             padded tokens, whose q, k, v are qkv.bias -- of qkv.bias */
 };
 
 #define PH_FLAG_RELU 1
@@ -214,6 +218,18 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
 #define PH_LOSS_BCE_DICE 2
 #define PH_LOSS_MASKED_SMOOTH_L1 3
 int ph_model_set_head_loss(ph_model* m, int32_t out_index, int32_t kind, const float* params, int32_t n_params);
+
+/* Per-sample scales of the residual branches (stochastic depth as torchvision's StochasticDepth(p, "row") applies it in train mode: bernoulli(1 - p) / (1 - p)
+ * per sample).  scales_dev: device float[n_branches][batch], borrowed until the ph_model_backward of the step has been enqueued; NULL clears it.
+ * n_branches must equal the number of PH_OP_LINEAR ops with PH_FLAG_RESIDUAL, which the rows follow in program order.  While set, the i-th such op computes
+ * dst = s[i][b] * (acc + bias) + src1 in ph_model_forward (the row GEMM without its residual, then one element-wise pass), and ph_model_backward feeds
+ * s[i][b] * G(dst) to its weight, bias and data gradients and the plain G(dst) to src1.  A forward or backward whose batch differs from `batch`, or a forward
+ * in a non-fp32 format, is refused while scales are set.  With none set the launch sequence is what it is without this call. */
+int ph_model_set_branch_scales(ph_model* m, const float* scales_dev, int32_t n_branches, int32_t batch);
+/* Byte offset, in the gradient workspace of a (batch, height, width) step, of the (3C) vector that holds the padded tokens' share of a qkv.bias gradient
+ * (sum of dq | dk | dv over the padded tokens of the windows) between the attention op's step and the qkv Linear's; after ph_model_backward it holds that
+ * of the program's FIRST attention op, *n_floats = its 3C.  For tests and tools. */
+int64_t ph_model_backward_pad_vector(const ph_model* m, int32_t batch, int32_t height, int32_t width, int32_t* n_floats);
 
 /* The two losses on their own (deterministic: fixed-order partial sums, no float atomics; three launches on `stream`, no host synchronisation).
  *   ph_loss_bce_dice: logits / target (B, 1, h, w) fp32, target values in {0, 1}.  BCE = binary_cross_entropy_with_logits (mean, optional pos_weight:
@@ -383,8 +399,14 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_WINDOW_ATTN 21 /* window_attn_kernel: one wave per (window, head), q k^T and p v on v_mfma_f32_32x32x2_f32, softmax in registers */
 #define PH_KV_WINDOW_ATTN_F16 22 /* window_attn_f16_kernel: the same plan on v_mfma_f32_32x32x16_f16, fp16 q / k / v / p, fp32 logits and softmax statistics ("swint_f16") */
 #define PH_KV_SWIN_F16_MERGE_LN 23 /* patch_merge_ln_f16_kernel: four-phase gather + LayerNorm(4C) on fp16 activations, fp32 moments ("swint_f16") */
+#define PH_KV_WINDOW_ATTN_BWD 24 /* window_attn_bwd_kernel (ph_model_last_backward_kernels): backward of the attention core, one wave per (window, head), fixed-order slices */
 #define PH_KV_FUSED 11   /* no launch of its own: a 1x1 head computed in the epilogue of the conv that produces its input */
 int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
+/* Per-op times of the LAST ph_model_backward, recorded while profiling is on (ph_model_set_profiling).  op_ms[i]: op i's step of the reverse sweep; op_ms_first[i]: its part up to the
+ * first data-gradient GEMM (Linear / 2x2-stride-2 ops: the scaling pass and the weight-gradient GEMM; 0 elsewhere); *loss_ms: losses and head-output gradients. */
+int ph_model_backward_profile_read(ph_model* m, double* op_ms, double* op_ms_first, int32_t n_ops, double* loss_ms);
+/* ... and of the LAST ph_model_backward: PH_KV_WINDOW_ATTN_BWD for a PH_OP_WINDOW_ATTN step, PH_KV_ROWGEMM for a Linear / 2x2-stride-2 step, 0 elsewhere. */
+int ph_model_last_backward_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
 
 /* Which workspace byte ranges every launch of the LAST ph_model_forward was handed, as the run-time routing decided them (tests of the
  * planner / router agreement: no launch may write a range it, or a later launch, still reads).  One row of six int64 per range:

@@ -24,6 +24,7 @@ LOSS_MSE, LOSS_BCE_DICE, LOSS_MASKED_SMOOTH_L1 = 1, 2, 3  # PH_LOSS_*: ph_model_
 # FLOPs that family puts through the matrix cores
 KV_NONE, KV_DIRECT, KV_WINO1D, KV_WINO2D, KV_W16, KV_C16, KV_ROWGEMM, KV_WINO4, KV_F16, KV_STEM, KV_WINO2D_KS, KV_FUSED, KV_SMALLMAP, KV_F16_ROWS, KV_F16_BLOCK, KV_MLP = range(16)
 SWIN_KV_WINDOW_ATTN = 21  # PH_KV_WINDOW_ATTN (swin_kernels.hip); not named KV_* either, for the reason below
+SWIN_KV_WINDOW_ATTN_BWD = 24  # PH_KV_WINDOW_ATTN_BWD (swin_train_kernels.hip): reported by ph_model_last_backward_kernels
 SWIN_KV_WINDOW_ATTN_F16, SWIN_KV_F16_MERGE_LN = 22, 23  # PH_KV_WINDOW_ATTN_F16 / PH_KV_SWIN_F16_MERGE_LN: the Swin ops on fp16 activations (swin_f16_kernels.hip, handle option swint_f16)
 CNX_KV_F16_STEM, CNX_KV_F16_DW, CNX_KV_F16_LN, CNX_KV_F16_GEMM, CNX_KV_F16_ELTWISE = 16, 17, 18, 19, 20  # PH_KV_CNX_F16_*: the ConvNeXt encoder ops on fp16 activations (convnext_f16_kernels.hip); not named KV_*: that prefix lists the families a 3x3 conv can come back with (benchlegs.common.conv_kernel_short_names)
 KV_NAMES = {KV_NONE: "none", KV_DIRECT: "conv3x3_mfma_dma_persist_kernel (direct)", KV_WINO1D: "conv3x3_wino_persist_kernel (Winograd F(2,3) along x)",
@@ -41,9 +42,10 @@ KV_NAMES = {KV_NONE: "none", KV_DIRECT: "conv3x3_mfma_dma_persist_kernel (direct
             CNX_KV_F16_GEMM: "gemm_f16_kernel (row GEMM on v_mfma_f32_32x32x16_f16: Linear / 2x2-stride-2 conv)",
             CNX_KV_F16_ELTWISE: "gelu_fmt_kernel / scale_add_fmt_kernel (fp16 activations)",
             SWIN_KV_WINDOW_ATTN: "window_attn_kernel (shifted-window attention, one wave per window and head, v_mfma_f32_32x32x2_f32)",
+            SWIN_KV_WINDOW_ATTN_BWD: "window_attn_bwd_kernel (backward of the shifted-window attention core, v_mfma_f32_32x32x2_f32, fixed-order slices)",
             SWIN_KV_WINDOW_ATTN_F16: "window_attn_f16_kernel (shifted-window attention on v_mfma_f32_32x32x16_f16: fp16 q / k / v / p, fp32 logits)",
             SWIN_KV_F16_MERGE_LN: "patch_merge_ln_f16_kernel (four-phase gather + LayerNorm(4C), fp16 storage, fp32 moments)"}
-KV_MFMA_SHARE = {KV_NONE: 0.0, KV_DIRECT: 1.0, KV_WINO1D: 2.0 / 3.0, KV_WINO2D: 4.0 / 9.0, KV_W16: 4.0 / 9.0, KV_C16: 1.0, KV_ROWGEMM: 1.0, KV_WINO4: 0.25, KV_F16: 1.0, KV_STEM: 4.0 / 9.0, KV_WINO2D_KS: 4.0 / 9.0, KV_FUSED: 0.0, KV_SMALLMAP: 4.0 / 9.0, KV_F16_ROWS: 1.0, KV_F16_BLOCK: 1.0, KV_MLP: 1.0, CNX_KV_F16_STEM: 0.0, CNX_KV_F16_DW: 0.0, CNX_KV_F16_LN: 0.0, CNX_KV_F16_GEMM: 1.0, CNX_KV_F16_ELTWISE: 0.0, SWIN_KV_WINDOW_ATTN: 1.0, SWIN_KV_WINDOW_ATTN_F16: 1.0, SWIN_KV_F16_MERGE_LN: 0.0}
+KV_MFMA_SHARE = {KV_NONE: 0.0, KV_DIRECT: 1.0, KV_WINO1D: 2.0 / 3.0, KV_WINO2D: 4.0 / 9.0, KV_W16: 4.0 / 9.0, KV_C16: 1.0, KV_ROWGEMM: 1.0, KV_WINO4: 0.25, KV_F16: 1.0, KV_STEM: 4.0 / 9.0, KV_WINO2D_KS: 4.0 / 9.0, KV_FUSED: 0.0, KV_SMALLMAP: 4.0 / 9.0, KV_F16_ROWS: 1.0, KV_F16_BLOCK: 1.0, KV_MLP: 1.0, CNX_KV_F16_STEM: 0.0, CNX_KV_F16_DW: 0.0, CNX_KV_F16_LN: 0.0, CNX_KV_F16_GEMM: 1.0, CNX_KV_F16_ELTWISE: 0.0, SWIN_KV_WINDOW_ATTN: 1.0, SWIN_KV_WINDOW_ATTN_BWD: 1.0, SWIN_KV_WINDOW_ATTN_F16: 1.0, SWIN_KV_F16_MERGE_LN: 0.0}
 
 
 class OpDesc(C.Structure):
@@ -99,6 +101,10 @@ SIGNATURES = {
     "ph_model_backward": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_f32), _vp, _i32, _f32,
                                     _i32, _i32, _f32, _vp, _vp, _vp]),
     "ph_model_set_head_loss": (C.c_int, [_vp, _i32, _i32, C.POINTER(_f32), _i32]),
+    "ph_model_set_branch_scales": (C.c_int, [_vp, _vp, _i32, _i32]),
+    "ph_model_backward_pad_vector": (_i64, [_vp, _i32, _i32, _i32, C.POINTER(_i32)]),
+    "ph_model_backward_profile_read": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32, C.POINTER(C.c_double)]),
+    "ph_model_last_backward_kernels": (C.c_int, [_vp, C.POINTER(_i32), _i32]),
     "ph_loss_scratch_bytes": (_i64, [_i32, _i32]),
     "ph_loss_bce_dice": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _i64, _vp]),
     "ph_loss_masked_smooth_l1": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i64, _vp]),

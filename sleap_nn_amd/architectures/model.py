@@ -25,7 +25,7 @@ PRECISIONS = {"exact": 0, "split": 1, "fp16": 2}
 
 
 def get_backbone(backbone: str, backbone_config):
-    """architectures/model.py:36-67.  ``unet``, ``convnext`` and ``swint`` (inference) are built natively."""
+    """architectures/model.py:36-67.  ``unet``, ``convnext`` and ``swint`` are built natively."""
     if backbone == "unet":
         return UNet.from_config(backbone_config)
     if backbone == "convnext":
@@ -267,11 +267,25 @@ class Model:
     def eval(self) -> "Model":
         return self.set_fusion(True)
 
-    def train(self, mode: bool = True) -> "Model":
-        """Training keeps every activation: the op-by-op (unfused) program runs."""
-        if mode and self.backbone_type == "swint":
-            raise NotImplementedError("training a 'swint' backbone is not implemented on the MI355X path (inference only)")
+    def train(self, mode: bool = True, allow_swint: bool = False) -> "Model":
+        """Training keeps every activation: the op-by-op (unfused) program runs.  A Swin backbone trains on request only
+        (``allow_swint=True``; ``TrainingModule(model, swint_training=True)`` passes it): its backward is the window-attention,
+        patch-merge and residual steps of ``ph_model_backward`` (csrc/swin_train_kernels.hip)."""
+        if mode and self.backbone_type == "swint" and not allow_swint:
+            raise NotImplementedError("training a 'swint' backbone is opt-in on the MI355X path: Model.train(True, allow_swint=True), or "
+                                      "TrainingModule(model, swint_training=True)")
         return self.set_fusion(not mode)
+
+    def residual_branches(self) -> int:
+        """Number of residual Linear ops (``FLAG_RESIDUAL``) of the current program: the rows of ``ph_model_set_branch_scales``."""
+        return sum(1 for o in self.ops if o.kind == L.OP_LINEAR and (o.flags & L.FLAG_RESIDUAL))
+
+    def last_backward_kernels(self):
+        """PH_KV_* code of the kernel each op's step of the LAST ``ph_model_backward`` ran (``ph_model_last_backward_kernels``)."""
+        n = len(self.ops)
+        arr = (C.c_int32 * n)()
+        L.check(L.lib().ph_model_last_backward_kernels(self._handle, arr, n))
+        return list(arr)
 
     def set_fusion(self, fused: bool) -> "Model":
         want = self.fused_ops if fused else self.unfused_ops

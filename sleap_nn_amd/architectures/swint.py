@@ -1,4 +1,4 @@
-"""Swin Transformer encoder + UNet-style decoder -> op program for libposehip (inference).
+"""Swin Transformer encoder + UNet-style decoder -> op program for libposehip (inference and, on request, training).
 
 Reproduces the structure and the checkpoint parameter names of the reference ``SwinTWrapper``
 (``sleap_nn/architectures/swint.py:41-163`` encoder, ``:166-400`` wrapper) without torch modules.  The encoder
@@ -11,8 +11,14 @@ In the NHWC layout of the kernels a block is seven launches: LayerNorm -> row GE
 un-rolled map) -> window attention (pad, roll, partition, bias, band mask, softmax, reverse and crop in one
 kernel) -> row GEMM C->C whose epilogue adds the block input -> LayerNorm -> row GEMM C->4C with the erf-GELU in
 its epilogue -> row GEMM 4C->C whose epilogue adds the residual.  Patch merging is the four-phase gather with its
-LayerNorm in one launch, then a bias-less row GEMM.  All norms have eps 1e-5.  Stochastic depth and dropout are
-the identity at inference; training a Swin program is not implemented.  The same program runs in exact fp32 (the default) or,
+LayerNorm in one launch, then a bias-less row GEMM.  All norms have eps 1e-5.  Dropout is 0 in the reference; stochastic
+depth is the identity at inference.  Training is opt-in (``Model.train(True, allow_swint=True)``,
+``TrainingModule(model, swint_training=True)``): the op-by-op program keeps the qkv slot, the attention output, both
+LayerNorm inputs and the GELU input, and ``ph_model_backward`` runs the attention core's backward
+(``csrc/swin_train_kernels.hip``: S and P recomputed, fixed-order reductions), the patch-merge backward
+and the residual fan-out.  Stochastic depth -- the reference builds its encoder with torchvision's default
+``stochastic_depth_prob = 0.1`` (swint.py:80, :117-133) -- is a per-sample scale of each residual branch, drawn by
+``draw_branch_scales`` and handed to the library with ``ph_model_set_branch_scales``.  The same program runs in exact fp32 (the default) or,
 with ``Model.set_precision("fp16", swint_f16=True)``, whole on fp16 activations (``csrc/swin_f16_kernels.hip``).
 
 The pool / middle / decoder half is the ConvNeXt wrapper's, as in the reference (swint.py:266-339).
@@ -47,6 +53,22 @@ def relative_position_index(window: int) -> torch.Tensor:
     rel[:, :, 1] += window - 1
     rel[:, :, 0] *= 2 * window - 1
     return rel.sum(-1).flatten()
+
+
+def stochastic_depth_probs(depths, stochastic_depth_prob: float = 0.1) -> List[float]:
+    """Drop probability of block k (over all stages, in order): ``stochastic_depth_prob * k / (total_blocks - 1)`` (swint.py:110-137, torchvision's schedule)."""
+    total = int(sum(depths))
+    return [float(stochastic_depth_prob) * float(k) / (total - 1) for k in range(total)]
+
+
+def draw_branch_scales(depths, batch: int, stochastic_depth_prob: float = 0.1, generator=None, device="cpu") -> torch.Tensor:
+    """``(2 * sum(depths), batch)`` fp32 scales of the residual branches in program order (attention branch, then MLP branch, of each block):
+    ``bernoulli(1 - p_k) / (1 - p_k)`` per sample, what torchvision's ``StochasticDepth(p_k, "row")`` multiplies a branch by in train mode.  Both
+    branches of a block share p_k and are drawn independently."""
+    p = torch.tensor(stochastic_depth_probs(depths, stochastic_depth_prob), dtype=torch.float32, device=device).repeat_interleave(2)
+    keep = (1.0 - p)[:, None].expand(-1, int(batch))
+    drawn = torch.bernoulli(keep, generator=generator)
+    return (drawn / keep).contiguous()
 
 
 @dataclass

@@ -165,7 +165,7 @@ int64_t chan_reduce_scratch_floats(int cp) { return (int64_t)RED_SLICES * cp; }
 // recomputed from the saved input and also written to `stats` (npix x 2) for the weight gradient.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ gamma,
-                                                            float* __restrict__ gx, float* __restrict__ stats, int accumulate, int c, int cp, size_t npix) {
+                                                            float* __restrict__ gx, float* __restrict__ stats, int accumulate, int c, int cp, size_t npix, float eps) {
   const int sub = threadIdx.x & 15;
   const int quads = cp >> 2;
   const float inv_c = 1.0f / (float)c;
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
         ss += (q * 4 + e < c) ? d * d : 0.f;
       }
     }
-    const float rstd = 1.0f / sqrtf(red16(ss) * inv_c + LN_EPS_T);
+    const float rstd = 1.0f / sqrtf(red16(ss) * inv_c + eps);
     float s1 = 0.f, s2 = 0.f;  // sum_c g*dy, sum_c g*dy*xhat   (gamma is zero-padded: pad channels drop out)
     for (int q = sub; q < quads; q += 16) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(px + q * 4);
@@ -235,9 +235,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
     }
   }
 }
-int launch_layernorm_bwd(const float* x, const float* gy, const float* gamma, float* gx, float* stats, int accumulate, int c, int cp, size_t npix, hipStream_t s) {
+int launch_layernorm_bwd(const float* x, const float* gy, const float* gamma, float* gx, float* stats, int accumulate, int c, int cp, size_t npix, hipStream_t s, float eps) {
   const int blocks = (int)std::min<size_t>((npix + 15) / 16, 256 * 32);
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(blocks), dim3(256), 0, s, x, gy, gamma, gx, stats, accumulate, c, cp, npix);
+  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(blocks), dim3(256), 0, s, x, gy, gamma, gx, stats, accumulate, c, cp, npix, eps);
   PH_HIP_CHECK(hipGetLastError());
   return PH_OK;
 }

@@ -1083,6 +1083,7 @@ void ph_model_destroy(ph_model* m) {
   if (!m) return;
   for (void* p : m->allocs) (void)hipFree(p);
   for (hipEvent_t e : m->ev) (void)hipEventDestroy(e);
+  for (hipEvent_t e : m->bwd_ev) (void)hipEventDestroy(e);
   for (hipEvent_t e : m->comm_events_owned) (void)hipEventDestroy(e);
   delete m;
 }
@@ -1122,6 +1123,9 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
   hipStream_t s = static_cast<hipStream_t>(stream);
   Plan plan;
   const int fmt = forward_format(m);
+  PH_REQUIRE(!m->branch_scales || (fmt == FMT_F32 && batch == m->branch_batch),
+             "ph_model_forward: branch scales are set for batch %d in exact fp32; this forward has batch %d%s", m->branch_batch, batch, fmt == FMT_F32 ? "" : " and a non-fp32 format");
+  int branch = 0;  // residual Linear ops seen so far (row of the branch scales)
   int rc = build_plan(m, batch, height, width, plan, fmt);
   if (rc != PH_OK) return rc;
   if (fmt != FMT_F32) {
@@ -1989,6 +1993,16 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           a.scale = op.w2_dev;
           a.residual = rd(d.src1);
         } else if (d.flags & PH_FLAG_RESIDUAL) {  // dst = acc + bias + src1
+          if (m->branch_scales) {  // dst = s[branch][b] * (acc + bias) + src1: the GEMM without its residual, then one element-wise pass
+            kv[op_index - 1] = PH_KV_ROWGEMM;
+            a.late_split = m->gemm_late_split;
+            rc = launch_gemm(a, s);
+            ++launch_no;
+            if (rc == PH_OK)
+              rc = launch_scale_samples_add(static_cast<float*>(wr(d.dst)), static_cast<const float*>(rd(d.src1)), m->branch_scales + (size_t)branch * batch, (size_t)so.h * so.w * so.cp, batch, s);
+            ++branch;
+            break;
+          }
           a.residual = rd(d.src1);
         }
         a.late_split = m->gemm_late_split;

@@ -116,6 +116,13 @@ struct ph_model {
   int last_batch = 0;
   std::vector<int> last_variant;  // PH_KV_* code of the kernel each op of the last forward ran (ph_model_last_kernels)
   std::vector<ph::RangeRec> last_ranges;  // workspace ranges each launch of the last forward read / wrote (ph_model_last_ranges)
+  std::vector<hipEvent_t> bwd_ev;         // profiling on: [0] before the losses, [1 + 2 (n - 1 - i)] before op i's step of the reverse sweep, [2 + 2 (n - 1 - i)] between its weight- and data-gradient
+                                          // launches (Linear ops; elsewhere recorded at once), [2 n + 1] after the sweep (ph_model_backward_profile_read)
+  bool bwd_ev_recorded = false;
+  std::vector<int> last_bwd_variant;      // PH_KV_* code of the kernel each op's step of the last ph_model_backward ran (ph_model_last_backward_kernels)
+  // ph_model_set_branch_scales: (branch_n, branch_batch) per-sample scales of the residual Linears' branches (stochastic depth), borrowed; nullptr = none
+  const float* branch_scales = nullptr;
+  int branch_n = 0, branch_batch = 0;
   // optional per-op HIP-event timing (ph_model_set_profiling)
   bool profiling = false;
   bool events_pending = false;

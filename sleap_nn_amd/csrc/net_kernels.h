@@ -160,6 +160,32 @@ struct WindowAttnArgs {
   int sh = 0, sw = 0;               // per-axis shift (0 where the window covers the padded axis)
 };
 int launch_window_attn(const WindowAttnArgs& a, hipStream_t s);
+// Backward of the attention core (swin_train_kernels.hip): S and P are recomputed from q and k, nothing but the qkv slot is kept by the forward
+struct WindowAttnBwdArgs {
+  const float* qkv = nullptr;       // the forward's qkv slot (B, H, W, 3C)
+  const float* table = nullptr;     // head-major bias table, as WindowAttnArgs
+  const float* qkv_bias = nullptr;  // (3C)
+  const float* gout = nullptr;      // gradient of the attention output (B, H, W, C)
+  float* gqkv = nullptr;            // gradient of the qkv slot (B, H, W, 3C): every element written exactly once
+  float* gtable = nullptr;          // gradient of relative_position_bias_table, canonical ((2w - 1)^2, heads)
+  float* gpad = nullptr;            // (3C): sum of dq | dk | dv over the padded tokens (belongs to qkv.bias)
+  float* scratch = nullptr;         // window_attn_bwd_scratch_floats(...) floats: the slice partials of gtable and gpad
+  int B = 0, H = 0, W = 0, C = 0, heads = 0;
+  int w = 0;
+  int sh = 0, sw = 0;
+};
+int64_t window_attn_bwd_scratch_floats(int B, int H, int W, int C, int heads, int w);
+int launch_window_attn_bwd(const WindowAttnBwdArgs& a, hipStream_t s);
+// Patch merging backward in three steps around layernorm_bwd_kernel: gather of the four phases to (npix, 4C), scatter of the gathered gradient back to
+// the 2x2 phases of (B, H, W, C) (accumulate: add to what is there; the zero padding past an odd edge receives nothing)
+int launch_patch_merge_gather(const float* src, float* dst, int B, int H, int W, int c, hipStream_t s);
+int launch_patch_merge_scatter(const float* gsrc, float* gdst, int accumulate, int B, int H, int W, int c, hipStream_t s);
+// Small element-wise passes of the Swin training step: gx (+)= gy; dst[b] = scale[b] * src[b] over per_sample elements each;
+// dst[b] = scale[b] * dst[b] + res[b]; dst += src
+int launch_grad_fanout(const float* gy, float* gx, int accumulate, size_t n, hipStream_t s);
+int launch_scale_samples(const float* src, const float* scale, float* dst, size_t per_sample, int B, hipStream_t s);
+int launch_scale_samples_add(float* dst, const float* res, const float* scale, size_t per_sample, int B, hipStream_t s);
+int launch_vec_add(float* dst, const float* src, int n, hipStream_t s);
 // 2x2 phase gather (zero fill past an odd edge) + LayerNorm over the 4C gathered channels: (B, H, W, C) -> (B, ceil(H/2), ceil(W/2), 4C)
 int launch_patch_merge_ln(const float* src, const float* gamma, const float* beta, float* dst, int B, int H, int W, int c, float eps, hipStream_t s);
 // ... on plain-fp16 activations (swin_f16_kernels.hip; FMT_F16, C a multiple of 32: no pad channels)

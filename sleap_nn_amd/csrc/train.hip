@@ -19,14 +19,19 @@ struct BwdPlan {
   Plan act;                         // activation slots (same layout as the forward workspace)
   std::vector<int64_t> head_dy_off; // per output: NCHW dY buffer offset in the grad workspace
   int64_t scratch_off = 0, scratch_bytes = 0, total = 0;
+  // Swin programs: the padded tokens' (3C) share of a qkv.bias gradient lives from the attention op's step until the qkv Linear's step (whose weight-gradient
+  // GEMM owns the scratch) has written that bias gradient; the residual Linears' scaled output gradient (branch scales set) is an operand of that GEMM
+  int64_t pad_off = -1, scaled_off = -1;
 };
+
+inline float ln_eps(const ph_op_desc& d) { return (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f; }
 
 int build_bwd_plan(const ph_model* m, int B, int H, int W, BwdPlan& bp) {
   int rc = build_plan(m, B, H, W, bp.act);
   if (rc != PH_OK) return rc;
   int64_t off = bp.act.total;  // gradient slots mirror the activation slots one to one
   bp.head_dy_off.assign(m->n_outputs, -1);
-  int64_t scratch = 0;
+  int64_t scratch = 0, pad_floats = 0, scaled_floats = 0;
   for (const PackedOp& op : m->ops) {
     const ph_op_desc& d = op.d;
     if (d.kind == PH_OP_STEM || (d.kind == PH_OP_CONV && d.dst2 >= 0)) {
@@ -62,8 +67,16 @@ int build_bwd_plan(const ph_model* m, int B, int H, int W, BwdPlan& bp) {
         case PH_OP_LINEAR:
         case PH_OP_PATCH_CONV: need = std::max(need, row_wgrad_slab_floats((int)npix, d.cout, d.cin0)); break;
         case PH_OP_SCALE_ADD: need = std::max(need, chan_reduce_scratch_floats(so.cp)); break;
+        case PH_OP_PATCH_MERGE: need = std::max(need, 2 * npix + chan_reduce_scratch_floats(so.cp) + 2 * npix * so.cp); break;  // statistics, reduction partials, gather, its gradient
+        case PH_OP_WINDOW_ATTN: {
+          const SlotShape& si = bp.act.slots[d.src0];
+          need = std::max(need, window_attn_bwd_scratch_floats(B, si.h, si.w, d.cout, d.cin1, d.ksize));
+          pad_floats = std::max<int64_t>(pad_floats, d.cin0);
+          break;
+        }
         default: break;
       }
+      if (d.kind == PH_OP_LINEAR && (d.flags & PH_FLAG_RESIDUAL)) scaled_floats = std::max<int64_t>(scaled_floats, npix * so.cp);
       scratch = std::max(scratch, need);
       continue;
     }
@@ -85,6 +98,14 @@ int build_bwd_plan(const ph_model* m, int B, int H, int W, BwdPlan& bp) {
       scratch = std::max<int64_t>(scratch, input_wgrad_scratch_floats(d.cin0, d.cout));
       scratch = std::max<int64_t>(scratch, bias_scratch_floats(pad16(d.cout)));
     }
+  }
+  if (pad_floats > 0) {
+    bp.pad_off = off;
+    off += align_up(pad_floats * 4, 256);
+  }
+  if (scaled_floats > 0) {
+    bp.scaled_off = off;
+    off += align_up(scaled_floats * 4, 256);
   }
   bp.scratch_off = off;
   bp.scratch_bytes = align_up(scratch * 4, 256);
@@ -270,9 +291,24 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
              "ph_model_backward: null argument");
   PH_REQUIRE(((uintptr_t)grad_workspace_dev & 255) == 0, "gradient workspace must be 256-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  for (const auto& op : m->ops)  // refused before any launch: the sweep would otherwise run the decoder's gradients first
-    PH_REQUIRE(op.d.kind != PH_OP_WINDOW_ATTN && op.d.kind != PH_OP_PATCH_MERGE && !(op.d.kind == PH_OP_LINEAR && (op.d.flags & PH_FLAG_RESIDUAL)),
-               "ph_model_backward: the Swin Transformer encoder ops have no backward pass: inference only");
+  // per-sample branch scales (ph_model_set_branch_scales): residual Linear i of the program (in program order) is scaled by row i
+  std::vector<int> branch_of(m->ops.size(), -1);
+  {
+    int n_res = 0;
+    for (size_t i = 0; i < m->ops.size(); ++i)
+      if (m->ops[i].d.kind == PH_OP_LINEAR && (m->ops[i].d.flags & PH_FLAG_RESIDUAL)) branch_of[i] = n_res++;
+    PH_REQUIRE(!m->branch_scales || (m->branch_n == n_res && m->branch_batch == batch),
+               "ph_model_backward: branch scales are set for %d branches x batch %d, the step has %d x %d", m->branch_n, m->branch_batch, n_res, batch);
+  }
+  m->last_bwd_variant.assign(m->ops.size(), PH_KV_NONE);
+  const size_t n_ops = m->ops.size();
+  const bool prof = m->profiling;  // per-op events of this sweep (ph_model_backward_profile_read)
+  if (prof && m->bwd_ev.size() != 2 * n_ops + 2) {
+    for (auto& e : m->bwd_ev) (void)hipEventDestroy(e);
+    m->bwd_ev.assign(2 * n_ops + 2, nullptr);
+    for (auto& e : m->bwd_ev) PH_HIP_CHECK(hipEventCreate(&e));
+  }
+  m->bwd_ev_recorded = false;
   for (const auto& op : m->ops) {  // the MSE / cross-entropy gradients below are not these heads' losses: they train only with a loss chosen by ph_model_set_head_loss
     if (op.d.kind != PH_OP_HEAD) continue;
     PH_REQUIRE(op.d.out_index >= 0 && op.d.out_index < PH_MAX_OUTPUTS, "ph_model_backward: head output index %d out of range", op.d.out_index);
@@ -293,6 +329,9 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
   auto A = [&](int slot) { return reinterpret_cast<const float*>(aws + bp.act.slots[slot].offset); };
   auto G = [&](int slot) { return reinterpret_cast<float*>(gws + bp.act.slots[slot].offset); };
   float* scratch = reinterpret_cast<float*>(gws + bp.scratch_off);
+  float* pad_vec = bp.pad_off >= 0 ? reinterpret_cast<float*>(gws + bp.pad_off) : nullptr;
+  float* scaled_gy = bp.scaled_off >= 0 ? reinterpret_cast<float*>(gws + bp.scaled_off) : nullptr;
+  int pad_bias = -1, pad_n = 0;  // weights[] index of the qkv.bias whose gradient still lacks the padded tokens' share (pad_vec), and its length
   std::vector<char> init(m->n_slots, 0);
   std::vector<char> fused_away(m->ops.size(), 0);
   // ReLU-mask folding: the gradient of a conv + ReLU output is complete when its FIRST consumer (program order = last in this sweep)
@@ -313,6 +352,7 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
   ok.max_hard = max_hard_keypoints;
   ok.loss_scale = ohkm_loss_scale;
 
+  if (prof) PH_HIP_CHECK(hipEventRecord(m->bwd_ev[0], s));
   // ---- losses and head-output gradients (loss_dev: [0] = total, [1 + i] = head i)
   std::vector<float> lw(loss_weights_host, loss_weights_host + m->n_outputs);
   for (const PackedOp& op : m->ops) {
@@ -355,6 +395,11 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
   for (int oi = (int)m->ops.size() - 1; oi >= 0; --oi) {
     const PackedOp& op = m->ops[oi];
     const ph_op_desc& d = op.d;
+    const size_t ev_i = 1 + 2 * (n_ops - 1 - (size_t)oi);
+    if (prof) {
+      PH_HIP_CHECK(hipEventRecord(m->bwd_ev[ev_i], s));
+      if (d.kind != PH_OP_LINEAR && d.kind != PH_OP_PATCH_CONV) PH_HIP_CHECK(hipEventRecord(m->bwd_ev[ev_i + 1], s));
+    }
     switch (d.kind) {
       case PH_OP_HEAD: {
         const SlotShape& s0 = bp.act.slots[d.src0];
@@ -670,13 +715,21 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
         }
         // a Linear layer's bias gradient (column sums of dY) comes out of its weight-gradient GEMM, which stages every dY row anyway
         const bool bias_in_wgrad = !patch && !(d.flags & PH_FLAG_RELU) && d.bias >= 0;
+        // a residual Linear under branch scales: its weight, bias and data gradients see s[branch][b] * G(dst) (one scaling pass), its residual source the plain G(dst)
+        const float* gy = G(d.dst);
+        if (branch_of[oi] >= 0 && m->branch_scales) {
+          PH_REQUIRE(scaled_gy, "backward plan has no region for the scaled gradient");
+          rc = launch_scale_samples(G(d.dst), m->branch_scales + (size_t)branch_of[oi] * batch, scaled_gy, (size_t)so.h * so.w * so.cp, batch, s);
+          if (rc != PH_OK) return rc;
+          gy = scaled_gy;
+        }
         if (d.flags & PH_FLAG_RELU)
           rc = launch_relu_mask_bias_grad(G(d.dst), A(d.dst), (size_t)M, so.cp, d.cout, grads_flat_dev + m->weight_offset[d.bias], scratch, s);
-        else if (!bias_in_wgrad)
+        else if (!bias_in_wgrad && d.bias >= 0)  // (Linear(bias=False): Swin's patch-merging reduction has none)
           rc = launch_bias_grad(G(d.dst), (size_t)M, so.cp, d.cout, grads_flat_dev + m->weight_offset[d.bias], scratch, s);
         for (int tap = 0; tap < taps && rc == PH_OK; ++tap) {
           RowWgradArgs w{};
-          w.dy = G(d.dst);
+          w.dy = gy;
           w.x = A(d.src0);
           w.slab = scratch;
           w.np = so.cp;
@@ -692,8 +745,9 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
           w.W = si.w;
           rc = launch_row_wgrad(w, d.cout, d.cin0, taps, grads_flat_dev + m->weight_offset[d.weight], s);
           if (rc != PH_OK) break;
+          if (prof && tap == 0) PH_HIP_CHECK(hipEventRecord(m->bwd_ev[ev_i + 1], s));  // (a 2x2-stride-2 conv interleaves its four taps: all but the first weight-gradient GEMM count as data gradient)
           GemmArgs g{};
-          g.src0 = G(d.dst);
+          g.src0 = gy;
           g.c0p = so.cp;
           g.wpack = op.wd_gemm_dev[tap];
           g.bias = op.zero_bias_dev;
@@ -719,6 +773,64 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
           init[m->ops[gelu_op].d.src0] = 1;
           fused_away[gelu_op] = 1;
         }
+        m->last_bwd_variant[oi] = PH_KV_ROWGEMM;
+        if (rc == PH_OK && d.kind == PH_OP_LINEAR && (d.flags & PH_FLAG_RESIDUAL)) {  // dst = acc + bias + src1: the residual source takes G(dst) as it is
+          rc = launch_grad_fanout(G(d.dst), G(d.src1), init[d.src1], (size_t)M * so.cp, s);
+          init[d.src1] = 1;
+        }
+        if (rc == PH_OK && pad_bias >= 0 && d.kind == PH_OP_LINEAR && d.bias == pad_bias) {  // the qkv Linear has written qkv.bias's gradient: add the padded tokens' share
+          rc = launch_vec_add(grads_flat_dev + m->weight_offset[d.bias], pad_vec, pad_n, s);
+          pad_bias = -1;
+        }
+        break;
+      }
+      case PH_OP_WINDOW_ATTN: {
+        const SlotShape& si = bp.act.slots[d.src0];
+        PH_REQUIRE(init[d.dst], "window attention output slot %d received no gradient", d.dst);
+        PH_REQUIRE(!init[d.src0] && pad_bias < 0 && pad_vec, "window attention: the qkv slot %d must have the attention core as its only reader", d.src0);
+        WindowAttnBwdArgs w{};
+        w.qkv = A(d.src0);
+        w.table = op.w_dev;
+        w.qkv_bias = op.b_dev;
+        w.gout = G(d.dst);
+        w.gqkv = G(d.src0);
+        w.gtable = grads_flat_dev + m->weight_offset[d.weight];
+        w.gpad = pad_vec;
+        w.scratch = scratch;
+        w.B = batch;
+        w.H = si.h;
+        w.W = si.w;
+        w.C = d.cout;
+        w.heads = d.cin1;
+        w.w = d.ksize;
+        w.sh = d.ksize >= (si.h + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;  // per axis, as the forward
+        w.sw = d.ksize >= (si.w + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;
+        rc = launch_window_attn_bwd(w, s);
+        m->last_bwd_variant[oi] = PH_KV_WINDOW_ATTN_BWD;
+        init[d.src0] = 1;
+        pad_bias = d.bias;
+        pad_n = d.cin0;
+        break;
+      }
+      case PH_OP_PATCH_MERGE: {  // dst = LayerNorm(gather(src0)) over 4C channels; the gathered tensor is rebuilt in scratch
+        const SlotShape& so = bp.act.slots[d.dst];
+        const SlotShape& si = bp.act.slots[d.src0];
+        PH_REQUIRE(init[d.dst], "patch merge output slot %d received no gradient", d.dst);
+        const size_t npix = (size_t)batch * so.h * so.w;
+        float* xg = scratch;
+        float* gxg = xg + npix * so.cp;
+        float* stats = gxg + npix * so.cp;
+        float* red = stats + 2 * npix;
+        rc = launch_patch_merge_gather(A(d.src0), xg, batch, si.h, si.w, d.cin0, s);
+        if (rc != PH_OK) return rc;
+        rc = launch_layernorm_bwd(xg, G(d.dst), op.w_dev, gxg, stats, 0, so.c, so.cp, npix, s, ln_eps(d));
+        if (rc != PH_OK) return rc;
+        rc = launch_chan_reduce(G(d.dst), xg, stats, npix, so.cp, so.c, grads_flat_dev + m->weight_offset[d.weight], red, s);
+        if (rc != PH_OK) return rc;
+        rc = launch_chan_reduce(G(d.dst), nullptr, nullptr, npix, so.cp, so.c, grads_flat_dev + m->weight_offset[d.bias], red, s);
+        if (rc != PH_OK) return rc;
+        rc = launch_patch_merge_scatter(gxg, G(d.src0), init[d.src0], batch, si.h, si.w, d.cin0, s);
+        init[d.src0] = 1;
         break;
       }
       case PH_OP_LAYERNORM: {
@@ -727,7 +839,7 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
         const size_t npix = (size_t)batch * so.h * so.w;
         float* stats = scratch;
         float* red = scratch + 2 * npix;
-        rc = launch_layernorm_bwd(A(d.src0), G(d.dst), op.w_dev, G(d.src0), stats, init[d.src0], so.c, so.cp, npix, s);
+        rc = launch_layernorm_bwd(A(d.src0), G(d.dst), op.w_dev, G(d.src0), stats, init[d.src0], so.c, so.cp, npix, s, ln_eps(d));
         if (rc != PH_OK) return rc;
         rc = launch_chan_reduce(G(d.dst), A(d.src0), stats, npix, so.cp, so.c, grads_flat_dev + m->weight_offset[d.weight], red, s);
         if (rc != PH_OK) return rc;
@@ -788,6 +900,11 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
       }
     }
   }
+  PH_REQUIRE(pad_bias < 0, "window attention: no qkv Linear took the padded tokens' share of its bias gradient");
+  if (prof) {
+    PH_HIP_CHECK(hipEventRecord(m->bwd_ev[2 * n_ops + 1], s));
+    m->bwd_ev_recorded = true;
+  }
   if (m->bucket_event && split_op < 0) PH_HIP_CHECK(hipEventRecord(m->bucket_event, s));
   if (exchange) {  // head bucket (the whole arena when it does not split), then the caller's stream joins the side stream
     PH_HIP_CHECK(hipEventRecord(m->comm_ev[1], s));
@@ -797,6 +914,71 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
     PH_HIP_CHECK(hipEventRecord(m->comm_ev[2], m->comm_stream));
     PH_HIP_CHECK(hipStreamWaitEvent(s, m->comm_ev[2], 0));
   }
+  return PH_OK;
+}
+
+int ph_model_set_branch_scales(ph_model* m, const float* scales_dev, int32_t n_branches, int32_t batch) {
+  PH_REQUIRE(m, "ph_model_set_branch_scales: null model");
+  if (!scales_dev) {
+    m->branch_scales = nullptr;
+    m->branch_n = m->branch_batch = 0;
+    return PH_OK;
+  }
+  int n_res = 0;
+  for (const auto& op : m->ops)
+    if (op.d.kind == PH_OP_LINEAR && (op.d.flags & PH_FLAG_RESIDUAL)) n_res += 1;
+  PH_REQUIRE(n_res > 0, "ph_model_set_branch_scales: the program has no residual Linear (PH_FLAG_RESIDUAL)");
+  PH_REQUIRE(n_branches == n_res, "ph_model_set_branch_scales: %d branches given, the program has %d residual Linear ops", n_branches, n_res);
+  PH_REQUIRE(batch > 0, "ph_model_set_branch_scales: batch %d", batch);
+  m->branch_scales = scales_dev;
+  m->branch_n = n_branches;
+  m->branch_batch = batch;
+  return PH_OK;
+}
+
+int64_t ph_model_backward_pad_vector(const ph_model* m, int32_t batch, int32_t height, int32_t width, int32_t* n_floats) {
+  if (!m || batch <= 0 || height <= 0 || width <= 0) {
+    set_error("ph_model_backward_pad_vector: bad arguments");
+    return PH_E_INVALID;
+  }
+  BwdPlan bp;
+  int rc = build_bwd_plan(m, batch, height, width, bp);
+  if (rc != PH_OK) return rc;
+  int n = 0;
+  for (const auto& op : m->ops)
+    if (op.d.kind == PH_OP_WINDOW_ATTN) {  // the sweep runs in reverse: the first attention op of the program is the last to write the region
+      n = op.d.cin0;
+      break;
+    }
+  if (bp.pad_off < 0 || n == 0) {
+    set_error("ph_model_backward_pad_vector: the program has no window attention op");
+    return PH_E_INVALID;
+  }
+  if (n_floats) *n_floats = n;
+  return bp.pad_off;
+}
+
+int ph_model_backward_profile_read(ph_model* m, double* op_ms, double* op_ms_first, int32_t n_ops, double* loss_ms) {
+  PH_REQUIRE(m && op_ms && op_ms_first && loss_ms, "ph_model_backward_profile_read: null argument");
+  PH_REQUIRE(n_ops == (int32_t)m->ops.size(), "ph_model_backward_profile_read: model has %d ops", (int)m->ops.size());
+  PH_REQUIRE(m->bwd_ev_recorded && m->bwd_ev.size() == 2 * (size_t)n_ops + 2, "ph_model_backward_profile_read: no profiled ph_model_backward (ph_model_set_profiling first)");
+  PH_HIP_CHECK(hipEventSynchronize(m->bwd_ev[2 * n_ops + 1]));
+  float ms = 0.f;
+  PH_HIP_CHECK(hipEventElapsedTime(&ms, m->bwd_ev[0], m->bwd_ev[1]));
+  *loss_ms = ms;
+  for (int i = 0; i < n_ops; ++i) {
+    const size_t e = 1 + 2 * (size_t)(n_ops - 1 - i);
+    PH_HIP_CHECK(hipEventElapsedTime(&ms, m->bwd_ev[e], m->bwd_ev[e + 1]));
+    op_ms_first[i] = ms;
+    PH_HIP_CHECK(hipEventElapsedTime(&ms, m->bwd_ev[e], m->bwd_ev[e + 2]));
+    op_ms[i] = ms;
+  }
+  return PH_OK;
+}
+
+int ph_model_last_backward_kernels(const ph_model* m, int32_t* codes, int32_t n_ops) {
+  PH_REQUIRE(m && codes && n_ops >= 0, "ph_model_last_backward_kernels: bad arguments");
+  for (int i = 0; i < n_ops; ++i) codes[i] = i < (int)m->last_bwd_variant.size() ? m->last_bwd_variant[i] : PH_KV_NONE;
   return PH_OK;
 }
 

@@ -43,14 +43,20 @@ class TrainingModule:
                  optimizer: str = "Adam", weight_decay: Optional[float] = None,
                  loss_weights: Optional[Sequence[float]] = None, ohkm: Optional[OHKMConfig] = None,
                  negative_loss_weight: float = 1.0, lr_scheduler=None, max_epochs: Optional[int] = None, wino4: bool = True,
-                 native_allreduce: Optional[bool] = None) -> None:
+                 native_allreduce: Optional[bool] = None, swint_training: bool = False, stochastic_depth_prob: float = 0.1,
+                 stochastic_depth_seed: int = 0) -> None:
         """``negative_loss_weight``: weight of frames flagged ``is_negative`` in the train-stage MSE (lightning_modules.py:149-153,
         526-545).  ``lr_scheduler``: the reference's scheduler config (a name or ``{name: {...}}``, lightning_modules.py:765-857);
         ``self.lr`` then follows it: one ``on_epoch_end(val_loss)`` per epoch, like Lightning steps the scheduler.
         ``wino4``: the K-heavy 3x3 convolutions of the forward and of the data gradients run the Winograd F(4x4,3x3) kernel in the
         training plan too (handle option ``conv_wino4 = 2``; gradients within ~1e-5 of their tensor's scale of the F(2x2,3x3) ones).
         ``native_allreduce``: with more than one rank, exchange the gradients through the C ABI's own RCCL communicator (``ph_model_set_comm``: the two buckets are
-        enqueued by ``ph_model_backward`` itself) instead of ``torch.distributed``; default: when the process group's backend is nccl (= RCCL on ROCm)."""
+        enqueued by ``ph_model_backward`` itself) instead of ``torch.distributed``; default: when the process group's backend is nccl (= RCCL on ROCm).
+        ``swint_training``: train a Swin Transformer backbone (opt-in, as ``Model.train(True, allow_swint=True)``).  In the ``"train"`` stage every step then
+        draws the per-sample scales of the residual branches on the device -- torchvision's stochastic depth, which the reference trains this backbone with
+        (``stochastic_depth_prob`` 0.1, block k dropped with probability ``prob * k / (blocks - 1)``; ``architectures.swint.draw_branch_scales``) -- from a
+        generator seeded by ``stochastic_depth_seed``, the rank and the step count; no other stage passes scales, ``stochastic_depth_prob=0`` never does, and
+        ``set_branch_scales`` overrides the draw of the next step."""
         from sleap_nn_amd.architectures.heads import SEGMENTATION_MODEL_TYPES
 
         if getattr(model, "model_type", None) in SEGMENTATION_MODEL_TYPES and not self._trains_segmentation:
@@ -63,7 +69,17 @@ class TrainingModule:
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
         self.device = dev
-        self.model = model.train(True).to(dev)
+        self._swint = getattr(model, "backbone_type", None) == "swint"
+        if self._swint and not swint_training:
+            raise NotImplementedError("training a 'swint' backbone is opt-in: TrainingModule(model, swint_training=True)")
+        self.stochastic_depth_prob = float(stochastic_depth_prob)
+        self.stochastic_depth_seed = int(stochastic_depth_seed)
+        if not (0.0 <= self.stochastic_depth_prob < 1.0):
+            raise ValueError(f"stochastic_depth_prob must be in [0, 1), got {stochastic_depth_prob}")
+        self._next_scales: Optional[torch.Tensor] = None   # set_branch_scales: the next train-stage step's scales instead of a draw
+        self._active_scales: Optional[torch.Tensor] = None  # what the handle borrows between the forward and the backward of a step
+        self.last_branch_scales: Optional[torch.Tensor] = None  # scales of the last step that had any (kept alive while its kernels run)
+        self.model = (model.train(True, allow_swint=True) if self._swint else model.train(True)).to(dev)
         self.model.set_option("conv_wino4", 2 if wino4 else 1)
         self.lr, self.betas, self.eps, self.amsgrad = lr, betas, eps, amsgrad
         if optimizer not in ("Adam", "AdamW"):
@@ -133,6 +149,45 @@ class TrainingModule:
             x = x.to(torch.float32)
             code = 2 if bool(x.max() > 1.0) else 1
         x = x.contiguous()
+        B, Cin, H, W = x.shape
+        lib = L.lib()
+        m = self.model
+        self._bind_branch_scales(B, stage)
+        try:
+            return self._forward_backward(x, code, targets, is_negative, stage)
+        finally:  # borrowed until the backward has been enqueued: a later eval() / validation forward sees none
+            if self._active_scales is not None and getattr(m, "_handle", None) is not None:
+                lib.ph_model_set_branch_scales(m._handle, None, 0, 0)
+            self._active_scales = None
+
+    def set_branch_scales(self, scales: Optional[torch.Tensor]) -> None:
+        """Scales of the residual branches for the NEXT train-stage step instead of a draw: ``(n_branches, B)``, rows in program order (attention branch, then MLP
+        branch, of each block); ``None`` withdraws an override that has not been used yet."""
+        self._next_scales = None if scales is None else torch.as_tensor(scales, dtype=torch.float32).to(self.device).contiguous()
+
+    def _bind_branch_scales(self, B: int, stage: str) -> None:
+        if not self._swint or stage != "train":
+            return
+        scales, self._next_scales = self._next_scales, None
+        if scales is None and self.stochastic_depth_prob > 0.0:
+            from sleap_nn_amd.architectures.swint import draw_branch_scales
+
+            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+            g = torch.Generator(device=self.device)
+            g.manual_seed((self.stochastic_depth_seed * 1000003 + rank) * 1000003 + self.step_count)
+            scales = draw_branch_scales(self.model.backbone.depths, B, self.stochastic_depth_prob, generator=g, device=self.device)
+        if scales is None:
+            return
+        m = self.model
+        n = m.residual_branches()
+        if tuple(scales.shape) != (n, B):
+            raise ValueError(f"branch scales have shape {tuple(scales.shape)}, the step needs ({n}, {B})")
+        m._ensure(self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ph_model_set_branch_scales(m._handle, C.c_void_p(scales.data_ptr()), n, B))
+        self._active_scales = self.last_branch_scales = scales
+
+    def _forward_backward(self, x: torch.Tensor, code: int, targets: Dict[str, torch.Tensor], is_negative, stage: str) -> torch.Tensor:
         out = self.model.forward(x, in_dtype=None if code == 0 else code)
         B, Cin, H, W = x.shape
         lib = L.lib()
@@ -179,6 +234,13 @@ class TrainingModule:
             )
         self._last_out = out
         return self._loss
+
+    def padded_token_vector(self, batch: int, height: int, width: int) -> torch.Tensor:
+        """Swin programs: the (3C) share of ``qkv.bias``'s gradient that came through the padded tokens of the program's first attention op in the last
+        ``forward_backward`` of this shape (``ph_model_backward_pad_vector``): exactly zero where the map needs no padding."""
+        n = C.c_int32()
+        off = L.check(L.lib().ph_model_backward_pad_vector(self.model._handle, batch, height, width, C.byref(n)))
+        return self._grad_ws[int(off) : int(off) + 4 * n.value].view(torch.float32).clone()
 
     def _target_shape(self, head_index: int, pred_shape: tuple) -> tuple:
         """Shape of head ``head_index``'s target for a prediction of ``pred_shape`` (a subclass's loss may take more channels)."""
