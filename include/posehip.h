@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 121
+#define PH_VERSION 122
 
 /* error codes */
 #define PH_OK 0
@@ -803,6 +803,47 @@ int ph_track_pose_scores(const double* cur, int32_t B, const double* hist, int32
 int ph_track_mask_pairs(const void* labels_dev, int32_t label_bytes, int32_t B, int32_t h, int32_t w, const void* hist_dev, int32_t L, int32_t n_hist,
                         const int32_t* row_weight_dev, const int32_t* col_weight_dev, int64_t image_pixels, int32_t P, int32_t* inter_dev, int32_t* area_dev,
                         void* stream);
+
+/* ph_track_pose_scores for candidates whose features differ per current frame (the flow-shift tracker: a past instance's keypoints are moved onto each
+ * current frame before the feature function).  cur (B, I, N, 2) as above; hist (B, L, I, N, 2): [b][g][j] = the feature of candidate j
+ * of group g (a lag, or a reference frame) as seen from frame b; counts_cur int32 (B); counts_hist int32 (B, L): 0 for a group that does not exist.  out double
+ * (B, L, I, I): [b][g][i][j] = the score of instance i of frame b against candidate j of group g, by the same pair functions; NaN beyond a count.  1 <= L <= 32. */
+int ph_track_pose_scores_shifted(const double* cur, int32_t B, const double* hist, int32_t L, int32_t I, int32_t N, const int32_t* counts_cur,
+                                 const int32_t* counts_hist, int32_t method, double oks_stddev, double* out);
+
+/* ------------------------------------------------------------------------------------
+ * Pyramidal Lucas-Kanade optical flow (the flow-shift tracker; sleap_nn_amd/tracking/flow.py pyr_lk is the definition)
+ * ---------------------------------------------------------------------------------- */
+
+#define PH_FLOW_MAX_LEVELS 8 /* max_level 0..7: levels 0..7 */
+
+/* One job of ph_flow_track: the pyramids of a reference frame and of a current frame (device pointers per level, level 0 = the frame itself, all uint8,
+ * dense rows, the sizes ph_flow_pyramid gives for the launch's H, W, win and max_level) and the points [pt_begin, pt_end) of the launch's point array,
+ * which lie on the reference frame.  136 bytes. */
+typedef struct ph_flow_job {
+  const uint8_t* ref[PH_FLOW_MAX_LEVELS];
+  const uint8_t* cur[PH_FLOW_MAX_LEVELS];
+  int32_t pt_begin, pt_end;
+} ph_flow_job;
+int ph_flow_job_size(void);
+
+/* Levels of the pyramid of an H x W frame: level l + 1 is ((w + 1) / 2, (h + 1) / 2) and exists while both sides exceed win, up to max_level.  Returns the
+ * number of levels (1 .. max_level + 1) and writes their (height, width) pairs to sizes (int32[2 * PH_FLOW_MAX_LEVELS], may be null); PH_E_INVALID for win
+ * outside 3..41, max_level outside 0..7 or a side below 2. */
+int ph_flow_levels(int32_t H, int32_t W, int32_t win, int32_t max_level, int32_t* sizes);
+
+/* Every level above 0 of B uint8 frames (B, H, W): separable [1 4 6 4 1] at (2x, 2y), reflect-101 borders, (sum + 128) >> 8 -- bit-identical to pyr_lk's
+ * levels.  out_dev: B records of S = sum over levels l >= 1 of h_l * w_l bytes, the levels of a frame one after another (level 1 first); out_bytes >= B * S.
+ * One launch per level on `stream`, no host synchronisation.  Returns the number of levels. */
+int ph_flow_pyramid(const uint8_t* frames_dev, int32_t B, int32_t H, int32_t W, int32_t win, int32_t max_level, uint8_t* out_dev, int64_t out_bytes, void* stream);
+
+/* pyr_lk for a list of jobs in ONE launch: one wave works one point through all of its levels.  jobs_dev: n_jobs ph_flow_job records ON THE DEVICE;
+ * points_dev float32 (n_points, 2) (x, y), NaN = no point; every point must belong to exactly one job's range.  shifted_dev float32 (n_points, 2): the
+ * point on the current frame, NaN where status is 0; status_dev uint8 (n_points).  The grid is (max_job_points, n_jobs): a job's points beyond
+ * max_job_points, and points no job names, come back lost (NaN, status 0).  max_iter 1..100, eps > 0 (the reference: 30, 0.01).  No atomics, no host
+ * synchronisation.  win 3..41 and max_level 0..7, PH_E_INVALID beyond. */
+int ph_flow_track(const ph_flow_job* jobs_dev, int32_t n_jobs, int32_t max_job_points, const float* points_dev, int32_t n_points, int32_t H, int32_t W,
+                  int32_t win, int32_t max_level, int32_t max_iter, double eps, float* shifted_dev, uint8_t* status_dev, void* stream);
 
 #ifdef __cplusplus
 }

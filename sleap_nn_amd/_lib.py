@@ -157,6 +157,11 @@ SIGNATURES = {
     "ph_mask_boundary": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
     "ph_track_pose_scores": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, C.c_double, _vp]),
     "ph_track_mask_pairs": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "ph_track_pose_scores_shifted": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, C.c_double, _vp]),
+    "ph_flow_job_size": (C.c_int, []),
+    "ph_flow_levels": (C.c_int, [_i32, _i32, _i32, _i32, _vp]),
+    "ph_flow_pyramid": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "ph_flow_track": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp]),
     "ph_group_batch": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, C.c_double, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 

@@ -131,3 +131,54 @@ extern "C" int ph_track_pose_scores(const double* cur, int32_t B, const double* 
     }
   return PH_OK;
 }
+
+// The same pair functions where a candidate's feature differs per current frame (the flow-shift tracker, tracker.py:722-807: a past instance's keypoints are
+// moved onto the current frame by optical flow before the feature function): hist is (B, L, I, N, 2), one candidate table per current frame.
+extern "C" int ph_track_pose_scores_shifted(const double* cur, int32_t B, const double* hist, int32_t L, int32_t I, int32_t N, const int32_t* counts_cur,
+                                            const int32_t* counts_hist, int32_t method, double oks_stddev, double* out) {
+  if (!cur || !hist || !counts_cur || !counts_hist || !out) {
+    ph::set_error("ph_track_pose_scores_shifted: null pointer");
+    return PH_E_INVALID;
+  }
+  if (B < 1 || L < 1 || L > 32 || I < 1 || N < 1) {
+    ph::set_error("ph_track_pose_scores_shifted: bad shape B=%d L=%d (1..32) I=%d N=%d", B, L, I, N);
+    return PH_E_INVALID;
+  }
+  if (method < PH_TRACK_OKS || method > PH_TRACK_COSINE || (method == PH_TRACK_IOU && N != 2)) {
+    ph::set_error("ph_track_pose_scores_shifted: method %d is none of oks 0, iou 1 (N = 2: one box), euclidean_dist 2, cosine_sim 3", method);
+    return PH_E_INVALID;
+  }
+  if ((int64_t)B * L * I * I > 0x7fffffffLL) {
+    ph::set_error("ph_track_pose_scores_shifted: %lld scores per call; at most 2^31 - 1", (long long)B * L * I * I);
+    return PH_E_INVALID;
+  }
+  for (int f = 0; f < B; ++f)
+    if (counts_cur[f] < 0 || counts_cur[f] > I) {
+      ph::set_error("ph_track_pose_scores_shifted: counts_cur[%d] = %d is outside [0, %d]", f, counts_cur[f], I);
+      return PH_E_INVALID;
+    }
+  for (int f = 0; f < B * L; ++f)
+    if (counts_hist[f] < 0 || counts_hist[f] > I) {
+      ph::set_error("ph_track_pose_scores_shifted: counts_hist[%d] = %d is outside [0, %d]", f, counts_hist[f], I);
+      return PH_E_INVALID;
+    }
+  const size_t fs = (size_t)N * 2;
+  const int D = 2 * N;
+  for (int b = 0; b < B; ++b)
+    for (int g = 0; g < L; ++g) {
+      double* o = out + ((size_t)b * L + g) * I * I;
+      const double* past = hist + ((size_t)b * L + g) * I * fs;
+      const int n_cur = counts_cur[b], n_past = counts_hist[(size_t)b * L + g];
+      for (int i = 0; i < I; ++i)
+        for (int j = 0; j < I; ++j) {
+          double v = kNaN;
+          if (i < n_cur && j < n_past) {
+            const double* a = cur + ((size_t)b * I + i) * fs;
+            const double* p = past + (size_t)j * fs;
+            v = method == PH_TRACK_OKS ? oks(a, p, N, oks_stddev) : method == PH_TRACK_IOU ? iou(a, p) : method == PH_TRACK_EUCLID ? neg_euclid(a, p, D) : cosine(a, p, D);
+          }
+          o[(size_t)i * I + j] = v;
+        }
+    }
+  return PH_OK;
+}

@@ -272,7 +272,8 @@ class Predictor:
         if self.tracker_config is not None:
             from sleap_nn_amd.tracking import apply_tracking
 
-            outs = apply_tracking(outs, self.tracker_config)
+            flow = bool(getattr(self.tracker_config, "use_flow", False))  # the flow-shift tracker reads the frames themselves
+            outs = apply_tracking(outs, self.tracker_config, frames=frames) if flow else apply_tracking(outs, self.tracker_config)
         return outs
 
     def _predict(self, frames, pipelined: bool = True) -> List[Outputs]:

@@ -1,7 +1,8 @@
 """``TrackerConfig`` and ``apply_tracking`` (sleap_nn/inference/tracking.py:49-362) on ``Outputs`` batches.
 
 ``apply_tracking(list_of_outputs, config)`` resolves the task defaults as the reference does on the labels' content, builds one fresh ``Tracker`` and tracks
-the batches in (video, frame) order with ``Tracker.track_outputs``.  The post-tracking cleanup (``tracking_clean_instance_count``,
+the batches in (video, frame) order with ``Tracker.track_outputs``.  ``use_flow=True`` (with ``allow_flow=True``, this project's opt-in: see ``tracker.py``) needs the
+original frames, ``apply_tracking(..., frames=...)``; ``Predictor.predict`` hands them over.  The post-tracking cleanup (``tracking_clean_instance_count``,
 ``post_connect_single_breaks``) is not built: each raises ``NotImplementedError`` naming the knob.
 """
 from __future__ import annotations
@@ -49,6 +50,7 @@ class TrackerConfig:
     scoring_method_explicit: bool = True
     features_explicit: bool = True
     candidates_method_explicit: bool = True
+    allow_flow: bool = False  # OURS, not the reference's: use_flow=True is built only with it (the flow is this project's pyr_lk / ph_flow_track, not OpenCV's)
 
 
 def is_mask_mode(outputs_list: Sequence) -> bool:
@@ -97,7 +99,8 @@ def resolve_config(config: TrackerConfig, n_nodes: Optional[int], mask_mode: boo
                 of_img_scale=config.of_img_scale, of_window_size=config.of_window_size, of_max_levels=config.of_max_levels, use_kalman=config.use_kalman,
                 kf_track_features=config.kf_track_features, kf_init_frame_count=config.kf_init_frame_count, kf_node_indices=config.kf_node_indices,
                 kf_reset_gap_size=config.kf_reset_gap_size, tracking_target_instance_count=config.tracking_target_instance_count,
-                tracking_pre_cull_to_target=config.tracking_pre_cull_to_target, tracking_pre_cull_iou_threshold=config.tracking_pre_cull_iou_threshold)
+                tracking_pre_cull_to_target=config.tracking_pre_cull_to_target, tracking_pre_cull_iou_threshold=config.tracking_pre_cull_iou_threshold,
+                allow_flow=config.allow_flow)
 
 
 def build_tracker(config: TrackerConfig, outputs_list: Sequence) -> Tracker:
@@ -105,12 +108,24 @@ def build_tracker(config: TrackerConfig, outputs_list: Sequence) -> Tracker:
     return Tracker.from_config(**resolve_config(config, None if kp is None else int(kp.shape[2]), is_mask_mode(outputs_list)))
 
 
-def apply_tracking(outputs_list: Sequence, config: TrackerConfig, use_tables: bool = True) -> List:
+def apply_tracking(outputs_list: Sequence, config: TrackerConfig, use_tables: bool = True, frames=None) -> List:
     """Track every frame of ``outputs_list`` (one ``Outputs`` per batch) with a fresh ``Tracker``: batches in (video, first frame) order, frames inside a batch
     in ``frame_indices`` order.  Returns the tracked ``Outputs`` in the order given; they share one ``track_objects`` dict, so that ``to_instances`` /
-    ``to_labels`` hand out ONE ``sio.Track`` per id across the batches."""
+    ``to_labels`` hand out ONE ``sio.Track`` per id across the batches.  ``frames``: with ``use_flow`` the ORIGINAL frames of the whole call, ``(N, H, W)``,
+    ``(N, H, W, 1)`` or ``(N, 1, H, W)``, indexed by each batch's ``frame_indices`` (host or device; a batch's frames are uploaded once)."""
     outputs_list = list(outputs_list)
     tracker = build_tracker(config, outputs_list)
+    if tracker.use_flow and frames is None:
+        raise ValueError("use_flow=True needs the frames: apply_tracking(outputs, config, frames=...)")
+
+    def images_of(o):
+        if not tracker.use_flow:
+            return None
+        if o.frame_indices is None:
+            if len(outputs_list) != 1:
+                raise ValueError("use_flow: Outputs.frame_indices is needed to find a batch's frames")
+            return frames
+        return [frames[int(i)] for i in o.frame_indices]
 
     def key(i):
         o = outputs_list[i]
@@ -121,5 +136,5 @@ def apply_tracking(outputs_list: Sequence, config: TrackerConfig, use_tables: bo
     shared: dict = {}
     out: List = [None] * len(outputs_list)
     for i in sorted(range(len(outputs_list)), key=key):
-        out[i] = replace(tracker.track_outputs(outputs_list[i], use_tables=use_tables), track_objects=shared)
+        out[i] = replace(tracker.track_outputs(outputs_list[i], images=images_of(outputs_list[i]), use_tables=use_tables), track_objects=shared)
     return out

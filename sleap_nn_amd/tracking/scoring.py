@@ -226,3 +226,28 @@ def mask_pair_counts(labels, hist, n_hist: int, row_weight, col_weight, P: int, 
         L_.check(L_.lib().ph_track_mask_pairs(p(labels), labels.element_size(), B, h, w, p(hist), L, int(n_hist), p(rw), p(cw), int(image_pixels), P, p(inter), p(area),
                                               L_.current_stream_ptr()))
     return rec, inter, area
+
+
+def pose_pair_scores_shifted(cur: np.ndarray, hist: np.ndarray, counts_cur: np.ndarray, counts_hist: np.ndarray, method: str, oks_stddev: float = 0.025) -> np.ndarray:
+    """``ph_track_pose_scores_shifted``: ``cur`` float64 (B, I, N, 2) features of the batch's frames; ``hist`` (B, L, I, N, 2): per current frame b and group g (a
+    lag, or a reference frame) the features of that group's candidates AS SEEN FROM frame b (the flow-shift tracker moves a past instance onto each current frame);
+    ``counts_cur`` int32 (B,), ``counts_hist`` int32 (B, L).  Returns float64 (B, L, I, I): ``[b][g][i][j]`` = the score of instance i of frame b against candidate
+    j of group g, NaN beyond a count."""
+    from sleap_nn_amd import _lib as L_
+
+    cur = np.ascontiguousarray(cur, dtype=np.float64)
+    hist = np.ascontiguousarray(hist, dtype=np.float64)
+    B, I, N = cur.shape[0], cur.shape[1], cur.shape[2]
+    if hist.ndim != 5 or hist.shape[0] != B or hist.shape[2:] != cur.shape[1:]:
+        raise ValueError(f"pose_pair_scores_shifted: cur {cur.shape} and hist {hist.shape} do not fit (B, I, N, 2) / (B, L, I, N, 2)")
+    L = hist.shape[1]
+    counts_cur = np.ascontiguousarray(counts_cur, dtype=np.int32)
+    counts_hist = np.ascontiguousarray(counts_hist, dtype=np.int32)
+    if counts_cur.shape != (B,) or counts_hist.shape != (B, L):
+        raise ValueError(f"pose_pair_scores_shifted: counts of shapes {counts_cur.shape} / {counts_hist.shape}, expected ({B},) / ({B}, {L})")
+    if method not in METHODS:
+        raise ValueError(f"pose_pair_scores_shifted: method must be one of {sorted(METHODS)}, got {method!r}")
+    out = np.empty((B, L, I, I), dtype=np.float64)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    L_.check(L_.lib().ph_track_pose_scores_shifted(p(cur), B, p(hist), L, I, N, p(counts_cur), p(counts_hist), METHODS[method], float(oks_stddev), p(out)))
+    return out

@@ -24,7 +24,18 @@ The reference's quirks decide the ids and are kept: the fixed window's ``current
 queue only starts at the first frame that spawns a track; ``local_queues`` assigns the COLUMN INDEX as the track id; new ids are ``max + 1``; the pre-cull's
 list handling (``cull_frame_instances``) is ported as it is, duplicates and all (an entry that appears twice is tracked twice; the later assignment wins).
 
-Refused (``NotImplementedError`` naming the knob): ``use_flow`` (OpenCV's pyramidal LK), ``use_kalman`` (pykalman's EM), ``features="image"``.
+``use_flow`` (the reference's ``FlowShiftTracker``, ``from_config(use_flow=True, allow_flow=True)``): a candidate's feature is the feature of the past instance's
+keypoints MOVED onto the current frame by pyramidal Lucas-Kanade flow between the two ORIGINAL frames (``image=`` / ``images=``; lost nodes NaN); the support test
+stays on the source instance, and every instance of a queued frame is a candidate of its id (not only the first).  The flow is ``flow.pyr_lk`` -- OURS, a stand-in for
+``cv2.calcOpticalFlowPyrLK`` that has not been compared with OpenCV, hence the opt-in -- on the host, ``ph_flow_pyramid`` / ``ph_flow_track`` (csrc/flow_kernels.hip) on
+the device; a frame's pyramid is built once, not once per pair as in the reference.  The shifted points depend on no assignment, so with the fixed window
+``track_outputs`` computes ALL (frame, lag <= min(window_size, 32), instance) flows of a batch in ONE launch, against the batch itself and the retained frames of the
+last calls, and scores them with ``ph_track_pose_scores_shifted``; ``local_queues`` (a candidate can be arbitrarily old: each queue entry holds its frame's pyramid,
+alive as long as the entry), ``track()`` and a window beyond 32 take one launch per frame with one job per distinct reference frame.  Without a GPU and with host
+frames the same code runs ``pyr_lk``.  DESIGN.md section 4.2g.
+
+Refused (``NotImplementedError`` naming the knob): ``use_flow`` without ``allow_flow``, ``of_img_scale != 1`` (``cv2.resize``), frames with more than one channel
+(``cv2.cvtColor``), ``use_kalman`` (pykalman's EM), ``features="image"``.
 """
 from __future__ import annotations
 
@@ -35,6 +46,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from sleap_nn_amd.tracking import flow as F
 from sleap_nn_amd.tracking import scoring as S
 
 _FEATURES = {"keypoints": S.keypoints_feature, "centroids": S.centroid_feature, "bboxes": S.bbox_feature, "masks": S.mask_feature}
@@ -48,15 +60,40 @@ class _Entry:
     """One instance of one call: ``src`` (keypoints or the mask entry), its feature, its support (non-NaN nodes, or mask area in image pixels), where the pair
     tables hold it (``call``, ``slot``), its row in the caller's input (``index``) and its detection score (the pre-cull sorts by it)."""
 
-    __slots__ = ("src", "feature", "support", "call", "slot", "index", "score", "track_id", "tracking_score")
+    __slots__ = ("src", "feature", "support", "call", "slot", "index", "score", "track_id", "tracking_score", "image", "frame_idx")
 
-    def __init__(self, src, feature, support, call, slot, index, score):
+    def __init__(self, src, feature, support, call, slot, index, score, image=None, frame_idx=None):
         self.src, self.feature, self.support, self.call, self.slot, self.index, self.score = src, feature, support, call, slot, index, score
         self.track_id: Optional[int] = None
         self.tracking_score: Optional[float] = None
+        self.image, self.frame_idx = image, frame_idx  # the flow tracker: the instance's frame (a ``_FlowFrame``, kept alive by this reference) and its index
 
     def again(self) -> "_Entry":
-        return _Entry(self.src, self.feature, self.support, self.call, self.slot, self.index, self.score)
+        return _Entry(self.src, self.feature, self.support, self.call, self.slot, self.index, self.score, self.image, self.frame_idx)
+
+
+class _FlowFrame:
+    """A frame as the flow reads it: the uint8 image on the host with its pyramid (built on first use), or the device pyramid (``levels``, level 0 first)."""
+
+    __slots__ = ("host", "levels", "_pyramid")
+
+    def __init__(self, host=None, levels=None):
+        self.host, self.levels, self._pyramid = host, levels, None
+
+    def pyramid(self, win: int, max_level: int):
+        if self._pyramid is None:
+            self._pyramid = F.build_pyramid(self.host, win, max_level)
+        return self._pyramid
+
+
+class _FlowScores:
+    """Scores of one frame's instances against flow-shifted candidates the batch table does not hold: ``rows[id(past)][cur.slot]``."""
+
+    def __init__(self):
+        self.rows: Dict[int, np.ndarray] = {}
+
+    def lookup(self, cur: _Entry, past: _Entry) -> float:
+        return float(self.rows[id(past)][cur.slot])
 
 
 class _Frame:
@@ -184,6 +221,14 @@ class FixedWindowCandidates:
                 out.append(fr.entries[fr.track_ids.index(track_id)])
         return out
 
+    def flow_candidates(self) -> Dict[Any, List[_Entry]]:
+        """The flow tracker's candidates per track id (tracker.py:770-805): EVERY instance of every queued frame under its id, not only the first of a frame."""
+        out: Dict[Any, List[_Entry]] = defaultdict(list)
+        for fr in self.tracker_queue:
+            for i, e in enumerate(fr.entries):
+                out[fr.track_ids[i]].append(e)
+        return out
+
     def add_new_tracks(self, cur: _Frame, add_to_queue: bool = True) -> _Frame:
         new = False
         for i, e in enumerate(cur.entries):
@@ -220,6 +265,19 @@ class LocalQueueCandidates:
 
     def candidates_of(self, track_id) -> List[_Entry]:
         return list(self.tracker_queue[track_id])
+
+    def flow_candidates(self) -> Dict[Any, List[_Entry]]:
+        """The flow tracker's candidates per track id in the reference's order (tracker.py:731-768): the queues' instances grouped by frame index, groups in
+        the order the queues name them, each instance under its track id."""
+        groups: Dict[Any, List[_Entry]] = {}
+        for _tid, q in self.tracker_queue.items():
+            for e in q:
+                groups.setdefault(e.frame_idx, []).append(e)
+        out: Dict[Any, List[_Entry]] = defaultdict(list)
+        for lst in groups.values():
+            for e in lst:
+                out[e.track_id].append(e)
+        return out
 
     def _new_track_id(self) -> Optional[int]:
         if not self.current_tracks:
@@ -271,7 +329,8 @@ class _Table:
 class Tracker:
     def __init__(self, candidate, min_match_points: int = 0, features: str = "keypoints", scoring_method: str = "oks", scoring_reduction: str = "mean",
                  track_matching_method: str = "hungarian", robust_best_instance: float = 1.0, oks_stddev: float = 0.025, is_local_queue: bool = False,
-                 tracking_target_instance_count: Optional[int] = None, tracking_pre_cull_to_target: int = 0, tracking_pre_cull_iou_threshold: float = 0) -> None:
+                 tracking_target_instance_count: Optional[int] = None, tracking_pre_cull_to_target: int = 0, tracking_pre_cull_iou_threshold: float = 0,
+                 use_flow: bool = False, of_window_size: int = 21, of_max_levels: int = 3) -> None:
         self.candidate = candidate
         self.min_match_points = min_match_points
         self.features, self.scoring_method, self.scoring_reduction = features, scoring_method, scoring_reduction
@@ -280,7 +339,11 @@ class Tracker:
         self.tracking_target_instance_count = tracking_target_instance_count
         self.tracking_pre_cull_to_target = tracking_pre_cull_to_target
         self.tracking_pre_cull_iou_threshold = tracking_pre_cull_iou_threshold
-        self.use_flow = False
+        self.use_flow, self.of_window_size, self.of_max_levels = bool(use_flow), int(of_window_size), int(of_max_levels)
+        self.flow_device: Optional[bool] = None  # where the flow runs: None = the device when the frames are there or a GPU is present, False = pyr_lk on the host
+        self.flow_launches = 0  # ph_flow_track launches / pyr_lk calls so far
+        self.flow_cpu_calls = 0
+        self._flow_ring: Optional[deque] = None  # (frame, points (I, N, 2) float32) of the last calls, newest last: what the batch's flow jobs reach back to
         self.n_calls = 0  # calls of track so far: a past instance's lag is counted in calls
         self.last_scores: Optional[np.ndarray] = None  # get_scores' matrix of the last call (None when the queue was empty)
         self.table_hits = 0  # pair scores read from a table / computed pair by pair
@@ -298,9 +361,10 @@ class Tracker:
                     kf_init_frame_count: int = 10, kf_node_indices: Optional[List[int]] = None, kf_reset_gap_size: int = 5, kf_prediction_blend: float = 0.5,
                     kf_gate_step_mult: float = 8.0, kf_min_gate_px: float = 40.0, kf_velocity_cap_mult: float = 3.0, kf_min_velocity_cap_px: float = 15.0,
                     tracking_target_instance_count: Optional[int] = None, tracking_pre_cull_to_target: int = 0,
-                    tracking_pre_cull_iou_threshold: float = 0) -> "Tracker":
+                    tracking_pre_cull_iou_threshold: float = 0, allow_flow: bool = False) -> "Tracker":
         """The reference's signature and defaults (tracker.py:128-158).  ``max_tracks`` with ``fixed_window`` switches to ``local_queues`` (the only maker that
-        honours the cap); ``oks_stddev=None`` resolves to 0.025."""
+        honours the cap); ``oks_stddev=None`` resolves to 0.025.  ``allow_flow`` is OURS, not the reference's: ``use_flow=True`` builds the flow-shift tracker only
+        with it, because its optical flow is this project's ``pyr_lk`` / ``ph_flow_track`` and has not been compared with OpenCV's numbers."""
         if max_tracks is not None and candidates_method == "fixed_window":
             candidates_method = "local_queues"
         if candidates_method == "fixed_window":
@@ -311,8 +375,16 @@ class Tracker:
             raise ValueError(f"{candidates_method} is not a valid method. Please choose one of [`fixed_window`, `local_queues`]")
         if use_kalman and use_flow:
             raise ValueError("`use_kalman` and `use_flow` are mutually exclusive; choose one tracker (Kalman tracking does not use optical flow).")
+        if use_flow and not allow_flow:
+            raise NotImplementedError("use_flow=True runs this project's own pyramidal Lucas-Kanade flow (sleap_nn_amd/tracking/flow.py), which has not been compared "
+                                      "with OpenCV's: pass allow_flow=True to use it; see sleap_nn_amd/tracking/tracker.py")
         if use_flow:
-            raise NotImplementedError("use_flow=True is not built on the MI355X path (OpenCV's pyramidal Lucas-Kanade flow): see sleap_nn_amd/tracking/tracker.py")
+            if of_img_scale != 1:
+                raise NotImplementedError("of_img_scale != 1 is not built on the MI355X path (cv2.resize of the frames): see sleap_nn_amd/tracking/tracker.py")
+            if features == "masks" or scoring_method == "mask_iou":
+                raise ValueError("use_flow moves keypoints: features='masks' / scoring_method='mask_iou' cannot be combined with it")
+            if not (F.MIN_WIN <= int(of_window_size) <= F.MAX_WIN) or not (0 <= int(of_max_levels) < F.MAX_LEVELS):
+                raise ValueError(f"of_window_size must lie in [{F.MIN_WIN}, {F.MAX_WIN}] and of_max_levels in [0, {F.MAX_LEVELS - 1}], got {of_window_size} and {of_max_levels}")
         if use_kalman:
             raise NotImplementedError("use_kalman=True is not built on the MI355X path (pykalman's EM fit): see sleap_nn_amd/tracking/tracker.py")
         if features == "image":
@@ -322,7 +394,7 @@ class Tracker:
         return cls(candidate=candidate, min_match_points=min_match_points, features=features, scoring_method=scoring_method, scoring_reduction=scoring_reduction,
                    robust_best_instance=robust_best_instance, oks_stddev=oks_stddev, track_matching_method=track_matching_method, is_local_queue=local,
                    tracking_target_instance_count=tracking_target_instance_count, tracking_pre_cull_to_target=tracking_pre_cull_to_target,
-                   tracking_pre_cull_iou_threshold=tracking_pre_cull_iou_threshold)
+                   tracking_pre_cull_iou_threshold=tracking_pre_cull_iou_threshold, use_flow=use_flow, of_window_size=of_window_size, of_max_levels=of_max_levels)
 
     # -- one pair ---------------------------------------------------------------------------------------------------
     def _check(self) -> None:
@@ -348,14 +420,159 @@ class Tracker:
             return S.cosine_sim(a, b)
         return S.neg_euclidean(a, b)
 
-    def _score(self, cur: _Entry, past: _Entry, table: Optional[_Table]) -> float:
-        if table is not None:
-            k = cur.call - past.call
-            if 1 <= k <= len(table.valid) and table.valid[k - 1] and cur.slot >= 0 and past.slot >= 0:
-                self.table_hits += 1
-                return float(table.scores[k - 1, cur.slot, past.slot])
+    @staticmethod
+    def _in_table(call: int, slot: int, past: _Entry, table: Optional[_Table]) -> bool:
+        if table is None:
+            return False
+        k = call - past.call
+        return bool(1 <= k <= len(table.valid) and table.valid[k - 1] and slot >= 0 and past.slot >= 0)
+
+    def _score(self, cur: _Entry, past: _Entry, table: Optional[_Table], shifted: Optional[_FlowScores] = None) -> float:
+        if self._in_table(cur.call, cur.slot, past, table):
+            self.table_hits += 1
+            return float(table.scores[cur.call - past.call - 1, cur.slot, past.slot])
         self.pair_calls += 1
+        if self.use_flow:  # (the candidate's feature is its SHIFTED pose: never the pair function on the past instance itself)
+            return shifted.lookup(cur, past)
         return self.pair_score(self._feature(cur), self._feature(past))
+
+    # -- optical flow (tracker.py:680-807) --------------------------------------------------------------------------
+    def _flow_frames(self, images, n: int) -> List[_FlowFrame]:
+        """``n`` frames (a tensor / array with a leading frame axis, or a list of frames) as ``_FlowFrame``s: gray uint8, on the device -- uploaded in one copy,
+        the pyramids of all in one ``ph_flow_pyramid`` call -- when the frames are device tensors or a GPU is present, on the host otherwise."""
+        import torch
+
+        if images is None:
+            raise ValueError("use_flow=True needs the frames: pass image= to track() / images= to track_outputs() (the ORIGINAL frames, the space of the keypoints)")
+        if len(images) != n:
+            raise ValueError(f"use_flow: {len(images)} frames for {n} calls")
+        if n == 0:
+            return []
+        grays = [F.as_gray_u8(im) for im in images]
+        batch = torch.stack(grays)
+        if (batch.is_cuda or torch.cuda.is_available()) if self.flow_device is None else self.flow_device:
+            batch = batch.cuda() if not batch.is_cuda else batch
+            return [_FlowFrame(levels=lv) for lv in F.pyramid_device(batch, self.of_window_size, self.of_max_levels)]
+        host = batch.cpu().numpy()
+        return [_FlowFrame(host=host[i]) for i in range(n)]
+
+    def _run_flow(self, jobs: List[Tuple[_FlowFrame, _FlowFrame, np.ndarray]]) -> List[np.ndarray]:
+        """``(reference frame, current frame, points (P, 2) float32)`` per job -> the shifted points per job, float32 with NaN for lost points.  All jobs of a
+        call are ONE ``ph_flow_track`` launch on the device; on the host one ``pyr_lk`` per job, the pyramids built once per frame."""
+        if not jobs:
+            return []
+        win, lv = self.of_window_size, self.of_max_levels
+        if jobs[0][1].levels is not None:
+            self.flow_launches += 1
+            return [s for s, _st in F.track_device([(r.levels, c.levels, p) for r, c, p in jobs], win, lv)]
+        out = []
+        for r, c, p in jobs:
+            self.flow_cpu_calls += 1
+            out.append(F.pyr_lk(None, None, p, win, lv, ref_pyramid=r.pyramid(win, lv), new_pyramid=c.pyramid(win, lv))[0])
+        return out
+
+    def _native_block(self, feats: list) -> Optional[np.ndarray]:
+        """Features as ``(n, D / 2, 2)`` float64 for the native pair scores; None for shapes the NumPy functions refuse (they are left to refuse them)."""
+        if self.scoring_method not in S.METHODS or not feats:
+            return None
+        first = np.asarray(feats[0])
+        D = first.size
+        if D == 0 or D % 2 or (self.scoring_method == "iou" and D != 4) or (self.scoring_method == "cosine_sim" and first.ndim != 1):
+            return None
+        return np.stack([np.asarray(f, dtype=np.float64).reshape(D // 2, 2) for f in feats])
+
+    def _shifted_scores(self, cur_feats: list, groups: List[list]) -> List[np.ndarray]:
+        """Scores of one frame's features against groups of shifted candidate features: per group ``(len(cur_feats), len(group))``, ``ph_track_pose_scores_shifted``
+        in chunks of 32 groups."""
+        cur = self._native_block(cur_feats)
+        blocks = [self._native_block(g) for g in groups]
+        if cur is None or any(b is None or b.shape[1:] != cur.shape[1:] for b in blocks):
+            return [np.array([[self.pair_score(a, p) for p in g] for a in cur_feats], dtype=np.float64).reshape(len(cur_feats), len(g)) for g in groups]
+        I = max(len(cur), max(len(b) for b in blocks))
+        cur_t = np.full((1, I) + cur.shape[1:], np.nan)
+        cur_t[0, : len(cur)] = cur
+        out = []
+        for s in range(0, len(blocks), S.MAX_TABLE_LAGS):
+            part = blocks[s : s + S.MAX_TABLE_LAGS]
+            hist = np.full((1, len(part), I) + cur.shape[1:], np.nan)
+            for g, b in enumerate(part):
+                hist[0, g, : len(b)] = b
+            sc = S.pose_pair_scores_shifted(cur_t, hist, np.array([len(cur)], np.int32), np.array([[len(b) for b in part]], np.int32), self.scoring_method, self.oks_stddev)
+            out.extend(sc[0, g, : len(cur), : len(b)] for g, b in enumerate(part))
+        return out
+
+    def _flow_scores(self, cur_entries: List[_Entry], pasts: List[_Entry], image: _FlowFrame) -> Optional[_FlowScores]:
+        """One frame against the candidates ``pasts`` no batch table holds: the candidates grouped by their frame (``local_queues``: by frame index, the first
+        one's image, as the reference groups them), one flow job per distinct frame in one launch, the feature function on the shifted points, native scores."""
+        if not pasts or not cur_entries:
+            return None
+        groups: Dict[Any, List[_Entry]] = {}
+        for p in pasts:
+            groups.setdefault(p.frame_idx if self.is_local_queue else id(p.image), []).append(p)
+        lists = list(groups.values())
+        jobs = [(g[0].image, image, np.concatenate([np.asarray(p.src, dtype=np.float32) for p in g]).reshape(-1, 2)) for g in lists]
+        fn = _FEATURES[self.features]
+        feats = []
+        for g, sh in zip(lists, self._run_flow(jobs)):
+            n_nodes = len(g[0].src)
+            feats.append([fn(sh[i * n_nodes : (i + 1) * n_nodes]) for i in range(len(g))])
+        by_slot = sorted(cur_entries, key=lambda e: e.slot)
+        assert [e.slot for e in by_slot] == list(range(len(by_slot)))
+        res = _FlowScores()
+        for g, sc in zip(lists, self._shifted_scores([e.feature for e in by_slot], feats)):
+            for j, p in enumerate(g):
+                res.rows[id(p)] = sc[:, j]
+        return res
+
+    def _flow_tables(self, frames: List[List[_Entry]], images: List[_FlowFrame], use_native: bool) -> List[Optional[_Table]]:
+        """The fixed window's batch: the flows of EVERY (frame b, lag k <= L, instance of the frame k calls earlier) -- the batch against itself and the retained
+        frames of the last L calls -- as ONE ``ph_flow_track`` launch before the frame-by-frame matching starts (a shifted point depends on no assignment), the
+        feature function on the shifted points, ``ph_track_pose_scores_shifted``.  Flows of instances that end up outside the queue are computed and ignored."""
+        B, L = len(frames), self.table_lags
+        ok = use_native and not self.is_local_queue and self.candidate.window_size <= S.MAX_TABLE_LAGS and self.scoring_method in S.METHODS and any(frames)
+        ring = self._flow_ring if self._flow_ring is not None and self._flow_ring.maxlen == L else deque(maxlen=L)
+        if ok:
+            n_nodes = {len(e.src) for fr in frames for e in fr} | {pts.shape[1] for _im, pts in ring if len(pts)}
+            ok = len(n_nodes) == 1
+        if not ok:
+            self._flow_ring = None
+            return [None] * B
+        N = n_nodes.pop()
+        pts_of = [np.stack([np.asarray(e.src, dtype=np.float32) for e in fr]) if fr else np.zeros((0, N, 2), np.float32) for fr in frames]
+        for fr in frames:
+            for s, e in enumerate(fr):
+                e.slot = s
+        past_of = lambda b, k: (images[b - k], pts_of[b - k]) if b >= k else (ring[len(ring) - (k - b)] if k - b <= len(ring) else None)
+        jobs, where = [], []
+        for b in range(B):
+            for k in range(1, L + 1):
+                past = past_of(b, k)
+                if past is not None and len(past[1]) and frames[b]:
+                    jobs.append((past[0], images[b], past[1].reshape(-1, 2)))
+                    where.append((b, k))
+        fn = _FEATURES[self.features]
+        cur_feats = [[e.feature for e in fr] for fr in frames]
+        probe = self._native_block([f for fr in cur_feats for f in fr])
+        if probe is None:
+            self._flow_ring = None
+            return [None] * B
+        I = max(max(len(fr) for fr in frames), max([len(pts) for _im, pts in ring], default=0))
+        cur = np.full((B, I) + probe.shape[1:], np.nan)
+        hist = np.full((B, L, I) + probe.shape[1:], np.nan)
+        counts_hist = np.zeros((B, L), np.int32)
+        for b, fr in enumerate(cur_feats):
+            if fr:
+                cur[b, : len(fr)] = self._native_block(fr)
+        for (b, k), sh in zip(where, self._run_flow(jobs)):
+            sh = sh.reshape(-1, N, 2)
+            hist[b, k - 1, : len(sh)] = self._native_block([fn(p) for p in sh])
+            counts_hist[b, k - 1] = len(sh)
+        sc = S.pose_pair_scores_shifted(cur, hist, np.array([len(fr) for fr in frames], np.int32), counts_hist, self.scoring_method, self.oks_stddev)
+        tables = [_Table(sc[b], np.array([past_of(b, k) is not None for k in range(1, L + 1)])) for b in range(B)]
+        for b in range(B):
+            ring.append((images[b], pts_of[b]))
+        self._flow_ring = ring
+        return tables
 
     @staticmethod
     def _feature(e: _Entry):
@@ -398,8 +615,14 @@ class Tracker:
                 return np.nanquantile(vals, q=self.robust_best_instance)
             return np.nanmax(vals)
 
-    def _track_entries(self, entries: List[_Entry], n: int, frame_idx, table: Optional[_Table] = None) -> Tuple[np.ndarray, np.ndarray]:
+    def _track_entries(self, entries: List[_Entry], n: int, frame_idx, table: Optional[_Table] = None, image: Optional[_FlowFrame] = None) -> Tuple[np.ndarray, np.ndarray]:
         masks = bool(entries) and isinstance(entries[0].src, dict)
+        all_entries = entries
+        if self.use_flow:
+            if masks:
+                raise ValueError("use_flow moves keypoints: it cannot track segmentation masks")
+            for e in entries:
+                e.image, e.frame_idx = image, frame_idx
         if not masks and self.tracking_target_instance_count and self.tracking_pre_cull_to_target:
             entries = cull_frame_instances(entries, self.tracking_target_instance_count, self.tracking_pre_cull_iou_threshold)
         cand = self.candidate
@@ -407,11 +630,18 @@ class Tracker:
         self.last_scores = None
         if cand.tracker_queue:
             tracks = cand.current_tracks
-            past = {t: cand.candidates_of(t) for t in tracks}
+            shifted = None
+            if self.use_flow:  # the candidates moved onto this frame; the support test stays on the SOURCE instance
+                moved = cand.flow_candidates()
+                past = {t: moved.get(t, []) for t in tracks}
+                slot = all_entries[0].slot if all_entries else -1
+                shifted = self._flow_scores(all_entries, [p for t in tracks for p in past[t] if not self._in_table(self.n_calls, slot, p, table)], image)
+            else:
+                past = {t: cand.candidates_of(t) for t in tracks}
             scores = np.zeros((len(entries), len(tracks)))
             for i, e in enumerate(entries):
                 for j, t in enumerate(tracks):
-                    scores[i][j] = self._reduce([self._score(e, p, table) for p in past[t] if p.support > self.min_match_points])
+                    scores[i][j] = self._reduce([self._score(e, p, table, shifted) for p in past[t] if p.support > self.min_match_points])
             self.last_scores = scores
             cost = -scores
             cost[np.isnan(cost)] = np.inf
@@ -426,11 +656,14 @@ class Tracker:
         self.n_calls += 1
         return ids, tsc
 
-    def track(self, instances, frame_idx, instance_scores=None) -> Tuple[np.ndarray, np.ndarray]:
+    def track(self, instances, frame_idx, instance_scores=None, image=None) -> Tuple[np.ndarray, np.ndarray]:
         """One frame, every score in NumPy.  ``instances``: ``(I, N, 2)`` keypoints (NaN = missing) or a list of ``pred_masks`` entries; ``instance_scores``
-        ``(I,)``: the detection scores the pre-cull sorts by (a mask entry's ``"score"`` by default)."""
-        ids, tsc = self._track_entries(self._entries(instances, instance_scores), len(instances), frame_idx)
-        self._pose_hist, self._pose_n_hist, self._mask_ring = None, 0, None  # the tables' history does not hold this call: start it again
+        ``(I,)``: the detection scores the pre-cull sorts by (a mask entry's ``"score"`` by default).  ``image``: the ORIGINAL frame (the reference's ``lf.image``,
+        the space of the keypoints), needed with ``use_flow`` and ignored without: ``(H, W)``, ``(H, W, 1)`` or ``(1, H, W)``, uint8 or float, host or device; the
+        flows of the frame are one launch with one job per queued frame, scored by ``ph_track_pose_scores_shifted``."""
+        handle = self._flow_frames([image] if image is not None else None, 1)[0] if self.use_flow else None
+        ids, tsc = self._track_entries(self._entries(instances, instance_scores), len(instances), frame_idx, image=handle)
+        self._pose_hist, self._pose_n_hist, self._mask_ring, self._flow_ring = None, 0, None, None  # the tables' history does not hold this call: start it again
         return ids, tsc
 
     # -- a batch ----------------------------------------------------------------------------------------------------
@@ -520,10 +753,11 @@ class Tracker:
         self._mask_ring = ring
         return tables
 
-    def track_outputs(self, outputs, use_tables: bool = True):
+    def track_outputs(self, outputs, images=None, use_tables: bool = True):
         """Track a whole batch: frames in ``frame_indices`` order, the pair tables computed first (``use_tables=False``: every score pair by pair on the host, the
         same numbers).  Returns a copy of ``outputs`` with ``instance_track_ids`` (B, I) int64 and ``instance_tracking_scores`` filled for poses; for masks
-        ``"track_id"`` / ``"tracking_score"`` are written into each ``pred_masks`` entry (new dicts, the inputs stay as they are)."""
+        ``"track_id"`` / ``"tracking_score"`` are written into each ``pred_masks`` entry (new dicts, the inputs stay as they are).  ``images``: with ``use_flow`` the
+        batch's ORIGINAL frames, ``(B, H, W)``, ``(B, H, W, 1)`` or ``(B, 1, H, W)``, in the order of the batch (see ``track``); host frames are uploaded once."""
         import torch
 
         fi = outputs.frame_indices
@@ -563,10 +797,17 @@ class Tracker:
             frames.append(ents)
             rows_of.append(rows)
         self.n_calls = call0
-        tables = self._pose_tables(frames, use_tables)
+        handles: List[Optional[_FlowFrame]] = [None] * B
+        if self.use_flow:
+            if images is not None and len(images) != B:
+                raise ValueError(f"use_flow: {len(images)} frames for a batch of {B}")
+            handles = self._flow_frames(None if images is None else [images[b] for b in order], B)
+            tables = self._flow_tables(frames, handles, use_tables)
+        else:
+            tables = self._pose_tables(frames, use_tables)
         ids_out = np.full(kp.shape[:2], -1, dtype=np.int64)
         tsc_out = np.full(kp.shape[:2], np.nan, dtype=np.float64)
         for k, b in enumerate(order):
-            ids, tsc = self._track_entries(frames[k], len(rows_of[k]), fidx(b), tables[k])
+            ids, tsc = self._track_entries(frames[k], len(rows_of[k]), fidx(b), tables[k], handles[k])
             ids_out[b, rows_of[k]], tsc_out[b, rows_of[k]] = ids, tsc
         return replace(outputs, instance_track_ids=torch.from_numpy(ids_out), instance_tracking_scores=torch.from_numpy(tsc_out))
