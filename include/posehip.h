@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 122
+#define PH_VERSION 123
 
 /* error codes */
 #define PH_OK 0
@@ -109,13 +109,18 @@ enum ph_op_kind {
   PH_OP_PATCH_MERGE = 16, /* (B, H, W, C) -> (B, ceil(H/2), ceil(W/2), 4C): concat of x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2] (zeros past an odd
                              edge) + LayerNorm over the 4C channels (weight / bias = its affine), one launch; the bias-less PH_OP_LINEAR `reduction` follows.
                              Backward: the gather is rebuilt in scratch, LayerNorm backward over it, scatter to the four phases (the padding receives nothing) */
-  PH_OP_WINDOW_ATTN = 17  /* shifted-window multi-head attention core: src0 = qkv slot (B, H, W, 3C) of the un-padded, un-rolled map (q | k | v, head a owns
+  PH_OP_WINDOW_ATTN = 17, /* shifted-window multi-head attention core: src0 = qkv slot (B, H, W, 3C) of the un-padded, un-rolled map (q | k | v, head a owns
                              channels 32 a .. 32 a + 31 of each), weight = relative_position_bias_table ((2 ksize - 1)^2, heads), bias = qkv.bias (3C; the q, k, v
                              of a padded token), ksize = window side (2..8), cin1 = heads (cout = 32 heads), cmid = nominal shift (an axis whose padded size the
                              window covers is not shifted).  dst (B, H, W, C) = softmax(q k^T / sqrt(32) + bias [- 100 across the shift's bands]) v at each
                              token's own pixel: pad, roll, window partition, reverse and crop are index arithmetic of the one launch.
                              Backward (window_attn_bwd_kernel): S and P are recomputed from the qkv slot; gradients of the slot, of the table and -- through the
                              padded tokens, whose q, k, v are qkv.bias -- of qkv.bias */
+  /* ConvNeXtV2 encoder (HuggingFace ConvNextV2Backbone behind the reference's PretrainedBackbone, architectures/pretrained.py).  Inference only, exact fp32. */
+  PH_OP_GRN = 18          /* Global Response Normalization over a (B, H, W, C) slot (cin0 = cout = C): G[b,c] = sqrt(sum_hw x^2), N[b,c] = G[b,c] / (mean_c G[b,:] + 1e-6),
+                             dst = weight[c] * (x * N[b,c]) + bias[c] + x; weight / bias (1,1,1,C).  Two launches (convnextv2_kernels.hip): grn_reduce_kernel writes
+                             per-(sample, pixel slice, channel) sums of squares into the scratch region -- fixed slices, no atomics, so two forwards are bit-identical --
+                             and grn_apply_kernel adds the slices in order, takes the channel mean over the C true channels and applies; pad channels come out zero */
 };
 
 #define PH_FLAG_RELU 1
@@ -127,7 +132,9 @@ enum ph_op_kind {
 #define PH_FLAG_NO_TRAIN 64 /* PH_OP_HEAD: a head of the segmentation model types, which neither MSE nor cross entropy trains; the forward ignores it,
                                ph_model_backward refuses the program unless ph_model_set_head_loss chose the head's loss on this handle */
 #define PH_FLAG_LN_EPS_1EM5 128 /* PH_OP_LAYERNORM / PH_OP_PATCH_MERGE: eps 1e-5 (nn.LayerNorm's default: the Swin norms) instead of 1e-6 */
-#define PH_FLAG_RESIDUAL 256    /* PH_OP_LINEAR: dst = acc + bias + src1 (a residual add without a layer scale: Swin's attn.proj and mlp.3) */
+#define PH_FLAG_RESIDUAL 256    /* PH_OP_LINEAR: dst = acc + bias + src1 (a residual add without a layer scale: Swin's attn.proj and mlp.3; ConvNeXtV2's pwconv2) */
+#define PH_FLAG_PAD0_NORM 512   /* PH_OP_PATCH_STEM: padding 0 instead of 1 and the input is (x / 255 - mean[ci]) / std[ci] with the handle's input statistics
+                                   (ph_model_set_input_norm; 0 and 1 until set): HuggingFace's ConvNextV2Embeddings behind PretrainedBackbone._normalize */
 
 typedef struct ph_op_desc {
   int32_t kind;      /* enum ph_op_kind                                              */
@@ -226,6 +233,9 @@ int ph_model_set_head_loss(ph_model* m, int32_t out_index, int32_t kind, const f
  * s[i][b] * G(dst) to its weight, bias and data gradients and the plain G(dst) to src1.  A forward or backward whose batch differs from `batch`, or a forward
  * in a non-fp32 format, is refused while scales are set.  With none set the launch sequence is what it is without this call. */
 int ph_model_set_branch_scales(ph_model* m, const float* scales_dev, int32_t n_branches, int32_t batch);
+/* Per-channel input statistics of a PH_OP_PATCH_STEM with PH_FLAG_PAD0_NORM (host arrays of n <= 4 floats, copied; std must be non-zero).  They are the
+ * checkpoint's image_mean / image_std buffers, not parameters: nothing in the parameter arena maps onto them. */
+int ph_model_set_input_norm(ph_model* m, const float* mean, const float* std, int32_t n);
 /* Byte offset, in the gradient workspace of a (batch, height, width) step, of the (3C) vector that holds the padded tokens' share of a qkv.bias gradient
  * (sum of dq | dk | dv over the padded tokens of the windows) between the attention op's step and the qkv Linear's; after ph_model_backward it holds that
  * of the program's FIRST attention op, *n_floats = its 3C.  For tests and tools. */
@@ -400,6 +410,9 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_WINDOW_ATTN_F16 22 /* window_attn_f16_kernel: the same plan on v_mfma_f32_32x32x16_f16, fp16 q / k / v / p, fp32 logits and softmax statistics ("swint_f16") */
 #define PH_KV_SWIN_F16_MERGE_LN 23 /* patch_merge_ln_f16_kernel: four-phase gather + LayerNorm(4C) on fp16 activations, fp32 moments ("swint_f16") */
 #define PH_KV_WINDOW_ATTN_BWD 24 /* window_attn_bwd_kernel (ph_model_last_backward_kernels): backward of the attention core, one wave per (window, head), fixed-order slices */
+#define PH_KV_GRN 25 /* grn_reduce_kernel + grn_apply_kernel: Global Response Normalization, fixed-slice sums of squares then the apply pass */
+#define PH_KV_GRN_FUSED 26 /* grn_finalize_kernel: the fused GRN plan ("grn_fuse"); the sums of squares come from the Linear in front (gemm_mfma_dma_kernel<.., EPI = 2>), the Linear behind runs per sample on weights scaled by grn_scale_weights_kernel */
+#define PH_KV_PATCH_STEM_NORM 27 /* patch_stem_norm_kernel: the padding-0 patch stem with input statistics (PH_FLAG_PAD0_NORM) */
 #define PH_KV_FUSED 11   /* no launch of its own: a 1x1 head computed in the epilogue of the conv that produces its input */
 int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
 /* Per-op times of the LAST ph_model_backward, recorded while profiling is on (ph_model_set_profiling).  op_ms[i]: op i's step of the reverse sweep; op_ms_first[i]: its part up to the

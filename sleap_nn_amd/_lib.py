@@ -17,8 +17,10 @@ PH_E_INVALID, PH_E_HIP, PH_E_CAPACITY, PH_E_INFEASIBLE, PH_E_WORKSPACE = -1, -2,
 OP_INPUT_CONV, OP_CONV, OP_POOL, OP_UPSAMPLE, OP_CONVT, OP_HEAD, OP_STEM = 1, 2, 3, 4, 5, 6, 7
 OP_PATCH_STEM, OP_DWCONV, OP_LAYERNORM, OP_LINEAR, OP_PATCH_CONV, OP_GELU, OP_SCALE_ADD, OP_GLOBAL_MAXPOOL = 8, 9, 10, 11, 12, 13, 14, 15
 OP_PATCH_MERGE, OP_WINDOW_ATTN = 16, 17  # Swin Transformer encoder (swin_kernels.hip)
+OP_GRN = 18  # ConvNeXtV2's Global Response Normalization (convnextv2_kernels.hip)
 FLAG_RELU, FLAG_SIGMOID, FLAG_GELU, FLAG_SCALE_RESIDUAL, FLAG_SOFTMAX, FLAG_SILU, FLAG_NO_TRAIN = 1, 2, 4, 8, 16, 32, 64
 FLAG_LN_EPS_1EM5, FLAG_RESIDUAL = 128, 256
+FLAG_PAD0_NORM = 512  # PH_OP_PATCH_STEM: padding 0 and (x / 255 - mean) / std with the handle's input statistics (ph_model_set_input_norm)
 LOSS_MSE, LOSS_BCE_DICE, LOSS_MASKED_SMOOTH_L1 = 1, 2, 3  # PH_LOSS_*: ph_model_set_head_loss
 # PH_KV_*: kernel family an op of the last forward ran (ph_model_last_kernels) and the share of its direct-convolution
 # FLOPs that family puts through the matrix cores
@@ -26,6 +28,7 @@ KV_NONE, KV_DIRECT, KV_WINO1D, KV_WINO2D, KV_W16, KV_C16, KV_ROWGEMM, KV_WINO4, 
 SWIN_KV_WINDOW_ATTN = 21  # PH_KV_WINDOW_ATTN (swin_kernels.hip); not named KV_* either, for the reason below
 SWIN_KV_WINDOW_ATTN_BWD = 24  # PH_KV_WINDOW_ATTN_BWD (swin_train_kernels.hip): reported by ph_model_last_backward_kernels
 SWIN_KV_WINDOW_ATTN_F16, SWIN_KV_F16_MERGE_LN = 22, 23  # PH_KV_WINDOW_ATTN_F16 / PH_KV_SWIN_F16_MERGE_LN: the Swin ops on fp16 activations (swin_f16_kernels.hip, handle option swint_f16)
+CNX2_KV_GRN, CNX2_KV_GRN_FUSED, CNX2_KV_PATCH_STEM_NORM = 25, 26, 27  # PH_KV_GRN / PH_KV_GRN_FUSED / PH_KV_PATCH_STEM_NORM (convnextv2_kernels.hip)
 CNX_KV_F16_STEM, CNX_KV_F16_DW, CNX_KV_F16_LN, CNX_KV_F16_GEMM, CNX_KV_F16_ELTWISE = 16, 17, 18, 19, 20  # PH_KV_CNX_F16_*: the ConvNeXt encoder ops on fp16 activations (convnext_f16_kernels.hip); not named KV_*: that prefix lists the families a 3x3 conv can come back with (benchlegs.common.conv_kernel_short_names)
 KV_NAMES = {KV_NONE: "none", KV_DIRECT: "conv3x3_mfma_dma_persist_kernel (direct)", KV_WINO1D: "conv3x3_wino_persist_kernel (Winograd F(2,3) along x)",
             KV_WINO2D: "conv3x3_wino2d_kernel<64> (Winograd F(2x2,3x3))", KV_W16: "conv3x3_w16_kernel (wave-private Winograd F(2x2,3x3), 16x16x4 MFMA)",
@@ -44,8 +47,11 @@ KV_NAMES = {KV_NONE: "none", KV_DIRECT: "conv3x3_mfma_dma_persist_kernel (direct
             SWIN_KV_WINDOW_ATTN: "window_attn_kernel (shifted-window attention, one wave per window and head, v_mfma_f32_32x32x2_f32)",
             SWIN_KV_WINDOW_ATTN_BWD: "window_attn_bwd_kernel (backward of the shifted-window attention core, v_mfma_f32_32x32x2_f32, fixed-order slices)",
             SWIN_KV_WINDOW_ATTN_F16: "window_attn_f16_kernel (shifted-window attention on v_mfma_f32_32x32x16_f16: fp16 q / k / v / p, fp32 logits)",
-            SWIN_KV_F16_MERGE_LN: "patch_merge_ln_f16_kernel (four-phase gather + LayerNorm(4C), fp16 storage, fp32 moments)"}
-KV_MFMA_SHARE = {KV_NONE: 0.0, KV_DIRECT: 1.0, KV_WINO1D: 2.0 / 3.0, KV_WINO2D: 4.0 / 9.0, KV_W16: 4.0 / 9.0, KV_C16: 1.0, KV_ROWGEMM: 1.0, KV_WINO4: 0.25, KV_F16: 1.0, KV_STEM: 4.0 / 9.0, KV_WINO2D_KS: 4.0 / 9.0, KV_FUSED: 0.0, KV_SMALLMAP: 4.0 / 9.0, KV_F16_ROWS: 1.0, KV_F16_BLOCK: 1.0, KV_MLP: 1.0, CNX_KV_F16_STEM: 0.0, CNX_KV_F16_DW: 0.0, CNX_KV_F16_LN: 0.0, CNX_KV_F16_GEMM: 1.0, CNX_KV_F16_ELTWISE: 0.0, SWIN_KV_WINDOW_ATTN: 1.0, SWIN_KV_WINDOW_ATTN_BWD: 1.0, SWIN_KV_WINDOW_ATTN_F16: 1.0, SWIN_KV_F16_MERGE_LN: 0.0}
+            SWIN_KV_F16_MERGE_LN: "patch_merge_ln_f16_kernel (four-phase gather + LayerNorm(4C), fp16 storage, fp32 moments)",
+            CNX2_KV_GRN: "grn_reduce_kernel + grn_apply_kernel (Global Response Normalization: fixed-slice sums of squares, then the apply pass)",
+            CNX2_KV_GRN_FUSED: "grn_finalize_kernel (fused GRN plan: sums of squares from the Linear in front, per-sample scaled weights for the Linear behind)",
+            CNX2_KV_PATCH_STEM_NORM: "patch_stem_norm_kernel (padding-0 patch stem with input statistics)"}
+KV_MFMA_SHARE = {KV_NONE: 0.0, KV_DIRECT: 1.0, KV_WINO1D: 2.0 / 3.0, KV_WINO2D: 4.0 / 9.0, KV_W16: 4.0 / 9.0, KV_C16: 1.0, KV_ROWGEMM: 1.0, KV_WINO4: 0.25, KV_F16: 1.0, KV_STEM: 4.0 / 9.0, KV_WINO2D_KS: 4.0 / 9.0, KV_FUSED: 0.0, KV_SMALLMAP: 4.0 / 9.0, KV_F16_ROWS: 1.0, KV_F16_BLOCK: 1.0, KV_MLP: 1.0, CNX_KV_F16_STEM: 0.0, CNX_KV_F16_DW: 0.0, CNX_KV_F16_LN: 0.0, CNX_KV_F16_GEMM: 1.0, CNX_KV_F16_ELTWISE: 0.0, SWIN_KV_WINDOW_ATTN: 1.0, SWIN_KV_WINDOW_ATTN_BWD: 1.0, SWIN_KV_WINDOW_ATTN_F16: 1.0, SWIN_KV_F16_MERGE_LN: 0.0, CNX2_KV_GRN: 0.0, CNX2_KV_GRN_FUSED: 0.0, CNX2_KV_PATCH_STEM_NORM: 0.0}
 
 
 class OpDesc(C.Structure):
@@ -102,6 +108,7 @@ SIGNATURES = {
                                     _i32, _i32, _f32, _vp, _vp, _vp]),
     "ph_model_set_head_loss": (C.c_int, [_vp, _i32, _i32, C.POINTER(_f32), _i32]),
     "ph_model_set_branch_scales": (C.c_int, [_vp, _vp, _i32, _i32]),
+    "ph_model_set_input_norm": (C.c_int, [_vp, C.POINTER(_f32), C.POINTER(_f32), _i32]),
     "ph_model_backward_pad_vector": (_i64, [_vp, _i32, _i32, _i32, C.POINTER(_i32)]),
     "ph_model_backward_profile_read": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32, C.POINTER(C.c_double)]),
     "ph_model_last_backward_kernels": (C.c_int, [_vp, C.POINTER(_i32), _i32]),

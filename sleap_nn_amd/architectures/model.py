@@ -16,6 +16,7 @@ import torch
 from sleap_nn_amd import _lib as L
 from sleap_nn_amd.architectures.heads import SEGMENTATION_MODEL_TYPES, ClassMapsHead, ClassVectorsHead, Head, SegmentationHead, get_head
 from sleap_nn_amd.architectures.convnext import ConvNextWrapper
+from sleap_nn_amd.architectures.pretrained import PretrainedBackbone
 from sleap_nn_amd.architectures.swint import SwinTWrapper
 from sleap_nn_amd.architectures.unet import OpSpec, UNet
 from sleap_nn_amd.utils import cfg_get, cfg_keys
@@ -25,7 +26,7 @@ PRECISIONS = {"exact": 0, "split": 1, "fp16": 2}
 
 
 def get_backbone(backbone: str, backbone_config):
-    """architectures/model.py:36-67.  ``unet``, ``convnext`` and ``swint`` are built natively."""
+    """architectures/model.py:36-67.  ``unet``, ``convnext``, ``swint`` and ``pretrained`` (the ConvNeXtV2 family, inference) are built natively."""
     if backbone == "unet":
         return UNet.from_config(backbone_config)
     if backbone == "convnext":
@@ -33,8 +34,8 @@ def get_backbone(backbone: str, backbone_config):
     if backbone == "swint":
         return SwinTWrapper.from_config(backbone_config)
     if backbone == "pretrained":
-        raise NotImplementedError(f"backbone '{backbone}' is not implemented on the MI355X path yet")
-    raise KeyError(f"Unsupported backbone: {backbone}. Supported backbones are: unet, convnext, swint")
+        return PretrainedBackbone.from_config(backbone_config)
+    raise KeyError(f"Unsupported backbone: {backbone}. Supported backbones are: unet, convnext, swint, pretrained")
 
 
 class Model:
@@ -47,12 +48,14 @@ class Model:
         self.model_type = model_type
         self.heads: List[Head] = get_head(model_type, head_configs)
         self.backbone: UNet = get_backbone(backbone_type, backbone_config)
-        self.in_channels = int(cfg_get(backbone_config, "in_channels", 1))
+        self.in_channels = int(cfg_get(backbone_config, "in_channels", 3 if backbone_type == "pretrained" else 1))
 
         self.ops: List[OpSpec] = list(self.backbone.ops)
         self.param_shapes = dict(self.backbone.param_shapes)
-        # checkpoint entries that are not parameters (Swin's relative_position_index): checked at load, kept out of the parameter arena
+        # checkpoint entries that are not parameters, kept out of the parameter arena: Swin's relative_position_index is checked at load; the
+        # `loaded_buffers` of a pretrained backbone (image_mean / image_std) are read from the checkpoint and handed to the handle (ph_model_set_input_norm)
         self.buffers: Dict[str, torch.Tensor] = dict(getattr(self.backbone, "buffers", {}))
+        self._loaded_buffers = tuple(getattr(self.backbone, "loaded_buffers", ()))
         self._head_ops_start = len(self.ops)
         for i, head in enumerate(self.heads):
             if isinstance(head, ClassVectorsHead):
@@ -218,8 +221,13 @@ class Model:
         unexpected = [k for k in sd if k not in self.param_shapes and k not in self.buffers]
         if strict and (missing or unexpected):
             raise RuntimeError(f"Error(s) in loading state_dict: missing {missing}, unexpected {unexpected}")
-        for k, want in self.buffers.items():  # the kernels compute these from coordinates: a checkpoint that disagrees was written by another definition
-            if k in sd:
+        for k, want in self.buffers.items():
+            if k in sd and k in self._loaded_buffers:  # the checkpoint's values are the ones the run was trained with: used, whatever the config would have given
+                got = torch.as_tensor(sd[k]).detach().to("cpu", torch.float32).contiguous()
+                if tuple(got.shape) != tuple(want.shape):
+                    raise RuntimeError(f"size mismatch for {k}: checkpoint {tuple(got.shape)} vs model {tuple(want.shape)}")
+                self.buffers[k] = got.clone()
+            elif k in sd:  # the kernels compute these from coordinates: a checkpoint that disagrees was written by another definition
                 got = torch.as_tensor(sd[k]).detach().to("cpu")
                 if tuple(got.shape) != tuple(want.shape) or not torch.equal(got.to(want.dtype), want):
                     raise RuntimeError(f"buffer {k} of the checkpoint differs from the canonical relative position index of a {self.backbone.window_size}x{self.backbone.window_size} window")
@@ -271,6 +279,9 @@ class Model:
         """Training keeps every activation: the op-by-op (unfused) program runs.  A Swin backbone trains on request only
         (``allow_swint=True``; ``TrainingModule(model, swint_training=True)`` passes it): its backward is the window-attention,
         patch-merge and residual steps of ``ph_model_backward`` (csrc/swin_train_kernels.hip)."""
+        if mode and self.backbone_type == "pretrained":
+            raise NotImplementedError("training a 'pretrained' (ConvNeXtV2) backbone is not built on the MI355X path: GRN and the padding-0 stem have no backward "
+                                      "(their ops carry PH_FLAG_NO_TRAIN); inference only")
         if mode and self.backbone_type == "swint" and not allow_swint:
             raise NotImplementedError("training a 'swint' backbone is opt-in on the MI355X path: Model.train(True, allow_swint=True), or "
                                       "TrainingModule(model, swint_training=True)")
@@ -328,6 +339,7 @@ class Model:
         on the fp16 matrix pipe with fp32 logits and softmax statistics, the patch-merge norm, the residual stream stored in
         fp16, then the fp16 decoder.  Without it a Swin program runs exact under every precision
         (tests/test_gpu_swint.py pins that); ``"split"`` is exact for it either way.
+        A ``pretrained`` (ConvNeXtV2) program has no fp16 form: it runs exact under every precision and whatever ``convnext_f16`` says (tests/test_gpu_pretrained.py).
         Programs with a class-vector head (global max pool, softmax) and every training program run exact whatever is set."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
@@ -435,6 +447,10 @@ class Model:
         self.generation += 1
         for k, v in self._options.items():
             L.check(lib.ph_model_set_option(self._handle, k.encode(), v))
+        if self._loaded_buffers:  # input statistics of the padding-0 patch stem
+            mean = [float(v) for v in self.buffers["backbone.image_mean"].reshape(-1)]
+            std = [float(v) for v in self.buffers["backbone.image_std"].reshape(-1)]
+            L.check(lib.ph_model_set_input_norm(self._handle, (C.c_float * len(mean))(*mean), (C.c_float * len(std))(*std), len(mean)))
         if self.ops is self.unfused_ops:
             self._apply_head_losses()
         if self._live_params is not None:  # the host copy in _state may be stale during training
@@ -556,7 +572,8 @@ class Model:
                 continue
             oh, ow = h, w
             if op.kind == L.OP_PATCH_STEM:
-                oh, ow = (h + 2 - op.ksize) // op.cmid + 1, (w + 2 - op.ksize) // op.cmid + 1
+                pad2 = 0 if op.flags & L.FLAG_PAD0_NORM else 2
+                oh, ow = (h + pad2 - op.ksize) // op.cmid + 1, (w + pad2 - op.ksize) // op.cmid + 1
             elif op.kind == L.OP_PATCH_CONV:
                 oh, ow = h // 2, w // 2
             elif op.kind == L.OP_PATCH_MERGE:

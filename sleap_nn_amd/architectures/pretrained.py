@@ -1,0 +1,296 @@
+"""HuggingFace ConvNeXtV2 encoder + UNet-style decoder -> op program for libposehip.
+
+Reproduces Case A (``mode="decoder"``) of the reference ``PretrainedBackbone``
+(``sleap_nn/architectures/pretrained.py:111-502``) for the ConvNeXtV2 family, without torch modules and
+without ``transformers``: the encoder is HuggingFace's ``ConvNextV2Backbone`` restated as ops, the checkpoint
+parameter names are the reference's (``backbone.enc.embeddings...``, ``backbone.enc.encoder.stages.{i}...``,
+``backbone.enc.hidden_states_norms.{stem,stage1..4}``, ``backbone.dec.decoder_stack.{b}.blocks.pretrained_dec...``)
+and the buffers ``backbone.image_mean`` / ``backbone.image_std`` are read from the checkpoint.
+
+Nothing here can reach a network: the architecture comes from a local directory with a ``config.json`` or from the
+size word of a ``convnextv2-<size>`` id; the weights come from the checkpoint.  Every other family, the encoder-only
+mode and a subset of the stages are refused by name.  Inference only: the ops carry ``FLAG_NO_TRAIN``.
+
+A block is six ops: depthwise 7x7 -> LayerNorm -> Linear C->4C -> GELU -> GRN -> Linear 4C->C with the residual add
+in its epilogue (no layer scale).  ``Model._fuse_cnblocks`` folds the GELU into the first Linear for inference.
+"""
+from __future__ import annotations
+
+import json
+import math
+import os
+import re
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Tuple
+
+import torch
+
+from sleap_nn_amd import _lib as L
+from sleap_nn_amd.architectures.unet import OpSpec
+from sleap_nn_amd.utils import cfg_get
+
+THIS_FILE = "sleap_nn_amd/architectures/pretrained.py"
+
+# depths / hidden sizes of the published ConvNeXtV2 sizes (the config.json of facebook/convnextv2-<size>-*)
+CONVNEXTV2_SIZES = {
+    "atto": {"depths": [2, 2, 6, 2], "hidden_sizes": [40, 80, 160, 320]},
+    "femto": {"depths": [2, 2, 6, 2], "hidden_sizes": [48, 96, 192, 384]},
+    "pico": {"depths": [2, 2, 6, 2], "hidden_sizes": [64, 128, 256, 512]},
+    "nano": {"depths": [2, 2, 8, 2], "hidden_sizes": [80, 160, 320, 640]},
+    "tiny": {"depths": [3, 3, 9, 3], "hidden_sizes": [96, 192, 384, 768]},
+    "base": {"depths": [3, 3, 27, 3], "hidden_sizes": [128, 256, 512, 1024]},
+    "large": {"depths": [3, 3, 27, 3], "hidden_sizes": [192, 384, 768, 1536]},
+    "huge": {"depths": [3, 3, 27, 3], "hidden_sizes": [352, 704, 1408, 2816]},
+}
+IMAGENET_MEAN = [0.485, 0.456, 0.406]  # pretrained.py:48-49: what _resolve_norm_stats falls back to without an image processor
+IMAGENET_STD = [0.229, 0.224, 0.225]
+DEFAULT_MODEL_NAME = "facebook/convnextv2-nano-22k-224"
+
+
+def _refuse(what: str) -> NotImplementedError:
+    return NotImplementedError(f"pretrained backbone: {what} is not built on the MI355X path; only the ConvNeXtV2 family in mode='decoder' with all stages is ({THIS_FILE})")
+
+
+def resolve_architecture(model_name: str, run_dir: Optional[str] = None) -> dict:
+    """``model_name`` -> {"depths", "hidden_sizes", "patch_size", "num_channels"} without touching a network.
+
+    (a) a directory holding a ``config.json`` (absolute as given; relative against ``run_dir``, then the working directory);
+    (b) the size word of a ``convnextv2-<size>`` id; (c) anything else is refused."""
+    name = str(model_name)
+    cands = [name] if os.path.isabs(name) else ([os.path.join(run_dir, name)] if run_dir else []) + [os.path.join(os.getcwd(), name)]
+    for d in cands:
+        path = os.path.join(d, "config.json")
+        if not os.path.isfile(path):
+            continue
+        with open(path) as f:
+            hf = json.load(f)
+        mt = hf.get("model_type")
+        if mt != "convnextv2":
+            raise _refuse(f"model_type {mt!r} of {path}")
+        if hf.get("hidden_act", "gelu") != "gelu":
+            raise _refuse(f"hidden_act {hf.get('hidden_act')!r} of {path}")
+        eps = float(hf.get("layer_norm_eps", 1e-12))  # (the classifier's pooled norm: no op of the backbone reads it)
+        depths = [int(v) for v in (hf.get("depths") or CONVNEXTV2_SIZES["tiny"]["depths"])]
+        hidden = [int(v) for v in (hf.get("hidden_sizes") or CONVNEXTV2_SIZES["tiny"]["hidden_sizes"])]
+        return {"depths": depths, "hidden_sizes": hidden, "patch_size": int(hf.get("patch_size", 4)), "num_channels": int(hf.get("num_channels", 3)),
+                "layer_norm_eps": eps, "source": path}
+    m = re.search(r"convnextv2-([a-z]+)", name.lower())
+    if m and m.group(1) in CONVNEXTV2_SIZES:
+        a = CONVNEXTV2_SIZES[m.group(1)]
+        return {"depths": list(a["depths"]), "hidden_sizes": list(a["hidden_sizes"]), "patch_size": 4, "num_channels": 3, "layer_norm_eps": 1e-12, "source": m.group(0)}
+    raise _refuse(f"model_name {name!r} (no local config.json, not a convnextv2-<size> id: ResNet, Swinv2, DINO and the isotropic ViTs are other families)")
+
+
+@dataclass
+class PretrainedBackbone:
+    """Config-derived description; ``from_config`` mirrors pretrained.py:436-461."""
+
+    source: str = "hf"
+    model_name: str = DEFAULT_MODEL_NAME
+    in_channels: int = 3
+    output_stride: int = 2
+    weights: bool = True  # ignored: the checkpoint supplies the weights
+    mode: str = "auto"
+    out_indices: Optional[List[int]] = None
+    freeze: bool = False  # accepted, unused (inference only)
+    revision: Optional[str] = None  # accepted, unused (nothing is downloaded)
+    normalize: bool = True
+    image_mean: Optional[List[float]] = None
+    image_std: Optional[List[float]] = None
+    filters_rate: float = 2.0
+    convs_per_block: int = 2
+    kernel_size: int = 3
+    up_interpolate: bool = True
+    depths: List[int] = field(default_factory=list)
+    channels: List[int] = field(default_factory=list)
+    patch_size: int = 4
+    ops: List[OpSpec] = field(default_factory=list)
+    n_slots: int = 0
+    decoder_stride_to_filters: Dict[int, int] = field(default_factory=dict)
+    decoder_slot_of_stride: Dict[int, int] = field(default_factory=dict)
+    middle_slot: int = -1
+    param_shapes: Dict[str, Tuple[int, ...]] = field(default_factory=dict)
+    labels: Dict[str, int] = field(default_factory=dict)
+    # checkpoint entries that are not parameters.  Unlike Swin's index buffers these are READ from the checkpoint (loaded_buffers): the values a run was
+    # trained with override what the config or the ImageNet default would give
+    buffers: Dict[str, torch.Tensor] = field(default_factory=dict)
+    loaded_buffers: Tuple[str, ...] = ("backbone.image_mean", "backbone.image_std")
+
+    @classmethod
+    def from_config(cls, config) -> "PretrainedBackbone":
+        source = cfg_get(config, "source", "hf")
+        if source != "hf":
+            raise ValueError(f"Unsupported pretrained backbone source: {source!r}. Only 'hf' (HuggingFace transformers) is currently supported.")
+        mode = cfg_get(config, "mode", "auto")
+        if mode not in ("auto", "decoder"):
+            raise _refuse(f"mode={mode!r} (the encoder-only pooled bottleneck)")
+        name = cfg_get(config, "model_name", None) or DEFAULT_MODEL_NAME
+        arch = resolve_architecture(name, cfg_get(config, "_run_dir", None))
+        oi = cfg_get(config, "out_indices", None)
+        if oi is not None and [int(i) for i in oi] != [0, 1, 2, 3, 4]:
+            raise _refuse(f"out_indices={list(oi)} (a subset of the stages)")
+        in_channels = int(cfg_get(config, "in_channels", 3))
+        if in_channels != arch["num_channels"]:
+            raise _refuse(f"in_channels={in_channels} for {name}, whose stem takes {arch['num_channels']} channels (gray frames are replicated by Model.forward; keep in_channels at {arch['num_channels']}),")
+        mean, std = cfg_get(config, "image_mean", None), cfg_get(config, "image_std", None)
+        net = cls(
+            source=source, model_name=str(name), in_channels=in_channels, output_stride=int(cfg_get(config, "output_stride", 2)),
+            weights=bool(cfg_get(config, "weights", True)), mode=mode, out_indices=None if oi is None else [int(i) for i in oi],
+            freeze=bool(cfg_get(config, "freeze", False)), revision=cfg_get(config, "revision", None), normalize=bool(cfg_get(config, "normalize", True)),
+            image_mean=None if mean is None else [float(v) for v in mean], image_std=None if std is None else [float(v) for v in std],
+            filters_rate=cfg_get(config, "filters_rate", 2.0), convs_per_block=int(cfg_get(config, "convs_per_block", 2)),
+            kernel_size=int(cfg_get(config, "kernel_size", 3)), up_interpolate=bool(cfg_get(config, "up_interpolate", True)),
+            depths=[int(d) for d in arch["depths"]], channels=[int(c) for c in arch["hidden_sizes"]], patch_size=int(arch["patch_size"]),
+        )
+        net._build()
+        return net
+
+    @property
+    def max_stride(self) -> int:
+        return self.patch_size * 2 ** (len(self.channels) - 1)  # the probed deepest stride (pretrained.py:353-362): 32
+
+    @property
+    def max_channels(self) -> int:
+        return int(self.channels[-1])  # middle_blocks[-1].filters: the bottleneck (pretrained.py:403-404)
+
+    def norm_stats(self) -> Tuple[List[float], List[float]]:
+        """pretrained.py:270-297 without the image processor (a network read): explicit values, identity when disabled, else ImageNet."""
+        if self.image_mean is not None and self.image_std is not None:
+            return list(self.image_mean), list(self.image_std)
+        if not self.normalize:
+            return [0.0] * self.in_channels, [1.0] * self.in_channels
+        return list(IMAGENET_MEAN), list(IMAGENET_STD)
+
+    # -- program construction ---------------------------------------------------------
+    def _new_slot(self) -> int:
+        self.n_slots += 1
+        return self.n_slots - 1
+
+    def _emit(self, op: OpSpec) -> int:
+        op.flags |= L.FLAG_NO_TRAIN if op.kind in (L.OP_GRN, L.OP_PATCH_STEM) else 0
+        self.ops.append(op)
+        return op.dst
+
+    def _conv3(self, name: str, src0: int, cin0: int, cout: int, src1: int = -1, cin1: int = 0) -> int:
+        dst = self._new_slot()
+        self.param_shapes[name + ".weight"] = (cout, cin0 + cin1, 3, 3)
+        self.param_shapes[name + ".bias"] = (cout,)
+        self.ops.append(OpSpec(L.OP_CONV, src0, src1, dst, cin0, cin1, cout, 3, L.FLAG_RELU, name + ".weight", name + ".bias", label=name))
+        self.labels[name] = dst
+        return dst
+
+    def _layernorm(self, name: str, src: int, c: int) -> int:
+        self.param_shapes[name + ".weight"] = (c,)
+        self.param_shapes[name + ".bias"] = (c,)
+        return self._emit(OpSpec(L.OP_LAYERNORM, src, -1, self._new_slot(), c, 0, c, 1, 0, name + ".weight", name + ".bias", label=name))
+
+    def _v2_block(self, name: str, x: int, c: int) -> int:
+        p = self.param_shapes
+        p[name + ".dwconv.weight"] = (c, 1, 7, 7)
+        p[name + ".dwconv.bias"] = (c,)
+        y = self._emit(OpSpec(L.OP_DWCONV, x, -1, self._new_slot(), c, 0, c, 7, 0, name + ".dwconv.weight", name + ".dwconv.bias", label=name + ".dwconv"))
+        y = self._layernorm(name + ".layernorm", y, c)
+        p[name + ".pwconv1.weight"] = (4 * c, c)
+        p[name + ".pwconv1.bias"] = (4 * c,)
+        y = self._emit(OpSpec(L.OP_LINEAR, y, -1, self._new_slot(), c, 0, 4 * c, 1, 0, name + ".pwconv1.weight", name + ".pwconv1.bias", label=name + ".pwconv1"))
+        y = self._emit(OpSpec(L.OP_GELU, y, -1, self._new_slot(), 4 * c, 0, 4 * c, 1, 0, label=name + ".act"))
+        p[name + ".grn.weight"] = (1, 1, 1, 4 * c)
+        p[name + ".grn.bias"] = (1, 1, 1, 4 * c)
+        y = self._emit(OpSpec(L.OP_GRN, y, -1, self._new_slot(), 4 * c, 0, 4 * c, 1, 0, name + ".grn.weight", name + ".grn.bias", label=name + ".grn"))
+        self.labels[name + ".grn"] = y
+        p[name + ".pwconv2.weight"] = (c, 4 * c)
+        p[name + ".pwconv2.bias"] = (c,)
+        # no layer scale, drop path is the identity in eval: the residual add is the GEMM's PH_FLAG_RESIDUAL epilogue
+        y = self._emit(OpSpec(L.OP_LINEAR, y, x, self._new_slot(), 4 * c, 0, c, 1, L.FLAG_RESIDUAL, name + ".pwconv2.weight", name + ".pwconv2.bias", label=name))
+        self.labels[name] = y
+        return y
+
+    def _build(self) -> None:
+        if self.kernel_size != 3:
+            raise ValueError("only kernel_size=3 is supported by the MFMA convolution kernels")
+        if len(self.channels) != 4 or len(self.depths) != 4:
+            raise _refuse(f"a ConvNeXtV2 with {len(self.channels)} stages")
+        if not (2 <= self.patch_size <= 8):
+            raise ValueError("patch_size must be in 2..8")
+        if self.in_channels < 1 or self.in_channels > 4:
+            raise ValueError("in_channels must be in 1..4")
+        mean, std = self.norm_stats()
+        self.buffers = {"backbone.image_mean": torch.tensor(mean, dtype=torch.float32).view(1, -1, 1, 1),
+                        "backbone.image_std": torch.tensor(std, dtype=torch.float32).view(1, -1, 1, 1)}
+        self._build_encoder()
+
+    def _build_encoder(self) -> None:
+        ch = self.channels
+        enc = "backbone.enc"
+        hn = f"{enc}.hidden_states_norms"
+        pe = f"{enc}.embeddings.patch_embeddings"
+        # embeddings: (x - mean) / std -> Conv2d(patch, stride patch, padding 0) -> LayerNorm (channels first)
+        self.param_shapes[pe + ".weight"] = (ch[0], self.in_channels, self.patch_size, self.patch_size)
+        self.param_shapes[pe + ".bias"] = (ch[0],)
+        x = self._emit(OpSpec(L.OP_PATCH_STEM, -1, -1, self._new_slot(), self.in_channels, 0, ch[0], self.patch_size, L.FLAG_PAD0_NORM, pe + ".weight", pe + ".bias",
+                              label=pe, cmid=self.patch_size))
+        x = self._layernorm(f"{enc}.embeddings.layernorm", x, ch[0])
+        self.labels[f"{enc}.embeddings"] = x
+        feats: List[Tuple[int, int]] = []  # (normed map slot, channels), finest first
+        for si, (depth, c) in enumerate(zip(self.depths, ch)):
+            st = f"{enc}.encoder.stages.{si}"
+            if si > 0:
+                x = self._layernorm(f"{st}.downsampling_layer.0", x, ch[si - 1])
+                name = f"{st}.downsampling_layer.1"
+                self.param_shapes[name + ".weight"] = (c, ch[si - 1], 2, 2)
+                self.param_shapes[name + ".bias"] = (c,)
+                x = self._emit(OpSpec(L.OP_PATCH_CONV, x, -1, self._new_slot(), ch[si - 1], 0, c, 2, 0, name + ".weight", name + ".bias", label=name))
+            for j in range(depth):
+                x = self._v2_block(f"{st}.layers.{j}", x, c)
+            # the map that leaves the encoder is normed; the stream into the next stage is not
+            f = self._layernorm(f"{hn}.stage{si + 1}", x, c)
+            self.labels[f"{hn}.stage{si + 1}"] = f
+            feats.append((f, c))
+        # the stem map shares stride 4 with stage1 and is dropped by the stride dedupe (pretrained.py:315-334): its norm is in every checkpoint, loads, and no op reads it
+        self.param_shapes[f"{hn}.stem.weight"] = (ch[0],)
+        self.param_shapes[f"{hn}.stem.bias"] = (ch[0],)
+        self._build_decoder(feats)
+
+    def _build_decoder(self, feats: List[Tuple[int, int]]) -> None:
+        """pretrained.py:336-404 + encoder_decoder.py:634-703: no additional pool, no middle blocks; Decoder(stem_blocks=1, down_blocks=n_skips - 1,
+        filters=channels[0], encoder_channels=channels[:-1][::-1], prefix="pretrained_dec"); blocks past the skips take the no-concat path with ONE refine conv."""
+        ch = self.channels
+        cur, cur_c = feats[-1]
+        self.middle_slot = cur
+        stride = self.max_stride
+        up_blocks = int(math.log2(stride / self.output_stride))
+        if up_blocks < 1:
+            raise ValueError(f"output_stride={self.output_stride} is >= the backbone's deepest stride {stride}; nothing to decode. Lower output_stride.")
+        skips = feats[:-1][::-1]  # deepest first
+        n_skips = len(skips)
+        self.decoder_stride_to_filters = {stride: cur_c}
+        for b in range(up_blocks):
+            fout = int(ch[0] * (self.filters_rate ** max(0, n_skips - 1 - b)))
+            nxt = stride // 2
+            name = f"backbone.dec.decoder_stack.{b}.blocks.pretrained_dec{b}_s{stride}_to_s{nxt}"
+            concat = b < n_skips
+            dst = self._new_slot()
+            if self.up_interpolate:
+                self.ops.append(OpSpec(L.OP_UPSAMPLE, cur, -1, dst, cur_c, label=name + "_interp_bilinear"))
+                up_c = cur_c
+            else:
+                tn = name + "_trans_conv"
+                self.param_shapes[tn + ".weight"] = (cur_c, fout, 3, 3)
+                self.param_shapes[tn + ".bias"] = (fout,)
+                self.ops.append(OpSpec(L.OP_CONVT, cur, -1, dst, cur_c, 0, fout, 3, L.FLAG_RELU, tn + ".weight", tn + ".bias", label=tn))
+                self.labels[tn] = dst
+                up_c = fout
+            cur, cur_c = dst, up_c
+            for i in range(self.convs_per_block if concat else 1):
+                cn = name + f"_refine_conv{i}"
+                if i == 0 and concat:
+                    sk, sk_c = skips[b]
+                    cur = self._conv3(cn, sk, sk_c, fout, src1=cur, cin1=cur_c)  # concat (skip, x)
+                else:
+                    if i == 0 and cur_c != fout:  # (the reference builds this conv with fout inputs: encoder_decoder.py:476-478)
+                        raise ValueError(f"decoder block {b} has no skip and {cur_c} input channels for a conv built with {fout}")
+                    cur = self._conv3(cn, cur, cur_c, fout)
+                cur_c = fout
+            self.decoder_stride_to_filters[nxt] = fout
+            self.decoder_slot_of_stride[nxt] = cur
+            stride = nxt

@@ -797,7 +797,8 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void gemm_mfma_dma_tile_kernel(G
   }
 }
 
-// EPI = 1: the training epilogues (act 3, dst_pre) are compiled in; the inference kernels (EPI = 0) do not carry them
+// EPI = 1: the training epilogues (act 3, dst_pre) are compiled in; the inference kernels (EPI = 0) do not carry them; EPI = 2: the inference epilogue plus the
+// per-(32-row block, sample) sums of squares of the outputs that the fused GRN plan reads (GemmArgs::sumsq)
 template <int MODE, int MT, int NTW, int WM, int WN, int NSTAGE, int MINW, int EPI = 0>
 __global__ __launch_bounds__(WM* WN * 64, MINW) void gemm_mfma_dma_kernel(GemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1065,7 +1066,7 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void gemm_mfma_dma_kernel(GemmAr
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int col = cbase + 8 * q;
-          if constexpr (EPI == 0) {
+          if constexpr (EPI != 1) {
             f32x4 v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -1073,6 +1074,23 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void gemm_mfma_dma_kernel(GemmAr
               if (a.act == 1) x = fmaxf(x, 0.f);
               if (a.act == 2) x = gelu_f(x);
               v[e] = x * scale4[q][e];
+            }
+            if constexpr (EPI == 2) {
+              // fused GRN (convnextv2_kernels.hip): sums of squares of this 32-row block's outputs, one partial per sample the block touches -- a block that
+              // straddles a sample boundary splits its sum there.  A fixed shuffle tree over the 32 pixel lanes of each half wave, plain stores: no atomics.
+              const int blk_row0 = m0 + (wm * MT + m) * 32;  // wave-uniform
+              if (blk_row0 < a.M && col < a.coutp) {
+                const int s_first = blk_row0 / a.sq_hw, s_last = min(blk_row0 + 31, a.M - 1) / a.sq_hw;
+                const int my_s = min(row, a.M - 1) / a.sq_hw;
+                for (int sg = s_first; sg <= s_last; ++sg) {
+                  f32x4 t = (row < a.M && my_s == sg) ? v * v : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                  for (int d = 16; d >= 1; d >>= 1)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) t[e] += __shfl_xor(t[e], d, 32);
+                  if (lx == 0) *reinterpret_cast<f32x4*>(a.sumsq + ((size_t)(blk_row0 >> 5) * a.sq_nseg + (sg - s_first)) * a.coutp + col) = t;
+                }
+              }
             }
             if (interior) {
               if (a.residual) v += *reinterpret_cast<const f32x4*>(a.residual + rofs + col);
@@ -1196,6 +1214,8 @@ int prepare_convnext_kernels() {
   PH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mfma_dma_kernel<2, MT, NTW, WM, WN, S, W>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                    (int)GemmCfg<MT, NTW, WM, WN, S, W>::LDS));                                                              \
   PH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mfma_dma_kernel<0, MT, NTW, WM, WN, S, W, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                   (int)GemmCfg<MT, NTW, WM, WN, S, W>::LDS));                                                              \
+  PH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mfma_dma_kernel<0, MT, NTW, WM, WN, S, W, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                    (int)GemmCfg<MT, NTW, WM, WN, S, W>::LDS));
   PH_GEMM_VARIANTS(X)
 #undef X
@@ -1224,6 +1244,8 @@ int launch_gemm_variant(int variant, const GemmArgs& a_in, hipStream_t s) {
   PH_REQUIRE(a.c1p == 0 || a.src1, "launch_gemm: second source missing");
   PH_REQUIRE((a.act != 3 && !a.dst_pre) || a.mode == 0, "launch_gemm: the training epilogues exist for the Linear mode only");
   PH_REQUIRE(a.act != 3 || a.aux, "launch_gemm: act 3 needs aux");
+  PH_REQUIRE(!a.sumsq || (a.mode == 0 && a.act != 3 && !a.dst_pre && !a.scale && !a.out_patch && a.sq_hw > 0 && a.M % a.sq_hw == 0 && a.sq_nseg >= 31 / a.sq_hw + 2),
+             "launch_gemm: the sum-of-squares epilogue exists for the plain Linear mode over whole samples");
   PH_REQUIRE(a.mode != 1 || (a.H >= 2 && a.W >= 2), "launch_gemm: 2x2 patches need H, W >= 2");
   PH_REQUIRE(a.mode != 2 || a.M % (a.H * a.W) == 0, "launch_gemm: conv rows must be whole images");
   PH_REQUIRE(gemm_variant_bn(variant) == a.bn, "launch_gemm: variant %d does not match the N tile %d of the packed weights", variant, a.bn);
@@ -1239,6 +1261,8 @@ int launch_gemm_variant(int variant, const GemmArgs& a_in, hipStream_t s) {
     const dim3 grid((unsigned)std::min<long>((long)((a.M + C::TM - 1) / C::TM) * ((a.coutp + C::BN - 1) / C::BN), (long)n_cu)); \
     if (a.mode == 0 && (a.act == 3 || a.dst_pre))                                                                              \
       hipLaunchKernelGGL((gemm_mfma_dma_kernel<0, MT, NTW, WM, WN, S, W, 1>), grid, dim3(C::THREADS), C::LDS, s, a);           \
+    else if (a.mode == 0 && a.sumsq)                                                                                           \
+      hipLaunchKernelGGL((gemm_mfma_dma_kernel<0, MT, NTW, WM, WN, S, W, 2>), grid, dim3(C::THREADS), C::LDS, s, a);           \
     else if (a.mode == 0)                                                                                                      \
       hipLaunchKernelGGL((gemm_mfma_dma_kernel<0, MT, NTW, WM, WN, S, W>), grid, dim3(C::THREADS), C::LDS, s, a);              \
     else if (a.mode == 1)                                                                                                      \

@@ -267,6 +267,8 @@ int forward_format(const ph_model* m) {
       case PH_OP_PATCH_MERGE:
         if (!enc_f16) return FMT_F32;
         break;
+      case PH_OP_GRN:  // a ConvNeXtV2 program has no fp16 form: exact whatever the precision and whatever "convnext_f16" says
+        return FMT_F32;
       case PH_OP_LINEAR:  // (a Linear with a ReLU is a class-vector head's: exact; PH_FLAG_RESIDUAL is a Swin block's, with or without a bias)
         if (!enc_f16 || (d.flags & ~(PH_FLAG_GELU | PH_FLAG_SCALE_RESIDUAL | (swin ? PH_FLAG_RESIDUAL : 0))) || !op.w_cnx_f16_dev) return FMT_F32;
         break;
@@ -321,6 +323,18 @@ bool fuses_mlp(const ph_model* m, size_t i, int fmt, bool reuse) {
   return only_reader_is_next(m, i);
 }
 
+// ConvNeXtV2 block on the fused GRN plan (handle option "grn_fuse"): op i = Linear + GELU, i + 1 = GRN, i + 2 = the residual Linear; nobody else reads the two tensors between
+bool fuses_grn(const ph_model* m, size_t i, int fmt) {
+  if (!m->grn_fuse || fmt != FMT_F32 || m->branch_scales || i + 2 >= m->ops.size()) return false;
+  const ph_op_desc& d = m->ops[i].d;
+  const ph_op_desc& g = m->ops[i + 1].d;
+  const ph_op_desc& l2 = m->ops[i + 2].d;
+  if (!(d.kind == PH_OP_LINEAR && d.flags == PH_FLAG_GELU && d.src0 >= 0)) return false;
+  if (!(g.kind == PH_OP_GRN && g.src0 == d.dst && g.cin0 == d.cout)) return false;
+  if (!(l2.kind == PH_OP_LINEAR && (l2.flags & PH_FLAG_RESIDUAL) && l2.src0 == g.dst && l2.cin0 == g.cout && m->ops[i + 2].b_grn_dev)) return false;
+  return only_reader_is_next(m, i) && only_reader_is_next(m, i + 1);
+}
+
 int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
   plan.slots.assign(m->n_slots, SlotShape());
   plan.fmt = fmt;
@@ -349,6 +363,9 @@ int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
       const ph_op_desc& nx = m->ops[j + 1].d;
       if (e.kind == PH_OP_UPSAMPLE && nx.kind == PH_OP_CONV && nx.src1 == e.dst && e.src0 >= 0 && e.src0 < m->n_slots) last_use[e.src0] = std::max(last_use[e.src0], j + 1);
     }
+  if (reuse)  // fused GRN plan: the residual Linear reads the GELU output itself, one op after the GRN op that is its last reader in the program
+    for (int j = 0; j + 2 < n_ops; ++j)
+      if (fuses_grn(m, (size_t)j, fmt)) last_use[m->ops[j].d.dst] = std::max(last_use[m->ops[j].d.dst], j + 2);
   plan.unread.assign(m->n_slots, 0);
   if (reuse)
     for (int sl = 0; sl < m->n_slots; ++sl) plan.unread[sl] = last_use[sl] < 0;
@@ -429,8 +446,9 @@ int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
     int oh = h, ow = w;
     if (d.kind == PH_OP_PATCH_STEM) {
       PH_REQUIRE(d.src0 < 0, "patch stem must read the network input");
-      oh = (h + 2 - d.ksize) / d.cmid + 1;
-      ow = (w + 2 - d.ksize) / d.cmid + 1;
+      const int pad2 = (d.flags & PH_FLAG_PAD0_NORM) ? 0 : 2;
+      oh = (h + pad2 - d.ksize) / d.cmid + 1;
+      ow = (w + pad2 - d.ksize) / d.cmid + 1;
       PH_REQUIRE(oh > 0 && ow > 0, "input %dx%d is too small for the %dx%d patch stem", h, w, d.ksize, d.ksize);
     } else if (d.kind == PH_OP_PATCH_CONV) {
       oh = h / 2;
@@ -466,6 +484,15 @@ int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
                  h, w, s1.h, s1.w);
     }
     if (d.kind == PH_OP_CONVT) tmp = std::max<int64_t>(tmp, (int64_t)B * oh * ow * fmt_cpad(fmt, d.cin0) * bpc);
+    if (d.kind == PH_OP_GRN) {  // the slice sums of grn_reduce_kernel
+      PH_REQUIRE(fmt == FMT_F32 && d.src0 >= 0 && plan.slots[d.src0].c == d.cin0 && d.cin0 == d.cout, "GRN channel mismatch");
+      tmp = std::max<int64_t>(tmp, grn_scratch_floats(B, h * w, pad16(d.cout)) * (int64_t)sizeof(float));
+      if (op_i >= 1 && fuses_grn(m, (size_t)op_i - 1, fmt)) {  // block sums of the first Linear's epilogue, then one scaled weight image per sample for the second
+        const PackedOp& l2 = m->ops[op_i + 1];
+        tmp = std::max<int64_t>(tmp, grn_fused_partial_floats(B * h * w, h * w, pad16(d.cout)) * (int64_t)sizeof(float));
+        tmp = std::max<int64_t>(tmp, (int64_t)B * gemm_pack_floats(pad16(l2.d.cout), pad16(d.cout), l2.bn) * (int64_t)sizeof(float));
+      }
+    }
     if (d.kind == PH_OP_CONV && d.ksize == 3 && fmt == FMT_F32 && (m->conv_splitk >= 2 || (m->conv_splitk == 1 && reuse))) {  // (auto: inference plans only, as the kernel choice below)  // partial-sum planes of a split-K launch (conv3x3_wino2d_kernel<.., KS>)
       int n_cu = 0;
       if (device_cu_count(&n_cu) != PH_OK || n_cu <= 0) n_cu = 256;
@@ -912,6 +939,7 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
         if (weight_numel[d.bias] != d.cout) return fail("bias size mismatch", i);
         if (d.kind == PH_OP_INPUT_CONV && (!(d.ksize & 1) || d.ksize < 1 || d.ksize > 9)) return fail("kernel_size must be odd and <= 9", i);
         if (d.kind == PH_OP_PATCH_STEM && (d.ksize < 2 || d.ksize > 8 || d.cmid < 1 || d.cmid > d.ksize)) return fail("patch stem needs 2 <= kernel <= 8 and 1 <= stride <= kernel", i);
+        if (d.kind == PH_OP_PATCH_STEM && (d.flags & PH_FLAG_PAD0_NORM) && (d.cin0 < 1 || d.cin0 > 4)) return fail("a padding-0 patch stem with input statistics takes 1..4 input channels", i);
         const int kk = d.ksize * d.ksize;
         if (weight_numel[d.weight] != (int64_t)d.cin0 * d.cout * kk) return fail("weight size mismatch", i);
         const int coutp = pad16(d.cout);
@@ -964,6 +992,14 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
       case PH_OP_LAYERNORM: {
         if (!widx_ok(d.weight) || !widx_ok(d.bias)) return fail("weight index out of range", i);
         if (d.cin0 != d.cout || weight_numel[d.weight] != d.cout || weight_numel[d.bias] != d.cout) return fail("LayerNorm affine size mismatch", i);
+        const int cp = pad16(d.cout);
+        ok = pack_upload(m, pad_vec(cp, d.cout), weights[d.weight], index_array(d.weight), &op.w_dev) == PH_OK &&
+             pack_upload(m, pad_vec(cp, d.cout), weights[d.bias], index_array(d.bias), &op.b_dev) == PH_OK;
+        break;
+      }
+      case PH_OP_GRN: {
+        if (!widx_ok(d.weight) || !widx_ok(d.bias)) return fail("weight index out of range", i);
+        if (d.cin0 != d.cout || d.src0 < 0 || weight_numel[d.weight] != d.cout || weight_numel[d.bias] != d.cout) return fail("GRN needs a (C) weight and bias", i);
         const int cp = pad16(d.cout);
         ok = pack_upload(m, pad_vec(cp, d.cout), weights[d.weight], index_array(d.weight), &op.w_dev) == PH_OK &&
              pack_upload(m, pad_vec(cp, d.cout), weights[d.bias], index_array(d.bias), &op.b_dev) == PH_OK;
@@ -1055,6 +1091,19 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
             m->derived.push_back(db);
             op.w_cnx_f16_dev = w;
           }
+        }
+        if (ok && d.kind == PH_OP_LINEAR && (d.flags & PH_FLAG_RESIDUAL) && !no_bias && i > 0 && ops[i - 1].kind == PH_OP_GRN && ops[i - 1].dst == d.src0 && ops[i - 1].cout == d.cin0 &&
+            widx_ok(ops[i - 1].bias) && weight_numel[ops[i - 1].bias] == d.cin0) {
+          // fused GRN plan: W2 (s x + grn.bias) + b2 = (W2 diag(s)) x + (W2 grn.bias + b2); the second term is constant per model (this backbone does not train: the fold is never stale)
+          std::vector<float> fb(npad, 0.f);
+          const float* w2 = weights[d.weight];
+          const float* gb = weights[ops[i - 1].bias];
+          for (int co = 0; co < d.cout; ++co) {
+            double acc = weights[d.bias][co];
+            for (int ci = 0; ci < d.cin0; ++ci) acc += (double)w2[(size_t)co * d.cin0 + ci] * (double)gb[ci];
+            fb[co] = (float)acc;
+          }
+          ok = upload(m, fb, &op.b_grn_dev) == PH_OK;
         }
         if (ok && (d.flags & PH_FLAG_SCALE_RESIDUAL)) {
           if (!widx_ok(d.weight2) || weight_numel[d.weight2] != d.cout || d.src1 < 0) return fail("layer-scale epilogue needs weight2 (C) and a residual source", i);
@@ -1187,6 +1236,7 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
   std::vector<char> head_done(m->ops.size(), 0);  // head ops the producing conv's epilogue already computed (see PH_OP_CONV)
   std::vector<char> conv_done(m->ops.size(), 0);  // conv ops the conv in front of them already computed (two-conv block kernel, see PH_OP_CONV)
   int deferred_up = -1;     // index of a bilinear op left to the conv that follows it (see PH_OP_UPSAMPLE / PH_OP_CONV)
+  int fused_grn = -1;       // fused GRN plan: 1-based index of the op of a ConvNeXtV2 block that ran last on that plan (Linear + GELU, then the GRN op; the residual Linear clears it)
   int fused_ln = -1;        // index of a LayerNorm op the producing depthwise conv already applied (see PH_OP_DWCONV)
   for (const PackedOp& op : m->ops) {
     const ph_op_desc& d = op.d;
@@ -1725,6 +1775,32 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
       case PH_OP_PATCH_STEM: {
         PH_REQUIRE(d.cin0 == in_channels, "input has %d channels, network expects %d", in_channels, d.cin0);
         const SlotShape& so = plan.slots[d.dst];
+        if (d.flags & PH_FLAG_PAD0_NORM) {  // ConvNeXtV2 embeddings: padding 0, (x / 255 - mean) / std on the way in
+          PH_REQUIRE(fmt == FMT_F32, "the padding-0 patch stem runs in exact fp32 only");
+          PatchStemArgs a{};
+          a.src = input_dev;
+          a.w = op.w_dev;
+          a.bias = op.b_dev;
+          a.dst = wr(d.dst);
+          a.dtype = in_dtype;
+          a.cin = d.cin0;
+          a.coutp = so.cp;
+          a.B = batch;
+          a.H = height;
+          a.W = width;
+          a.OH = so.h;
+          a.OW = so.w;
+          a.k = d.ksize;
+          a.stride = d.cmid;
+          a.pad0_norm = 1;
+          for (int c = 0; c < 4; ++c) {
+            a.mean[c] = m->in_mean[c];
+            a.std[c] = m->in_std[c];
+          }
+          kv[op_index - 1] = PH_KV_PATCH_STEM_NORM;
+          rc = launch_patch_stem_norm(a, s);
+          break;
+        }
         if (fmt == FMT_F16) {
           PatchStemF16Args f{};
           f.src = input_dev;
@@ -1975,6 +2051,43 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
             break;
           }
         }
+        if (fused_grn == (int)op_index - 1 && d.kind == PH_OP_LINEAR) {  // fused GRN plan: (W2 diag(s_b)) x + (W2 grn.bias + b2) + residual, one GEMM per sample on its own scaled weight image
+          fused_grn = -1;
+          const ph_op_desc& g = m->ops[op_index - 2].d;
+          const SlotShape& sx = plan.slots[g.src0];  // the GELU output: what the GEMM reads instead of the GRN slot
+          const int hw = sx.h * sx.w;
+          const int64_t wfl = gemm_pack_floats(so.cp, sx.cp, op.bn);
+          PH_REQUIRE(op.b_grn_dev && sx.cp == s0.cp && plan.tmp_bytes >= (int64_t)batch * wfl * (int64_t)sizeof(float), "fused GRN: scaled-weight scratch is missing from the plan");
+          float* wsc = reinterpret_cast<float*>(ws + plan.tmp_offset);
+          const float* scale = rd(d.src0);  // launch 0: the scales grn_finalize_kernel left in the GRN slot -> the per-sample weight images in the scratch region
+          note_tmp(1);
+          rc = launch_grn_scale_weights(op.w_dma_dev, scale, wsc, batch, so.cp, sx.cp, op.bn, s);
+          ++launch_no;
+          const float* x = rd(g.src0);      // launch 1 (one GEMM per sample, recorded once): GELU output, weight images, residual -> dst
+          note_tmp(0);
+          const float* res = rd(d.src1);
+          float* y = wr(d.dst);
+          kv[op_index - 1] = PH_KV_ROWGEMM;
+          for (int b = 0; b < batch && rc == PH_OK; ++b) {
+            GemmArgs f{};
+            f.src0 = x + (size_t)b * hw * sx.cp;
+            f.wpack = wsc + (size_t)b * wfl;
+            f.bias = op.b_grn_dev;
+            f.residual = res + (size_t)b * hw * so.cp;
+            f.dst = y + (size_t)b * hw * so.cp;
+            f.zeros = m->zeros_dev;
+            f.c0p = sx.cp;
+            f.coutp = so.cp;
+            f.bn = op.bn;
+            f.M = hw;
+            f.mode = 0;
+            f.H = s0.h;
+            f.W = s0.w;
+            f.late_split = m->gemm_late_split;
+            rc = launch_gemm(f, s);
+          }
+          break;
+        }
         GemmArgs a{};
         a.src0 = rd(d.src0);
         a.wpack = op.w_dma_dev;
@@ -2005,6 +2118,15 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
           }
           a.residual = rd(d.src1);
         }
+        if (fuses_grn(m, op_index - 1, fmt)) {  // fused GRN plan: the epilogue also leaves the per-(32-row block, sample) sums of squares of its output in the scratch region
+          const int hw = so.h * so.w;
+          PH_REQUIRE(plan.tmp_bytes >= grn_fused_partial_floats(a.M, hw, so.cp) * (int64_t)sizeof(float), "fused GRN scratch is missing from the plan");
+          a.sumsq = reinterpret_cast<float*>(ws + plan.tmp_offset);
+          a.sq_hw = hw;
+          a.sq_nseg = grn_fused_nseg(hw);
+          note_tmp(1);
+          fused_grn = (int)op_index;
+        }
         a.late_split = m->gemm_late_split;
         // training program (Linear and GELU as separate ops, the pre-activation is kept for the backward pass): the
         // GEMM epilogue writes both the pre-activation and GELU(pre-activation), the GELU op after it becomes a no-op
@@ -2031,6 +2153,35 @@ int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32
         }
         kv[op_index - 1] = PH_KV_ROWGEMM;
         rc = launch_gemm(a, s);
+        break;
+      }
+      case PH_OP_GRN: {
+        const SlotShape& s0 = plan.slots[d.src0];
+        PH_REQUIRE(fmt == FMT_F32 && s0.c == d.cin0 && s0.cp == pad16(d.cout) && plan.slots[d.dst].cp == s0.cp, "GRN channel mismatch");
+        PH_REQUIRE(plan.tmp_bytes >= grn_scratch_floats(batch, s0.h * s0.w, s0.cp) * (int64_t)sizeof(float), "GRN scratch is missing from the plan");
+        if (fused_grn == (int)op_index - 1) {  // fused GRN plan: the block sums the Linear in front left in the scratch region -> scale[b][c] = 1 + weight[c] N[b,c], kept in this op's own slot
+          fused_grn = (int)op_index;
+          note_tmp(0);
+          kv[op_index - 1] = PH_KV_GRN_FUSED;
+          rc = launch_grn_finalize(reinterpret_cast<const float*>(ws + plan.tmp_offset), op.w_dev, wr(d.dst), batch, s0.h * s0.w, d.cout, s0.cp, s);
+          break;
+        }
+        GrnArgs a{};
+        a.src = rd(d.src0);  // launch 0, the reduction: the slot -> the slice sums in the scratch region
+        note_tmp(1);
+        ++launch_no;
+        rd(d.src0);          // launch 1, the apply pass: the slot and the slice sums -> dst
+        note_tmp(0);
+        a.weight = op.w_dev;
+        a.bias = op.b_dev;
+        a.dst = wr(d.dst);
+        a.partial = reinterpret_cast<float*>(ws + plan.tmp_offset);
+        a.B = batch;
+        a.HW = s0.h * s0.w;
+        a.c = d.cout;
+        a.cp = s0.cp;
+        kv[op_index - 1] = PH_KV_GRN;
+        rc = launch_grn(a, s);
         break;
       }
       case PH_OP_GLOBAL_MAXPOOL: {
@@ -2127,6 +2278,7 @@ std::vector<OptionRef> option_table(ph_model* m) {
       {"conv_wino4_min_cin", &m->conv_wino4_min_cin, nullptr},  // padded input channels from which a layer takes it
       {"conv_n32_wino2d", &m->conv_n32_wino2d, nullptr},  // Cout-32 / K >= 64 layers on the F(2x2,3x3) kernel with a half-empty N tile (0: the N-tile-32 F(2,3) kernel)
       {"conv_splitk_finish", &m->conv_splitk_finish, nullptr},  // 0: the split-K second stage as a launch of its own (A/B, tests)
+      {"grn_fuse", &m->grn_fuse, nullptr},                // ConvNeXtV2 blocks on the fused GRN plan: 1 sums of squares from the first Linear's epilogue + per-sample scaled weights for the second; 0 (default, measured faster) two GRN launches
       {"mlp_fuse", &m->mlp_fuse, nullptr},                // inference plans: CNBlock's two Linears (+ GELU, layer scale, residual) in one launch (cnblock_mlp_kernel)
       {"block_fuse", &m->block_fuse, nullptr},          // plain fp16, inference plans: the two convs of a 32-channel encoder block in one launch (block2_c32_f16_kernel)
       {"stem_f16mfma", &m->stem_f16mfma, nullptr},      // plain fp16: the fused first block with BOTH convs on the fp16 matrix pipe (stem_f16_kernel) instead of stem_fused_kernel<CIN, 3>
@@ -2164,6 +2316,16 @@ std::vector<OptionRef> option_table(ph_model* m) {
   };
 }
 }  // namespace
+
+int ph_model_set_input_norm(ph_model* m, const float* mean, const float* std, int32_t n) {
+  PH_REQUIRE(m && mean && std && n >= 1 && n <= 4, "ph_model_set_input_norm: needs 1..4 channels");
+  for (int c = 0; c < n; ++c) PH_REQUIRE(std[c] != 0.f && std::isfinite(std[c]) && std::isfinite(mean[c]), "ph_model_set_input_norm: channel %d has a zero or non-finite statistic", c);
+  for (int c = 0; c < n; ++c) {
+    m->in_mean[c] = mean[c];
+    m->in_std[c] = std[c];
+  }
+  return PH_OK;
+}
 
 int ph_model_set_option(ph_model* m, const char* key, double value) {
   PH_REQUIRE(m && key, "ph_model_set_option: null argument");

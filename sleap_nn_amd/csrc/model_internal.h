@@ -18,6 +18,7 @@ struct PackedOp {
   float* w2_dev = nullptr;
   float* b2_dev = nullptr;
   float* w_dma_dev = nullptr;  // conv weights in the LDS-DMA (quad-major piece) layout
+  float* b_grn_dev = nullptr;  // residual Linear behind a PH_OP_GRN: W2 grn.bias + b2, the bias of the fused GRN plan ("grn_fuse"); folded once, at creation
   float* w_mlp_dev = nullptr;  // Linear of a CNBlock MLP pair (inference programs): its weight as cnblock_mlp_kernel's LDS images
   int bn = 0;
   float* wd_gemm_dev[4] = {nullptr, nullptr, nullptr, nullptr};  // Linear / 2x2 conv: transposed weights (per tap) for the data gradient
@@ -122,6 +123,9 @@ struct ph_model {
   std::vector<int> last_bwd_variant;      // PH_KV_* code of the kernel each op's step of the last ph_model_backward ran (ph_model_last_backward_kernels)
   // ph_model_set_branch_scales: (branch_n, branch_batch) per-sample scales of the residual Linears' branches (stochastic depth), borrowed; nullptr = none
   const float* branch_scales = nullptr;
+  // ph_model_set_input_norm: per-channel statistics of a PH_FLAG_PAD0_NORM patch stem (the checkpoint's image_mean / image_std buffers)
+  float in_mean[4] = {0.f, 0.f, 0.f, 0.f};
+  float in_std[4] = {1.f, 1.f, 1.f, 1.f};
   int branch_n = 0, branch_batch = 0;
   // optional per-op HIP-event timing (ph_model_set_profiling)
   bool profiling = false;
@@ -155,6 +159,7 @@ struct ph_model {
   int conv_wino4_min_cin = 64;                // "conv_wino4_min_cin": padded input channels (both sources) from which a layer takes that kernel
   int conv_n32_wino2d = 1;                    // "conv_n32_wino2d" (1: inference plans, 2: every plan, 0: never): Cout-32 layers with >= 64 input channels (the last decoder level of an output-stride-2 UNet: 96 -> 32) on the F(2x2,3x3) kernel with a half-empty N tile of 64 instead of the N-tile-32 F(2,3) kernel
   int block_fuse = 1;                         // "block_fuse"
+  int grn_fuse = 0;                           // "grn_fuse": ConvNeXtV2 blocks on the fused GRN plan (sums of squares from the first Linear's epilogue, per-sample scaled weights for the second); 0 (default): grn_reduce_kernel + grn_apply_kernel -- measured faster, DESIGN 4.4e
   int mlp_fuse = 1;                           // "mlp_fuse": CNBlock's Linear -> GELU -> Linear -> scale + residual in one launch (cnblock_mlp_kernel) where the width fits
   int stem_f16mfma = 1;                       // "stem_f16mfma"
   int upsample_f16math = 1;                   // "upsample_f16math"

@@ -101,6 +101,10 @@ struct PatchStemArgs {
   const float* ln_gamma = nullptr;
   const float* ln_beta = nullptr;
   int ln_c = 0;
+  // PH_FLAG_PAD0_NORM (convnextv2_kernels.hip: patch_stem_norm_kernel): padding 0 and (x / 255 - mean[ci]) / std[ci] on the way in; cin <= 4
+  int pad0_norm = 0;
+  float mean[4] = {0.f, 0.f, 0.f, 0.f};
+  float std[4] = {1.f, 1.f, 1.f, 1.f};
 };
 
 struct DwConvArgs {
@@ -144,6 +148,10 @@ struct GemmArgs {
   // output row mapping: 0 = row m; 1 = row m is output pixel (b, oy, ox) of a 2x2/stride-2 conv and the result is
   // written to input pixel (b, 2oy + (out_tap >> 1), 2ox + (out_tap & 1)) of an out_H x out_W map (its data gradient)
   int out_patch = 0, out_tap = 0, out_H = 0, out_W = 0;
+  // mode 0, inference: also write sumsq[32-row block][segment][coutp] = sum over the block's rows of sample (first sample of the block + segment) of dst^2
+  // (rows are samples of sq_hw pixels each; sq_nseg >= 31 / sq_hw + 2 segment places per block; the fused GRN plan, convnextv2_kernels.hip)
+  float* sumsq = nullptr;
+  int sq_hw = 0, sq_nseg = 0;
 };
 
 int launch_patch_stem(const PatchStemArgs& a, hipStream_t s);
@@ -201,6 +209,27 @@ struct WindowAttnF16Args {
 int launch_window_attn_f16(const WindowAttnF16Args& a, hipStream_t s);
 int launch_patch_merge_ln_f16(const void* src, const float* gamma, const float* beta, void* dst, int B, int H, int W, int c, float eps, hipStream_t s);
 int launch_gemm(const GemmArgs& a, hipStream_t s);
+// ConvNeXtV2 (convnextv2_kernels.hip): the padding-0 patch stem with input statistics, and Global Response Normalization in two launches
+int launch_patch_stem_norm(const PatchStemArgs& a, hipStream_t s);
+struct GrnArgs {
+  const float* src = nullptr;      // (B, HW, cp)
+  const float* weight = nullptr;   // [cp], zero-padded
+  const float* bias = nullptr;     // [cp], zero-padded
+  float* dst = nullptr;            // (B, HW, cp); may not overlap src
+  float* partial = nullptr;        // grn_scratch_floats(B, HW, cp) floats: [B][slices][cp] sums of squares
+  int B = 0, HW = 0, c = 0, cp = 0;  // c: true channels (the channel mean is over them; pad channels of src are zeros and come out zero)
+};
+int grn_slices(int HW);            // pixel slices per sample: a function of HW alone, so a frame's sums do not depend on the batch it is in
+int64_t grn_scratch_floats(int B, int HW, int cp);
+int launch_grn(const GrnArgs& a, hipStream_t s);
+// The fused GRN plan: the first Linear's epilogue leaves per-(32-row block, sample segment) sums of squares (GemmArgs::sumsq);
+// grn_finalize turns them into scale[b][c] = 1 + weight[c] * N[b,c]; grn_scale_weights makes one copy per sample of the second Linear's packed weight
+// (pack_gemm layout, one tap, one source) with input channel c multiplied by scale[b][c]: W2 (s x + bias) + b2 = (W2 diag(s_b)) x + (W2 bias + b2)
+int grn_fused_nseg(int HW);                                   // segment places per 32-row block
+int64_t grn_fused_partial_floats(int M, int HW, int cp);
+int launch_grn_finalize(const float* partial, const float* weight, float* scale, int B, int HW, int c, int cp, hipStream_t s);
+int64_t gemm_pack_floats(int coutp, int c0p, int bn);          // floats of a one-tap, one-source pack_gemm image
+int launch_grn_scale_weights(const float* wpack, const float* scale, float* dst, int B, int coutp, int c0p, int bn, hipStream_t s);
 // CNBlock's MLP in one launch (cnblock_mlp_kernels.hip): dst = residual + scale * (W2 gelu(W1 x + b1) + b2) over (M, C) rows
 struct MlpArgs {
   const float* x = nullptr;         // (M, C): the LayerNorm output

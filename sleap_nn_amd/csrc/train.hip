@@ -315,6 +315,8 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
     PH_REQUIRE(!((op.d.flags & PH_FLAG_NO_TRAIN) && m->head_loss_kind[op.d.out_index] == 0),
                "ph_model_backward: head %d belongs to a segmentation model type, whose losses (BCE + Dice, masked smooth-L1) are not built: inference only", op.d.out_index);
   }
+  for (const auto& op : m->ops)  // the ConvNeXtV2 ops (GRN, the padding-0 stem with input statistics) carry PH_FLAG_NO_TRAIN: they have no backward
+    PH_REQUIRE(!(op.d.kind != PH_OP_HEAD && (op.d.flags & PH_FLAG_NO_TRAIN)), "ph_model_backward: op kind %d is inference only (a 'pretrained' ConvNeXtV2 backbone does not train here)", op.d.kind);
   PH_REQUIRE(m->last_plan.fmt == FMT_F32, "backward needs the activations of an exact-fp32 forward (handle option conv_precision = 0)");
   PH_REQUIRE(!m->last_plan.reuse, "backward needs every activation of the forward (handle option workspace_reuse = 0)");
   BwdPlan bp;

@@ -70,12 +70,15 @@ class LoadedAssets:
     def build_model(self):
         from sleap_nn_amd.architectures.model import Model
 
+        bb_cfg = self.backbone_config
+        if self.backbone_type == "pretrained":  # a relative model_name (a directory with a config.json) is looked up next to the checkpoint first; the stored config stays as the yaml has it
+            bb_cfg = {**bb_cfg, "_run_dir": os.path.abspath(self.model_dir)}
         if self.model_type == "centered_instance_segmentation":
             # a lone SegmentationHead with the sigmoid in its epilogue: the semantic type's program, built from the same `segmentation` leaf (whose
             # anchor_part / crop_size are data-pipeline entries, not head arguments); `model_type` here keeps the real name
-            m = Model(self.backbone_type, self.backbone_config, {"segmentation": self.head_config["segmentation"]}, "semantic_segmentation")
+            m = Model(self.backbone_type, bb_cfg, {"segmentation": self.head_config["segmentation"]}, "semantic_segmentation")
         else:
-            m = Model(self.backbone_type, self.backbone_config, self.head_config, self.model_type)
+            m = Model(self.backbone_type, bb_cfg, self.head_config, self.model_type)
         m.load_state_dict(self.state_dict, strict=True)
         return m
 
@@ -91,7 +94,7 @@ def load_model_assets(model_dir: str, ckpt_name: str = "best.ckpt") -> LoadedAss
     if model_type is None:
         raise ValueError(f"no known head config in {cfg_path}: {list(heads)}")
     bb = mc["backbone_config"]
-    backbone_type = next((k for k in ("unet", "convnext", "swint") if bb.get(k)), None)
+    backbone_type = next((k for k in ("unet", "convnext", "swint", "pretrained") if bb.get(k)), None)
     if backbone_type is None:
         raise ValueError(f"no backbone config in {cfg_path}")
     skels = cfg.get("data_config", {}).get("skeletons") or []

@@ -62,6 +62,8 @@ class TrainingModule:
         if getattr(model, "model_type", None) in SEGMENTATION_MODEL_TYPES and not self._trains_segmentation:
             raise NotImplementedError(f"training a '{model.model_type}' model is not built here (BCE + Dice, masked smooth-L1 and mask targets): these model types are "
                                       "not trained with the MSE loss of the pose heads; use sleap_nn_amd.training.segmentation.SegmentationTrainingModule")
+        if getattr(model, "backbone_type", None) == "pretrained":
+            raise NotImplementedError("training a 'pretrained' (ConvNeXtV2) backbone is not built on the MI355X path (GRN and the padding-0 stem have no backward): inference only")
         L.lib()
         if not torch.cuda.is_available():
             raise RuntimeError("TrainingModule needs an MI355X; there is no CPU fallback")
