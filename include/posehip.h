@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 123
+#define PH_VERSION 124
 
 /* error codes */
 #define PH_OK 0
@@ -116,11 +116,15 @@ enum ph_op_kind {
                              token's own pixel: pad, roll, window partition, reverse and crop are index arithmetic of the one launch.
                              Backward (window_attn_bwd_kernel): S and P are recomputed from the qkv slot; gradients of the slot, of the table and -- through the
                              padded tokens, whose q, k, v are qkv.bias -- of qkv.bias */
-  /* ConvNeXtV2 encoder (HuggingFace ConvNextV2Backbone behind the reference's PretrainedBackbone, architectures/pretrained.py).  Inference only, exact fp32. */
+  /* ConvNeXtV2 encoder (HuggingFace ConvNextV2Backbone behind the reference's PretrainedBackbone, architectures/pretrained.py).  Exact fp32.  Its two ops of its own
+     (PH_OP_GRN, the PH_FLAG_PAD0_NORM stem) carry PH_FLAG_NO_TRAIN: ph_model_backward runs their steps on a handle whose option pretrained_train is 1
+     (convnextv2_train_kernels.hip; the stem's weight gradient is the patch stem's im2col + row-wgrad GEMM over normalised patches) and refuses the program otherwise. */
   PH_OP_GRN = 18          /* Global Response Normalization over a (B, H, W, C) slot (cin0 = cout = C): G[b,c] = sqrt(sum_hw x^2), N[b,c] = G[b,c] / (mean_c G[b,:] + 1e-6),
                              dst = weight[c] * (x * N[b,c]) + bias[c] + x; weight / bias (1,1,1,C).  Two launches (convnextv2_kernels.hip): grn_reduce_kernel writes
                              per-(sample, pixel slice, channel) sums of squares into the scratch region -- fixed slices, no atomics, so two forwards are bit-identical --
-                             and grn_apply_kernel adds the slices in order, takes the channel mean over the C true channels and applies; pad channels come out zero */
+                             and grn_apply_kernel adds the slices in order, takes the channel mean over the C true channels and applies; pad channels come out zero.
+                             Backward (T = sum_hw g x, D = mean_c G + 1e-6, dG = w T / D - (sum_c w T G) / (C D^2), K = dG / G where G > 0 else 0):
+                             dx = g (1 + w N) + x K, dweight[c] = sum_b T N, dbias[c] = sum_{b,hw} g; the same fixed slices, sums added in slice and sample order */
 };
 
 #define PH_FLAG_RELU 1
@@ -130,7 +134,8 @@ enum ph_op_kind {
 #define PH_FLAG_SOFTMAX 16 /* PH_OP_HEAD: softmax over the output channels (ClassVectorsHead, heads.py:536-537) */
 #define PH_FLAG_SILU 32    /* PH_OP_CONVT: SiLU instead of ReLU (the activation is an epilogue parameter of the phase GEMMs) */
 #define PH_FLAG_NO_TRAIN 64 /* PH_OP_HEAD: a head of the segmentation model types, which neither MSE nor cross entropy trains; the forward ignores it,
-                               ph_model_backward refuses the program unless ph_model_set_head_loss chose the head's loss on this handle */
+                               ph_model_backward refuses the program unless ph_model_set_head_loss chose the head's loss on this handle.
+                               PH_OP_GRN / PH_OP_PATCH_STEM with PH_FLAG_PAD0_NORM: refused unless the handle option pretrained_train is 1 */
 #define PH_FLAG_LN_EPS_1EM5 128 /* PH_OP_LAYERNORM / PH_OP_PATCH_MERGE: eps 1e-5 (nn.LayerNorm's default: the Swin norms) instead of 1e-6 */
 #define PH_FLAG_RESIDUAL 256    /* PH_OP_LINEAR: dst = acc + bias + src1 (a residual add without a layer scale: Swin's attn.proj and mlp.3; ConvNeXtV2's pwconv2) */
 #define PH_FLAG_PAD0_NORM 512   /* PH_OP_PATCH_STEM: padding 0 instead of 1 and the input is (x / 255 - mean[ci]) / std[ci] with the handle's input statistics
@@ -367,7 +372,11 @@ int ph_debug_row_wgrad_bench(int32_t M, int32_t n, int32_t k, int32_t iters, flo
  * depthwise / stem kernels), "wgrad_wino" (3x3 weight gradients in the Winograd domain), "mask_fold" (ReLU masks applied by the kernel
  * that completes a gradient), "conv_f16_rows" (plain fp16: conv3x3_f16_rows_kernel 1 where its plan is estimated faster | 2 wherever the shape fits | 0 never), "upsample_f16math"
  * (plain fp16: the bilinear x2 blended in packed fp16 arithmetic, folded or standalone: same bits), "stem_f16mfma" (plain fp16: stem_f16_kernel), "block_fuse" (plain fp16, inference plans:
- * the two convs of a 32-channel encoder block in one launch), "mlp_fuse" (inference plans: CNBlock's Linear + GELU + Linear + layer scale + residual in one launch at 96 / 192 channels).
+ * the two convs of a 32-channel encoder block in one launch), "mlp_fuse" (inference plans: CNBlock's Linear + GELU + Linear + layer scale + residual in one launch at 96 / 192 channels),
+ * "grn_fuse" (inference plans: ConvNeXtV2 blocks on the fused GRN plan; only a program whose first Linear carries the GELU can take it, so the unfused training program runs the
+ * two-launch GRN forward whatever this says).  Two keys are switches of ph_model_backward, not kernel variants: "pretrained_train" (1: the backward accepts a
+ * ConvNeXtV2 program, whose GRN and padding-0 stem ops carry PH_FLAG_NO_TRAIN; 0, the default: it refuses them) and "bwd_frozen_ops" (n: the first n ops of the program get no
+ * backward step and none of their parameters' gradients is written -- a frozen encoder; the bucket event and the two-bucket exchange still fire; 0, the default: every op).
  * Unknown key -> PH_E_INVALID. */
 int ph_model_set_option(ph_model* m, const char* key, double value);
 int ph_model_get_option(const ph_model* m, const char* key, double* value);
@@ -413,12 +422,14 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_GRN 25 /* grn_reduce_kernel + grn_apply_kernel: Global Response Normalization, fixed-slice sums of squares then the apply pass */
 #define PH_KV_GRN_FUSED 26 /* grn_finalize_kernel: the fused GRN plan ("grn_fuse"); the sums of squares come from the Linear in front (gemm_mfma_dma_kernel<.., EPI = 2>), the Linear behind runs per sample on weights scaled by grn_scale_weights_kernel */
 #define PH_KV_PATCH_STEM_NORM 27 /* patch_stem_norm_kernel: the padding-0 patch stem with input statistics (PH_FLAG_PAD0_NORM) */
+#define PH_KV_GRN_BWD 28 /* grn_bwd_reduce_kernel + grn_bwd_sample_kernel + grn_bwd_param_kernel + grn_bwd_apply_kernel (ph_model_last_backward_kernels): backward of a PH_OP_GRN step, fixed-slice sums, no atomics */
 #define PH_KV_FUSED 11   /* no launch of its own: a 1x1 head computed in the epilogue of the conv that produces its input */
 int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
 /* Per-op times of the LAST ph_model_backward, recorded while profiling is on (ph_model_set_profiling).  op_ms[i]: op i's step of the reverse sweep; op_ms_first[i]: its part up to the
  * first data-gradient GEMM (Linear / 2x2-stride-2 ops: the scaling pass and the weight-gradient GEMM; 0 elsewhere); *loss_ms: losses and head-output gradients. */
 int ph_model_backward_profile_read(ph_model* m, double* op_ms, double* op_ms_first, int32_t n_ops, double* loss_ms);
-/* ... and of the LAST ph_model_backward: PH_KV_WINDOW_ATTN_BWD for a PH_OP_WINDOW_ATTN step, PH_KV_ROWGEMM for a Linear / 2x2-stride-2 step, 0 elsewhere. */
+/* ... and of the LAST ph_model_backward: PH_KV_WINDOW_ATTN_BWD for a PH_OP_WINDOW_ATTN step, PH_KV_GRN_BWD for a PH_OP_GRN step, PH_KV_ROWGEMM for a Linear / 2x2-stride-2 step,
+ * 0 elsewhere -- and for every op of a frozen prefix (handle option bwd_frozen_ops), which runs no step. */
 int ph_model_last_backward_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
 
 /* Which workspace byte ranges every launch of the LAST ph_model_forward was handed, as the run-time routing decided them (tests of the

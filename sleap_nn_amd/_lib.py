@@ -29,6 +29,7 @@ SWIN_KV_WINDOW_ATTN = 21  # PH_KV_WINDOW_ATTN (swin_kernels.hip); not named KV_*
 SWIN_KV_WINDOW_ATTN_BWD = 24  # PH_KV_WINDOW_ATTN_BWD (swin_train_kernels.hip): reported by ph_model_last_backward_kernels
 SWIN_KV_WINDOW_ATTN_F16, SWIN_KV_F16_MERGE_LN = 22, 23  # PH_KV_WINDOW_ATTN_F16 / PH_KV_SWIN_F16_MERGE_LN: the Swin ops on fp16 activations (swin_f16_kernels.hip, handle option swint_f16)
 CNX2_KV_GRN, CNX2_KV_GRN_FUSED, CNX2_KV_PATCH_STEM_NORM = 25, 26, 27  # PH_KV_GRN / PH_KV_GRN_FUSED / PH_KV_PATCH_STEM_NORM (convnextv2_kernels.hip)
+CNX2_KV_GRN_BWD = 28  # PH_KV_GRN_BWD (convnextv2_train_kernels.hip): reported by ph_model_last_backward_kernels
 CNX_KV_F16_STEM, CNX_KV_F16_DW, CNX_KV_F16_LN, CNX_KV_F16_GEMM, CNX_KV_F16_ELTWISE = 16, 17, 18, 19, 20  # PH_KV_CNX_F16_*: the ConvNeXt encoder ops on fp16 activations (convnext_f16_kernels.hip); not named KV_*: that prefix lists the families a 3x3 conv can come back with (benchlegs.common.conv_kernel_short_names)
 KV_NAMES = {KV_NONE: "none", KV_DIRECT: "conv3x3_mfma_dma_persist_kernel (direct)", KV_WINO1D: "conv3x3_wino_persist_kernel (Winograd F(2,3) along x)",
             KV_WINO2D: "conv3x3_wino2d_kernel<64> (Winograd F(2x2,3x3))", KV_W16: "conv3x3_w16_kernel (wave-private Winograd F(2x2,3x3), 16x16x4 MFMA)",
@@ -50,8 +51,9 @@ KV_NAMES = {KV_NONE: "none", KV_DIRECT: "conv3x3_mfma_dma_persist_kernel (direct
             SWIN_KV_F16_MERGE_LN: "patch_merge_ln_f16_kernel (four-phase gather + LayerNorm(4C), fp16 storage, fp32 moments)",
             CNX2_KV_GRN: "grn_reduce_kernel + grn_apply_kernel (Global Response Normalization: fixed-slice sums of squares, then the apply pass)",
             CNX2_KV_GRN_FUSED: "grn_finalize_kernel (fused GRN plan: sums of squares from the Linear in front, per-sample scaled weights for the Linear behind)",
-            CNX2_KV_PATCH_STEM_NORM: "patch_stem_norm_kernel (padding-0 patch stem with input statistics)"}
-KV_MFMA_SHARE = {KV_NONE: 0.0, KV_DIRECT: 1.0, KV_WINO1D: 2.0 / 3.0, KV_WINO2D: 4.0 / 9.0, KV_W16: 4.0 / 9.0, KV_C16: 1.0, KV_ROWGEMM: 1.0, KV_WINO4: 0.25, KV_F16: 1.0, KV_STEM: 4.0 / 9.0, KV_WINO2D_KS: 4.0 / 9.0, KV_FUSED: 0.0, KV_SMALLMAP: 4.0 / 9.0, KV_F16_ROWS: 1.0, KV_F16_BLOCK: 1.0, KV_MLP: 1.0, CNX_KV_F16_STEM: 0.0, CNX_KV_F16_DW: 0.0, CNX_KV_F16_LN: 0.0, CNX_KV_F16_GEMM: 1.0, CNX_KV_F16_ELTWISE: 0.0, SWIN_KV_WINDOW_ATTN: 1.0, SWIN_KV_WINDOW_ATTN_BWD: 1.0, SWIN_KV_WINDOW_ATTN_F16: 1.0, SWIN_KV_F16_MERGE_LN: 0.0, CNX2_KV_GRN: 0.0, CNX2_KV_GRN_FUSED: 0.0, CNX2_KV_PATCH_STEM_NORM: 0.0}
+            CNX2_KV_PATCH_STEM_NORM: "patch_stem_norm_kernel (padding-0 patch stem with input statistics)",
+            CNX2_KV_GRN_BWD: "grn_bwd_reduce_kernel + grn_bwd_sample_kernel + grn_bwd_param_kernel + grn_bwd_apply_kernel (backward of Global Response Normalization, fixed-order sums)"}
+KV_MFMA_SHARE = {KV_NONE: 0.0, KV_DIRECT: 1.0, KV_WINO1D: 2.0 / 3.0, KV_WINO2D: 4.0 / 9.0, KV_W16: 4.0 / 9.0, KV_C16: 1.0, KV_ROWGEMM: 1.0, KV_WINO4: 0.25, KV_F16: 1.0, KV_STEM: 4.0 / 9.0, KV_WINO2D_KS: 4.0 / 9.0, KV_FUSED: 0.0, KV_SMALLMAP: 4.0 / 9.0, KV_F16_ROWS: 1.0, KV_F16_BLOCK: 1.0, KV_MLP: 1.0, CNX_KV_F16_STEM: 0.0, CNX_KV_F16_DW: 0.0, CNX_KV_F16_LN: 0.0, CNX_KV_F16_GEMM: 1.0, CNX_KV_F16_ELTWISE: 0.0, SWIN_KV_WINDOW_ATTN: 1.0, SWIN_KV_WINDOW_ATTN_BWD: 1.0, SWIN_KV_WINDOW_ATTN_F16: 1.0, SWIN_KV_F16_MERGE_LN: 0.0, CNX2_KV_GRN: 0.0, CNX2_KV_GRN_FUSED: 0.0, CNX2_KV_PATCH_STEM_NORM: 0.0, CNX2_KV_GRN_BWD: 0.0}
 
 
 class OpDesc(C.Structure):

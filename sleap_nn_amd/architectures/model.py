@@ -26,7 +26,7 @@ PRECISIONS = {"exact": 0, "split": 1, "fp16": 2}
 
 
 def get_backbone(backbone: str, backbone_config):
-    """architectures/model.py:36-67.  ``unet``, ``convnext``, ``swint`` and ``pretrained`` (the ConvNeXtV2 family, inference) are built natively."""
+    """architectures/model.py:36-67.  ``unet``, ``convnext``, ``swint`` and ``pretrained`` (the ConvNeXtV2 family) are built natively; all four train on the device."""
     if backbone == "unet":
         return UNet.from_config(backbone_config)
     if backbone == "convnext":
@@ -275,17 +275,62 @@ class Model:
     def eval(self) -> "Model":
         return self.set_fusion(True)
 
-    def train(self, mode: bool = True, allow_swint: bool = False) -> "Model":
+    def train(self, mode: bool = True, allow_swint: bool = False, allow_pretrained: bool = False) -> "Model":
         """Training keeps every activation: the op-by-op (unfused) program runs.  A Swin backbone trains on request only
         (``allow_swint=True``; ``TrainingModule(model, swint_training=True)`` passes it): its backward is the window-attention,
-        patch-merge and residual steps of ``ph_model_backward`` (csrc/swin_train_kernels.hip)."""
+        patch-merge and residual steps of ``ph_model_backward`` (csrc/swin_train_kernels.hip).  So does a ``pretrained`` (ConvNeXtV2)
+        backbone (``allow_pretrained=True``; ``TrainingModule(model, pretrained_training=True)``): its GRN and stem ops keep ``FLAG_NO_TRAIN`` and the handle
+        option ``pretrained_train`` lifts the refusal of ``ph_model_backward`` (csrc/convnextv2_train_kernels.hip).  The training program is the
+        unfused one: it runs the two-launch GRN forward whatever ``grn_fuse`` says."""
         if mode and self.backbone_type == "pretrained":
-            raise NotImplementedError("training a 'pretrained' (ConvNeXtV2) backbone is not built on the MI355X path: GRN and the padding-0 stem have no backward "
-                                      "(their ops carry PH_FLAG_NO_TRAIN); inference only")
+            if not allow_pretrained:
+                raise NotImplementedError("training a 'pretrained' (ConvNeXtV2) backbone is opt-in on the MI355X path (its GRN and padding-0 stem ops carry PH_FLAG_NO_TRAIN): "
+                                          "Model.train(True, allow_pretrained=True), or TrainingModule(model, pretrained_training=True)")
+            self.backbone.check_trainable()
+            self.set_option("pretrained_train", 1)
         if mode and self.backbone_type == "swint" and not allow_swint:
             raise NotImplementedError("training a 'swint' backbone is opt-in on the MI355X path: Model.train(True, allow_swint=True), or "
                                       "TrainingModule(model, swint_training=True)")
         return self.set_fusion(not mode)
+
+    def trainable_ranges(self, freeze_encoder: Optional[bool] = None) -> List[tuple]:
+        """``[(start, end), ...]`` of the flat parameter arena (``param_keys`` order) that an optimizer steps: sorted, disjoint, on parameter boundaries, neighbours
+        merged.  Left out are the parameters no op of the program reads (a ``pretrained`` backbone's ``hidden_states_norms.stem``: torch leaves their ``.grad`` at
+        ``None`` and its optimizers skip them, so not even AdamW's decay may touch them) and, with ``freeze_encoder`` (default: the backbone config's ``freeze``),
+        every ``backbone.enc.*`` parameter -- the reference's ``freeze_encoder()``."""
+        freeze = bool(getattr(self.backbone, "freeze", False)) if freeze_encoder is None else bool(freeze_encoder)
+        # an op is live when it is a head or a live op reads its output (a stage norm whose map the decoder does not take is an op, and dead: output_stride 8)
+        read, live_slots = set(), set()
+        for o in reversed(self.unfused_ops):
+            if o.kind == L.OP_HEAD or o.dst in live_slots or (o.dst2 >= 0 and o.dst2 in live_slots):
+                live_slots.update(s for s in (o.src0, o.src1) if s >= 0)
+                read.update(k for k in (o.weight, o.bias, o.weight2, o.bias2) if k)
+        out: List[tuple] = []
+        off = 0
+        for k in self.param_keys():
+            n = 1
+            for d in self.param_shapes[k]:
+                n *= int(d)
+            if k in read and not (freeze and k.startswith("backbone.enc.")):
+                if out and out[-1][1] == off:
+                    out[-1] = (out[-1][0], off + n)
+                else:
+                    out.append((off, off + n))
+            off += n
+        return out
+
+    def adapt_channels(self, x: torch.Tensor, code: int):
+        """architectures/model.py:239-245 (gray <-> rgb) for a frame whose channel count is not the network's: ``(x, dtype code)`` as the native calls take them.
+        Rare path, done with torch plumbing; the result is float in [0, 1] (code 1)."""
+        if x.shape[1] == self.in_channels:
+            return x, code
+        xf = x.float() / 255.0 if code in (0, 2) else x
+        if x.shape[1] == 1:
+            xf = xf.repeat(1, 3, 1, 1)
+        elif x.shape[1] == 3:
+            r, g, b = xf.unbind(dim=1)
+            xf = (0.2989 * r + 0.587 * g + 0.114 * b).unsqueeze(1)
+        return xf, 1
 
     def residual_branches(self) -> int:
         """Number of residual Linear ops (``FLAG_RESIDUAL``) of the current program: the rows of ``ph_model_set_branch_scales``."""
@@ -488,15 +533,7 @@ class Model:
         else:
             x = x.to(torch.float32)
             code = 1 if in_dtype is None else in_dtype
-        if x.shape[1] != self.in_channels:
-            # architectures/model.py:239-245 (gray <-> rgb); rare path, done with torch plumbing
-            xf = x.float() / 255.0 if code in (0, 2) else x
-            if x.shape[1] == 1:
-                xf = xf.repeat(1, 3, 1, 1)
-            elif x.shape[1] == 3:
-                r, g, b = xf.unbind(dim=1)
-                xf = (0.2989 * r + 0.587 * g + 0.114 * b).unsqueeze(1)
-            x, code = xf, 1
+        x, code = self.adapt_channels(x, code)
         x = x.contiguous()
         B, Cin, H, W = x.shape
         self._ensure(device)

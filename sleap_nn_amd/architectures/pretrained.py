@@ -9,7 +9,14 @@ and the buffers ``backbone.image_mean`` / ``backbone.image_std`` are read from t
 
 Nothing here can reach a network: the architecture comes from a local directory with a ``config.json`` or from the
 size word of a ``convnextv2-<size>`` id; the weights come from the checkpoint.  Every other family, the encoder-only
-mode and a subset of the stages are refused by name.  Inference only: the ops carry ``FLAG_NO_TRAIN``.
+mode and a subset of the stages are refused by name.
+
+Training is opt-in (``Model.train(True, allow_pretrained=True)``, ``TrainingModule(model, pretrained_training=True)``): the GRN and stem ops
+carry ``FLAG_NO_TRAIN``, which ``ph_model_backward`` honours unless the handle option ``pretrained_train`` is set; their backward steps are
+``csrc/convnextv2_train_kernels.hip`` and the normalised-patch weight gradient of ``csrc/convnext_train_kernels.hip``.  ``freeze: true``
+has the reference's meaning (``freeze_encoder()``, lightning_modules.py:232-236): no ``backbone.enc.*`` parameter receives a gradient or an optimizer
+update (``encoder_ops`` / ``Model.trainable_ranges``).  ``drop_path_rate`` of a local ``config.json`` is read and, where non-zero, refused at the opt-in:
+the published ConvNeXtV2 configs have 0.0.
 
 A block is six ops: depthwise 7x7 -> LayerNorm -> Linear C->4C -> GELU -> GRN -> Linear 4C->C with the residual add
 in its epilogue (no layer scale).  ``Model._fuse_cnblocks`` folds the GELU into the first Linear for inference.
@@ -73,11 +80,12 @@ def resolve_architecture(model_name: str, run_dir: Optional[str] = None) -> dict
         depths = [int(v) for v in (hf.get("depths") or CONVNEXTV2_SIZES["tiny"]["depths"])]
         hidden = [int(v) for v in (hf.get("hidden_sizes") or CONVNEXTV2_SIZES["tiny"]["hidden_sizes"])]
         return {"depths": depths, "hidden_sizes": hidden, "patch_size": int(hf.get("patch_size", 4)), "num_channels": int(hf.get("num_channels", 3)),
-                "layer_norm_eps": eps, "source": path}
+                "layer_norm_eps": eps, "drop_path_rate": float(hf.get("drop_path_rate", 0.0)), "source": path}
     m = re.search(r"convnextv2-([a-z]+)", name.lower())
     if m and m.group(1) in CONVNEXTV2_SIZES:
         a = CONVNEXTV2_SIZES[m.group(1)]
-        return {"depths": list(a["depths"]), "hidden_sizes": list(a["hidden_sizes"]), "patch_size": 4, "num_channels": 3, "layer_norm_eps": 1e-12, "source": m.group(0)}
+        return {"depths": list(a["depths"]), "hidden_sizes": list(a["hidden_sizes"]), "patch_size": 4, "num_channels": 3, "layer_norm_eps": 1e-12, "drop_path_rate": 0.0,
+                "source": m.group(0)}
     raise _refuse(f"model_name {name!r} (no local config.json, not a convnextv2-<size> id: ResNet, Swinv2, DINO and the isotropic ViTs are other families)")
 
 
@@ -92,7 +100,8 @@ class PretrainedBackbone:
     weights: bool = True  # ignored: the checkpoint supplies the weights
     mode: str = "auto"
     out_indices: Optional[List[int]] = None
-    freeze: bool = False  # accepted, unused (inference only)
+    freeze: bool = False  # the reference's freeze_encoder(): backbone.enc.* gets no gradient and no optimizer update (TrainingModule)
+    drop_path_rate: float = 0.0  # config.json's; the eval forward ignores it, a non-zero value is refused when training is switched on
     revision: Optional[str] = None  # accepted, unused (nothing is downloaded)
     normalize: bool = True
     image_mean: Optional[List[float]] = None
@@ -141,6 +150,7 @@ class PretrainedBackbone:
             filters_rate=cfg_get(config, "filters_rate", 2.0), convs_per_block=int(cfg_get(config, "convs_per_block", 2)),
             kernel_size=int(cfg_get(config, "kernel_size", 3)), up_interpolate=bool(cfg_get(config, "up_interpolate", True)),
             depths=[int(d) for d in arch["depths"]], channels=[int(c) for c in arch["hidden_sizes"]], patch_size=int(arch["patch_size"]),
+            drop_path_rate=float(arch.get("drop_path_rate", 0.0)),
         )
         net._build()
         return net
@@ -152,6 +162,16 @@ class PretrainedBackbone:
     @property
     def max_channels(self) -> int:
         return int(self.channels[-1])  # middle_blocks[-1].filters: the bottleneck (pretrained.py:403-404)
+
+    def encoder_ops(self) -> int:
+        """Number of leading ops of the program that belong to the encoder (everything up to the last op with a ``backbone.enc.*`` parameter): the
+        frozen prefix of ``ph_model_backward`` (handle option ``bwd_frozen_ops``) under ``freeze``."""
+        return 1 + max(i for i, o in enumerate(self.ops) if (o.weight or "").startswith("backbone.enc."))
+
+    def check_trainable(self) -> None:
+        """What the opt-in to training refuses by name."""
+        if self.drop_path_rate != 0.0:
+            raise _refuse(f"training with drop_path_rate={self.drop_path_rate} (stochastic depth of the ConvNeXtV2 blocks; the published configs have 0.0)")
 
     def norm_stats(self) -> Tuple[List[float], List[float]]:
         """pretrained.py:270-297 without the image processor (a network read): explicit values, identity when disabled, else ImageNet."""
@@ -200,7 +220,7 @@ class PretrainedBackbone:
         self.labels[name + ".grn"] = y
         p[name + ".pwconv2.weight"] = (c, 4 * c)
         p[name + ".pwconv2.bias"] = (c,)
-        # no layer scale, drop path is the identity in eval: the residual add is the GEMM's PH_FLAG_RESIDUAL epilogue
+        # no layer scale; drop path is the identity in eval and at drop_path_rate 0 (the only rate that trains here): the residual add is the GEMM's PH_FLAG_RESIDUAL epilogue
         y = self._emit(OpSpec(L.OP_LINEAR, y, x, self._new_slot(), 4 * c, 0, c, 1, L.FLAG_RESIDUAL, name + ".pwconv2.weight", name + ".pwconv2.bias", label=name))
         self.labels[name] = y
         return y

@@ -660,8 +660,12 @@ int launch_row_wgrad_part(const RowWgradArgs& a0, int n, int k, int k_total, int
 // The image patches are written once as rows [pixel][ci*k*k + tap] (im2col, <= 48 floats per pixel, padded
 // to a multiple of 16) and the gradient is one row-wgrad GEMM over them.
 // ---------------------------------------------------------------------------------------
+struct PatchNorm {  // input statistics of a PH_FLAG_PAD0_NORM stem: patches are (x / 255 - mean[ci]) / std[ci], the expression of patch_stem_norm_kernel
+  int on = 0;
+  float mean[4] = {0.f, 0.f, 0.f, 0.f}, std[4] = {1.f, 1.f, 1.f, 1.f};
+};
 __global__ __launch_bounds__(256) void patch_im2col_kernel(const void* __restrict__ img, int dtype, int B, int cin, int H, int W, int OH, int OW, int k, int stride, int pad,
-                                                           int kp, float* __restrict__ out) {
+                                                           int kp, float* __restrict__ out, PatchNorm norm) {
   const int kk = k * k, n_item = cin * kk;
   const size_t total = (size_t)B * OH * OW * kp;
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
@@ -683,19 +687,20 @@ __global__ __launch_bounds__(256) void patch_im2col_kernel(const void* __restric
           v = reinterpret_cast<const float*>(img)[o];
           if (dtype == 2) v = v / 255.0f;
         }
+        if (norm.on) v = (v - norm.mean[ci]) / norm.std[ci];  // (padding 0: no tap of such a stem lies outside the image)
       }
     }
     out[idx] = v;
   }
 }
-int launch_patch_stem_wgrad(const void* img, int dtype, const float* dy, int B, int cin, int H, int W, int OH, int OW, int k, int stride, int pad, int coutp, int cout, float* gw,
-                            float* scratch, hipStream_t s) {
+static int patch_stem_wgrad(const void* img, int dtype, const float* dy, int B, int cin, int H, int W, int OH, int OW, int k, int stride, int pad, int coutp, int cout, float* gw,
+                            float* scratch, const PatchNorm& norm, hipStream_t s) {
   const int n_item = cin * k * k, kp = pad16(n_item);
   const size_t npix = (size_t)B * OH * OW;
   float* patches = scratch;
   float* slab = scratch + align_up((int64_t)npix * kp, 64);
   const size_t total = npix * kp;
-  hipLaunchKernelGGL(patch_im2col_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 256 * 64)), dim3(256), 0, s, img, dtype, B, cin, H, W, OH, OW, k, stride, pad, kp, patches);
+  hipLaunchKernelGGL(patch_im2col_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 256 * 64)), dim3(256), 0, s, img, dtype, B, cin, H, W, OH, OW, k, stride, pad, kp, patches, norm);
   PH_HIP_CHECK(hipGetLastError());
   RowWgradArgs a{};
   a.dy = dy;
@@ -705,6 +710,21 @@ int launch_patch_stem_wgrad(const void* img, int dtype, const float* dy, int B, 
   a.kp = kp;
   a.M = (int)npix;
   return launch_row_wgrad(a, cout, n_item, 1, gw, s);  // canonical (cout, cin, k, k) == [co][ci*k*k + tap]
+}
+int launch_patch_stem_wgrad(const void* img, int dtype, const float* dy, int B, int cin, int H, int W, int OH, int OW, int k, int stride, int pad, int coutp, int cout, float* gw,
+                            float* scratch, hipStream_t s) {
+  return patch_stem_wgrad(img, dtype, dy, B, cin, H, W, OH, OW, k, stride, pad, coutp, cout, gw, scratch, PatchNorm{}, s);
+}
+int launch_patch_stem_wgrad_norm(const void* img, int dtype, const float* dy, int B, int cin, int H, int W, int OH, int OW, int k, int stride, int coutp, int cout, const float* mean4,
+                                 const float* std4, float* gw, float* scratch, hipStream_t s) {
+  PH_REQUIRE(cin >= 1 && cin <= 4 && OH == (H - k) / stride + 1 && OW == (W - k) / stride + 1 && OH > 0 && OW > 0, "patch stem weight gradient: %d input channels, output %d x %d do not fit padding 0", cin, OH, OW);
+  PatchNorm norm;
+  norm.on = 1;
+  for (int c = 0; c < 4; ++c) {
+    norm.mean[c] = mean4[c];
+    norm.std[c] = std4[c];
+  }
+  return patch_stem_wgrad(img, dtype, dy, B, cin, H, W, OH, OW, k, stride, 0, coutp, cout, gw, scratch, norm, s);
 }
 int64_t patch_stem_wgrad_scratch_floats(int cin, int cout, int k, int64_t npix) {
   const int kp = pad16(cin * k * k);

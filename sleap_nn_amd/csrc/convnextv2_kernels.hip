@@ -74,7 +74,7 @@ int launch_patch_stem_norm(const PatchStemArgs& a, hipStream_t s) {
 constexpr int GRN_MIN_SLICE = 256;  // pixels
 constexpr int GRN_MAX_SLICES = 32;
 
-static int grn_slice_pixels(int HW) { return std::max(GRN_MIN_SLICE, (HW + GRN_MAX_SLICES - 1) / GRN_MAX_SLICES); }
+int grn_slice_pixels(int HW) { return std::max(GRN_MIN_SLICE, (HW + GRN_MAX_SLICES - 1) / GRN_MAX_SLICES); }
 int grn_slices(int HW) { return (HW + grn_slice_pixels(HW) - 1) / grn_slice_pixels(HW); }
 int64_t grn_scratch_floats(int B, int HW, int cp) { return (int64_t)B * grn_slices(HW) * cp; }
 
@@ -215,6 +215,24 @@ __global__ __launch_bounds__(256) void grn_finalize_kernel(const float* __restri
 int launch_grn_finalize(const float* partial, const float* weight, float* scale, int B, int HW, int c, int cp, hipStream_t s) {
   PH_REQUIRE(partial && weight && scale && B > 0 && HW > 0 && c > 0 && c <= cp && (cp & 15) == 0 && cp <= 15360, "launch_grn_finalize: bad arguments");
   hipLaunchKernelGGL(grn_finalize_kernel, dim3(B), dim3(256), (size_t)cp * sizeof(float), s, partial, weight, scale, HW, c, cp, grn_fused_nseg(HW));
+  PH_HIP_CHECK(hipGetLastError());
+  return PH_OK;
+}
+
+// The fused plan's constant term W2 grn.bias + b2, recomputed from a device parameter arena (ph_model_set_params: ph_model_create folds it on the host, and the parameters
+// move once the backbone trains).  One thread per output channel, a double-precision sum in input-channel order: the products of two floats are exact in double, so
+// this is the host fold bit for bit.  cout x cin multiply-adds, once per parameter upload of an inference handle.
+__global__ __launch_bounds__(256) void grn_fold_bias_kernel(const float* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ grn_bias, float* __restrict__ dst, int cout, int cin) {
+  const int co = blockIdx.x * 256 + threadIdx.x;
+  if (co >= cout) return;
+  double acc = b2[co];
+  for (int ci = 0; ci < cin; ++ci) acc += (double)w2[(size_t)co * cin + ci] * (double)grn_bias[ci];
+  dst[co] = (float)acc;
+}
+
+int launch_grn_fold_bias(const float* w2, const float* b2, const float* grn_bias, float* dst, int cout, int cin, hipStream_t s) {
+  PH_REQUIRE(w2 && b2 && grn_bias && dst && cout > 0 && cin > 0, "launch_grn_fold_bias: bad arguments");
+  hipLaunchKernelGGL(grn_fold_bias_kernel, dim3((cout + 255) / 256), dim3(256), 0, s, w2, b2, grn_bias, dst, cout, cin);
   PH_HIP_CHECK(hipGetLastError());
   return PH_OK;
 }

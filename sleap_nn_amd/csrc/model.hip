@@ -1094,7 +1094,7 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
         }
         if (ok && d.kind == PH_OP_LINEAR && (d.flags & PH_FLAG_RESIDUAL) && !no_bias && i > 0 && ops[i - 1].kind == PH_OP_GRN && ops[i - 1].dst == d.src0 && ops[i - 1].cout == d.cin0 &&
             widx_ok(ops[i - 1].bias) && weight_numel[ops[i - 1].bias] == d.cin0) {
-          // fused GRN plan: W2 (s x + grn.bias) + b2 = (W2 diag(s)) x + (W2 grn.bias + b2); the second term is constant per model (this backbone does not train: the fold is never stale)
+          // fused GRN plan: W2 (s x + grn.bias) + b2 = (W2 diag(s)) x + (W2 grn.bias + b2); the second term is constant per set of parameters (ph_model_set_params recomputes it on the device, bit for bit this sum: launch_grn_fold_bias)
           std::vector<float> fb(npad, 0.f);
           const float* w2 = weights[d.weight];
           const float* gb = weights[ops[i - 1].bias];
@@ -2279,7 +2279,9 @@ std::vector<OptionRef> option_table(ph_model* m) {
       {"conv_n32_wino2d", &m->conv_n32_wino2d, nullptr},  // Cout-32 / K >= 64 layers on the F(2x2,3x3) kernel with a half-empty N tile (0: the N-tile-32 F(2,3) kernel)
       {"conv_splitk_finish", &m->conv_splitk_finish, nullptr},  // 0: the split-K second stage as a launch of its own (A/B, tests)
       {"grn_fuse", &m->grn_fuse, nullptr},                // ConvNeXtV2 blocks on the fused GRN plan: 1 sums of squares from the first Linear's epilogue + per-sample scaled weights for the second; 0 (default, measured faster) two GRN launches
-      {"mlp_fuse", &m->mlp_fuse, nullptr},                // inference plans: CNBlock's two Linears (+ GELU, layer scale, residual) in one launch (cnblock_mlp_kernel)
+      {"pretrained_train", &m->pretrained_train, nullptr},  // 1: ph_model_backward accepts a ConvNeXtV2 program (GRN backward, weight gradient of the padding-0 stem); 0 (default) refuses its PH_FLAG_NO_TRAIN ops
+      {"bwd_frozen_ops", &m->bwd_frozen_ops, nullptr},      // the first n ops get no backward step (frozen encoder); 0 (default) none
+      {"mlp_fuse", &m->mlp_fuse, nullptr},              // inference plans: CNBlock's two Linears (+ GELU, layer scale, residual) in one launch (cnblock_mlp_kernel)
       {"block_fuse", &m->block_fuse, nullptr},          // plain fp16, inference plans: the two convs of a 32-channel encoder block in one launch (block2_c32_f16_kernel)
       {"stem_f16mfma", &m->stem_f16mfma, nullptr},      // plain fp16: the fused first block with BOTH convs on the fp16 matrix pipe (stem_f16_kernel) instead of stem_fused_kernel<CIN, 3>
       {"upsample_f16math", &m->upsample_f16math, nullptr},  // a bilinear x2 folded into conv3x3_f16_rows_kernel blends in packed fp16 arithmetic (1) or in fp32 as upsample2x_fmt_kernel does (0)

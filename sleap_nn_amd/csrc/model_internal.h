@@ -18,7 +18,7 @@ struct PackedOp {
   float* w2_dev = nullptr;
   float* b2_dev = nullptr;
   float* w_dma_dev = nullptr;  // conv weights in the LDS-DMA (quad-major piece) layout
-  float* b_grn_dev = nullptr;  // residual Linear behind a PH_OP_GRN: W2 grn.bias + b2, the bias of the fused GRN plan ("grn_fuse"); folded once, at creation
+  float* b_grn_dev = nullptr;  // residual Linear behind a PH_OP_GRN: W2 grn.bias + b2, the bias of the fused GRN plan ("grn_fuse"); folded at creation, and again by ph_model_set_params in a program that can take that plan
   float* w_mlp_dev = nullptr;  // Linear of a CNBlock MLP pair (inference programs): its weight as cnblock_mlp_kernel's LDS images
   int bn = 0;
   float* wd_gemm_dev[4] = {nullptr, nullptr, nullptr, nullptr};  // Linear / 2x2 conv: transposed weights (per tap) for the data gradient
@@ -160,6 +160,8 @@ struct ph_model {
   int conv_n32_wino2d = 1;                    // "conv_n32_wino2d" (1: inference plans, 2: every plan, 0: never): Cout-32 layers with >= 64 input channels (the last decoder level of an output-stride-2 UNet: 96 -> 32) on the F(2x2,3x3) kernel with a half-empty N tile of 64 instead of the N-tile-32 F(2,3) kernel
   int block_fuse = 1;                         // "block_fuse"
   int grn_fuse = 0;                           // "grn_fuse": ConvNeXtV2 blocks on the fused GRN plan (sums of squares from the first Linear's epilogue, per-sample scaled weights for the second); 0 (default): grn_reduce_kernel + grn_apply_kernel -- measured faster, DESIGN 4.4e
+  int pretrained_train = 0;                   // "pretrained_train": 1 = ph_model_backward accepts the ConvNeXtV2 ops that carry PH_FLAG_NO_TRAIN (PH_OP_GRN: convnextv2_train_kernels.hip; the PH_FLAG_PAD0_NORM stem); 0 (default): refused, as before those backward steps existed
+  int bwd_frozen_ops = 0;                     // "bwd_frozen_ops": the first n ops of the program are frozen -- the reverse sweep of ph_model_backward runs no step for them and writes none of their gradients (the reference's freeze_encoder()); 0 (default): every op
   int mlp_fuse = 1;                           // "mlp_fuse": CNBlock's Linear -> GELU -> Linear -> scale + residual in one launch (cnblock_mlp_kernel) where the width fits
   int stem_f16mfma = 1;                       // "stem_f16mfma"
   int upsample_f16math = 1;                   // "upsample_f16math"

@@ -220,6 +220,7 @@ struct GrnArgs {
   int B = 0, HW = 0, c = 0, cp = 0;  // c: true channels (the channel mean is over them; pad channels of src are zeros and come out zero)
 };
 int grn_slices(int HW);            // pixel slices per sample: a function of HW alone, so a frame's sums do not depend on the batch it is in
+int grn_slice_pixels(int HW);      // pixels of a slice (the last one may be shorter); the backward (convnextv2_train_kernels.hip) walks the same slices
 int64_t grn_scratch_floats(int B, int HW, int cp);
 int launch_grn(const GrnArgs& a, hipStream_t s);
 // The fused GRN plan: the first Linear's epilogue leaves per-(32-row block, sample segment) sums of squares (GemmArgs::sumsq);
@@ -228,7 +229,8 @@ int launch_grn(const GrnArgs& a, hipStream_t s);
 int grn_fused_nseg(int HW);                                   // segment places per 32-row block
 int64_t grn_fused_partial_floats(int M, int HW, int cp);
 int launch_grn_finalize(const float* partial, const float* weight, float* scale, int B, int HW, int c, int cp, hipStream_t s);
-int64_t gemm_pack_floats(int coutp, int c0p, int bn);          // floats of a one-tap, one-source pack_gemm image
+int launch_grn_fold_bias(const float* w2, const float* b2, const float* grn_bias, float* dst, int cout, int cin, hipStream_t s);  // dst[co] = b2[co] + sum_ci w2[co][ci] grn_bias[ci] (canonical layouts)
+int64_t gemm_pack_floats(int coutp, int c0p, int bn);         // floats of a one-tap, one-source pack_gemm image
 int launch_grn_scale_weights(const float* wpack, const float* scale, float* dst, int B, int coutp, int c0p, int bn, hipStream_t s);
 // CNBlock's MLP in one launch (cnblock_mlp_kernels.hip): dst = residual + scale * (W2 gelu(W1 x + b1) + b2) over (M, C) rows
 struct MlpArgs {

@@ -67,6 +67,7 @@ int build_bwd_plan(const ph_model* m, int B, int H, int W, BwdPlan& bp) {
         case PH_OP_LINEAR:
         case PH_OP_PATCH_CONV: need = std::max(need, row_wgrad_slab_floats((int)npix, d.cout, d.cin0)); break;
         case PH_OP_SCALE_ADD: need = std::max(need, chan_reduce_scratch_floats(so.cp)); break;
+        case PH_OP_GRN: need = std::max(need, grn_bwd_scratch_floats(B, so.h * so.w, so.cp)); break;  // slice sums of x^2, g x, g; per-sample coefficients and parameter shares
         case PH_OP_PATCH_MERGE: need = std::max(need, 2 * npix + chan_reduce_scratch_floats(so.cp) + 2 * npix * so.cp); break;  // statistics, reduction partials, gather, its gradient
         case PH_OP_WINDOW_ATTN: {
           const SlotShape& si = bp.act.slots[d.src0];
@@ -203,6 +204,17 @@ int ph_model_set_params(ph_model* m, const float* params_flat_dev, void* stream)
                             : launch_stem_wino_pack(db.src, db.dst, static_cast<hipStream_t>(stream));
     if (rc != PH_OK) return rc;
   }
+  // fused GRN plan ("grn_fuse"): the constant term W2 grn.bias + b2 of a residual Linear behind a GRN op follows the parameters.  Only a program whose first Linear
+  // carries the GELU can take that plan (fuses_grn), so an unfused (training) program never pays for this
+  for (size_t i = 2; i < m->ops.size(); ++i) {
+    const PackedOp& op = m->ops[i];
+    const ph_op_desc& g = m->ops[i - 1].d;
+    const ph_op_desc& l1 = m->ops[i - 2].d;
+    if (!op.b_grn_dev || g.kind != PH_OP_GRN || !(l1.kind == PH_OP_LINEAR && l1.flags == PH_FLAG_GELU)) continue;
+    int rc = launch_grn_fold_bias(params_flat_dev + m->weight_offset[op.d.weight], params_flat_dev + m->weight_offset[op.d.bias], params_flat_dev + m->weight_offset[g.bias], op.b_grn_dev,
+                                  op.d.cout, op.d.cin0, static_cast<hipStream_t>(stream));
+    if (rc != PH_OK) return rc;
+  }
   return PH_OK;
 }
 
@@ -315,8 +327,12 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
     PH_REQUIRE(!((op.d.flags & PH_FLAG_NO_TRAIN) && m->head_loss_kind[op.d.out_index] == 0),
                "ph_model_backward: head %d belongs to a segmentation model type, whose losses (BCE + Dice, masked smooth-L1) are not built: inference only", op.d.out_index);
   }
-  for (const auto& op : m->ops)  // the ConvNeXtV2 ops (GRN, the padding-0 stem with input statistics) carry PH_FLAG_NO_TRAIN: they have no backward
-    PH_REQUIRE(!(op.d.kind != PH_OP_HEAD && (op.d.flags & PH_FLAG_NO_TRAIN)), "ph_model_backward: op kind %d is inference only (a 'pretrained' ConvNeXtV2 backbone does not train here)", op.d.kind);
+  for (const auto& op : m->ops)  // the ConvNeXtV2 ops (GRN, the padding-0 stem with input statistics) carry PH_FLAG_NO_TRAIN: their backward steps run on request only
+    PH_REQUIRE(m->pretrained_train || !(op.d.kind != PH_OP_HEAD && (op.d.flags & PH_FLAG_NO_TRAIN)),
+               "ph_model_backward: op kind %d is inference only on this handle (a 'pretrained' ConvNeXtV2 backbone trains with the handle option pretrained_train = 1)", op.d.kind);
+  // frozen prefix ("bwd_frozen_ops"): ops [0, frozen) get no step.  The program is in topological order, so nothing a frozen op reads is written by a trainable one:
+  // the trainable ops still leave their data gradients in the frozen ops' output slots (the skips), and nobody reads them
+  const int frozen = std::max(0, std::min(m->bwd_frozen_ops, (int)m->ops.size()));
   PH_REQUIRE(m->last_plan.fmt == FMT_F32, "backward needs the activations of an exact-fp32 forward (handle option conv_precision = 0)");
   PH_REQUIRE(!m->last_plan.reuse, "backward needs every activation of the forward (handle option workspace_reuse = 0)");
   BwdPlan bp;
@@ -394,6 +410,15 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
   const bool exchange = m->comm != nullptr;  // (a communicator of ONE rank runs the same schedule: two in-place sums that change nothing -- what the single-GPU test exercises)
   const int split_op = (m->bucket_event || exchange) ? bucket_split_op(m, &split_off) : -1;
   if (split_op < 0) split_off = m->n_params;
+  auto tail_final = [&]() -> int {  // gradients [bucket split, n_params) are final from here on
+    if (m->bucket_event) PH_HIP_CHECK(hipEventRecord(m->bucket_event, s));
+    if (exchange && split_off < m->n_params) {  // tail bucket: on the side stream, under the rest of the sweep
+      PH_HIP_CHECK(hipEventRecord(m->comm_ev[0], s));
+      PH_HIP_CHECK(hipStreamWaitEvent(m->comm_stream, m->comm_ev[0], 0));
+      return ph_allreduce(m->comm, grads_flat_dev + split_off, m->n_params - split_off, m->comm_stream);
+    }
+    return PH_OK;
+  };
   for (int oi = (int)m->ops.size() - 1; oi >= 0; --oi) {
     const PackedOp& op = m->ops[oi];
     const ph_op_desc& d = op.d;
@@ -401,6 +426,14 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
     if (prof) {
       PH_HIP_CHECK(hipEventRecord(m->bwd_ev[ev_i], s));
       if (d.kind != PH_OP_LINEAR && d.kind != PH_OP_PATCH_CONV) PH_HIP_CHECK(hipEventRecord(m->bwd_ev[ev_i + 1], s));
+    }
+    // an op whose output no op reads (a ConvNeXtV2 stage norm whose map the decoder does not take: output stride 8) has no gradient to pass on: like a frozen op
+    const bool dead = d.kind != PH_OP_HEAD && d.dst >= 0 && first_consumer[d.dst] < 0 && (d.dst2 < 0 || first_consumer[d.dst2] < 0);
+    if (oi < frozen || dead) {  // no step: the gradients of its parameters stay as the caller left them
+      if (prof && (d.kind == PH_OP_LINEAR || d.kind == PH_OP_PATCH_CONV)) PH_HIP_CHECK(hipEventRecord(m->bwd_ev[ev_i + 1], s));
+      if (oi == split_op) rc = tail_final();  // the split op lies in the frozen part: the tail was final when the last trainable op finished
+      if (rc != PH_OK) return rc;
+      continue;
     }
     switch (d.kind) {
       case PH_OP_HEAD: {
@@ -883,8 +916,34 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
         PH_REQUIRE(d.cin0 == in_channels, "input has %d channels, network expects %d", in_channels, d.cin0);
         rc = launch_bias_grad(G(d.dst), (size_t)batch * so.h * so.w, so.cp, d.cout, grads_flat_dev + m->weight_offset[d.bias], scratch, s);
         if (rc != PH_OK) return rc;
-        rc = launch_patch_stem_wgrad(input_dev, in_dtype, G(d.dst), batch, d.cin0, height, width, so.h, so.w, d.ksize, d.cmid, 1, so.cp, d.cout,
-                                     grads_flat_dev + m->weight_offset[d.weight], scratch, s);
+        if (d.flags & PH_FLAG_PAD0_NORM)  // ConvNeXtV2 embeddings: padding 0, patches of (x / 255 - mean) / std; the bias gradient above is the same
+          rc = launch_patch_stem_wgrad_norm(input_dev, in_dtype, G(d.dst), batch, d.cin0, height, width, so.h, so.w, d.ksize, d.cmid, so.cp, d.cout, m->in_mean, m->in_std,
+                                            grads_flat_dev + m->weight_offset[d.weight], scratch, s);
+        else
+          rc = launch_patch_stem_wgrad(input_dev, in_dtype, G(d.dst), batch, d.cin0, height, width, so.h, so.w, d.ksize, d.cmid, 1, so.cp, d.cout,
+                                       grads_flat_dev + m->weight_offset[d.weight], scratch, s);
+        break;
+      }
+      case PH_OP_GRN: {  // y = w (x N) + beta + x: convnextv2_train_kernels.hip
+        const SlotShape& so = bp.act.slots[d.dst];
+        PH_REQUIRE(init[d.dst], "GRN output slot %d received no gradient", d.dst);
+        PH_REQUIRE(bp.act.slots[d.src0].cp == so.cp && so.c == d.cout, "GRN channel mismatch");
+        GrnBwdArgs a{};
+        a.x = A(d.src0);
+        a.gy = G(d.dst);
+        a.weight = op.w_dev;
+        a.gx = G(d.src0);
+        a.gw = grads_flat_dev + m->weight_offset[d.weight];
+        a.gb = grads_flat_dev + m->weight_offset[d.bias];
+        a.scratch = scratch;
+        a.B = batch;
+        a.HW = so.h * so.w;
+        a.c = d.cout;
+        a.cp = so.cp;
+        a.accumulate = init[d.src0];
+        rc = launch_grn_bwd(a, s);
+        m->last_bwd_variant[oi] = PH_KV_GRN_BWD;
+        init[d.src0] = 1;
         break;
       }
       default:
@@ -892,14 +951,9 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
         rc = PH_E_INVALID;
     }
     if (rc != PH_OK) return rc;
-    if (oi == split_op) {  // gradients [bucket split, n_params) are final from here on
-      if (m->bucket_event) PH_HIP_CHECK(hipEventRecord(m->bucket_event, s));
-      if (exchange && split_off < m->n_params) {  // tail bucket: on the side stream, under the rest of the sweep
-        PH_HIP_CHECK(hipEventRecord(m->comm_ev[0], s));
-        PH_HIP_CHECK(hipStreamWaitEvent(m->comm_stream, m->comm_ev[0], 0));
-        rc = ph_allreduce(m->comm, grads_flat_dev + split_off, m->n_params - split_off, m->comm_stream);
-        if (rc != PH_OK) return rc;
-      }
+    if (oi == split_op) {
+      rc = tail_final();
+      if (rc != PH_OK) return rc;
     }
   }
   PH_REQUIRE(pad_bias < 0, "window attention: no qkv Linear took the padded tokens' share of its bias gradient");

@@ -91,6 +91,23 @@ int64_t row_wgrad_slab_floats(int M, int n, int k);
 int launch_patch_stem_wgrad(const void* img, int dtype, const float* dy, int B, int cin, int H, int W, int OH, int OW, int k, int stride, int pad, int coutp, int cout, float* gw,
                             float* scratch, hipStream_t s);  // pad 1: the ConvNeXt stem; pad k / 2 with stride 1: the first k x k "same" conv of a UNet
 int64_t patch_stem_wgrad_scratch_floats(int cin, int cout, int k, int64_t npix);
+// ... of the padding-0 stem with input statistics (PH_FLAG_PAD0_NORM): the same im2col + row-wgrad GEMM over patches (x / 255 - mean[ci]) / std[ci], pad = 0
+int launch_patch_stem_wgrad_norm(const void* img, int dtype, const float* dy, int B, int cin, int H, int W, int OH, int OW, int k, int stride, int coutp, int cout, const float* mean4,
+                                 const float* std4, float* gw, float* scratch, hipStream_t s);
+// Backward of Global Response Normalization (convnextv2_train_kernels.hip): dx = g (1 + w N) + x K, dw, dbeta; four launches, fixed-order sums, no atomics
+struct GrnBwdArgs {
+  const float* x = nullptr;       // (B, HW, cp): the forward's input, as kept in its slot
+  const float* gy = nullptr;      // (B, HW, cp): gradient of the output
+  const float* weight = nullptr;  // [cp], zero-padded
+  float* gx = nullptr;            // (B, HW, cp): gradient of the input; pad channels come out zero
+  float* gw = nullptr;            // [c]: gradient of weight (arena)
+  float* gb = nullptr;            // [c]: gradient of bias (arena)
+  float* scratch = nullptr;       // grn_bwd_scratch_floats(B, HW, cp) floats
+  int B = 0, HW = 0, c = 0, cp = 0;
+  int accumulate = 0;             // 1: gx already holds a gradient, add to it
+};
+int64_t grn_bwd_scratch_floats(int B, int HW, int cp);
+int launch_grn_bwd(const GrnBwdArgs& a, hipStream_t s);
 int launch_class_ce(const float* p, const float* y, int B, int C, float weight, float* dz, float* loss_out, hipStream_t s);
 int launch_global_maxpool_bwd(const float* x, const float* gy, int B, int HW, int cp, int accumulate, float* gx, hipStream_t s);
 

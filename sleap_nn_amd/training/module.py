@@ -44,7 +44,7 @@ class TrainingModule:
                  loss_weights: Optional[Sequence[float]] = None, ohkm: Optional[OHKMConfig] = None,
                  negative_loss_weight: float = 1.0, lr_scheduler=None, max_epochs: Optional[int] = None, wino4: bool = True,
                  native_allreduce: Optional[bool] = None, swint_training: bool = False, stochastic_depth_prob: float = 0.1,
-                 stochastic_depth_seed: int = 0) -> None:
+                 stochastic_depth_seed: int = 0, pretrained_training: bool = False, freeze_encoder: Optional[bool] = None) -> None:
         """``negative_loss_weight``: weight of frames flagged ``is_negative`` in the train-stage MSE (lightning_modules.py:149-153,
         526-545).  ``lr_scheduler``: the reference's scheduler config (a name or ``{name: {...}}``, lightning_modules.py:765-857);
         ``self.lr`` then follows it: one ``on_epoch_end(val_loss)`` per epoch, like Lightning steps the scheduler.
@@ -56,14 +56,25 @@ class TrainingModule:
         draws the per-sample scales of the residual branches on the device -- torchvision's stochastic depth, which the reference trains this backbone with
         (``stochastic_depth_prob`` 0.1, block k dropped with probability ``prob * k / (blocks - 1)``; ``architectures.swint.draw_branch_scales``) -- from a
         generator seeded by ``stochastic_depth_seed``, the rank and the step count; no other stage passes scales, ``stochastic_depth_prob=0`` never does, and
-        ``set_branch_scales`` overrides the draw of the next step."""
+        ``set_branch_scales`` overrides the draw of the next step.
+        ``pretrained_training``: train a ``pretrained`` (ConvNeXtV2) backbone (opt-in, as ``Model.train(True, allow_pretrained=True)``): GRN backward and the
+        weight gradient of the padding-0 stem on the device; a non-zero ``drop_path_rate`` of the backbone's ``config.json`` is refused.
+        ``freeze_encoder``: the reference's ``freeze_encoder()`` for that backbone (lightning_modules.py:232-236); ``None`` takes the backbone config's ``freeze``.
+        Frozen, the backward sweep stops behind the decoder (handle option ``bwd_frozen_ops``), every ``backbone.enc.*`` gradient stays exactly zero and the
+        optimizer steps only ``Model.trainable_ranges`` of the arena, so neither Adam nor AdamW's decoupled decay moves a frozen parameter.  The same ranges leave
+        out the parameters no op reads (``hidden_states_norms.stem``), frozen or not."""
         from sleap_nn_amd.architectures.heads import SEGMENTATION_MODEL_TYPES
 
         if getattr(model, "model_type", None) in SEGMENTATION_MODEL_TYPES and not self._trains_segmentation:
             raise NotImplementedError(f"training a '{model.model_type}' model is not built here (BCE + Dice, masked smooth-L1 and mask targets): these model types are "
                                       "not trained with the MSE loss of the pose heads; use sleap_nn_amd.training.segmentation.SegmentationTrainingModule")
-        if getattr(model, "backbone_type", None) == "pretrained":
-            raise NotImplementedError("training a 'pretrained' (ConvNeXtV2) backbone is not built on the MI355X path (GRN and the padding-0 stem have no backward): inference only")
+        self._pretrained = getattr(model, "backbone_type", None) == "pretrained"
+        if self._pretrained and not pretrained_training:
+            raise NotImplementedError("training a 'pretrained' (ConvNeXtV2) backbone is opt-in: TrainingModule(model, pretrained_training=True)")
+        if freeze_encoder is not None and not self._pretrained:
+            raise ValueError("freeze_encoder freezes the encoder of a 'pretrained' backbone; this model has none")
+        if self._pretrained:
+            model.backbone.check_trainable()  # (before anything touches the device)
         L.lib()
         if not torch.cuda.is_available():
             raise RuntimeError("TrainingModule needs an MI355X; there is no CPU fallback")
@@ -81,7 +92,12 @@ class TrainingModule:
         self._next_scales: Optional[torch.Tensor] = None   # set_branch_scales: the next train-stage step's scales instead of a draw
         self._active_scales: Optional[torch.Tensor] = None  # what the handle borrows between the forward and the backward of a step
         self.last_branch_scales: Optional[torch.Tensor] = None  # scales of the last step that had any (kept alive while its kernels run)
-        self.model = (model.train(True, allow_swint=True) if self._swint else model.train(True)).to(dev)
+        self.model = (model.train(True, allow_swint=True) if self._swint else model.train(True, allow_pretrained=self._pretrained)).to(dev)
+        # what the optimizer steps: the whole arena, or -- a pretrained backbone -- what is read and not frozen; the frozen prefix of the backward sweep
+        self.frozen_encoder = self._pretrained and bool(model.backbone.freeze if freeze_encoder is None else freeze_encoder)
+        self._ranges = model.trainable_ranges(self.frozen_encoder) if self._pretrained else [(0, model.num_parameters())]
+        if self._pretrained:
+            self.model.set_option("bwd_frozen_ops", model.backbone.encoder_ops() if self.frozen_encoder else 0)
         self.model.set_option("conv_wino4", 2 if wino4 else 1)
         self.lr, self.betas, self.eps, self.amsgrad = lr, betas, eps, amsgrad
         if optimizer not in ("Adam", "AdamW"):
@@ -150,6 +166,8 @@ class TrainingModule:
         if x.dtype != torch.uint8:
             x = x.to(torch.float32)
             code = 2 if bool(x.max() > 1.0) else 1
+        if self._pretrained:  # a gray frame is replicated here, as Model.forward would: the backward reads the frames the stem saw
+            x, code = self.model.adapt_channels(x, code)
         x = x.contiguous()
         B, Cin, H, W = x.shape
         lib = L.lib()
@@ -265,14 +283,15 @@ class TrainingModule:
     def optimizer_step(self, grad_scale: float = 1.0) -> None:
         self.step_count += 1
         with torch.cuda.device(self.device):
-            L.check(
-                L.lib().ph_adamw_step(
-                    C.c_void_p(self.params.data_ptr()), C.c_void_p(self.grads.data_ptr()), C.c_void_p(self.exp_avg.data_ptr()),
-                    C.c_void_p(self.exp_avg_sq.data_ptr()), C.c_void_p(self.max_exp_avg_sq.data_ptr()) if self.max_exp_avg_sq is not None else None,
-                    self.params.numel(), float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), self.step_count,
-                    float(grad_scale), L.current_stream_ptr(),
+            for lo, hi in self._ranges:  # (one range, the whole arena, unless a pretrained backbone leaves parameters out)
+                p = lambda t: C.c_void_p(t.data_ptr() + 4 * lo)  # noqa: E731
+                L.check(
+                    L.lib().ph_adamw_step(
+                        p(self.params), p(self.grads), p(self.exp_avg), p(self.exp_avg_sq), p(self.max_exp_avg_sq) if self.max_exp_avg_sq is not None else None,
+                        hi - lo, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), self.step_count,
+                        float(grad_scale), L.current_stream_ptr(),
+                    )
                 )
-            )
         self._push_params()
 
     def training_step(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:

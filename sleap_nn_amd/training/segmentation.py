@@ -30,7 +30,8 @@ class SegmentationTrainingModule(TrainingModule):
 
     ``bce_weight`` / ``dice_weight`` (default 0.5 each) and ``bce_pos_weight`` (default None) come from the ``segmentation`` leaf of the model's head
     config, ``loss_weight`` from each head.  A batch is ``{"image", "SegmentationHead"[, "InstanceCenterHead", "CenterOffsetHead",
-    "foreground_weight"]}``: what ``SegmentationTargetGenerator`` returns beside the image."""
+    "foreground_weight"]}``: what ``SegmentationTargetGenerator`` returns beside the image.  Every other keyword is ``TrainingModule``'s and is passed through:
+    ``pretrained_training=True`` (with ``freeze_encoder``) trains a model on a ``pretrained`` (ConvNeXtV2) backbone, ``swint_training=True`` one on a Swin backbone."""
 
     _trains_segmentation = True
 
