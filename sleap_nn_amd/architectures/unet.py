@@ -3,7 +3,7 @@
 Reproduces the *structure* and the checkpoint parameter names of the reference UNet
 (``sleap_nn/architectures/unet.py:49-253`` and ``encoder_decoder.py:274-316,634-703``)
 without any torch modules: the network is a flat list of ops over activation slots that the
-C side (csrc/model.hip) executes with hand-written gfx950 kernels.
+C side (csrc/plan.hip, csrc/forward.hip) executes with hand-written gfx950 kernels.
 """
 from __future__ import annotations
 

@@ -1,5 +1,5 @@
-// Host runtime of the network path: op program, weight re-packing, workspace planning and
-// the forward launch sequence (C ABI: ph_model_*).  Replaces TorchBackend.__call__ ->
+// Host runtime of the network path: the handle (ph_model_create / ph_model_destroy), weight re-packing, the options table and the small accessors of the
+// C ABI (ph_model_*); the workspace plan is plan.hip, the forward launch sequence forward.hip.  Together they replace TorchBackend.__call__ ->
 // LightningModule.forward -> Model.forward -> UNet.forward of the reference
 // (sleap_nn/inference/layers/backends/torch_backend.py:113-153,
 //  training/lightning_modules.py:1840-1848, architectures/model.py:237-261,
@@ -14,9 +14,6 @@
 
 #include "model_internal.h"
 #include "train_kernels.h"
-
-// diagnostic clock probe (ph_model_set_clock_probe): 64-bit words reserved per op of the program -- the largest writer (the F(2x2,3x3) kernel's stamps) takes 256 x 8 x 8
-static constexpr size_t PH_PROBE_WORDS_PER_OP = 32768;
 
 namespace ph {
 
@@ -80,6 +77,18 @@ static int upload_packed(ph_model* m, const std::vector<float>& packed_val, cons
   if (rc != PH_OK) return rc;
   m->packed.push_back(pb);
   return PH_OK;
+}
+
+// Note a buffer that is computed on the device from `src`, so that ph_model_set_params recomputes it
+static DerivedBuffer& add_derived(ph_model* m, DerivedKind kind, const float* src, float* dst, int panels = 0, int bn = 0) {
+  DerivedBuffer db;
+  db.kind = kind;
+  db.src = src;
+  db.dst = dst;
+  db.panels = panels;
+  db.bn = bn;
+  m->derived.push_back(db);
+  return m->derived.back();
 }
 
 // Run one packing routine twice -- on the weight values and on their canonical indices -- and upload both.
@@ -237,293 +246,6 @@ void apply_conv_options(const ph_model* m, ConvArgs& a) {
   a.use_sm = 0;  // (ph_model_forward: the kind of plan decides)
 }
 
-// Programs made only of the UNet-style ops can run on the fp16 matrix pipe (handle option "conv_precision"); so can, in the
-// plain fp16 precision and with the handle option "convnext_f16" set, programs with the ConvNeXt encoder ops (convnext_f16_kernels.hip).  Anything else (class-vector heads
-// and the global max pool in front of them, non-3x3 kernels, ConvNeXt programs in the split precision) and every training program
-// (conv_precision 0) stays in exact fp32.  A program with the Swin ops (window attention, patch merging) answers to the handle option
-// "swint_f16" instead of "convnext_f16" (swin_f16_kernels.hip): the two options are independent, neither changes the other's programs.
-int forward_format(const ph_model* m) {
-  if (m->conv_precision != 1 && m->conv_precision != 2) return FMT_F32;
-  bool swin = false;
-  for (const PackedOp& op : m->ops) swin = swin || op.d.kind == PH_OP_WINDOW_ATTN || op.d.kind == PH_OP_PATCH_MERGE;
-  const bool enc_f16 = m->conv_precision == 2 && (swin ? m->swint_f16 : m->convnext_f16) != 0;  // the encoder ops have an fp16 form and may use it
-  for (const PackedOp& op : m->ops) {
-    const ph_op_desc& d = op.d;
-    switch (d.kind) {
-      case PH_OP_STEM:
-      case PH_OP_INPUT_CONV:
-      case PH_OP_POOL:
-      case PH_OP_UPSAMPLE:
-        break;
-      case PH_OP_PATCH_STEM:
-      case PH_OP_DWCONV:
-      case PH_OP_LAYERNORM:
-      case PH_OP_PATCH_CONV:
-      case PH_OP_GELU:
-      case PH_OP_SCALE_ADD:
-        if (!enc_f16) return FMT_F32;
-        break;
-      case PH_OP_WINDOW_ATTN:
-      case PH_OP_PATCH_MERGE:
-        if (!enc_f16) return FMT_F32;
-        break;
-      case PH_OP_GRN:  // a ConvNeXtV2 program has no fp16 form: exact whatever the precision and whatever "convnext_f16" says
-        return FMT_F32;
-      case PH_OP_LINEAR:  // (a Linear with a ReLU is a class-vector head's: exact; PH_FLAG_RESIDUAL is a Swin block's, with or without a bias)
-        if (!enc_f16 || (d.flags & ~(PH_FLAG_GELU | PH_FLAG_SCALE_RESIDUAL | (swin ? PH_FLAG_RESIDUAL : 0))) || !op.w_cnx_f16_dev) return FMT_F32;
-        break;
-      case PH_OP_CONV:
-      case PH_OP_CONVT:
-        if (d.ksize != 3) return FMT_F32;
-        break;
-      case PH_OP_HEAD:
-        if (d.flags & PH_FLAG_SOFTMAX) return FMT_F32;
-        break;
-      default:
-        return FMT_F32;
-    }
-  }
-  return m->conv_precision == 1 ? FMT_SPLIT : FMT_F16;
-}
-
-static bool only_reader_is_next(const ph_model* m, size_t i) {  // nothing but op i + 1 reads op i's dst
-  const int slot = m->ops[i].d.dst;
-  for (size_t k = 0; k < m->ops.size(); ++k)
-    if (k != i + 1 && (m->ops[k].d.src0 == slot || m->ops[k].d.src1 == slot)) return false;
-  return true;
-}
-
-// inference plans, plain fp16: conv(<= 16 -> 32) + ReLU whose only reader is the next op, a conv(32 -> 32) (+ ReLU, + pool): both in ONE launch, the intermediate
-// tensor stays in LDS (block2_c32_f16_kernel).  The conditions are on PADDED channel counts, and the pool is optional: with three convs per block the router takes
-// enc0's second and third conv ((16 -> 16), (16 -> 16) + pool: weights and biases zero-padded to 32) and enc1's first and second ((16 -> 32), (32 -> 32) with NO pool
-// behind it: dst_pool = nullptr, only the full-resolution tensor is stored) -- both under test in tests/test_gpu_block_structure.py
-bool fuses_block2(const ph_model* m, size_t i, int fmt, bool reuse) {
-  if (fmt != FMT_F16 || !m->block_fuse || !reuse || i + 1 >= m->ops.size()) return false;
-  const PackedOp& op = m->ops[i];
-  const PackedOp& nxo = m->ops[i + 1];
-  const ph_op_desc& d = op.d;
-  const ph_op_desc& nx = nxo.d;
-  if (!(d.kind == PH_OP_CONV && d.src0 >= 0 && d.src1 < 0 && d.ksize == 3 && d.dst2 < 0 && op.bn == 32 && fmt_cpad(fmt, d.cout) == 32 && fmt_cpad(fmt, d.cin0) == 32 && d.cin0 <= 16)) return false;
-  if (!(nx.kind == PH_OP_CONV && nx.ksize == 3 && nx.src0 == d.dst && nx.src1 < 0 && nxo.bn == 32 && fmt_cpad(fmt, nx.cout) == 32 && nx.cin0 == d.cout)) return false;
-  return only_reader_is_next(m, i);
-}
-
-// CNBlock's MLP in one launch (inference plans that recycle slots: the 4C-wide hidden tensor is nobody else's business): Linear + GELU whose only reader is a
-// Linear with layer scale + residual, both at a width cnblock_mlp_kernel takes
-bool fuses_mlp(const ph_model* m, size_t i, int fmt, bool reuse) {
-  if (!m->mlp_fuse || !reuse || fmt != FMT_F32 || i + 1 >= m->ops.size()) return false;  // (fp32 only: the fp16 pipe runs the pair as two row GEMMs)
-  const PackedOp& op = m->ops[i];
-  const PackedOp& nxo = m->ops[i + 1];
-  const ph_op_desc& d = op.d;
-  const ph_op_desc& nx = nxo.d;
-  if (!(d.kind == PH_OP_LINEAR && (d.flags & PH_FLAG_GELU) && op.w_mlp_dev && d.src0 >= 0 && fmt_cpad(fmt, d.cin0) == d.cin0)) return false;
-  if (!(nx.kind == PH_OP_LINEAR && (nx.flags & PH_FLAG_SCALE_RESIDUAL) && nxo.w_mlp_dev && nx.src0 == d.dst && nx.src1 >= 0 && nx.src1 != d.dst && nx.cin0 == d.cout && nx.cout == d.cin0 &&
-        fmt_cpad(fmt, nx.cout) == nx.cout))
-    return false;
-  return only_reader_is_next(m, i);
-}
-
-// ConvNeXtV2 block on the fused GRN plan (handle option "grn_fuse"): op i = Linear + GELU, i + 1 = GRN, i + 2 = the residual Linear; nobody else reads the two tensors between
-bool fuses_grn(const ph_model* m, size_t i, int fmt) {
-  if (!m->grn_fuse || fmt != FMT_F32 || m->branch_scales || i + 2 >= m->ops.size()) return false;
-  const ph_op_desc& d = m->ops[i].d;
-  const ph_op_desc& g = m->ops[i + 1].d;
-  const ph_op_desc& l2 = m->ops[i + 2].d;
-  if (!(d.kind == PH_OP_LINEAR && d.flags == PH_FLAG_GELU && d.src0 >= 0)) return false;
-  if (!(g.kind == PH_OP_GRN && g.src0 == d.dst && g.cin0 == d.cout)) return false;
-  if (!(l2.kind == PH_OP_LINEAR && (l2.flags & PH_FLAG_RESIDUAL) && l2.src0 == g.dst && l2.cin0 == g.cout && m->ops[i + 2].b_grn_dev)) return false;
-  return only_reader_is_next(m, i) && only_reader_is_next(m, i + 1);
-}
-
-int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
-  plan.slots.assign(m->n_slots, SlotShape());
-  plan.fmt = fmt;
-  plan.bpc = fmt_bytes_per_channel(fmt);
-  const int bpc = plan.bpc;
-  int64_t off = 0, tmp = 0;
-  // Slot allocation.  Default: every slot gets its own range (training keeps every activation; ph_model_read_slot can read any of
-  // them back).  With the handle option "workspace_reuse" (inference programs) a slot's range returns to a free list after its
-  // last reader and later slots take the best-fitting free block: 9.0 -> 3.6 GB at cfg3 x 32 frames, and a layer's output is
-  // written where an older tensor has just left the caches.
-  const bool reuse = m->workspace_reuse != 0;
-  plan.reuse = reuse;
-  const int n_ops = (int)m->ops.size();
-  std::vector<int> last_use(m->n_slots, -1);
-  std::vector<int64_t> slot_bytes(m->n_slots, 0);
-  std::vector<char> released(m->n_slots, 0);
-  if (reuse)
-    for (int j = 0; j < n_ops; ++j) {
-      const ph_op_desc& e = m->ops[j].d;
-      if (e.src0 >= 0 && e.src0 < m->n_slots) last_use[e.src0] = j;
-      if (e.src1 >= 0 && e.src1 < m->n_slots) last_use[e.src1] = j;
-    }
-  if (reuse)  // a bilinear op the next conv may fold into its input transform (ph_model_forward, PH_OP_UPSAMPLE): that conv then reads the op's SOURCE
-    for (int j = 0; j + 1 < n_ops; ++j) {
-      const ph_op_desc& e = m->ops[j].d;
-      const ph_op_desc& nx = m->ops[j + 1].d;
-      if (e.kind == PH_OP_UPSAMPLE && nx.kind == PH_OP_CONV && nx.src1 == e.dst && e.src0 >= 0 && e.src0 < m->n_slots) last_use[e.src0] = std::max(last_use[e.src0], j + 1);
-    }
-  if (reuse)  // fused GRN plan: the residual Linear reads the GELU output itself, one op after the GRN op that is its last reader in the program
-    for (int j = 0; j + 2 < n_ops; ++j)
-      if (fuses_grn(m, (size_t)j, fmt)) last_use[m->ops[j].d.dst] = std::max(last_use[m->ops[j].d.dst], j + 2);
-  plan.unread.assign(m->n_slots, 0);
-  if (reuse)
-    for (int sl = 0; sl < m->n_slots; ++sl) plan.unread[sl] = last_use[sl] < 0;
-  std::vector<std::pair<int64_t, int64_t>> free_list;  // (offset, bytes), kept sorted and coalesced
-  auto release = [&](int slot) {
-    free_list.emplace_back(plan.slots[slot].offset, slot_bytes[slot]);
-    std::sort(free_list.begin(), free_list.end());
-    for (size_t k = 0; k + 1 < free_list.size();)
-      if (free_list[k].first + free_list[k].second == free_list[k + 1].first) {
-        free_list[k].second += free_list[k + 1].second;
-        free_list.erase(free_list.begin() + k + 1);
-      } else
-        ++k;
-    released[slot] = 1;
-  };
-  auto alloc = [&](int slot, int64_t bytes) {
-    bytes = align_up(bytes, 256);
-    slot_bytes[slot] = bytes;
-    int best = -1;
-    for (size_t k = 0; k < free_list.size(); ++k)
-      if (free_list[k].second >= bytes && (best < 0 || free_list[k].second < free_list[best].second)) best = (int)k;
-    if (best >= 0) {
-      const int64_t o = free_list[best].first;
-      free_list[best].first += bytes;
-      free_list[best].second -= bytes;
-      if (free_list[best].second == 0) free_list.erase(free_list.begin() + best);
-      return o;
-    }
-    if (!free_list.empty() && free_list.back().first + free_list.back().second == off) {  // grow the trailing free block
-      const int64_t o = free_list.back().first;
-      free_list.pop_back();
-      off = o + bytes;
-      return o;
-    }
-    const int64_t o = off;
-    off += bytes;
-    return o;
-  };
-  int op_i = -1;
-  for (const PackedOp& op : m->ops) {
-    const ph_op_desc& d = op.d;
-    ++op_i;
-    // Run-time fusions let op i write op i + 1's dst one op early (pool_peephole: a conv's epilogue writes the pool that follows it;
-    // fuse_gelu_fwd: a Linear writes its GELU or its layer-scale + residual; dw_ln_fuse: a depthwise / stem conv writes its LayerNorm).  Such a dst must not land on
-    // a range op i is still reading, so the releases due before a pool / GELU / LayerNorm of the previous op's output wait one op.  The same for the second conv of a pair
-    // block2_c32_f16_kernel takes (fuses_block2, the router's own predicate): its dst and pooled dst are stored by the launch that DMA-loads the first conv's src0, halo
-    // pixels of other workgroups' tiles included, tile rounds apart -- that src0 (released here: its last reader is the first conv) must stay out of the free list.
-    // (cnblock_mlp_kernel's pair is NOT held: a row tile reads all of its x and residual rows before it stores them and no other tile reads them, so y exactly on x
-    // is safe; ph_model_forward refuses the fusion for any other overlap.)
-    const bool forwarded = op_i > 0 && (((d.kind == PH_OP_POOL || d.kind == PH_OP_GELU || d.kind == PH_OP_LAYERNORM || d.kind == PH_OP_SCALE_ADD) && d.src0 >= 0 && d.src0 == m->ops[op_i - 1].d.dst) ||
-                                        fuses_block2(m, (size_t)op_i - 1, fmt, reuse));
-    if (reuse && !forwarded)  // slots whose last reader ran before this op (a slot nobody reads is released right after the op that wrote it)
-      for (int sl = 0; sl < m->n_slots; ++sl)
-        if (!released[sl] && plan.slots[sl].offset >= 0 && slot_bytes[sl] > 0 && std::max(last_use[sl], plan.slots[sl].def_op) < op_i) release(sl);
-    int h, w;
-    if (d.src0 < 0) {
-      h = H;
-      w = W;
-    } else {
-      PH_REQUIRE(d.src0 < m->n_slots && plan.slots[d.src0].offset >= 0, "op reads slot %d before it is written", d.src0);
-      h = plan.slots[d.src0].h;
-      w = plan.slots[d.src0].w;
-    }
-    if (d.kind == PH_OP_HEAD) continue;
-    if (d.kind == PH_OP_STEM) {
-      PH_REQUIRE(d.src0 < 0, "stem op must read the network input");
-      PH_REQUIRE(d.dst2 >= 0 && d.dst2 < m->n_slots && d.dst < m->n_slots, "bad stem slots");
-      if (d.dst >= 0) {
-        SlotShape& f = plan.slots[d.dst];
-        f.c = d.cout; f.cp = fmt_cpad(fmt, 16); f.h = h; f.w = w; f.def_op = op_i;
-        f.offset = alloc(d.dst, (int64_t)B * h * w * f.cp * bpc);
-      }
-      SlotShape& p = plan.slots[d.dst2];
-      p.c = d.cout; p.cp = fmt_cpad(fmt, 16); p.h = (h + 1) / 2; p.w = (w + 1) / 2; p.def_op = op_i;
-      p.offset = alloc(d.dst2, (int64_t)B * p.h * p.w * p.cp * bpc);
-      continue;
-    }
-    int oh = h, ow = w;
-    if (d.kind == PH_OP_PATCH_STEM) {
-      PH_REQUIRE(d.src0 < 0, "patch stem must read the network input");
-      const int pad2 = (d.flags & PH_FLAG_PAD0_NORM) ? 0 : 2;
-      oh = (h + pad2 - d.ksize) / d.cmid + 1;
-      ow = (w + pad2 - d.ksize) / d.cmid + 1;
-      PH_REQUIRE(oh > 0 && ow > 0, "input %dx%d is too small for the %dx%d patch stem", h, w, d.ksize, d.ksize);
-    } else if (d.kind == PH_OP_PATCH_CONV) {
-      oh = h / 2;
-      ow = w / 2;
-      PH_REQUIRE(oh > 0 && ow > 0, "input of a 2x2/stride-2 convolution is smaller than 2x2");
-    } else if (d.kind == PH_OP_PATCH_MERGE) {  // pad to even, four phases on the channels
-      oh = (h + 1) / 2;
-      ow = (w + 1) / 2;
-      PH_REQUIRE(plan.slots[d.src0].c == d.cin0 && d.cout == 4 * d.cin0, "patch merge channel mismatch");
-    } else if (d.kind == PH_OP_WINDOW_ATTN) {
-      PH_REQUIRE(d.src0 >= 0 && plan.slots[d.src0].c == d.cin0 && d.cin0 == 3 * d.cout, "window attention reads a (3C)-channel qkv slot");
-    } else if ((d.kind == PH_OP_LINEAR && (d.flags & (PH_FLAG_SCALE_RESIDUAL | PH_FLAG_RESIDUAL))) || d.kind == PH_OP_SCALE_ADD) {
-      PH_REQUIRE(d.src1 >= 0 && d.src1 < m->n_slots && plan.slots[d.src1].offset >= 0, "residual slot %d is not written yet", d.src1);
-      const SlotShape& s1 = plan.slots[d.src1];
-      PH_REQUIRE(s1.h == h && s1.w == w && s1.c == d.cout, "residual shape mismatch");
-    }
-    if (d.kind == PH_OP_GLOBAL_MAXPOOL) {
-      oh = 1;
-      ow = 1;
-    }
-    if (d.kind == PH_OP_POOL) {
-      oh = (h + 1) / 2;
-      ow = (w + 1) / 2;
-    } else if (d.kind == PH_OP_UPSAMPLE || d.kind == PH_OP_CONVT) {
-      oh = 2 * h;
-      ow = 2 * w;
-    }
-    if (d.kind == PH_OP_CONV && d.src1 >= 0) {
-      const SlotShape& s1 = plan.slots[d.src1];
-      PH_REQUIRE(s1.offset >= 0, "op reads slot %d before it is written", d.src1);
-      PH_REQUIRE(s1.h == h && s1.w == w,
-                 "concat sources differ in size (%dx%d vs %dx%d): input H,W must be multiples of the model max stride",
-                 h, w, s1.h, s1.w);
-    }
-    if (d.kind == PH_OP_CONVT) tmp = std::max<int64_t>(tmp, (int64_t)B * oh * ow * fmt_cpad(fmt, d.cin0) * bpc);
-    if (d.kind == PH_OP_GRN) {  // the slice sums of grn_reduce_kernel
-      PH_REQUIRE(fmt == FMT_F32 && d.src0 >= 0 && plan.slots[d.src0].c == d.cin0 && d.cin0 == d.cout, "GRN channel mismatch");
-      tmp = std::max<int64_t>(tmp, grn_scratch_floats(B, h * w, pad16(d.cout)) * (int64_t)sizeof(float));
-      if (op_i >= 1 && fuses_grn(m, (size_t)op_i - 1, fmt)) {  // block sums of the first Linear's epilogue, then one scaled weight image per sample for the second
-        const PackedOp& l2 = m->ops[op_i + 1];
-        tmp = std::max<int64_t>(tmp, grn_fused_partial_floats(B * h * w, h * w, pad16(d.cout)) * (int64_t)sizeof(float));
-        tmp = std::max<int64_t>(tmp, (int64_t)B * gemm_pack_floats(pad16(l2.d.cout), pad16(d.cout), l2.bn) * (int64_t)sizeof(float));
-      }
-    }
-    if (d.kind == PH_OP_CONV && d.ksize == 3 && fmt == FMT_F32 && (m->conv_splitk >= 2 || (m->conv_splitk == 1 && reuse))) {  // (auto: inference plans only, as the kernel choice below)  // partial-sum planes of a split-K launch (conv3x3_wino2d_kernel<.., KS>)
-      int n_cu = 0;
-      if (device_cu_count(&n_cu) != PH_OK || n_cu <= 0) n_cu = 256;
-      tmp = std::max<int64_t>(tmp, wino2d_split_scratch_bytes(B, h, w, pad16(d.cin0) + (d.src1 >= 0 ? pad16(d.cin1) : 0), pad16(d.cout), m->conv_splitk, n_cu));
-      if (m->conv_wino4) tmp = std::max<int64_t>(tmp, wino4_split_scratch_bytes(B, h, w, pad16(d.cin0) + (d.src1 >= 0 ? pad16(d.cin1) : 0), pad16(d.cout), m->conv_splitk, n_cu));
-    }
-    PH_REQUIRE(d.dst >= 0 && d.dst < m->n_slots, "bad dst slot %d", d.dst);
-    SlotShape& s = plan.slots[d.dst];
-    s.c = (d.kind == PH_OP_POOL || d.kind == PH_OP_UPSAMPLE || d.kind == PH_OP_GLOBAL_MAXPOOL) ? d.cin0 : d.cout;
-    s.cp = fmt_cpad(fmt, s.c);
-    s.h = oh;
-    s.w = ow;
-    s.def_op = op_i;
-    s.offset = alloc(d.dst, (int64_t)B * oh * ow * s.cp * bpc);
-    if (d.kind == PH_OP_CONV && d.dst2 >= 0) {  // fused 2x2 max pool of the conv output
-      PH_REQUIRE(d.dst2 < m->n_slots && (d.flags & PH_FLAG_RELU), "fused pool needs a valid slot and a ReLU conv");
-      SlotShape& p = plan.slots[d.dst2];
-      p.c = d.cout;
-      p.cp = fmt_cpad(fmt, d.cout);
-      p.h = (oh + 1) / 2;
-      p.w = (ow + 1) / 2;
-      p.def_op = op_i;
-      p.offset = alloc(d.dst2, (int64_t)B * p.h * p.w * p.cp * bpc);
-    }
-  }
-  plan.tmp_offset = off;
-  plan.tmp_bytes = align_up(tmp, 256);
-  plan.total = off + plan.tmp_bytes;
-  return PH_OK;
-}
-
 // fp16 weight packs of every 3x3 conv / transposed conv, derived on the device from the fp32 LDS-DMA panels the first time a
 // forward needs them (and again after every ph_model_set_params, through m->derived).  Allocates: not capturable -- a
 // hipGraph user runs one eager forward first (HipBackend does).
@@ -539,22 +261,17 @@ int ensure_f16_weights(ph_model* m, int plain, hipStream_t s) {
     m->allocs.push_back(w);
     int rc = launch_f16_weight_pack(op.w_dma_dev, w, n_tiles, chunks0, chunks1, op.bn, plain, s);
     if (rc != PH_OK) return rc;
-    DerivedBuffer db;
-    db.kind = 1;
-    db.src = op.w_dma_dev;
-    db.dst = w;
+    DerivedBuffer& db = add_derived(m, DERIVED_F16_PACK, op.w_dma_dev, w, 0, op.bn);
     db.n_tiles = n_tiles;
     db.chunks0 = chunks0;
     db.chunks1 = chunks1;
-    db.bn = op.bn;
     db.plain = plain;
-    m->derived.push_back(db);
     op.w_f16_dev[plain] = w;
   }
   return PH_OK;
 }
 
-static int drain_events(ph_model* m) {
+int drain_events(ph_model* m) {
   if (!m->events_pending) return PH_OK;
   const size_t n = m->ops.size();
   PH_HIP_CHECK(hipEventSynchronize(m->ev[n]));
@@ -672,10 +389,7 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
           if (ok) {
             m->allocs.push_back(w);
             ok = launch_stem_wino_pack(op.w2_dev, w, nullptr) == PH_OK;
-            DerivedBuffer db;
-            db.src = op.w2_dev;
-            db.dst = w;
-            m->derived.push_back(db);
+            add_derived(m, DERIVED_WINO, op.w2_dev, w);  // (bn 0: the stem's form)
             op.w_wino_dev = w;
           }
         }
@@ -685,11 +399,7 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
           if (ok) {
             m->allocs.push_back(w);
             ok = launch_stem_wino2d_pack(op.w2_dev, w, nullptr) == PH_OK;
-            DerivedBuffer db;
-            db.src = op.w2_dev;
-            db.dst = w;
-            db.kind = 4;
-            m->derived.push_back(db);
+            add_derived(m, DERIVED_STEM_WINO2D, op.w2_dev, w);
             op.w_stem2_dev = w;
           }
         }
@@ -755,12 +465,7 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
           if (hipMalloc(&w, (size_t)wino_pack_floats(panels, bn) * sizeof(float)) != hipSuccess) return false;
           m->allocs.push_back(w);
           if (launch_wino_pack(src, w, panels, bn, nullptr) != PH_OK) return false;
-          DerivedBuffer db;
-          db.src = src;
-          db.dst = w;
-          db.panels = panels;
-          db.bn = bn;
-          m->derived.push_back(db);
+          add_derived(m, DERIVED_WINO, src, w, panels, bn);
           *dst = w;
           return true;
         };
@@ -773,13 +478,7 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
           if (hipMalloc(&w, (size_t)wino2d_pack_floats(panels, 64) * sizeof(float)) != hipSuccess) return false;
           m->allocs.push_back(w);
           if (launch_wino2d_pack(src, w, panels, 64, nullptr) != PH_OK) return false;
-          DerivedBuffer db;
-          db.src = src;
-          db.dst = w;
-          db.panels = panels;
-          db.bn = 64;
-          db.kind = 2;
-          m->derived.push_back(db);
+          add_derived(m, DERIVED_WINO2D, src, w, panels, 64);
           *dst = w;
           return true;
         };
@@ -798,13 +497,7 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
           if (hipMalloc(&w, (size_t)wino4_pack_floats(ntiles, nchunks) * sizeof(float)) != hipSuccess) return false;
           m->allocs.push_back(w);
           if (launch_wino4_pack(src, w, ntiles, nchunks, nullptr) != PH_OK) return false;
-          DerivedBuffer db;
-          db.src = src;
-          db.dst = w;
-          db.panels = ntiles;
-          db.bn = nchunks;
-          db.kind = 5;
-          m->derived.push_back(db);
+          add_derived(m, DERIVED_WINO4, src, w, ntiles, nchunks);
           *dst = w;
           return true;
         };
@@ -820,13 +513,7 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
           if (hipMalloc(&w, (size_t)w16_pack_floats(chunks, nbs) * sizeof(float)) != hipSuccess) return false;
           m->allocs.push_back(w);
           if (launch_w16_pack(src, w, chunks, nbs, nullptr) != PH_OK) return false;
-          DerivedBuffer db;
-          db.src = src;
-          db.dst = w;
-          db.panels = chunks;
-          db.bn = nbs;
-          db.kind = 3;
-          m->derived.push_back(db);
+          add_derived(m, DERIVED_W16, src, w, chunks, nbs);
           *dst = w;
           return true;
         };
@@ -838,14 +525,7 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
           if (ok) {
             m->allocs.push_back(w);
             ok = launch_sm_pack(op.w_dev, w, nblocks, chunks16, op.bn, nullptr) == PH_OK;
-            DerivedBuffer db;
-            db.src = op.w_dev;
-            db.dst = w;
-            db.panels = nblocks;
-            db.bn = chunks16;
-            db.n_tiles = op.bn;
-            db.kind = 6;
-            m->derived.push_back(db);
+            add_derived(m, DERIVED_SMALLMAP, op.w_dev, w, nblocks, chunks16).n_tiles = op.bn;
             op.w_sm_dev = w;
           }
         }
@@ -1080,15 +760,9 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
           if (ok) {
             m->allocs.push_back(w);
             ok = launch_gemm_f16_weight_image(op.w_dma_dev, w, d.cout, d.cin0, coutp32, cinp32, segs, op.bn, nullptr) == PH_OK;
-            DerivedBuffer db;
-            db.src = op.w_dma_dev;
-            db.dst = static_cast<float*>(w);
-            db.panels = d.cout;
+            DerivedBuffer& db = add_derived(m, DERIVED_GEMM_F16_IMAGE, op.w_dma_dev, static_cast<float*>(w), d.cout, op.bn);
             db.n_tiles = d.cin0;
             db.chunks0 = segs;
-            db.bn = op.bn;
-            db.kind = 7;
-            m->derived.push_back(db);
             op.w_cnx_f16_dev = w;
           }
         }
@@ -1162,1093 +836,6 @@ int ph_model_output_shape(const ph_model* m, int32_t out_index, int32_t height, 
     }
   set_error("no head writes output %d", out_index);
   return PH_E_INVALID;
-}
-
-int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32_t batch, int32_t in_channels, int32_t height,
-                     int32_t width, void* workspace_dev, int64_t workspace_bytes, float* const* out_dev, void* stream) {
-  PH_REQUIRE(m && input_dev && workspace_dev && out_dev, "ph_model_forward: null argument");
-  PH_REQUIRE(in_dtype >= 0 && in_dtype <= 2, "ph_model_forward: bad in_dtype %d", in_dtype);
-  PH_REQUIRE(((uintptr_t)workspace_dev & 255) == 0, "workspace must be 256-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  Plan plan;
-  const int fmt = forward_format(m);
-  PH_REQUIRE(!m->branch_scales || (fmt == FMT_F32 && batch == m->branch_batch),
-             "ph_model_forward: branch scales are set for batch %d in exact fp32; this forward has batch %d%s", m->branch_batch, batch, fmt == FMT_F32 ? "" : " and a non-fp32 format");
-  int branch = 0;  // residual Linear ops seen so far (row of the branch scales)
-  int rc = build_plan(m, batch, height, width, plan, fmt);
-  if (rc != PH_OK) return rc;
-  if (fmt != FMT_F32) {
-    rc = ensure_f16_weights(m, fmt == FMT_F16 ? 1 : 0, s);
-    if (rc != PH_OK) return rc;
-  }
-  const int rs_div = 4 / plan.bpc;  // pixel stride in 4-byte units = cp / rs_div
-  if (plan.total > workspace_bytes) {
-    set_error("workspace too small: need %lld bytes, got %lld", (long long)plan.total, (long long)workspace_bytes);
-    return PH_E_WORKSPACE;
-  }
-  char* ws = static_cast<char*>(workspace_dev);
-  // Every slot pointer that goes into a launcher's arguments is taken through rd() (a source) or wr() (a destination), which note the slot's byte range under the
-  // current op and launch (ph_model_last_ranges): the record follows the routing below, whatever it decides.  Host bookkeeping only.
-  size_t op_index = 0;
-  int launch_no = 0;  // launch ordinal within the current op
-  std::vector<RangeRec>& rr = m->last_ranges;
-  rr.clear();
-  auto note = [&](int is_dst, int slot, int64_t offset, int64_t bytes) { rr.push_back(RangeRec{(int)op_index - 1, launch_no, is_dst, slot, offset, bytes}); };
-  auto slot_bytes = [&](int sidx) { const SlotShape& q = plan.slots[sidx]; return (int64_t)batch * q.h * q.w * q.cp * plan.bpc; };
-  auto rd = [&](int sidx) { note(0, sidx, plan.slots[sidx].offset, slot_bytes(sidx)); return reinterpret_cast<float*>(ws + plan.slots[sidx].offset); };
-  auto wr = [&](int sidx) { note(1, sidx, plan.slots[sidx].offset, slot_bytes(sidx)); return reinterpret_cast<float*>(ws + plan.slots[sidx].offset); };
-  auto note_tmp = [&](int is_dst) { note(is_dst, -1, plan.tmp_offset, plan.tmp_bytes); };  // the scratch region behind the slots
-  auto unnote = [&](int is_dst, int sidx) {  // a pointer of the current launch that was replaced before the launch
-    for (size_t k = rr.size(); k-- > 0 && rr[k].op == (int)op_index - 1;)
-      if (rr[k].launch == launch_no && rr[k].is_dst == is_dst && rr[k].slot == sidx) {
-        rr.erase(rr.begin() + k);
-        return;
-      }
-  };
-  auto launch_before = [&]() {  // the ranges noted so far belong to a launch that runs AFTER the one about to be made (a deferred bilinear produced after all)
-    for (size_t k = rr.size(); k-- > 0 && rr[k].op == (int)op_index - 1;)
-      if (rr[k].launch == launch_no) rr[k].launch += 1;
-  };
-  if (m->profiling) {
-    rc = drain_events(m);
-    if (rc != PH_OK) return rc;
-  }
-  if (m->wino4_stale && (m->conv_wino4 >= 2 || (m->conv_wino4 == 1 && plan.reuse) || m->conv_smallmap >= 2 || (m->conv_smallmap == 1 && plan.reuse))) {  // (the inference-only weight forms: F(4x4,3x3), small-map)
-    for (const DerivedBuffer& db : m->derived)
-      if (db.kind == 5 || db.kind == 6) {
-        rc = db.kind == 5 ? launch_wino4_pack(db.src, db.dst, db.panels, db.bn, s) : launch_sm_pack(db.src, db.dst, db.panels, db.bn, db.n_tiles, s);
-        if (rc != PH_OK) return rc;
-      }
-    m->wino4_stale = false;
-  }
-  if (m->cnx_f16_stale && fmt == FMT_F16) {  // (the fp16 row-GEMM images ph_model_set_params left for the first forward that reads them)
-    for (const DerivedBuffer& db : m->derived)
-      if (db.kind == 7) {
-        rc = launch_gemm_f16_weight_image(db.src, db.dst, db.panels, db.n_tiles, fmt_cpad(FMT_F16, db.panels), fmt_cpad(FMT_F16, db.n_tiles), db.chunks0, db.bn, s);
-        if (rc != PH_OK) return rc;
-      }
-    m->cnx_f16_stale = false;
-  }
-  m->last_variant.assign(m->ops.size(), PH_KV_NONE);
-  int* const kv = m->last_variant.data();
-  bool skip_next_gelu = false, skip_next_scale_add = false, skip_next_linear = false;
-  int pooled_by_conv = -1;  // slot whose 2x2 max pool the producing conv's epilogue already wrote (run-time fusion of an unfused program, see PH_OP_CONV)
-  std::vector<char> head_done(m->ops.size(), 0);  // head ops the producing conv's epilogue already computed (see PH_OP_CONV)
-  std::vector<char> conv_done(m->ops.size(), 0);  // conv ops the conv in front of them already computed (two-conv block kernel, see PH_OP_CONV)
-  int deferred_up = -1;     // index of a bilinear op left to the conv that follows it (see PH_OP_UPSAMPLE / PH_OP_CONV)
-  int fused_grn = -1;       // fused GRN plan: 1-based index of the op of a ConvNeXtV2 block that ran last on that plan (Linear + GELU, then the GRN op; the residual Linear clears it)
-  int fused_ln = -1;        // index of a LayerNorm op the producing depthwise conv already applied (see PH_OP_DWCONV)
-  for (const PackedOp& op : m->ops) {
-    const ph_op_desc& d = op.d;
-    if (m->profiling) PH_HIP_CHECK(hipEventRecord(m->ev[op_index], s));
-    ++op_index;
-    launch_no = 0;
-    switch (d.kind) {
-      case PH_OP_INPUT_CONV: {
-        PH_REQUIRE(d.cin0 == in_channels, "input has %d channels, network expects %d", in_channels, d.cin0);
-        InputConvArgs a{};
-        a.src = input_dev;
-        a.w = op.w_dev;
-        a.bias = op.b_dev;
-        a.dst = wr(d.dst);
-        a.dtype = in_dtype;
-        a.cin = d.cin0;
-        a.coutp = pad16(d.cout);
-        a.B = batch;
-        a.H = height;
-        a.W = width;
-        a.relu = (d.flags & PH_FLAG_RELU) ? 1 : 0;
-        a.ksize = d.ksize;
-        a.out_fmt = fmt;
-        a.dst_cp = plan.slots[d.dst].cp;
-        rc = launch_input_conv(a, s);
-        break;
-      }
-      case PH_OP_STEM: {
-        PH_REQUIRE(d.cin0 == in_channels, "input has %d channels, network expects %d", in_channels, d.cin0);
-        StemArgs a{};
-        a.src = input_dev;
-        a.w0 = op.w_dev;
-        a.b0 = op.b_dev;
-        a.w1 = op.w2_dev;
-        a.w1w = op.w_wino_dev;
-        a.w1w2 = op.w_stem2_dev;
-        a.b1 = op.b2_dev;
-        a.dst_full = d.dst >= 0 ? wr(d.dst) : nullptr;
-        a.dst_pool = wr(d.dst2);
-        a.dtype = in_dtype;
-        a.cin = d.cin0;
-        a.B = batch;
-        a.H = height;
-        a.W = width;
-        a.wino = m->stem_wino;
-        a.f16_mfma = m->stem_f16mfma;
-        a.out_fmt = fmt;
-        kv[op_index - 1] = PH_KV_STEM;
-        rc = launch_stem(a, s);
-        break;
-      }
-      case PH_OP_CONV: {
-        const SlotShape& s0 = plan.slots[d.src0];
-        if (conv_done[op_index - 1]) {  // computed by the conv in front of it (block2_c32_f16_kernel, below)
-          kv[op_index - 1] = PH_KV_FUSED;
-          break;
-        }
-        if (fmt != FMT_F32) {
-          PH_REQUIRE(s0.c == d.cin0 && (d.src1 < 0 || plan.slots[d.src1].c == d.cin1), "conv channel mismatch");
-          const SlotShape& so = plan.slots[d.dst];
-          if (fuses_block2(m, op_index - 1, fmt, plan.reuse)) {  // (the predicate build_plan holds this pair's releases on)
-            const PackedOp& nxo = m->ops[op_index];
-            const ph_op_desc& nx = nxo.d;
-            if (nxo.w_f16_dev[1] && op.w_f16_dev[1] && so.cp == 32 && s0.cp == 32 && plan.slots[nx.dst].cp == 32) {
-              Block2Args b2{};
-              b2.src = rd(d.src0);
-              b2.wa = op.w_f16_dev[1];
-              b2.wb = nxo.w_f16_dev[1];
-              b2.ba = op.b_dev;
-              b2.bb = nxo.b_dev;
-              const bool full_unread = nx.dst2 >= 0 && !plan.unread.empty() && plan.unread[nx.dst];
-              b2.dst_full = full_unread ? nullptr : wr(nx.dst);
-              b2.dst_pool = nx.dst2 >= 0 ? wr(nx.dst2) : nullptr;
-              b2.B = batch;
-              b2.H = s0.h;
-              b2.W = s0.w;
-              b2.relu_a = (d.flags & PH_FLAG_RELU) ? 1 : 0;
-              b2.relu_b = (nx.flags & PH_FLAG_RELU) ? 1 : 0;
-              b2.zeros = m->zeros_dev;
-              conv_done[op_index] = 1;
-              kv[op_index - 1] = PH_KV_F16_BLOCK;
-              rc = launch_block2_c32_f16(b2, s);
-              break;
-            }
-          }
-          const int cdiv = fmt == FMT_F16 ? 32 : 16;
-          ConvF16Args f{};
-          f.src0 = rd(d.src0);
-          f.rs0 = s0.cp / rs_div;
-          f.chunks0 = s0.cp / cdiv;
-          if (d.src1 >= 0) {
-            f.src1 = rd(d.src1);
-            f.rs1 = plan.slots[d.src1].cp / rs_div;
-            f.chunks1 = plan.slots[d.src1].cp / cdiv;
-          }
-          f.wpack = op.w_f16_dev[fmt == FMT_F16 ? 1 : 0];
-          f.bias = op.b_dev;
-          f.dst = wr(d.dst);
-          f.dst_pool = d.dst2 >= 0 ? wr(d.dst2) : nullptr;
-          f.skip_dst = (f.dst_pool && plan.reuse && !plan.unread.empty() && plan.unread[d.dst]) ? 1 : 0;
-          f.rs_dst = so.cp / rs_div;
-          f.coutp = so.cp;
-          f.B = batch;
-          f.H = s0.h;
-          f.W = s0.w;
-          f.relu = (d.flags & PH_FLAG_RELU) ? 1 : 0;
-          f.bn = op.bn;
-          f.prec = fmt == FMT_F16 ? 1 : 3;
-          f.zeros = m->zeros_dev;
-          f.clock_probe = m->clock_probe ? m->clock_probe + PH_PROBE_WORDS_PER_OP * (op_index - 1) : nullptr;  // one record block per op
-          if (m->head_fuse && fmt == FMT_F16 && !f.dst_pool && op.bn == 64 && (so.cp == 64 || (so.cp == 128 && m->conv_f16_rows))) {
-            // plain fp16: a 1x1 head that reads this conv's 64-channel output rides in its epilogue (four MFMAs on the staged fp16 row); when nothing else reads the tensor it never reaches HBM
-            // (128 channels: only conv3x3_f16_rows_kernel holds both N tiles of a pixel in one workgroup -- undone below if that kernel does not take the layer)
-            for (size_t j = op_index; j < m->ops.size(); ++j) {
-              const ph_op_desc& hx = m->ops[j].d;
-              if (hx.kind != PH_OP_HEAD || hx.src0 != d.dst) continue;
-              if (!(hx.flags & PH_FLAG_SOFTMAX) && out_dev[hx.out_index] && hx.cout <= 32 && fmt_cpad(FMT_F16, hx.cin0) == so.cp) {
-                f.head_w = m->ops[j].w_dev;
-                f.head_b = m->ops[j].b_dev;
-                f.head_dst = out_dev[hx.out_index];
-                f.head_cout = hx.cout;
-                f.head_wcp = so.cp;
-                f.head_sigmoid = head_sigmoid(m, plan, hx);
-                head_done[j] = 1;
-                if (plan.reuse) {
-                  bool other = false;
-                  for (size_t k = 0; k < m->ops.size(); ++k)
-                    if (k != j && (m->ops[k].d.src0 == d.dst || m->ops[k].d.src1 == d.dst)) other = true;
-                  if (!other) f.skip_dst = 1;
-                }
-              }
-              break;
-            }
-          }
-          if (deferred_up >= 0 || (fmt == FMT_F16 && m->conv_f16_rows)) {
-            // conv3x3_f16_rows_kernel (row tiles, loader waves, weights L2 -> registers; f16_rows_kernels.hip) where its plan is estimated faster ("conv_f16_rows" 2: wherever
-            // the shape fits).  A bilinear x2 in front of this conv that only feeds its second source was not launched (PH_OP_UPSAMPLE): the kernel reads the
-            // half-resolution tensor itself; if it does not take the layer, the tensor is produced now.
-            int n_cu = 0;
-            if (device_cu_count(&n_cu) != PH_OK || n_cu <= 0) n_cu = 256;
-            bool on_rows = false;
-            if (fmt == FMT_F16 && m->conv_f16_rows) {
-              ConvF16Args r = f;
-              const size_t mark = rr.size();
-              if (deferred_up >= 0) {
-                const ph_op_desc& up = m->ops[deferred_up].d;
-                r.src1 = rd(up.src0);
-                r.rs1 = plan.slots[up.src0].cp / rs_div;
-                r.src1_lowres = 1;
-                r.rows_blend16 = m->upsample_f16math ? 1 : 0;
-              }
-              const double c_rows = f16_rows_plan(r, n_cu);
-              double c_old = f16_conv_cost(f, n_cu);
-              if (deferred_up >= 0) c_old += f16_upsample_cost(batch, s0.h / 2, s0.w / 2, plan.slots[d.src1].cp, n_cu);
-              if (f.head_w && !(f.bn == 64 && f.coutp == 64))  // a head only the row-tile kernel fuses: the other way costs head1x1_mfma_kernel's launch (its bytes at ~5 TB/s + the boundary)
-                c_old += (double)batch * s0.h * s0.w * (f.coutp * 2.0 + f.head_cout * 4.0) / 2500.0 + 3000.0;
-              if (c_rows >= 0 && (m->conv_f16_rows >= 2 || c_rows < 0.95 * c_old)) {  // (the estimates are good to a few per cent: a tie stays with the round-2 kernel, measured 6 - 8 % faster on the 2-chunk 192 x 192 layers of cfg5)
-                f = r;
-                on_rows = true;
-                if (deferred_up >= 0) unnote(0, d.src1);  // (the half-resolution tensor took the up-sampled one's place)
-              } else {
-                rr.resize(mark);
-              }
-            }
-            if (deferred_up >= 0 && !on_rows) {
-              const ph_op_desc& up = m->ops[deferred_up].d;
-              const SlotShape& sl = plan.slots[up.src0];
-              launch_before();
-              rc = launch_upsample_fmt(fmt, rd(up.src0), wr(up.dst), batch, sl.h, sl.w, sl.cp, s, (fmt == FMT_F16 && m->upsample_f16math) ? 1 : 0);
-              if (rc != PH_OK) return rc;
-              ++launch_no;
-            }
-            deferred_up = -1;
-            if (on_rows) {
-              kv[op_index - 1] = PH_KV_F16_ROWS;
-              rc = launch_conv3x3_f16_rows(f, s);
-              break;
-            }
-            if (f.head_w && (f.bn != 64 || f.coutp != 64)) {  // (a head only the row-tile kernel fuses: leave it to its own launch)
-              for (size_t j = op_index; j < m->ops.size(); ++j)
-                if (m->ops[j].d.kind == PH_OP_HEAD && m->ops[j].d.src0 == d.dst && head_done[j]) head_done[j] = 0;
-              f.head_w = nullptr;
-              f.skip_dst = (f.dst_pool && plan.reuse && !plan.unread.empty() && plan.unread[d.dst]) ? 1 : 0;
-            }
-          }
-          kv[op_index - 1] = PH_KV_F16;
-          rc = launch_conv3x3_f16(f, s);
-          break;
-        }
-        if (d.ksize != 3) {  // k x k "same" conv: k^2-tap row GEMM
-          PH_REQUIRE(s0.c == d.cin0 && (d.src1 < 0 || plan.slots[d.src1].c == d.cin1), "conv channel mismatch");
-          GemmArgs g{};
-          g.src0 = rd(d.src0);
-          g.c0p = s0.cp;
-          g.src1 = d.src1 >= 0 ? rd(d.src1) : nullptr;
-          g.c1p = d.src1 >= 0 ? plan.slots[d.src1].cp : 0;
-          g.wpack = op.w_gemm_dev;
-          g.bias = op.b_gemm_dev;
-          g.dst = wr(d.dst);
-          g.zeros = m->zeros_dev;
-          g.coutp = pad16(d.cout);
-          g.bn = op.bn_g;
-          g.M = batch * s0.h * s0.w;
-          g.mode = 5;
-          g.ksize = d.ksize;
-          g.H = s0.h;
-          g.W = s0.w;
-          g.act = (d.flags & PH_FLAG_RELU) ? 1 : 0;
-          g.late_split = m->gemm_late_split;
-          kv[op_index - 1] = PH_KV_ROWGEMM;
-          rc = launch_gemm(g, s);
-          if (rc == PH_OK && d.dst2 >= 0) {  // the fused-pool flag of the plan, unfused here
-            ++launch_no;
-            rc = launch_pool(rd(d.dst), wr(d.dst2), batch, s0.h, s0.w, g.coutp, s);
-          }
-          break;
-        }
-        ConvArgs a{};
-        a.src0 = rd(d.src0);
-        a.c0p = s0.cp;
-        a.src1 = d.src1 >= 0 ? rd(d.src1) : nullptr;
-        a.c1p = d.src1 >= 0 ? plan.slots[d.src1].cp : 0;
-        PH_REQUIRE(s0.c == d.cin0 && (d.src1 < 0 || plan.slots[d.src1].c == d.cin1), "conv channel mismatch");
-        a.wpack = op.w_dev;
-        a.bias = op.b_dev;
-        a.dst = wr(d.dst);
-        a.coutp = pad16(d.cout);
-        a.B = batch;
-        a.H = s0.h;
-        a.W = s0.w;
-        a.relu = (d.flags & PH_FLAG_RELU) ? 1 : 0;
-        a.bn = op.bn;
-        a.clock_probe = m->clock_probe ? m->clock_probe + PH_PROBE_WORDS_PER_OP * (op_index - 1) : nullptr;  // one record block per op (diagnostic builds / kernels that stamp)
-        a.dst_pool = d.dst2 >= 0 ? wr(d.dst2) : nullptr;
-        a.skip_dst = (a.dst_pool && plan.reuse && !plan.unread.empty() && plan.unread[d.dst]) ? 1 : 0;  // e.g. cfg3's second encoder block: 1 GiB per 32 frames nobody reads
-        a.wpack_dma = op.w_dma_dev;
-        a.wpack_wino = op.w_wino_dev;
-        a.wpack_wino2 = op.w_wino2_dev;
-        a.wpack_w16 = op.w_w16_dev;
-        a.w16 = op.w16_dev;
-        a.zeros = m->zeros_dev;
-        apply_conv_options(m, a);
-        a.wpack_sm = op.w_sm_dev;
-        a.use_sm = m->conv_smallmap >= 2 ? 2 : ((m->conv_smallmap == 1 && m->conv_splitk == 1 && plan.reuse && m->use_dma) ? 1 : 0);
-        a.wpack_wino4 = op.w_wino4_dev;
-        a.use_wino4 = m->conv_wino4 == 3 ? 2 : ((m->conv_wino4 == 2 || (m->conv_wino4 == 1 && plan.reuse)) ? 1 : 0);
-        // (the two round-4 routings below -- Cout-32 layers on the N-tile-64 kernels, split K -- apply to inference plans only: a training program's forward keeps the kernels its
-        // gradient tests were pinned with.  The wave-private kernel's two-source (16 + 32 -> 16) and fused-head forms are NOT gated that way: they are shapes of conv_w16 itself and
-        // run in every plan; tests/test_gpu_training.py's default network (filters 8, output stride 2: concat 16 + 32 -> 16) trains through the two-source form, its gradients are
-        // compared with autograd's)
-        if (op.w_n64_dev && op.w_wino2_dev && op.w_wino_dev && (m->conv_n32_wino2d >= 2 || (m->conv_n32_wino2d == 1 && plan.reuse)) && m->use_dma && m->conv_wino && m->conv_wino2d && m->conv_persist && !w16_fits(a) && wino2d_fits(a)) {
-          // Cout 32, K >= 64 (and not a shape of the wave-private kernel): N tile 64 with its upper half empty -- the F(2x2,3x3) kernel skips the missing half's MFMAs
-          a.bn = 64;
-          a.wpack = op.w_n64_dev;
-          a.bias = op.b_n64_dev;
-          a.wpack_dma = nullptr;
-        }
-        if (a.splitk == 1 && !plan.reuse) a.splitk = 0;
-        if (plan.tmp_bytes > 0) {
-          a.split_scratch = reinterpret_cast<float*>(ws + plan.tmp_offset);
-          a.split_scratch_bytes = plan.tmp_bytes;
-        }
-        if (deferred_up >= 0) {
-          // The op before this one is a bilinear x2 that only feeds this conv's second source and was not launched: the F(4x4,3x3) kernel
-          // reads the half-resolution tensor itself (the up-sampling rides in its input transform); any other kernel gets the tensor now.
-          const ph_op_desc& up = m->ops[deferred_up].d;
-          const SlotShape& sl = plan.slots[up.src0];
-          ConvArgs f = a;
-          const size_t mark = rr.size();
-          f.src1 = rd(up.src0);
-          f.src1_lowres = 1;
-          if ((m->use_dma && conv3x3_dma_is_wino4(f)) || conv3x3_takes_sm(f)) {
-            a = f;
-            unnote(0, d.src1);  // (the half-resolution tensor took the up-sampled one's place)
-          } else {
-            rr.resize(mark);
-            launch_before();
-            rc = launch_upsample(rd(up.src0), wr(up.dst), batch, sl.h, sl.w, sl.cp, s);
-            if (rc != PH_OK) return rc;
-            ++launch_no;
-          }
-          deferred_up = -1;
-        }
-        const bool on_sm = conv3x3_takes_sm(a);  // small maps at small batches: (8 x 8 pixels, 16 channels) units, one launch, no split K (conv3x3_sm_kernel)
-        const double fill = (double)s0.h * s0.w / ((double)((s0.h + 15) / 16 * 16) * ((s0.w + 31) / 32 * 32));
-        // the halo kernel pads Cout to a multiple of its N tile (64): e.g. Cout = 96 does 33 % extra MFMA work there,
-        // none in the row GEMM (N tiles of 96 / 128)
-        const double n_fill = (double)a.coutp / ((a.coutp + op.bn - 1) / op.bn * op.bn);
-        const int bn_g = op.bn_g > 0 ? op.bn_g : 128;
-        const double n_fill_g = (double)a.coutp / ((a.coutp + bn_g - 1) / bn_g * bn_g);
-        // the halo kernel runs Winograd F(2,3) (2/3 of the MFMA work) where its weights exist: it wins down to ~0.5 tile fill (measured on the ConvNeXt decoder: 48x48 and 24x24 maps)
-        double halo_gain = (op.w_wino_dev && m->use_dma) ? m->gemm_fill_threshold / m->gemm_fill_threshold_wino : 1.0;
-        double halo_fill = fill;
-        if (m->use_dma && m->conv_wino && m->conv_wino2d && m->conv_persist && op.w_wino2_dev && a.bn == 64 && a.c0p + a.c1p >= 32 && wino2d_fits(a)) {
-          // the F(2x2,3x3) kernel: 16x16-pixel tiles and 4/9 of the MFMA work -- it beats the 9-tap row GEMM down to ~0.4 tile fill
-          halo_fill = (double)s0.h * s0.w / ((double)((s0.h + 15) / 16 * 16) * ((s0.w + 15) / 16 * 16));
-          halo_gain = m->gemm_fill_threshold / m->gemm_fill_threshold_wino2d;
-        }
-        if (!on_sm && m->use_dma && d.dst2 < 0 && op.w_gemm_dev && !a.src1_lowres && (halo_fill * halo_gain < m->gemm_fill_threshold || n_fill * halo_fill * halo_gain < 0.8 * n_fill_g)) {
-          // small feature map (the 16x32-pixel tiles of the halo kernel would be mostly padding) or a Cout that
-          // fits the halo kernel's N tile badly -> 9-tap row GEMM
-          GemmArgs g{};
-          g.src0 = a.src0;
-          g.src1 = a.src1;
-          g.c0p = a.c0p;
-          g.c1p = a.c1p;
-          g.wpack = op.w_gemm_dev;
-          g.bias = op.b_gemm_dev;
-          g.dst = a.dst;
-          g.zeros = m->zeros_dev;
-          g.coutp = a.coutp;
-          g.bn = op.bn_g;
-          g.M = batch * s0.h * s0.w;
-          g.mode = 2;
-          g.H = s0.h;
-          g.W = s0.w;
-          g.act = a.relu ? 1 : 0;
-          g.late_split = m->gemm_late_split;
-          g.persist2 = m->gemm_persist2;
-          kv[op_index - 1] = PH_KV_ROWGEMM;
-          rc = launch_gemm(g, s);
-          break;
-        }
-        if (m->head_fuse && !a.dst_pool && ((a.coutp == 64 && a.bn == 64) || ((a.coutp == 16 || a.coutp == 32) && a.bn == 32)) && m->use_dma) {
-          // A 1x1 head that reads this conv's 64-channel output rides in the F(2x2,3x3) kernel's epilogue (the accumulator layout is the
-          // MFMA's B operand: conv3x3_wino2d_kernel); when nothing else reads the tensor (inference plans) it never reaches HBM.
-          for (size_t j = op_index; j < m->ops.size(); ++j) {
-            const ph_op_desc& hx = m->ops[j].d;
-            if (hx.kind != PH_OP_HEAD || hx.src0 != d.dst) continue;
-            ConvArgs no4 = a;  // (a fused head beats F(4x4,3x3) + a head launch on the 64-channel layers both could take: ask what runs without that kernel; head_w then keeps it off)
-            no4.use_wino4 = 0;
-            const bool on_w2d = a.coutp == 64 && hx.cout <= 32 && pad16(hx.cin0) == 64 && conv3x3_dma_is_wino2d(no4) && wino2d_ksplit(no4) <= 1;
-            const bool on_w16 = a.coutp <= 32 && hx.cout <= 16 && pad16(hx.cin0) == a.coutp && conv3x3_dma_is_w16_head(a);  // (conv3x3_w16_kernel<.., HEAD>)
-            const bool sm_head = on_sm && a.coutp <= 32 && pad16(hx.cin0) == a.coutp;  // (conv3x3_sm_kernel: the workgroup holds every channel of its pixels)
-            if (!(hx.flags & PH_FLAG_SOFTMAX) && out_dev[hx.out_index] && (sm_head || (!on_sm && (on_w2d || on_w16)))) {
-              a.head_w = m->ops[j].w_dev;
-              a.head_b = m->ops[j].b_dev;
-              a.head_dst = out_dev[hx.out_index];
-              a.head_cout = hx.cout;
-              a.head_wcp = a.coutp;
-              a.head_sigmoid = head_sigmoid(m, plan, hx);
-              head_done[j] = 1;
-              if (plan.reuse) {  // training keeps every activation
-                bool other = false;
-                for (size_t k = 0; k < m->ops.size(); ++k)
-                  if (k != j && (m->ops[k].d.src0 == d.dst || m->ops[k].d.src1 == d.dst)) other = true;
-                if (!other) a.skip_dst = 1;
-              }
-            }
-            break;
-          }
-        }
-        if (m->pool_peephole && !a.dst_pool && !a.head_w && a.relu && m->use_dma && (a.bn == 64 || m->dma32) && op_index < m->ops.size()) {
-          // An UNFUSED program (the training forward: the backward walks one op per activation) still gets the conv kernels' fused
-          // 2x2 max pool: when the next op is the pool of this conv's output, the epilogue writes both tensors and the pool op is skipped.
-          const ph_op_desc& nx = m->ops[op_index].d;
-          if (nx.kind == PH_OP_POOL && nx.src0 == d.dst) {
-            a.dst_pool = wr(nx.dst);
-            if (conv3x3_dma_is_f2x2(a)) {  // the F(2x2,3x3) kernels (a Winograd tile is a pool window); other kernels keep the separate pool
-              pooled_by_conv = d.dst;
-            } else {
-              a.dst_pool = nullptr;
-              unnote(1, nx.dst);
-            }
-          }
-        }
-        if (a.split_scratch) note_tmp(1);  // (partial-sum planes of a split-K launch)
-        if (on_sm) {
-          kv[op_index - 1] = PH_KV_SMALLMAP;
-          rc = launch_conv3x3_sm(a, s);
-          break;
-        }
-        kv[op_index - 1] = (m->use_dma && (a.bn == 64 || m->dma32)) ? conv3x3_dma_variant(a) : PH_KV_DIRECT;
-        rc = (m->use_dma && (a.bn == 64 || m->dma32)) ? launch_conv3x3_dma(a, s) : launch_conv3x3(a, s);
-        break;
-      }
-      case PH_OP_POOL: {
-        if (pooled_by_conv == d.src0) {  // written by the producing conv's epilogue
-          pooled_by_conv = -1;
-          break;
-        }
-        const SlotShape& s0 = plan.slots[d.src0];
-        float* const src = rd(d.src0);
-        float* const dst = wr(d.dst);
-        rc = fmt == FMT_F32 ? launch_pool(src, dst, batch, s0.h, s0.w, s0.cp, s) : launch_pool_fmt(fmt, src, dst, batch, s0.h, s0.w, s0.cp, s);
-        break;
-      }
-      case PH_OP_UPSAMPLE: {
-        const SlotShape& s0 = plan.slots[d.src0];
-        if (fmt == FMT_F32 && plan.reuse && m->upsample_fold && (m->conv_wino4 || m->conv_smallmap) && m->use_dma && op_index < m->ops.size()) {
-          // inference plans: when the NEXT op is a 3x3 conv that takes this tensor as its second source and nothing else reads it, the conv
-          // decides (it may run the F(4x4,3x3) kernel, which up-samples in its input transform) -- see PH_OP_CONV
-          const PackedOp& nxo = m->ops[op_index];
-          const ph_op_desc& nx = nxo.d;
-          bool only = nx.kind == PH_OP_CONV && nx.ksize == 3 && nx.src1 == d.dst && nx.src0 != d.dst && nx.dst2 < 0 && ((m->conv_wino4 && nxo.w_wino4_dev != nullptr) || (m->conv_smallmap && nxo.w_sm_dev != nullptr));  // (a form that is switched off does not defer the launch)
-          for (size_t k = 0; only && k < m->ops.size(); ++k)
-            if (k != op_index && (m->ops[k].d.src0 == d.dst || m->ops[k].d.src1 == d.dst)) only = false;
-          if (only) {
-            deferred_up = (int)op_index - 1;
-            break;
-          }
-        }
-        if (fmt == FMT_F16 && plan.reuse && m->upsample_fold && m->conv_f16_rows && op_index < m->ops.size()) {
-          // the same on the fp16 pipe: conv3x3_f16_rows_kernel's loader waves blend the half-resolution tensor into the halo
-          const PackedOp& nxo = m->ops[op_index];
-          const ph_op_desc& nx = nxo.d;
-          bool only = nx.kind == PH_OP_CONV && nx.ksize == 3 && nx.src1 == d.dst && nx.src0 != d.dst && nxo.bn == 64 && plan.slots[nx.src0].h == 2 * s0.h && plan.slots[nx.src0].w == 2 * s0.w;
-          for (size_t k = 0; only && k < m->ops.size(); ++k)
-            if (k != op_index && (m->ops[k].d.src0 == d.dst || m->ops[k].d.src1 == d.dst)) only = false;
-          if (only) {
-            deferred_up = (int)op_index - 1;
-            break;
-          }
-        }
-        float* const src = rd(d.src0);
-        float* const dst = wr(d.dst);
-        rc = fmt == FMT_F32 ? launch_upsample(src, dst, batch, s0.h, s0.w, s0.cp, s)
-                            : launch_upsample_fmt(fmt, src, dst, batch, s0.h, s0.w, s0.cp, s, (fmt == FMT_F16 && m->upsample_f16math) ? 1 : 0);
-        break;
-      }
-      case PH_OP_CONVT: {
-        const SlotShape& s0 = plan.slots[d.src0];
-        PH_REQUIRE(s0.c == d.cin0, "convT channel mismatch");
-        if (fmt == FMT_F32 && m->convt_phase && op.wt_phase_dev[0]) {  // four output-phase GEMMs: 9 taps per INPUT pixel, no zero-stuffed tensor
-          const SlotShape& so = plan.slots[d.dst];
-          for (int ph = 0; ph < (m->convt_one_launch ? 1 : 4) && rc == PH_OK; ++ph) {  // one launch for the four phases (grid.y), or four launches
-            GemmArgs g{};
-            launch_no = ph;
-            g.src0 = rd(d.src0);
-            g.c0p = s0.cp;
-            g.wpack = op.wt_phase_dev[ph];
-            g.bias = op.bt_dev;
-            g.dst = wr(d.dst);
-            g.zeros = m->zeros_dev;
-            g.coutp = so.cp;
-            g.bn = op.bn_t;
-            g.M = batch * s0.h * s0.w;
-            g.mode = 3;
-            g.ntaps = (1 + (ph >> 1)) * (1 + (ph & 1));
-            g.H = s0.h;
-            g.W = s0.w;
-            g.out_patch = 1;
-            g.out_tap = ph;
-            if (m->convt_one_launch) {
-              g.all_phases = 1;
-              for (int q = 0; q < 4; ++q) g.wpack_ph[q] = op.wt_phase_dev[q];
-            }
-            g.out_H = 2 * s0.h;
-            g.out_W = 2 * s0.w;
-            g.act = (d.flags & PH_FLAG_SILU) ? 4 : ((d.flags & PH_FLAG_RELU) ? 1 : 0);
-            g.scale = op.wt_scale_dev;
-            g.shift = op.wt_shift_dev;
-            g.affine_first = op.wt_scale_dev ? 1 : 0;
-            g.late_split = m->gemm_late_split;
-            rc = launch_gemm(g, s);
-          }
-          kv[op_index - 1] = PH_KV_ROWGEMM;
-          break;
-        }
-        PH_REQUIRE(!op.wt_scale_dev && !(d.flags & PH_FLAG_SILU), "folded BatchNorm / SiLU on a transposed conv need the phase GEMMs (exact precision, convt_phase = 1)");
-        float* tmp = reinterpret_cast<float*>(ws + plan.tmp_offset);
-        note_tmp(1);
-        rc = launch_zero_stuff(rd(d.src0), tmp, batch, s0.h, s0.w, s0.cp / rs_div, s);  // 16-B quads: format-agnostic
-        if (rc != PH_OK) break;
-        ++launch_no;
-        note_tmp(0);  // (the conv below reads the zero-stuffed tensor)
-        if (fmt != FMT_F32) {
-          const SlotShape& so = plan.slots[d.dst];
-          ConvF16Args f{};
-          f.src0 = tmp;
-          f.rs0 = s0.cp / rs_div;
-          f.chunks0 = s0.cp / (fmt == FMT_F16 ? 32 : 16);
-          f.wpack = op.w_f16_dev[fmt == FMT_F16 ? 1 : 0];
-          f.bias = op.b_dev;
-          f.dst = wr(d.dst);
-          f.rs_dst = so.cp / rs_div;
-          f.coutp = so.cp;
-          f.B = batch;
-          f.H = 2 * s0.h;
-          f.W = 2 * s0.w;
-          f.relu = (d.flags & PH_FLAG_RELU) ? 1 : 0;
-          f.bn = op.bn;
-          f.prec = fmt == FMT_F16 ? 1 : 3;
-          f.zeros = m->zeros_dev;
-          f.clock_probe = m->clock_probe ? m->clock_probe + PH_PROBE_WORDS_PER_OP * (op_index - 1) : nullptr;  // one record block per op
-          if (m->head_fuse && fmt == FMT_F16 && !f.dst_pool && op.bn == 64 && so.cp == 64) {
-            // plain fp16: a 1x1 head that reads this conv's 64-channel output rides in its epilogue (four MFMAs on the staged fp16 row); when nothing else reads the tensor it never reaches HBM
-            for (size_t j = op_index; j < m->ops.size(); ++j) {
-              const ph_op_desc& hx = m->ops[j].d;
-              if (hx.kind != PH_OP_HEAD || hx.src0 != d.dst) continue;
-              if (!(hx.flags & PH_FLAG_SOFTMAX) && out_dev[hx.out_index] && hx.cout <= 32 && pad16(hx.cin0) == 64) {
-                f.head_w = m->ops[j].w_dev;
-                f.head_b = m->ops[j].b_dev;
-                f.head_dst = out_dev[hx.out_index];
-                f.head_cout = hx.cout;
-                f.head_wcp = 64;
-                f.head_sigmoid = head_sigmoid(m, plan, hx);
-                head_done[j] = 1;
-                if (plan.reuse) {
-                  bool other = false;
-                  for (size_t k = 0; k < m->ops.size(); ++k)
-                    if (k != j && (m->ops[k].d.src0 == d.dst || m->ops[k].d.src1 == d.dst)) other = true;
-                  if (!other) f.skip_dst = 1;
-                }
-              }
-              break;
-            }
-          }
-          kv[op_index - 1] = PH_KV_F16;
-          rc = launch_conv3x3_f16(f, s);
-          break;
-        }
-        ConvArgs a{};
-        a.src0 = tmp;
-        a.c0p = s0.cp;
-        a.src1 = nullptr;
-        a.c1p = 0;
-        a.wpack = op.w_dev;
-        a.bias = op.b_dev;
-        a.dst = wr(d.dst);
-        a.coutp = pad16(d.cout);
-        a.B = batch;
-        a.H = 2 * s0.h;
-        a.W = 2 * s0.w;
-        a.relu = (d.flags & PH_FLAG_RELU) ? 1 : 0;
-        a.bn = op.bn;
-        a.clock_probe = nullptr;
-        a.dst_pool = nullptr;
-        a.wpack_dma = op.w_dma_dev;
-        a.zeros = m->zeros_dev;
-        apply_conv_options(m, a);
-        kv[op_index - 1] = (m->use_dma && (a.bn == 64 || m->dma32)) ? conv3x3_dma_variant(a) : PH_KV_DIRECT;
-        rc = (m->use_dma && (a.bn == 64 || m->dma32)) ? launch_conv3x3_dma(a, s) : launch_conv3x3(a, s);
-        break;
-      }
-      case PH_OP_PATCH_STEM: {
-        PH_REQUIRE(d.cin0 == in_channels, "input has %d channels, network expects %d", in_channels, d.cin0);
-        const SlotShape& so = plan.slots[d.dst];
-        if (d.flags & PH_FLAG_PAD0_NORM) {  // ConvNeXtV2 embeddings: padding 0, (x / 255 - mean) / std on the way in
-          PH_REQUIRE(fmt == FMT_F32, "the padding-0 patch stem runs in exact fp32 only");
-          PatchStemArgs a{};
-          a.src = input_dev;
-          a.w = op.w_dev;
-          a.bias = op.b_dev;
-          a.dst = wr(d.dst);
-          a.dtype = in_dtype;
-          a.cin = d.cin0;
-          a.coutp = so.cp;
-          a.B = batch;
-          a.H = height;
-          a.W = width;
-          a.OH = so.h;
-          a.OW = so.w;
-          a.k = d.ksize;
-          a.stride = d.cmid;
-          a.pad0_norm = 1;
-          for (int c = 0; c < 4; ++c) {
-            a.mean[c] = m->in_mean[c];
-            a.std[c] = m->in_std[c];
-          }
-          kv[op_index - 1] = PH_KV_PATCH_STEM_NORM;
-          rc = launch_patch_stem_norm(a, s);
-          break;
-        }
-        if (fmt == FMT_F16) {
-          PatchStemF16Args f{};
-          f.src = input_dev;
-          f.w = op.w_dev;
-          f.bias = op.b_dev;
-          f.dst = wr(d.dst);
-          f.dtype = in_dtype;
-          f.cin = d.cin0;
-          f.wcp = pad16(d.cout);
-          f.cp = so.cp;
-          f.B = batch;
-          f.H = height;
-          f.W = width;
-          f.OH = so.h;
-          f.OW = so.w;
-          f.k = d.ksize;
-          f.stride = d.cmid;
-          kv[op_index - 1] = PH_KV_CNX_F16_STEM;
-          rc = launch_patch_stem_f16(f, s);
-          break;
-        }
-        PatchStemArgs a{};
-        a.src = input_dev;
-        a.w = op.w_dev;
-        a.bias = op.b_dev;
-        a.dst = wr(d.dst);
-        a.dtype = in_dtype;
-        a.cin = d.cin0;
-        a.coutp = so.cp;
-        a.B = batch;
-        a.H = height;
-        a.W = width;
-        a.OH = so.h;
-        a.OW = so.w;
-        a.k = d.ksize;
-        a.stride = d.cmid;
-        if (m->dw_ln_fuse && plan.reuse && fmt == FMT_F32 && op_index < m->ops.size() && a.cin == 1 && a.coutp <= 128 && a.k >= 2 && a.k <= 4 && a.stride >= 1 && a.stride <= 4) {
-          // the stem's LayerNorm2d rides in the patch kernel (inference plans: nothing else reads the un-normalised tensor)
-          const ph_op_desc& nx = m->ops[op_index].d;
-          if (nx.kind == PH_OP_LAYERNORM && !(nx.flags & PH_FLAG_LN_EPS_1EM5) && nx.src0 == d.dst && nx.cin0 == d.cout) {  // (the fused form has eps 1e-6 built in)
-            bool other = false;
-            for (size_t k = 0; k < m->ops.size(); ++k)
-              if (k != op_index && (m->ops[k].d.src0 == d.dst || m->ops[k].d.src1 == d.dst)) other = true;
-            if (!other) {
-              a.ln_gamma = m->ops[op_index].w_dev;
-              a.ln_beta = m->ops[op_index].b_dev;
-              a.ln_c = d.cout;
-              unnote(1, d.dst);
-              a.dst = wr(nx.dst);
-              fused_ln = (int)op_index;
-            }
-          }
-        }
-        rc = launch_patch_stem(a, s);
-        break;
-      }
-      case PH_OP_DWCONV: {
-        const SlotShape& s0 = plan.slots[d.src0];
-        PH_REQUIRE(s0.c == d.cin0, "depthwise conv channel mismatch");
-        if (fmt == FMT_F16) {
-          DwConvF16Args f{};
-          f.src = rd(d.src0);
-          f.w = op.w_dev;
-          f.bias = op.b_dev;
-          f.dst = wr(d.dst);
-          f.wcp = pad16(d.cout);
-          f.cp = s0.cp;
-          f.B = batch;
-          f.H = s0.h;
-          f.W = s0.w;
-          if (m->dw_ln_fuse && plan.reuse && f.cp <= 1024 && op_index < m->ops.size()) {  // as below: the LayerNorm rides in the depthwise kernel
-            const ph_op_desc& nx = m->ops[op_index].d;
-            if (nx.kind == PH_OP_LAYERNORM && nx.src0 == d.dst && nx.cin0 == d.cout) {
-              bool other = false;
-              for (size_t k = 0; k < m->ops.size(); ++k)
-                if (k != op_index && (m->ops[k].d.src0 == d.dst || m->ops[k].d.src1 == d.dst)) other = true;
-              if (!other) {
-                f.ln_gamma = m->ops[op_index].w_dev;
-                f.ln_beta = m->ops[op_index].b_dev;
-                f.ln_c = d.cout;
-                unnote(1, d.dst);
-                f.dst = wr(nx.dst);
-                fused_ln = (int)op_index;
-              }
-            }
-          }
-          kv[op_index - 1] = PH_KV_CNX_F16_DW;
-          rc = launch_dwconv7_f16(f, s);
-          break;
-        }
-        DwConvArgs a{};
-        a.src = rd(d.src0);
-        a.w = op.w_dev;
-        a.bias = op.b_dev;
-        a.dst = wr(d.dst);
-        a.cp = s0.cp;
-        a.B = batch;
-        a.H = s0.h;
-        a.W = s0.w;
-        if (m->dw_ln_fuse && plan.reuse && fmt == FMT_F32 && op_index < m->ops.size()) {
-          // CNBlock: the LayerNorm that follows rides in the depthwise kernel (inference plans: nothing else reads the depthwise output)
-          const ph_op_desc& nx = m->ops[op_index].d;
-          if (nx.kind == PH_OP_LAYERNORM && nx.src0 == d.dst && nx.cin0 == d.cout) {
-            bool other = false;
-            for (size_t k = 0; k < m->ops.size(); ++k)
-              if (k != op_index && (m->ops[k].d.src0 == d.dst || m->ops[k].d.src1 == d.dst)) other = true;
-            if (!other) {
-              a.ln_gamma = m->ops[op_index].w_dev;
-              a.ln_beta = m->ops[op_index].b_dev;
-              a.ln_c = d.cout;
-              unnote(1, d.dst);
-              a.dst = wr(nx.dst);
-              fused_ln = (int)op_index;
-            }
-          }
-        }
-        rc = launch_dwconv7(a, s);
-        break;
-      }
-      case PH_OP_LAYERNORM: {
-        if (fused_ln == (int)op_index - 1) {  // applied by the depthwise conv before it
-          fused_ln = -1;
-          if (fmt == FMT_F16) kv[op_index - 1] = PH_KV_FUSED;
-          break;
-        }
-        const SlotShape& s0 = plan.slots[d.src0];
-        PH_REQUIRE(s0.c == d.cin0, "LayerNorm channel mismatch");
-        if (fmt == FMT_F16) {
-          kv[op_index - 1] = PH_KV_CNX_F16_LN;
-          rc = launch_layernorm_f16(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), s0.c, pad16(s0.c), s0.cp, (size_t)batch * s0.h * s0.w, s, (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f);
-          break;
-        }
-        rc = launch_layernorm(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), s0.c, s0.cp, (size_t)batch * s0.h * s0.w, s, (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f);
-        break;
-      }
-      case PH_OP_PATCH_MERGE: {
-        const SlotShape& s0 = plan.slots[d.src0];
-        const SlotShape& so = plan.slots[d.dst];
-        PH_REQUIRE((fmt == FMT_F32 || fmt == FMT_F16) && s0.c == d.cin0 && s0.cp == d.cin0 && so.cp == d.cout, "patch merge channel mismatch");
-        if (fmt == FMT_F16) {
-          kv[op_index - 1] = PH_KV_SWIN_F16_MERGE_LN;
-          rc = launch_patch_merge_ln_f16(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), batch, s0.h, s0.w, d.cin0, (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f, s);
-          break;
-        }
-        rc = launch_patch_merge_ln(rd(d.src0), op.w_dev, op.b_dev, wr(d.dst), batch, s0.h, s0.w, d.cin0, (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f, s);
-        break;
-      }
-      case PH_OP_WINDOW_ATTN: {
-        const SlotShape& s0 = plan.slots[d.src0];
-        const SlotShape& so = plan.slots[d.dst];
-        PH_REQUIRE((fmt == FMT_F32 || fmt == FMT_F16) && s0.c == d.cin0 && s0.cp == d.cin0 && so.cp == d.cout, "window attention channel mismatch");
-        if (fmt == FMT_F16) {
-          WindowAttnF16Args f{};
-          f.qkv = rd(d.src0);
-          f.table = op.w_dev;
-          f.qkv_bias = op.b_dev;
-          f.dst = wr(d.dst);
-          f.B = batch;
-          f.H = s0.h;
-          f.W = s0.w;
-          f.C = d.cout;
-          f.heads = d.cin1;
-          f.w = d.ksize;
-          f.sh = d.ksize >= (s0.h + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;  // (per axis, as below)
-          f.sw = d.ksize >= (s0.w + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;
-          kv[op_index - 1] = PH_KV_WINDOW_ATTN_F16;
-          rc = launch_window_attn_f16(f, s);
-          break;
-        }
-        WindowAttnArgs a{};
-        a.qkv = rd(d.src0);
-        a.table = op.w_dev;
-        a.qkv_bias = op.b_dev;
-        a.dst = wr(d.dst);
-        a.B = batch;
-        a.H = s0.h;
-        a.W = s0.w;
-        a.C = d.cout;
-        a.heads = d.cin1;
-        a.w = d.ksize;
-        // an axis the window covers whole (window >= padded size) is not shifted: decided per axis, from this launch's map
-        a.sh = d.ksize >= (s0.h + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;
-        a.sw = d.ksize >= (s0.w + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;
-        kv[op_index - 1] = PH_KV_WINDOW_ATTN;
-        rc = launch_window_attn(a, s);
-        break;
-      }
-      case PH_OP_LINEAR:
-      case PH_OP_PATCH_CONV: {
-        if (skip_next_linear) {  // the second Linear of a CNBlock MLP that cnblock_mlp_kernel computed with the first
-          skip_next_linear = false;
-          kv[op_index - 1] = PH_KV_MLP;
-          break;
-        }
-        const SlotShape& s0 = plan.slots[d.src0];
-        const SlotShape& so = plan.slots[d.dst];
-        PH_REQUIRE(s0.c == d.cin0, "GEMM channel mismatch");
-        if (fmt == FMT_F16) {
-          PH_REQUIRE(op.w_cnx_f16_dev && !(d.flags & ~(PH_FLAG_GELU | PH_FLAG_SCALE_RESIDUAL | PH_FLAG_RESIDUAL)), "op has no fp16 row-GEMM form");
-          GemmF16Args f{};
-          f.src = rd(d.src0);
-          f.wimg = op.w_cnx_f16_dev;
-          f.bias = (d.kind == PH_OP_LINEAR && d.bias == -1) ? nullptr : op.b_dev;  // Linear(bias=False): the patch-merging reduction
-          f.dst = wr(d.dst);
-          f.cinp = s0.cp;
-          f.coutp = so.cp;
-          f.M = batch * so.h * so.w;
-          f.taps = d.kind == PH_OP_PATCH_CONV ? 4 : 1;
-          f.H = s0.h;
-          f.W = s0.w;
-          f.gelu = (d.flags & PH_FLAG_GELU) ? 1 : 0;
-          if (d.flags & PH_FLAG_SCALE_RESIDUAL) {
-            f.scale = op.w2_dev;
-            f.residual = rd(d.src1);
-          } else if (d.flags & PH_FLAG_RESIDUAL) {  // dst = acc + bias + src1
-            f.residual = rd(d.src1);
-          }
-          kv[op_index - 1] = PH_KV_CNX_F16_GEMM;
-          rc = launch_gemm_f16(f, s);
-          break;
-        }
-        if (fuses_mlp(m, op_index - 1, fmt, plan.reuse)) {
-          const PackedOp& nxo = m->ops[op_index];
-          const ph_op_desc& nx = nxo.d;
-          bool pair = s0.cp == d.cin0 && plan.slots[nx.dst].cp == nx.cout && plan.slots[nx.src1].cp == nx.cout;
-          // build_plan releases x (d.src0) before it places y (nx.dst): y may come to lie on x's range, or across it where free blocks have coalesced.  cnblock_mlp_kernel is
-          // safe for y EXACTLY on x (or on the residual) -- a row tile reads all of its x rows at its start and its residual elements in the epilogue, each before the store of
-          // the same elements, and no other tile reads those rows -- and for nothing else: y shifted against x would overwrite rows another tile has yet to read.  Then: two GEMMs.
-          for (int src : {d.src0, nx.src1}) {
-            const int64_t ys = plan.slots[nx.dst].offset, ye = ys + slot_bytes(nx.dst), xs = plan.slots[src].offset, xe = xs + slot_bytes(src);
-            if (ys < xe && xs < ye && !(ys == xs && ye == xe)) pair = false;
-          }
-          if (pair) {
-            MlpArgs f{};
-            f.x = rd(d.src0);
-            f.w1img = op.w_mlp_dev;
-            f.w2img = nxo.w_mlp_dev;
-            f.b1 = op.b_dev;
-            f.b2 = nxo.b_dev;
-            f.scale = nxo.w2_dev;
-            f.residual = rd(nx.src1);
-            f.dst = wr(nx.dst);
-            f.M = batch * so.h * so.w;
-            f.C = d.cin0;
-            kv[op_index - 1] = PH_KV_MLP;
-            skip_next_linear = true;
-            rc = launch_cnblock_mlp(f, s);
-            break;
-          }
-        }
-        if (fused_grn == (int)op_index - 1 && d.kind == PH_OP_LINEAR) {  // fused GRN plan: (W2 diag(s_b)) x + (W2 grn.bias + b2) + residual, one GEMM per sample on its own scaled weight image
-          fused_grn = -1;
-          const ph_op_desc& g = m->ops[op_index - 2].d;
-          const SlotShape& sx = plan.slots[g.src0];  // the GELU output: what the GEMM reads instead of the GRN slot
-          const int hw = sx.h * sx.w;
-          const int64_t wfl = gemm_pack_floats(so.cp, sx.cp, op.bn);
-          PH_REQUIRE(op.b_grn_dev && sx.cp == s0.cp && plan.tmp_bytes >= (int64_t)batch * wfl * (int64_t)sizeof(float), "fused GRN: scaled-weight scratch is missing from the plan");
-          float* wsc = reinterpret_cast<float*>(ws + plan.tmp_offset);
-          const float* scale = rd(d.src0);  // launch 0: the scales grn_finalize_kernel left in the GRN slot -> the per-sample weight images in the scratch region
-          note_tmp(1);
-          rc = launch_grn_scale_weights(op.w_dma_dev, scale, wsc, batch, so.cp, sx.cp, op.bn, s);
-          ++launch_no;
-          const float* x = rd(g.src0);      // launch 1 (one GEMM per sample, recorded once): GELU output, weight images, residual -> dst
-          note_tmp(0);
-          const float* res = rd(d.src1);
-          float* y = wr(d.dst);
-          kv[op_index - 1] = PH_KV_ROWGEMM;
-          for (int b = 0; b < batch && rc == PH_OK; ++b) {
-            GemmArgs f{};
-            f.src0 = x + (size_t)b * hw * sx.cp;
-            f.wpack = wsc + (size_t)b * wfl;
-            f.bias = op.b_grn_dev;
-            f.residual = res + (size_t)b * hw * so.cp;
-            f.dst = y + (size_t)b * hw * so.cp;
-            f.zeros = m->zeros_dev;
-            f.c0p = sx.cp;
-            f.coutp = so.cp;
-            f.bn = op.bn;
-            f.M = hw;
-            f.mode = 0;
-            f.H = s0.h;
-            f.W = s0.w;
-            f.late_split = m->gemm_late_split;
-            rc = launch_gemm(f, s);
-          }
-          break;
-        }
-        GemmArgs a{};
-        a.src0 = rd(d.src0);
-        a.wpack = op.w_dma_dev;
-        a.bias = op.b_dev;
-        a.dst = wr(d.dst);
-        a.zeros = m->zeros_dev;
-        a.c0p = s0.cp;
-        a.coutp = so.cp;
-        a.bn = op.bn;
-        a.M = batch * so.h * so.w;
-        a.mode = d.kind == PH_OP_PATCH_CONV ? 1 : 0;
-        a.H = s0.h;
-        a.W = s0.w;
-        a.act = (d.flags & PH_FLAG_GELU) ? 2 : ((d.flags & PH_FLAG_RELU) ? 1 : 0);
-        if (d.flags & PH_FLAG_SCALE_RESIDUAL) {
-          a.scale = op.w2_dev;
-          a.residual = rd(d.src1);
-        } else if (d.flags & PH_FLAG_RESIDUAL) {  // dst = acc + bias + src1
-          if (m->branch_scales) {  // dst = s[branch][b] * (acc + bias) + src1: the GEMM without its residual, then one element-wise pass
-            kv[op_index - 1] = PH_KV_ROWGEMM;
-            a.late_split = m->gemm_late_split;
-            rc = launch_gemm(a, s);
-            ++launch_no;
-            if (rc == PH_OK)
-              rc = launch_scale_samples_add(static_cast<float*>(wr(d.dst)), static_cast<const float*>(rd(d.src1)), m->branch_scales + (size_t)branch * batch, (size_t)so.h * so.w * so.cp, batch, s);
-            ++branch;
-            break;
-          }
-          a.residual = rd(d.src1);
-        }
-        if (fuses_grn(m, op_index - 1, fmt)) {  // fused GRN plan: the epilogue also leaves the per-(32-row block, sample) sums of squares of its output in the scratch region
-          const int hw = so.h * so.w;
-          PH_REQUIRE(plan.tmp_bytes >= grn_fused_partial_floats(a.M, hw, so.cp) * (int64_t)sizeof(float), "fused GRN scratch is missing from the plan");
-          a.sumsq = reinterpret_cast<float*>(ws + plan.tmp_offset);
-          a.sq_hw = hw;
-          a.sq_nseg = grn_fused_nseg(hw);
-          note_tmp(1);
-          fused_grn = (int)op_index;
-        }
-        a.late_split = m->gemm_late_split;
-        // training program (Linear and GELU as separate ops, the pre-activation is kept for the backward pass): the
-        // GEMM epilogue writes both the pre-activation and GELU(pre-activation), the GELU op after it becomes a no-op
-        if (m->fuse_gelu_fwd && a.mode == 0 && a.act == 0 && !a.residual && op_index < m->ops.size()) {
-          const ph_op_desc& nx = m->ops[op_index].d;
-          if (nx.kind == PH_OP_GELU && nx.src0 == d.dst && nx.dst != d.dst) {
-            a.act = 2;
-            a.dst_pre = a.dst;
-            a.dst = wr(nx.dst);
-            skip_next_gelu = true;
-          }
-        }
-        // ... and (CNBlock's second Linear -> layer scale + residual, separate ops in a training program because the backward needs the un-scaled
-        // output): the epilogue writes the un-scaled output AND scale * output + residual, the scale-add op after it becomes a no-op
-        if (m->fuse_gelu_fwd && a.mode == 0 && a.act == 0 && !a.residual && !a.dst_pre && op_index < m->ops.size() && so.cp % a.bn == 0) {
-          const ph_op_desc& nx = m->ops[op_index].d;
-          if (nx.kind == PH_OP_SCALE_ADD && nx.src0 == d.dst && nx.dst != d.dst && nx.src1 != d.dst && nx.src1 >= 0 && nx.cin0 == d.cout) {
-            a.scale = m->ops[op_index].w_dev;
-            a.residual = rd(nx.src1);
-            a.dst_pre = a.dst;
-            a.dst = wr(nx.dst);
-            skip_next_scale_add = true;
-          }
-        }
-        kv[op_index - 1] = PH_KV_ROWGEMM;
-        rc = launch_gemm(a, s);
-        break;
-      }
-      case PH_OP_GRN: {
-        const SlotShape& s0 = plan.slots[d.src0];
-        PH_REQUIRE(fmt == FMT_F32 && s0.c == d.cin0 && s0.cp == pad16(d.cout) && plan.slots[d.dst].cp == s0.cp, "GRN channel mismatch");
-        PH_REQUIRE(plan.tmp_bytes >= grn_scratch_floats(batch, s0.h * s0.w, s0.cp) * (int64_t)sizeof(float), "GRN scratch is missing from the plan");
-        if (fused_grn == (int)op_index - 1) {  // fused GRN plan: the block sums the Linear in front left in the scratch region -> scale[b][c] = 1 + weight[c] N[b,c], kept in this op's own slot
-          fused_grn = (int)op_index;
-          note_tmp(0);
-          kv[op_index - 1] = PH_KV_GRN_FUSED;
-          rc = launch_grn_finalize(reinterpret_cast<const float*>(ws + plan.tmp_offset), op.w_dev, wr(d.dst), batch, s0.h * s0.w, d.cout, s0.cp, s);
-          break;
-        }
-        GrnArgs a{};
-        a.src = rd(d.src0);  // launch 0, the reduction: the slot -> the slice sums in the scratch region
-        note_tmp(1);
-        ++launch_no;
-        rd(d.src0);          // launch 1, the apply pass: the slot and the slice sums -> dst
-        note_tmp(0);
-        a.weight = op.w_dev;
-        a.bias = op.b_dev;
-        a.dst = wr(d.dst);
-        a.partial = reinterpret_cast<float*>(ws + plan.tmp_offset);
-        a.B = batch;
-        a.HW = s0.h * s0.w;
-        a.c = d.cout;
-        a.cp = s0.cp;
-        kv[op_index - 1] = PH_KV_GRN;
-        rc = launch_grn(a, s);
-        break;
-      }
-      case PH_OP_GLOBAL_MAXPOOL: {
-        const SlotShape& s0 = plan.slots[d.src0];
-        PH_REQUIRE(s0.c == d.cin0, "global pool channel mismatch");
-        rc = launch_global_maxpool(rd(d.src0), wr(d.dst), batch, s0.h * s0.w, s0.cp, s);
-        break;
-      }
-      case PH_OP_GELU: {
-        if (skip_next_gelu) {  // already produced by the preceding Linear's epilogue
-          skip_next_gelu = false;
-          break;
-        }
-        const SlotShape& s0 = plan.slots[d.src0];
-        if (fmt == FMT_F16) {
-          kv[op_index - 1] = PH_KV_CNX_F16_ELTWISE;
-          rc = launch_gelu_fmt(fmt, rd(d.src0), wr(d.dst), (size_t)batch * s0.h * s0.w, s0.cp, s);
-          break;
-        }
-        rc = launch_gelu_fwd(rd(d.src0), wr(d.dst), (size_t)batch * s0.h * s0.w * s0.cp, s);
-        break;
-      }
-      case PH_OP_SCALE_ADD: {
-        if (skip_next_scale_add) {  // already produced by the preceding Linear's epilogue
-          skip_next_scale_add = false;
-          break;
-        }
-        const SlotShape& s0 = plan.slots[d.src0];
-        PH_REQUIRE(s0.c == d.cin0, "scale-add channel mismatch");
-        if (fmt == FMT_F16) {
-          kv[op_index - 1] = PH_KV_CNX_F16_ELTWISE;
-          rc = launch_scale_add_fmt(fmt, rd(d.src0), rd(d.src1), op.w_dev, wr(d.dst), (size_t)batch * s0.h * s0.w, pad16(d.cout), s0.cp, s);
-          break;
-        }
-        rc = launch_scale_add_fwd(rd(d.src0), rd(d.src1), op.w_dev, wr(d.dst), s0.cp, (size_t)batch * s0.h * s0.w * s0.cp, s);
-        break;
-      }
-      case PH_OP_HEAD: {
-        if (head_done[op_index - 1]) {  // computed by its producer's epilogue
-          kv[op_index - 1] = PH_KV_FUSED;
-          break;
-        }
-        const SlotShape& s0 = plan.slots[d.src0];
-        PH_REQUIRE(s0.c == d.cin0, "head channel mismatch");
-        PH_REQUIRE(out_dev[d.out_index] != nullptr, "output %d is null", d.out_index);
-        rc = launch_head_fmt(fmt, rd(d.src0), op.w_dev, op.b_dev, out_dev[d.out_index], batch, s0.h * s0.w, s0.cp, pad16(d.cin0), d.cout,
-                             head_sigmoid(m, plan, d), s);
-        if (rc == PH_OK && (d.flags & PH_FLAG_SOFTMAX)) {
-          PH_REQUIRE(s0.h == 1 && s0.w == 1, "softmax head expects a pooled (1x1) feature");
-          rc = launch_softmax_rows(out_dev[d.out_index], batch, d.cout, s);
-        }
-        break;
-      }
-      default:
-        set_error("unknown op kind %d", d.kind);
-        rc = PH_E_INVALID;
-    }
-    if (rc != PH_OK) return rc;
-  }
-  if (m->profiling) {
-    PH_HIP_CHECK(hipEventRecord(m->ev[m->ops.size()], s));
-    m->events_pending = true;
-  }
-  m->last_plan = plan;
-  m->last_ws = ws;
-  m->last_batch = batch;
-  return PH_OK;
 }
 
 int32_t ph_op_desc_size(void) { return (int32_t)sizeof(ph_op_desc); }

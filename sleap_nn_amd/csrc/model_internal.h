@@ -1,4 +1,4 @@
-// Internal structures of the network runtime shared by model.hip (forward) and train.hip (backward).
+// Internal structures of the network runtime shared by model.hip (handle, weight forms), plan.hip (workspace plan), forward.hip (forward) and train.hip (backward).
 #pragma once
 #include <string>
 #include <vector>
@@ -67,13 +67,25 @@ struct PackedBuffer {
   size_t n = 0;
 };
 
+// What a DerivedBuffer holds, i.e. which launch recomputes it from src (ph_model_set_params; the inference-only forms lazily, in ph_model_forward)
+enum DerivedKind {
+  DERIVED_WINO = 0,            // Winograd F(2,3) transform of src (launch_wino_pack); bn == 0: the fused stem's second conv (launch_stem_wino_pack)
+  DERIVED_F16_PACK = 1,        // fp16 weight pack of the LDS-DMA panels (launch_f16_weight_pack: n_tiles, chunks0, chunks1, plain)
+  DERIVED_WINO2D = 2,          // F(2x2,3x3) transform (launch_wino2d_pack)
+  DERIVED_W16 = 3,             // wave-private F(2x2,3x3) transform (launch_w16_pack: panels = chunks, bn = N blocks of 16)
+  DERIVED_STEM_WINO2D = 4,     // the fused stem's F(2x2,3x3) transform (launch_stem_wino2d_pack)
+  DERIVED_WINO4 = 5,           // F(4x4,3x3) transform (launch_wino4_pack: panels = N tiles, bn = 16-channel chunks); inference plans only
+  DERIVED_SMALLMAP = 6,        // small-map F(2x2,3x3) transform (launch_sm_pack: panels = N blocks of 16, bn = 16-channel chunks, n_tiles = the source packing's N tile); inference plans only
+  DERIVED_GEMM_F16_IMAGE = 7,  // fp16 row-GEMM weight image of a Linear / 2x2-stride-2 conv (launch_gemm_f16_weight_image: panels = cout, n_tiles = cin, chunks0 = taps, bn = the source packing's N tile)
+};
+
 // A buffer computed on the device from a packed buffer (not a pure gather of parameters): Winograd conv weights.
 struct DerivedBuffer {
   const float* src = nullptr;
   float* dst = nullptr;
-  int panels = 0, bn = 0;  // bn == 0: the fused stem's second conv (launch_stem_wino_pack)
-  int kind = 0;            // 0: Winograd transform of src; 1: fp16 weight pack of the LDS-DMA panels (launch_f16_weight_pack); 2: F(2x2,3x3) transform; 3: wave-private F(2x2,3x3) transform (panels = chunks); 4: the fused stem's F(2x2,3x3) transform; 5: F(4x4,3x3) transform (panels = N tiles, bn = 16-channel chunks); 6: small-map F(2x2,3x3) transform (panels = N blocks of 16, bn = 16-channel chunks, n_tiles = the source packing's N tile); 7: fp16 row-GEMM weight image of a Linear / 2x2-stride-2 conv (launch_gemm_f16_weight_image: panels = cout, n_tiles = cin, chunks0 = taps, bn = the source packing's N tile)
-  int n_tiles = 0, chunks0 = 0, chunks1 = 0, plain = 0;  // kind 1
+  int panels = 0, bn = 0;
+  DerivedKind kind = DERIVED_WINO;
+  int n_tiles = 0, chunks0 = 0, chunks1 = 0, plain = 0;  // DERIVED_F16_PACK (n_tiles, chunks0: also DERIVED_SMALLMAP / DERIVED_GEMM_F16_IMAGE, as listed above)
 };
 
 struct SlotShape {
@@ -202,12 +214,20 @@ struct ph_model {
 namespace ph {
 int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt = FMT_F32);
 int forward_format(const ph_model* m);
-// Run-time fusions in which the launch of op i also computes op i + 1, so that op i + 1's dst is written while op i's sources are still being read.  Conditions on the
-// program, the handle options and the plan's format only -- what is known before any weight form is derived.  fuses_block2 is called by BOTH ph_model_forward (which fuses)
-// and build_plan (which holds the releases due at op i + 1, so that its dst stays off the ranges op i reads): the two cannot drift apart.  fuses_mlp is the router's alone:
-// cnblock_mlp_kernel is safe with y exactly on x, build_plan does not hold that pair, and ph_model_forward refuses the fusion for any other overlap of the plan's ranges.
+int drain_events(ph_model* m);  // profiling: fold the events of the last forward into op_ms
+bool has_other_reader(const ph_model* m, int slot, size_t except_op);  // an op other than `except_op` reads `slot`
+// Run-time fusions in which the launch of op i also computes op i + 1 (or leaves op i to the launch of op i + 1), so that a dst is written while an earlier op's sources are
+// still being read.  Conditions on the program, the handle options and the plan only -- what is known before any weight form is derived; defined in plan.hip.  fuses_block2 and
+// fuses_grn are called by BOTH the router (forward.hip, which fuses) and build_plan (which holds the releases due at op i + 1 / extends the GELU output's lifetime): the two
+// cannot drift apart.  The others are the router's alone -- fuses_mlp: cnblock_mlp_kernel is safe with y exactly on x, build_plan does not hold that pair, and fwd_linear_mlp
+// refuses the fusion for any other overlap of the plan's ranges; the rest: build_plan covers them by the kinds of the two ops (its `forwarded` rule), not by these predicates.
 bool fuses_block2(const ph_model* m, size_t i, int fmt, bool reuse);  // block2_c32_f16_kernel: conv(<= 16 -> 32) + conv(32 -> 32) (+ pool)
 bool fuses_mlp(const ph_model* m, size_t i, int fmt, bool reuse);     // cnblock_mlp_kernel: Linear + GELU + Linear + layer scale + residual
+bool fuses_grn(const ph_model* m, size_t i, int fmt);                 // fused GRN plan: Linear + GELU, GRN, residual Linear
+bool fuses_pool(const ph_model* m, size_t i);                         // pool peephole: conv + ReLU writes the pool op behind it
+bool fuses_layernorm(const ph_model* m, size_t i, bool reuse);        // the LayerNorm behind a patch stem / depthwise conv rides in that kernel
+bool defers_upsample_f32(const ph_model* m, size_t i, const Plan& plan);  // a bilinear x2 left to the fp32 conv behind it
+bool defers_upsample_f16(const ph_model* m, size_t i, const Plan& plan);  // ... to the fp16 row-tile conv behind it
 int ensure_f16_weights(ph_model* m, int plain, hipStream_t s);  // format the forward of this program runs in under the handle's conv_precision
 int upload(ph_model* m, const std::vector<float>& host, float** dev);
 int upload_ints(ph_model* m, const std::vector<int>& host, int** dev);

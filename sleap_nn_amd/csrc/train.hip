@@ -154,7 +154,7 @@ int ph_model_set_params(ph_model* m, const float* params_flat_dev, void* stream)
       std::vector<PackSegment> seg;
       unsigned blocks = 0;
       for (const DerivedBuffer& db : m->derived) {
-        const bool mine = kind == 0 ? (db.kind == 0 && db.bn != 0) : db.kind == 2;
+        const bool mine = kind == 0 ? (db.kind == DERIVED_WINO && db.bn != 0) : db.kind == DERIVED_WINO2D;
         if (!mine) continue;
         const unsigned long long total = (unsigned long long)(kind == 0 ? wino_pack_floats(db.panels, db.bn) : wino2d_pack_floats(db.panels, db.bn));
         if (total == 0) continue;
@@ -179,17 +179,17 @@ int ph_model_set_params(ph_model* m, const float* params_flat_dev, void* stream)
     if (rc != PH_OK) return rc;
   }
   for (const DerivedBuffer& db : m->derived) {
-    if ((db.kind == 0 && db.bn != 0) || db.kind == 2) continue;  // in the two launches above
-    if (db.kind == 5 || db.kind == 6) {  // F(4x4,3x3) / small-map weights: only inference plans read them (conv_wino4 = conv_smallmap = 1) -- a training step does not pay for the re-derivation,
-      if ((db.kind == 5 ? m->conv_wino4 : m->conv_smallmap) < 2 && !m->workspace_reuse) {  // the next forward that wants them refreshes them (ph_model_forward)
+    if ((db.kind == DERIVED_WINO && db.bn != 0) || db.kind == DERIVED_WINO2D) continue;  // in the two launches above
+    if (db.kind == DERIVED_WINO4 || db.kind == DERIVED_SMALLMAP) {  // F(4x4,3x3) / small-map weights: only inference plans read them (conv_wino4 = conv_smallmap = 1) -- a training step does not pay for the re-derivation,
+      if ((db.kind == DERIVED_WINO4 ? m->conv_wino4 : m->conv_smallmap) < 2 && !m->workspace_reuse) {  // the next forward that wants them refreshes them (ph_model_forward)
         m->wino4_stale = true;
         continue;
       }
-      const int rc5 = db.kind == 5 ? launch_wino4_pack(db.src, db.dst, db.panels, db.bn, static_cast<hipStream_t>(stream)) : launch_sm_pack(db.src, db.dst, db.panels, db.bn, db.n_tiles, static_cast<hipStream_t>(stream));
+      const int rc5 = db.kind == DERIVED_WINO4 ? launch_wino4_pack(db.src, db.dst, db.panels, db.bn, static_cast<hipStream_t>(stream)) : launch_sm_pack(db.src, db.dst, db.panels, db.bn, db.n_tiles, static_cast<hipStream_t>(stream));
       if (rc5 != PH_OK) return rc5;
       continue;
     }
-    if (db.kind == 7) {  // fp16 row-GEMM images: only a plain-fp16 forward reads them -- a training step does not pay for them, the next such forward refreshes them (ph_model_forward)
+    if (db.kind == DERIVED_GEMM_F16_IMAGE) {  // fp16 row-GEMM images: only a plain-fp16 forward reads them -- a training step does not pay for them, the next such forward refreshes them (ph_model_forward)
       if (m->conv_precision != 2 || !(m->convnext_f16 || m->swint_f16)) {
         m->cnx_f16_stale = true;
         continue;
@@ -198,9 +198,9 @@ int ph_model_set_params(ph_model* m, const float* params_flat_dev, void* stream)
       if (rc7 != PH_OK) return rc7;
       continue;
     }
-    int rc = db.kind == 1 ? launch_f16_weight_pack(db.src, db.dst, db.n_tiles, db.chunks0, db.chunks1, db.bn, db.plain, static_cast<hipStream_t>(stream))
-             : db.kind == 3 ? launch_w16_pack(db.src, db.dst, db.panels, db.bn, static_cast<hipStream_t>(stream))
-             : db.kind == 4 ? launch_stem_wino2d_pack(db.src, db.dst, static_cast<hipStream_t>(stream))
+    int rc = db.kind == DERIVED_F16_PACK ? launch_f16_weight_pack(db.src, db.dst, db.n_tiles, db.chunks0, db.chunks1, db.bn, db.plain, static_cast<hipStream_t>(stream))
+             : db.kind == DERIVED_W16 ? launch_w16_pack(db.src, db.dst, db.panels, db.bn, static_cast<hipStream_t>(stream))
+             : db.kind == DERIVED_STEM_WINO2D ? launch_stem_wino2d_pack(db.src, db.dst, static_cast<hipStream_t>(stream))
                             : launch_stem_wino_pack(db.src, db.dst, static_cast<hipStream_t>(stream));
     if (rc != PH_OK) return rc;
   }

@@ -6,7 +6,7 @@ block2_c32_f16_kernel) through three and more rounds with an XCD boundary inside
 
 Round 6's block_fuse broke the invariant on every plain-fp16 UNet plan: the fused launch read enc0's pooled tensor and wrote enc1's output through the same bytes
 (``unet fp16 (64, 96) fused, defaults: launch of op 1 (kernel 14): destination slot 4 [0, 196608) lies on source slot 2 [0, 196608) of the same launch``, and the same at
-72 x 104, with the transposed-conv decoder and at 3 x 512 x 1024); build_plan now holds the pair's releases for one op (csrc/model.hip: fuses_block2, the router's own
+72 x 104, with the transposed-conv decoder and at 3 x 512 x 1024); build_plan now holds the pair's releases for one op (csrc/plan.hip: fuses_block2, the router's own
 predicate)."""
 import pytest
 import torch
