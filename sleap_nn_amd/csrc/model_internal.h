@@ -1,4 +1,5 @@
-// Internal structures of the network runtime shared by model.hip (handle, weight forms), plan.hip (workspace plan), forward.hip (forward) and train.hip (backward).
+// Internal structures of the network runtime shared by model.hip (handle, weight forms), plan.hip (workspace plan), forward.hip (forward), backward.hip (backward) and
+// train.hip (parameter arena, bucket split, branch scales, head losses).
 #pragma once
 #include <string>
 #include <vector>
@@ -216,6 +217,7 @@ int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt = FMT
 int forward_format(const ph_model* m);
 int drain_events(ph_model* m);  // profiling: fold the events of the last forward into op_ms
 bool has_other_reader(const ph_model* m, int slot, size_t except_op);  // an op other than `except_op` reads `slot`
+int bucket_split_op(const ph_model* m, int64_t* offset_out);  // train.hip: the op whose backward step makes the arena tail [*offset_out, n_params) final; -1 = no clean split
 // Run-time fusions in which the launch of op i also computes op i + 1 (or leaves op i to the launch of op i + 1), so that a dst is written while an earlier op's sources are
 // still being read.  Conditions on the program, the handle options and the plan only -- what is known before any weight form is derived; defined in plan.hip.  fuses_block2 and
 // fuses_grn are called by BOTH the router (forward.hip, which fuses) and build_plan (which holds the releases due at op i + 1 / extends the GELU output's lifetime): the two
