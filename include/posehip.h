@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 124
+#define PH_VERSION 125
 
 /* error codes */
 #define PH_OK 0
@@ -431,6 +431,47 @@ int ph_model_backward_profile_read(ph_model* m, double* op_ms, double* op_ms_fir
 /* ... and of the LAST ph_model_backward: PH_KV_WINDOW_ATTN_BWD for a PH_OP_WINDOW_ATTN step, PH_KV_GRN_BWD for a PH_OP_GRN step, PH_KV_ROWGEMM for a Linear / 2x2-stride-2 step,
  * 0 elsewhere -- and for every op of a frozen prefix (handle option bwd_frozen_ops), which runs no step. */
 int ph_model_last_backward_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
+/* ... and which route each op's step of the LAST ph_model_backward took, one bit field per op, written where the sweep takes the decision (tests pin every route to a
+ * float64 reference without restating a predicate).  0 for an op that ran no step: a frozen prefix (bwd_frozen_ops), an op whose output nobody reads.
+ *   bits  0..10  concat part 0: weight-gradient route PH_BR_WG_* (4 bits), data-gradient route (6 bits), 1 bit "accumulated into a gradient that was there"
+ *   bits 11..21  concat part 1, the same layout
+ *   bits 22..23  who applied the ReLU mask to the op's own output gradient: PH_BR_MASK_*
+ *   bits 24..26  who summed the op's bias gradient: PH_BR_BIAS_*
+ *   bits 27..30  PH_BR_FOLDED_MASK, PH_BR_SUMMED_BIAS, PH_BR_GELU_FUSED, PH_BR_NO_LAUNCH
+ * The data-gradient route of a 3x3 conv on the LDS-DMA family is the PH_KV_* code of its kernel (all below 32); the other routes are PH_BR_DG_*. */
+#define PH_BR_PART_BITS 11
+#define PH_BR_WG_NONE 0
+#define PH_BR_WG_DIRECT 1      /* launch_wgrad: the 32x32-tile nine-tap kernel                                  */
+#define PH_BR_WG_WINO 2        /* launch_wgrad_wino: Winograd F(2x2,3x3) domain                                */
+#define PH_BR_WG_WINO16 3      /* launch_wgrad16_wino: 16 -> 16 padded channels                                */
+#define PH_BR_WG_ROWS9 4       /* nine row-wgrad GEMMs on a 3x3 conv ("wgrad_rows")                            */
+#define PH_BR_WG_ROWSKK 5      /* k^2 row-wgrad GEMMs of a k x k conv                                          */
+#define PH_BR_WG_INPUT 6       /* launch_input_wgrad: the first 3x3 conv, from the image                       */
+#define PH_BR_WG_PATCH_STEM 7  /* launch_patch_stem_wgrad(_norm): im2col + one row-wgrad GEMM                  */
+#define PH_BR_WG_CONVT_TAPS 8  /* transposed conv: nine stride-2-gathered row-wgrad GEMMs                      */
+#define PH_BR_WG_ROW_GEMM 9    /* Linear / 2x2-stride-2 conv: one row-wgrad GEMM per tap                       */
+#define PH_BR_DG_NONE 0
+#define PH_BR_DG_REGSTAGED 32  /* launch_conv3x3: the register-staged 3x3 kernel                               */
+#define PH_BR_DG_GEMM5 33      /* row GEMM mode 5: k x k taps on the flipped, swapped weights                  */
+#define PH_BR_DG_GEMM4 34      /* row GEMM mode 4: 3x3 stride-2 conv (transposed conv's data gradient)         */
+#define PH_BR_DG_GEMM0 35      /* row GEMM mode 0: Linear / 2x2-stride-2 conv                                  */
+#define PH_BR_ACCUMULATE (1 << 10) /* (within a part) the source slot already held a gradient                  */
+#define PH_BR_MASK_SHIFT 22
+#define PH_BR_MASK_NONE 0
+#define PH_BR_MASK_OWN 1       /* this step's launch_relu_mask / launch_relu_mask_bias_grad                    */
+#define PH_BR_MASK_EARLIER 2   /* the step that completed the gradient applied it as it stored ("mask_fold")   */
+#define PH_BR_BIAS_SHIFT 24
+#define PH_BR_BIAS_NONE 0
+#define PH_BR_BIAS_OWN 1         /* this step's launch_bias_grad                                               */
+#define PH_BR_BIAS_WITH_MASK 2   /* launch_relu_mask_bias_grad: one pass with the mask                         */
+#define PH_BR_BIAS_CLOSER 3      /* the pool / head step that completed the gradient summed it                 */
+#define PH_BR_BIAS_INPUT_WGRAD 4 /* the spare column of launch_input_wgrad                                     */
+#define PH_BR_BIAS_ROW_WGRAD 5   /* a Linear's weight-gradient row GEMM (column sums of dY)                    */
+#define PH_BR_FOLDED_MASK (1 << 27) /* this step applied the ReLU mask of the op that produced its source      */
+#define PH_BR_SUMMED_BIAS (1 << 28) /* ... and summed that op's bias gradient                                  */
+#define PH_BR_GELU_FUSED (1 << 29)  /* Linear: the GELU derivative rode in the data-gradient GEMM's epilogue   */
+#define PH_BR_NO_LAUNCH (1 << 30)   /* GELU: its step launched nothing (fused away by its consumer)            */
+int ph_model_last_backward_routes(const ph_model* m, int32_t* routes, int32_t n_ops);
 
 /* Which workspace byte ranges every launch of the LAST ph_model_forward was handed, as the run-time routing decided them (tests of the
  * planner / router agreement: no launch may write a range it, or a later launch, still reads).  One row of six int64 per range:

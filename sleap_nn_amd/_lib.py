@@ -53,6 +53,56 @@ KV_NAMES = {KV_NONE: "none", KV_DIRECT: "conv3x3_mfma_dma_persist_kernel (direct
             CNX2_KV_GRN_FUSED: "grn_finalize_kernel (fused GRN plan: sums of squares from the Linear in front, per-sample scaled weights for the Linear behind)",
             CNX2_KV_PATCH_STEM_NORM: "patch_stem_norm_kernel (padding-0 patch stem with input statistics)",
             CNX2_KV_GRN_BWD: "grn_bwd_reduce_kernel + grn_bwd_sample_kernel + grn_bwd_param_kernel + grn_bwd_apply_kernel (backward of Global Response Normalization, fixed-order sums)"}
+# PH_BR_*: the route word of one op's step of the last backward (ph_model_last_backward_routes, include/posehip.h).  Per concat part p (0 / 1), at bit 11 p:
+# weight-gradient route (4 bits), data-gradient route (6 bits), "accumulated into an existing gradient" (1 bit); then the op's own output gradient (who applied the
+# ReLU mask, who summed the bias gradient) and the flags of a step that closes another op's gradient or fuses / skips a launch
+BR_PART_BITS = 11
+BR_WG_NONE, BR_WG_DIRECT, BR_WG_WINO, BR_WG_WINO16, BR_WG_ROWS9, BR_WG_ROWSKK, BR_WG_INPUT, BR_WG_PATCH_STEM, BR_WG_CONVT_TAPS, BR_WG_ROW_GEMM = range(10)
+BR_WG_NAMES = {BR_WG_NONE: "none", BR_WG_DIRECT: "launch_wgrad (32x32 tiles)", BR_WG_WINO: "launch_wgrad_wino", BR_WG_WINO16: "launch_wgrad16_wino",
+               BR_WG_ROWS9: "nine row GEMMs (conv_wgrad_rows on a 3x3 conv)", BR_WG_ROWSKK: "k^2 row GEMMs (k x k conv)", BR_WG_INPUT: "launch_input_wgrad",
+               BR_WG_PATCH_STEM: "launch_patch_stem_wgrad", BR_WG_CONVT_TAPS: "transposed-conv taps (nine gathered row GEMMs)", BR_WG_ROW_GEMM: "Linear / 2x2-stride-2 conv row GEMM"}
+# data-gradient route: 0 = none, a KV_* code below 32 = the LDS-DMA family's kernel (conv3x3_dma_variant), else one of
+BR_DG_NONE, BR_DG_REGSTAGED, BR_DG_GEMM5, BR_DG_GEMM4, BR_DG_GEMM0 = 0, 32, 33, 34, 35
+BR_DG_NAMES = {BR_DG_NONE: "none", BR_DG_REGSTAGED: "launch_conv3x3 (register-staged)", BR_DG_GEMM5: "row GEMM mode 5 (k x k taps)", BR_DG_GEMM4: "row GEMM mode 4 (3x3 stride 2)",
+               BR_DG_GEMM0: "row GEMM mode 0 (Linear / 2x2-stride-2 conv)"}
+BR_DG_DMA_CODES = (KV_DIRECT, KV_WINO1D, KV_WINO2D, KV_W16, KV_C16, KV_WINO4, KV_WINO2D_KS)  # what conv3x3_dma_variant can return
+BR_MASK_NONE, BR_MASK_OWN, BR_MASK_EARLIER = range(3)
+BR_MASK_NAMES = {BR_MASK_NONE: "none", BR_MASK_OWN: "this step (launch_relu_mask / launch_relu_mask_bias_grad)", BR_MASK_EARLIER: "an earlier step's stores (mask_fold)"}
+BR_BIAS_NONE, BR_BIAS_OWN, BR_BIAS_WITH_MASK, BR_BIAS_CLOSER, BR_BIAS_INPUT_WGRAD, BR_BIAS_ROW_WGRAD = range(6)
+BR_BIAS_NAMES = {BR_BIAS_NONE: "none", BR_BIAS_OWN: "own launch_bias_grad", BR_BIAS_WITH_MASK: "launch_relu_mask_bias_grad", BR_BIAS_CLOSER: "the closing pool / head step",
+                 BR_BIAS_INPUT_WGRAD: "spare column of launch_input_wgrad", BR_BIAS_ROW_WGRAD: "the Linear's weight-gradient row GEMM"}
+BR_FLAGS = ("folded_mask", "summed_bias", "gelu_fused", "no_launch")  # bits 27..30
+_BR_MASK_SHIFT, _BR_BIAS_SHIFT, _BR_FLAG_SHIFT = 22, 24, 27
+
+
+def br_dgrad_name(code: int) -> str:
+    return BR_DG_NAMES[code] if code in BR_DG_NAMES else KV_NAMES[code]
+
+
+def br_encode(wgrad=(0, 0), dgrad=(0, 0), accumulate=(0, 0), mask=0, bias=0, **flags) -> int:
+    """The route word of the given fields (the inverse of ``br_decode``)."""
+    word = 0
+    for p in (0, 1):
+        assert 0 <= wgrad[p] < 16 and 0 <= dgrad[p] < 64
+        word |= (int(wgrad[p]) | int(dgrad[p]) << 4 | (1 if accumulate[p] else 0) << 10) << (BR_PART_BITS * p)
+    assert 0 <= mask < 4 and 0 <= bias < 8 and set(flags) <= set(BR_FLAGS)
+    word |= int(mask) << _BR_MASK_SHIFT | int(bias) << _BR_BIAS_SHIFT
+    for i, name in enumerate(BR_FLAGS):
+        word |= (1 if flags.get(name) else 0) << (_BR_FLAG_SHIFT + i)
+    return word
+
+
+def br_decode(word: int) -> dict:
+    """Fields of one route word: ``wgrad`` / ``dgrad`` / ``accumulate`` per concat part, ``mask``, ``bias`` and the four flags of ``BR_FLAGS``."""
+    word = int(word)
+    parts = [(word >> (BR_PART_BITS * p)) & ((1 << BR_PART_BITS) - 1) for p in (0, 1)]
+    out = {"wgrad": tuple(q & 15 for q in parts), "dgrad": tuple((q >> 4) & 63 for q in parts), "accumulate": tuple((q >> 10) & 1 for q in parts),
+           "mask": (word >> _BR_MASK_SHIFT) & 3, "bias": (word >> _BR_BIAS_SHIFT) & 7}
+    for i, name in enumerate(BR_FLAGS):
+        out[name] = (word >> (_BR_FLAG_SHIFT + i)) & 1
+    return out
+
+
 KV_MFMA_SHARE = {KV_NONE: 0.0, KV_DIRECT: 1.0, KV_WINO1D: 2.0 / 3.0, KV_WINO2D: 4.0 / 9.0, KV_W16: 4.0 / 9.0, KV_C16: 1.0, KV_ROWGEMM: 1.0, KV_WINO4: 0.25, KV_F16: 1.0, KV_STEM: 4.0 / 9.0, KV_WINO2D_KS: 4.0 / 9.0, KV_FUSED: 0.0, KV_SMALLMAP: 4.0 / 9.0, KV_F16_ROWS: 1.0, KV_F16_BLOCK: 1.0, KV_MLP: 1.0, CNX_KV_F16_STEM: 0.0, CNX_KV_F16_DW: 0.0, CNX_KV_F16_LN: 0.0, CNX_KV_F16_GEMM: 1.0, CNX_KV_F16_ELTWISE: 0.0, SWIN_KV_WINDOW_ATTN: 1.0, SWIN_KV_WINDOW_ATTN_BWD: 1.0, SWIN_KV_WINDOW_ATTN_F16: 1.0, SWIN_KV_F16_MERGE_LN: 0.0, CNX2_KV_GRN: 0.0, CNX2_KV_GRN_FUSED: 0.0, CNX2_KV_PATCH_STEM_NORM: 0.0, CNX2_KV_GRN_BWD: 0.0}
 
 
@@ -114,6 +164,7 @@ SIGNATURES = {
     "ph_model_backward_pad_vector": (_i64, [_vp, _i32, _i32, _i32, C.POINTER(_i32)]),
     "ph_model_backward_profile_read": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32, C.POINTER(C.c_double)]),
     "ph_model_last_backward_kernels": (C.c_int, [_vp, C.POINTER(_i32), _i32]),
+    "ph_model_last_backward_routes": (C.c_int, [_vp, C.POINTER(_i32), _i32]),
     "ph_loss_scratch_bytes": (_i64, [_i32, _i32]),
     "ph_loss_bce_dice": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _i64, _vp]),
     "ph_loss_masked_smooth_l1": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i64, _vp]),

@@ -343,6 +343,14 @@ class Model:
         L.check(L.lib().ph_model_last_backward_kernels(self._handle, arr, n))
         return list(arr)
 
+    def last_backward_routes(self):
+        """PH_BR_* route word of each op's step of the LAST ``ph_model_backward`` (``ph_model_last_backward_routes``; ``_lib.br_decode`` names the fields).  0 for an op
+        that ran no step (a frozen prefix, an op nobody reads)."""
+        n = len(self.ops)
+        arr = (C.c_int32 * n)()
+        L.check(L.lib().ph_model_last_backward_routes(self._handle, arr, n))
+        return list(arr)
+
     def set_fusion(self, fused: bool) -> "Model":
         want = self.fused_ops if fused else self.unfused_ops
         if want is not self.ops:

@@ -81,6 +81,13 @@ struct BackwardCtx {
     return PH_OK;
   }
 
+  // ---- the route record of the current step (ph_model_last_backward_routes, PH_BR_* of posehip.h): each step notes a route in the branch that launches it
+  void note(int32_t bits) { m->last_bwd_route[oi] |= bits; }
+  void note_wgrad(int part, int route) { note(route << (PH_BR_PART_BITS * part)); }
+  void note_dgrad(int part, int route, bool accumulate) { note((route << 4 | (accumulate ? PH_BR_ACCUMULATE : 0)) << (PH_BR_PART_BITS * part)); }
+  void note_mask(int who) { note(who << PH_BR_MASK_SHIFT); }
+  void note_bias(int who) { note(who << PH_BR_BIAS_SHIFT); }
+
   // ---- accessors
   const SlotShape& slot(int i) const { return bp.act.slots[i]; }
   const float* A(int i) const { return reinterpret_cast<const float*>(aws + bp.act.slots[i].offset); }  // activation of slot i
@@ -135,16 +142,28 @@ int finish_output_grad(BackwardCtx& c, const ph_op_desc& d, bool bias_elsewhere)
   const SlotShape& so = c.slot(d.dst);
   const size_t npix = c.npix(so);
   if (c.masked[d.dst]) {  // the last contributor applied the ReLU mask already (and, if it was a max pool's or a head's backward, may have summed the bias gradient)
-    if (d.bias >= 0 && !c.bias_done[d.dst] && !bias_elsewhere) return launch_bias_grad(c.G(d.dst), npix, so.cp, d.cout, c.grad_of(d.bias), c.scratch(), c.s);
+    c.note_mask(PH_BR_MASK_EARLIER);
+    if (d.bias >= 0 && c.bias_done[d.dst]) c.note_bias(PH_BR_BIAS_CLOSER);
+    if (d.bias >= 0 && !c.bias_done[d.dst] && !bias_elsewhere) {
+      c.note_bias(PH_BR_BIAS_OWN);
+      return launch_bias_grad(c.G(d.dst), npix, so.cp, d.cout, c.grad_of(d.bias), c.scratch(), c.s);
+    }
     return PH_OK;
   }
-  if ((d.flags & PH_FLAG_RELU) && d.bias >= 0)  // mask + bias gradient in one pass
+  if ((d.flags & PH_FLAG_RELU) && d.bias >= 0) {  // mask + bias gradient in one pass
+    c.note_mask(PH_BR_MASK_OWN);
+    c.note_bias(PH_BR_BIAS_WITH_MASK);
     return launch_relu_mask_bias_grad(c.G(d.dst), c.A(d.dst), npix, so.cp, d.cout, c.grad_of(d.bias), c.scratch(), c.s);
+  }
   if (d.flags & PH_FLAG_RELU) {
+    c.note_mask(PH_BR_MASK_OWN);
     int rc = launch_relu_mask(c.G(d.dst), c.A(d.dst), npix * so.cp, c.s);
     if (rc != PH_OK) return rc;
   }
-  if (d.bias >= 0) return launch_bias_grad(c.G(d.dst), npix, so.cp, d.cout, c.grad_of(d.bias), c.scratch(), c.s);
+  if (d.bias >= 0) {
+    c.note_bias(PH_BR_BIAS_OWN);
+    return launch_bias_grad(c.G(d.dst), npix, so.cp, d.cout, c.grad_of(d.bias), c.scratch(), c.s);
+  }
   return PH_OK;
 }
 
@@ -259,6 +278,7 @@ int bwd_head(BackwardCtx& c, const PackedOp& op) {
   int rc = launch_head_bwd(c.head_dy(d.out_index), c.head_out_dev[d.out_index], head_sigmoid(c.m, c.m->last_plan, d), c.A(d.src0), op.w_dev, c.batch, s0.h * s0.w, d.cin0, s0.cp,
                            d.cout, c.init[d.src0], c.G(d.src0), c.grad_of(d.weight), d.bias >= 0 ? c.grad_of(d.bias) : nullptr, c.scratch(), c.s, fold ? c.A(d.src0) : nullptr,
                            sum_bias ? c.grad_of(pr->bias) : nullptr, sum_bias ? pr->cout : 0);
+  c.note((fold ? PH_BR_FOLDED_MASK : 0) | (sum_bias ? PH_BR_SUMMED_BIAS : 0));
   c.init[d.src0] = 1;
   if (fold) c.masked[d.src0] = 1;
   c.bias_done[d.src0] = sum_bias ? 1 : 0;
@@ -302,8 +322,10 @@ int bwd_conv_kxk(BackwardCtx& c, const PackedOp& op) {
   for (int part = 0; part < 2; ++part) {
     const ConvPart p = conv_part(d, part);
     if (!p.present()) continue;
+    c.note_wgrad(part, PH_BR_WG_ROWSKK);
     int rc = conv_wgrad_rows(c, d, p);
     if (rc != PH_OK) return rc;
+    c.note_dgrad(part, PH_BR_DG_GEMM5, c.init[p.src]);
     GemmArgs g{};
     g.src0 = c.G(d.dst);
     g.c0p = so.cp;
@@ -329,12 +351,15 @@ int bwd_conv_kxk(BackwardCtx& c, const PackedOp& op) {
 
 // 3 x 3 weight gradient of source `p`: nine row-wgrad GEMMs on 128x128 MFMA tiles for wide layers ("wgrad_rows"), else the 32x32-tile kernel, in the Winograd
 // F(2x2,3x3) domain where "wgrad_wino" and the channel counts allow
-int conv3x3_wgrad(BackwardCtx& c, const ph_op_desc& d, const ConvPart& p) {
+int conv3x3_wgrad(BackwardCtx& c, const ph_op_desc& d, int part, const ConvPart& p) {
   const ph_model* m = c.m;
   const SlotShape& so = c.slot(d.dst);
   const SlotShape& si = c.slot(p.src);
   const double tile_fill = ((double)si.cp / ((si.cp + 127) / 128 * 128)) * ((double)so.cp / ((so.cp + 127) / 128 * 128));
-  if (m->wgrad_rows == 2 || (m->wgrad_rows == 1 && si.cp >= 128 && so.cp >= 128 && tile_fill >= 0.8)) return conv_wgrad_rows(c, d, p);
+  if (m->wgrad_rows == 2 || (m->wgrad_rows == 1 && si.cp >= 128 && so.cp >= 128 && tile_fill >= 0.8)) {
+    c.note_wgrad(part, PH_BR_WG_ROWS9);
+    return conv_wgrad_rows(c, d, p);
+  }
   WgradArgs w{};
   w.x = c.A(p.src);
   w.dy = c.G(d.dst);
@@ -344,8 +369,15 @@ int conv3x3_wgrad(BackwardCtx& c, const ph_op_desc& d, const ConvPart& p) {
   w.B = c.batch;
   w.H = so.h;
   w.W = so.w;
-  if (m->wgrad_wino && w.cxp == 16 && w.coutp == 16) return launch_wgrad16_wino(w, p.cin, d.cout, d.cin0 + d.cin1, p.off, c.grad_of(d.weight), c.s);
-  if (m->wgrad_wino && w.coutp >= 32) return launch_wgrad_wino(w, p.cin, d.cout, d.cin0 + d.cin1, p.off, c.grad_of(d.weight), c.s);
+  if (m->wgrad_wino && w.cxp == 16 && w.coutp == 16) {
+    c.note_wgrad(part, PH_BR_WG_WINO16);
+    return launch_wgrad16_wino(w, p.cin, d.cout, d.cin0 + d.cin1, p.off, c.grad_of(d.weight), c.s);
+  }
+  if (m->wgrad_wino && w.coutp >= 32) {
+    c.note_wgrad(part, PH_BR_WG_WINO);
+    return launch_wgrad_wino(w, p.cin, d.cout, d.cin0 + d.cin1, p.off, c.grad_of(d.weight), c.s);
+  }
+  c.note_wgrad(part, PH_BR_WG_DIRECT);
   return launch_wgrad(w, p.cin, d.cout, d.cin0 + d.cin1, p.off, c.grad_of(d.weight), c.s);
 }
 
@@ -386,7 +418,9 @@ int conv3x3_dgrad(BackwardCtx& c, const PackedOp& op, int part, const ConvPart& 
   if (dma && c.relu_producer_closed_by(p.src, PH_OP_CONV, PH_OP_INPUT_CONV) && d.src0 != d.src1 && conv3x3_dma_honours_mask(a)) {
     a.relu_mask_src = c.A(p.src);
     c.masked[p.src] = 1;
+    c.note(PH_BR_FOLDED_MASK);
   }
+  c.note_dgrad(part, dma ? conv3x3_dma_variant(a) : PH_BR_DG_REGSTAGED, a.accumulate != 0);
   int rc = dma ? launch_conv3x3_dma(a, c.s) : launch_conv3x3(a, c.s);
   if (rc != PH_OK) return rc;
   c.init[p.src] = 1;
@@ -402,7 +436,7 @@ int bwd_conv(BackwardCtx& c, const PackedOp& op) {
   for (int part = 0; part < 2; ++part) {
     const ConvPart p = conv_part(d, part);
     if (!p.present()) continue;
-    rc = conv3x3_wgrad(c, d, p);
+    rc = conv3x3_wgrad(c, d, part, p);
     if (rc != PH_OK) return rc;
     rc = conv3x3_dgrad(c, op, part, p);
     if (rc != PH_OK) return rc;
@@ -422,14 +456,19 @@ int bwd_convt(BackwardCtx& c, const PackedOp& op) {
   const SlotShape& si = c.slot(d.src0);
   PH_REQUIRE(c.init[d.dst], "transposed conv output slot %d received no gradient", d.dst);
   int rc;
-  if (d.flags & PH_FLAG_RELU)
+  if (d.flags & PH_FLAG_RELU) {
+    c.note_mask(PH_BR_MASK_OWN);
+    c.note_bias(PH_BR_BIAS_WITH_MASK);
     rc = launch_relu_mask_bias_grad(c.G(d.dst), c.A(d.dst), c.npix(so), so.cp, d.cout, c.grad_of(d.bias), c.scratch(), c.s);
-  else
+  } else {
+    c.note_bias(PH_BR_BIAS_OWN);
     rc = launch_bias_grad(c.G(d.dst), c.npix(so), so.cp, d.cout, c.grad_of(d.bias), c.scratch(), c.s);
+  }
   // dWt[ci][co][ky][kx] = sum over input pixels (y, x) of x[y, x, ci] * dY[2y - 1 + ky, 2x - 1 + kx, co]: one row-wgrad GEMM per tap, rows = input pixels, the dY
   // operand gathered with stride 2 (patch 3); the result lands in the IOHW layout directly.  The operands are exchanged: the "n" operand is the INPUT (input
   // channels), the gathered "k" operand the output gradient (output channels)
   const WgradDst to{c.grad_of(d.weight), d.cin0, d.cout, d.cout, 0, 9};
+  c.note_wgrad(0, PH_BR_WG_CONVT_TAPS);
   for (int tap = 0; tap < 9 && rc == PH_OK; ++tap)
     rc = launch_wgrad_tap(c, /*n operand*/ c.A(d.src0), si.cp, /*gathered k operand*/ c.G(d.dst), so.cp, c.batch * si.h * si.w, TapGather{3, 3, so.h, so.w}, to, tap);
   if (rc != PH_OK) return rc;
@@ -449,6 +488,7 @@ int bwd_convt(BackwardCtx& c, const PackedOp& op) {
   g.H = so.h;
   g.W = so.w;
   g.late_split = c.m->gemm_late_split;
+  c.note_dgrad(0, PH_BR_DG_GEMM4, g.residual != nullptr);
   rc = launch_gemm(g, c.s);
   c.init[d.src0] = 1;
   return rc;
@@ -472,9 +512,13 @@ int bwd_input_conv(BackwardCtx& c, const PackedOp& op) {
   const bool bias_in_wgrad = c.masked[d.dst] && d.bias >= 0 && d.ksize == 3 && !c.bias_done[d.dst];
   int rc = finish_output_grad(c, d, bias_in_wgrad);
   if (rc != PH_OK) return rc;
-  if (d.ksize != 3)  // first k x k "same" conv: im2col of the image + one row-wgrad GEMM (as the ConvNeXt patch stem, padding k / 2, stride 1)
+  if (d.ksize != 3) {  // first k x k "same" conv: im2col of the image + one row-wgrad GEMM (as the ConvNeXt patch stem, padding k / 2, stride 1)
+    c.note_wgrad(0, PH_BR_WG_PATCH_STEM);
     return launch_patch_stem_wgrad(c.input_dev, c.in_dtype, c.G(d.dst), c.batch, d.cin0, c.height, c.width, so.h, so.w, d.ksize, 1, d.ksize / 2, so.cp, d.cout, c.grad_of(d.weight),
                                    c.scratch(), c.s);
+  }
+  c.note_wgrad(0, PH_BR_WG_INPUT);
+  if (bias_in_wgrad) c.note_bias(PH_BR_BIAS_INPUT_WGRAD);
   return launch_input_wgrad(c.input_dev, c.in_dtype, c.G(d.dst), c.batch, d.cin0, c.height, c.width, so.cp, d.cout, c.grad_of(d.weight), c.scratch(), c.s,
                             bias_in_wgrad ? c.grad_of(d.bias) : nullptr);
 }
@@ -493,6 +537,7 @@ int bwd_pool(BackwardCtx& c, const PackedOp& op) {  // (scratch: the bias partia
   const bool sum_bias = fold && pr->bias >= 0 && pool_bwd_can_sum_bias(si.cp);
   int rc = launch_pool_bwd(c.G(d.dst), c.A(d.src0), c.batch, si.h, si.w, si.cp, c.init[d.src0], fold ? 1 : 0, c.G(d.src0), sum_bias ? c.grad_of(pr->bias) : nullptr,
                            sum_bias ? pr->cout : 0, c.scratch(), c.s);
+  c.note((fold ? PH_BR_FOLDED_MASK : 0) | (sum_bias ? PH_BR_SUMMED_BIAS : 0));
   c.init[d.src0] = 1;
   c.masked[d.src0] = fold ? 1 : 0;
   c.bias_done[d.src0] = sum_bias ? 1 : 0;
@@ -519,7 +564,10 @@ int bwd_global_maxpool(BackwardCtx& c, const PackedOp& op) {
 
 int bwd_gelu(BackwardCtx& c, const PackedOp& op) {
   const ph_op_desc& d = op.d;
-  if (c.fused_away[c.oi]) return PH_OK;  // its consumer's data-gradient GEMM already wrote G(src0) through the GELU derivative
+  if (c.fused_away[c.oi]) {  // its consumer's data-gradient GEMM already wrote G(src0) through the GELU derivative
+    c.note(PH_BR_NO_LAUNCH);
+    return PH_OK;
+  }
   const SlotShape& so = c.slot(d.dst);
   PH_REQUIRE(c.init[d.dst], "GELU output slot %d received no gradient", d.dst);
   int rc = launch_gelu_bwd(c.G(d.dst), c.A(d.src0), c.G(d.src0), c.init[d.src0], c.npix(so) * so.cp, c.s);
@@ -608,10 +656,19 @@ int bwd_linear(BackwardCtx& c, const PackedOp& op) {  // PH_OP_LINEAR and PH_OP_
     if (rc != PH_OK) return rc;
     gy = c.scaled_gy();
   }
-  if (d.flags & PH_FLAG_RELU)
+  if (d.flags & PH_FLAG_RELU) {
+    c.note_mask(PH_BR_MASK_OWN);
+    c.note_bias(PH_BR_BIAS_WITH_MASK);
     rc = launch_relu_mask_bias_grad(c.G(d.dst), c.A(d.dst), (size_t)M, so.cp, d.cout, c.grad_of(d.bias), c.scratch(), c.s);
-  else if (!bias_in_wgrad && d.bias >= 0)  // (Linear(bias=False): Swin's patch-merging reduction has none)
+  } else if (!bias_in_wgrad && d.bias >= 0) {  // (Linear(bias=False): Swin's patch-merging reduction has none)
+    c.note_bias(PH_BR_BIAS_OWN);
     rc = launch_bias_grad(c.G(d.dst), (size_t)M, so.cp, d.cout, c.grad_of(d.bias), c.scratch(), c.s);
+  } else if (bias_in_wgrad) {
+    c.note_bias(PH_BR_BIAS_ROW_WGRAD);
+  }
+  c.note_wgrad(0, PH_BR_WG_ROW_GEMM);
+  c.note_dgrad(0, PH_BR_DG_GEMM0, false);  // (the source has no gradient yet: required above)
+  if (gelu_op >= 0) c.note(PH_BR_GELU_FUSED);
   const WgradDst to{c.grad_of(d.weight), d.cout, d.cin0, d.cin0, 0, taps};
   for (int tap = 0; tap < taps && rc == PH_OK; ++tap) {
     rc = launch_wgrad_tap(c, gy, so.cp, c.A(d.src0), si.cp, M, TapGather{patch ? 1 : 0, 3, si.h, si.w}, to, tap, bias_in_wgrad ? c.grad_of(d.bias) : nullptr, bias_in_wgrad ? d.cout : 0);
@@ -757,6 +814,8 @@ int bwd_patch_stem(BackwardCtx& c, const PackedOp& op) {
   const SlotShape& so = c.slot(d.dst);
   PH_REQUIRE(c.init[d.dst], "stem output received no gradient");
   PH_REQUIRE(d.cin0 == c.in_channels, "input has %d channels, network expects %d", c.in_channels, d.cin0);
+  c.note_bias(PH_BR_BIAS_OWN);
+  c.note_wgrad(0, PH_BR_WG_PATCH_STEM);
   int rc = launch_bias_grad(c.G(d.dst), c.npix(so), so.cp, d.cout, c.grad_of(d.bias), c.scratch(), c.s);
   if (rc != PH_OK) return rc;
   if (d.flags & PH_FLAG_PAD0_NORM)  // ConvNeXtV2 embeddings: padding 0, patches of (x / 255 - mean) / std; the bias gradient above is the same
@@ -910,6 +969,7 @@ int check_backward_handle(ph_model* m, int batch) {
              "ph_model_backward: branch scales are set for %d branches x batch %d, the step has %d x %d", m->branch_n, m->branch_batch, n_res, batch);
   const size_t n_ops = m->ops.size();
   m->last_bwd_variant.assign(n_ops, PH_KV_NONE);
+  m->last_bwd_route.assign(n_ops, 0);
   if (m->profiling && m->bwd_ev.size() != 2 * n_ops + 2) {
     for (auto& e : m->bwd_ev) (void)hipEventDestroy(e);
     m->bwd_ev.assign(2 * n_ops + 2, nullptr);

@@ -134,6 +134,7 @@ struct ph_model {
                                           // launches (Linear ops; elsewhere recorded at once), [2 n + 1] after the sweep (ph_model_backward_profile_read)
   bool bwd_ev_recorded = false;
   std::vector<int> last_bwd_variant;      // PH_KV_* code of the kernel each op's step of the last ph_model_backward ran (ph_model_last_backward_kernels)
+  std::vector<int32_t> last_bwd_route;    // PH_BR_* route word of each op's step of the last ph_model_backward, written where the step decides (ph_model_last_backward_routes)
   // ph_model_set_branch_scales: (branch_n, branch_batch) per-sample scales of the residual Linears' branches (stochastic depth), borrowed; nullptr = none
   const float* branch_scales = nullptr;
   // ph_model_set_input_norm: per-channel statistics of a PH_FLAG_PAD0_NORM patch stem (the checkpoint's image_mean / image_std buffers)

@@ -221,6 +221,12 @@ int ph_model_last_backward_kernels(const ph_model* m, int32_t* codes, int32_t n_
   return PH_OK;
 }
 
+int ph_model_last_backward_routes(const ph_model* m, int32_t* routes, int32_t n_ops) {
+  PH_REQUIRE(m && routes && n_ops >= 0, "ph_model_last_backward_routes: bad arguments");
+  for (int i = 0; i < n_ops; ++i) routes[i] = i < (int)m->last_bwd_route.size() ? m->last_bwd_route[i] : 0;
+  return PH_OK;
+}
+
 int ph_model_set_head_loss(ph_model* m, int32_t out_index, int32_t kind, const float* params, int32_t n_params) {
   PH_REQUIRE(m, "ph_model_set_head_loss: null model");
   PH_REQUIRE(out_index >= 0 && out_index < m->n_outputs && out_index < PH_MAX_OUTPUTS, "ph_model_set_head_loss: output %d of %d", out_index, m->n_outputs);

@@ -4,7 +4,7 @@ move a launch, an argument or a byte.  The sibling of tools/forward_trace.py, wh
     python tools/backward_trace.py OUT.jsonl
 
 One JSON line per case: its name, ``ph_model_backward_workspace_bytes``, the pad-vector offset and length (Swin programs), the gradient arena's bucket split,
-``last_backward_kernels()`` and a SHA-256 of the loss tensor, of the gradient arena and of the whole gradient workspace.  Arena and workspace are zeroed before the recorded
+``last_backward_kernels()``, ``last_backward_routes()`` and a SHA-256 of the loss tensor, of the gradient arena and of the whole gradient workspace.  Arena and workspace are zeroed before the recorded
 step, which follows one unrecorded step that sizes the buffers.  Cases run with profiling record the SET of ops whose ``op_ms_first`` is non-zero (not the times).  Run it on
 a build of the commit before the change and on a build of the change, on the same device: the backward is deterministic by contract (fixed-order reductions, no float
 atomics), so the two files are byte-identical unless a route, an argument or the plan changed.  Under ``rocprofv3 --kernel-trace -- python tools/backward_trace.py ...`` the
@@ -83,7 +83,7 @@ def record(name, tm, img, targets, is_negative=None, scales=None, profile=False)
     step()
     need = int(L.check(lib.ph_model_backward_workspace_bytes(m._handle, B, H, W)))
     row = {"case": name, "workspace_bytes": need, "bucket_split": int(L.check(lib.ph_model_grad_bucket_split(m._handle))), "kernels": m.last_backward_kernels(),
-           "sha256": {"loss": sha(tm._loss), "grads": sha(tm.grads), "grad_workspace": sha(tm._grad_ws[:need])}}
+           "routes": m.last_backward_routes(), "sha256": {"loss": sha(tm._loss), "grads": sha(tm.grads), "grad_workspace": sha(tm._grad_ws[:need])}}
     if any(o.kind == L.OP_WINDOW_ATTN for o in m.ops):
         n = C.c_int32()
         row["pad_vector"] = [int(L.check(lib.ph_model_backward_pad_vector(m._handle, B, H, W, C.byref(n)))), n.value]
