@@ -496,8 +496,8 @@ ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const float* con
           float* w = nullptr;
           if (hipMalloc(&w, (size_t)wino4_pack_floats(ntiles, nchunks) * sizeof(float)) != hipSuccess) return false;
           m->allocs.push_back(w);
-          if (launch_wino4_pack(src, w, ntiles, nchunks, nullptr) != PH_OK) return false;
-          add_derived(m, DERIVED_WINO4, src, w, ntiles, nchunks);
+          if (launch_wino4_pack(src, w, pad16(cout_), nchunks, nullptr) != PH_OK) return false;
+          add_derived(m, DERIVED_WINO4, src, w, pad16(cout_), nchunks);
           *dst = w;
           return true;
         };

@@ -75,7 +75,7 @@ enum DerivedKind {
   DERIVED_WINO2D = 2,          // F(2x2,3x3) transform (launch_wino2d_pack)
   DERIVED_W16 = 3,             // wave-private F(2x2,3x3) transform (launch_w16_pack: panels = chunks, bn = N blocks of 16)
   DERIVED_STEM_WINO2D = 4,     // the fused stem's F(2x2,3x3) transform (launch_stem_wino2d_pack)
-  DERIVED_WINO4 = 5,           // F(4x4,3x3) transform (launch_wino4_pack: panels = N tiles, bn = 16-channel chunks); inference plans only
+  DERIVED_WINO4 = 5,           // F(4x4,3x3) transform (launch_wino4_pack: panels = padded output channels, bn = 16-channel chunks); inference plans only
   DERIVED_SMALLMAP = 6,        // small-map F(2x2,3x3) transform (launch_sm_pack: panels = N blocks of 16, bn = 16-channel chunks, n_tiles = the source packing's N tile); inference plans only
   DERIVED_GEMM_F16_IMAGE = 7,  // fp16 row-GEMM weight image of a Linear / 2x2-stride-2 conv (launch_gemm_f16_weight_image: panels = cout, n_tiles = cin, chunks0 = taps, bn = the source packing's N tile)
 };

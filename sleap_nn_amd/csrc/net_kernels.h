@@ -277,7 +277,8 @@ int launch_wino2d_pack(const float* wpack, float* wino, int panels, int bn, hipS
 int64_t wino2d_pack_floats(int panels, int bn);
 int launch_conv3x3_wino2d(const ConvArgs& a, hipStream_t s);
 // wpack [panel][tap 9][64][16] -> F(4x4,3x3) weights [n tile][quarter][wave][fragment slot][lane] (see conv3x3_wino4_kernel)
-int launch_wino4_pack(const float* wpack, float* wino, int ntiles, int nchunks, hipStream_t s);
+// (coutp: the layer's padded output channel count, ConvArgs::coutp of its launches -- the channel order inside the last N tile depends on it)
+int launch_wino4_pack(const float* wpack, float* wino, int coutp, int nchunks, hipStream_t s);
 int64_t wino4_pack_floats(int ntiles, int nchunks);
 int launch_conv3x3_wino4(const ConvArgs& a, hipStream_t s);
 bool wino4_fits(const ConvArgs& a);

@@ -37,9 +37,10 @@
 //     outside the image zeroed: the conv's padding) as four per-lane coefficients, the column pass forms the six up-sampled column
 //     samples first; the four low-resolution columns of a row start at an even column of the plane: two ds_read_b64 per row, 8 reads per thread.
 //   * Epilogue: two rounds through LDS (144 KiB each), every wave with half of its registers per round (channel quads 0, 1, then 2, 3, of both N
-//     halves); all eight waves apply A^T . A: one thread per (tile, channel quad, row half) reads the 36 positions and stores two rows of the 4 x 4
-//     tile: bias, ReLU, the backward pass' ReLU mask, the fused 2 x 2 max pool (its windows are inside a thread's rows), 16-byte stores, eight lanes =
-//     two 64-byte runs of a pixel.  (round 3's form: twelve waves, three per SIMD, weights and halo by LDS-DMA, ran the same arithmetic 6 - 8 % slower.)
+//     halves); all eight waves apply A^T . A: one thread per (tile, channel quad, channel pair) reads the 36 positions of its two channels and computes the 4 x 4
+//     tile: bias, ReLU; the two lanes of a quad then trade half of every row (DPP), so that a lane stores the whole quad of two columns: 16-byte stores (cache policy
+//     W4_ST_POLICY), the backward pass' ReLU mask, the fused 2 x 2 max pool (a window is inside a lane's two columns); eight lanes = 32 contiguous channels, one
+//     128-byte line of a pixel (the channel order of the accumulator rows: w4_tile_in_halves).  (round 3's form: twelve waves, three per SIMD, weights and halo by LDS-DMA, ran the same arithmetic 6 - 8 % slower.)
 #include <type_traits>
 
 #include "common.h"
@@ -47,6 +48,9 @@
 
 #ifndef W4_EXP
 #define W4_EXP 0  // timing experiments of tools/w4/w4_bench.hip only (results are wrong with any bit set): 1 no weight loads, 2 no input transform, 4 no per-quarter barrier, 8 no halo transfers, 16 no MFMAs, 32 weights always of the first quarter (cache-hot), 64 halo always of the first quarter, 128 transform without its arithmetic (LDS traffic only), 256 weights loaded once per tile, 512 no output stores.  Ablations that zero the operands (1, 8, 16) also raise the clock: compare cycles (-DW4_CLOCK), not milliseconds
+#endif
+#ifndef W4_ST_POLICY
+#define W4_ST_POLICY 2  // cache policy of the output stores: 0 plain, 1 nt, 2 sc1, 3 sc0 sc1.  sc1: the line leaves the XCD's L2 (the consumer runs a launch later; the weights every quarter re-reads stay); DESIGN.md 4.1c has the measurements of all four
 #endif
 
 namespace ph {
@@ -71,7 +75,11 @@ constexpr int P4_WAVE_FLOATS = 4 * 256 + 128;   // one wave's fragments of a qua
 
 // wpack [panel][tap 9][bn 64][16] (pack_conv) -> U = G g G^T in the order the waves load it:
 // [n tile][quarter][wave nt * 4 + pg][four 16-byte slots [lane (lh, lx)][ks * 2 + (pl & 1)] of the position pairs pl = (0, 1) .. (6, 7) | one 8-byte slot [lane][ks] of pl = 8]:
-// output channel n tile * 64 + nt * 32 + lx, input channel quarter * 4 + 2 lh + ks, position p = xi * 6 + nu = 9 pg + pl
+// output channel n tile * 64 + 32 (lx >> 4) + 16 nt + (lx & 15), input channel quarter * 4 + 2 lh + ks, position p = xi * 6 + nu = 9 pg + pl.
+// Accumulator rows 0..15 of the two N halves together are channels 0..31 of the N tile, rows 16..31 channels 32..63: an epilogue round (sixteen rows of both halves) stores 32
+// contiguous channels, one 128-byte line per pixel.  The exception is a layer's last N tile when it holds 32 channels or fewer (w4_tile_in_halves): there N half nt holds channels
+// 32 nt + lx, so that the waves of the empty half skip their MFMAs.  The pack kernel and the conv kernel decide by the same function of the padded output channel count.
+__host__ __device__ __forceinline__ bool w4_tile_in_halves(int coutp, int ntile) { return ntile * 64 + 32 >= coutp; }
 __device__ __forceinline__ float wino4_g_row(int k, float g0, float g1, float g2) {  // row k of G applied to (g0, g1, g2)
   switch (k) {
     case 0: return 0.25f * g0;
@@ -86,12 +94,13 @@ __device__ __forceinline__ float wino4_g_row(int k, float g0, float g1, float g2
 // loads its nine taps ONCE, forms all 36 positions in registers and drops them into LDS at their place in the unit; the unit then leaves as 36 coalesced
 // 1-KiB rows.  (One thread per destination element re-read the nine taps 36 times through 4-byte loads 64 B apart: 0.48 ms for the 2304 -> 768 layer's
 // 255 MB, 3.6 ms per ConvNeXt training step, where the weights change every step.)
-__global__ __launch_bounds__(256) void wino4_pack_kernel(const float* __restrict__ src, float* __restrict__ dst, int ntiles, int nchunks) {
+__global__ __launch_bounds__(256) void wino4_pack_kernel(const float* __restrict__ src, float* __restrict__ dst, int ntiles, int nchunks, int half_last) {
   __shared__ float unit[W4_Q_FLOATS];
   const int quarter = blockIdx.x % (4 * nchunks), ntile = blockIdx.x / (4 * nchunks);
   const int tid = threadIdx.x;
   const int row = tid >> 2, kcl = tid & 3;
-  const int nt = row >> 5, lx = row & 31, lh = kcl >> 1, j = kcl & 1;
+  const bool halves = half_last && ntile == ntiles - 1;  // w4_tile_in_halves
+  const int nt = halves ? row >> 5 : (row >> 4) & 1, lx = halves ? row & 31 : (row & 15) + 16 * (row >> 5), lh = kcl >> 1, j = kcl & 1;
   const float* w = src + (((size_t)ntile * nchunks + (quarter >> 2)) * 9 * 64 + row) * 16 + (quarter & 3) * 4 + kcl;
   const size_t ts = (size_t)64 * 16;  // tap stride
   float g[9];
@@ -115,8 +124,9 @@ __global__ __launch_bounds__(256) void wino4_pack_kernel(const float* __restrict
   for (int i = tid; i < W4_Q_FLOATS; i += 256) out[i] = unit[i];
 }
 int64_t wino4_pack_floats(int ntiles, int nchunks) { return (int64_t)ntiles * 4 * nchunks * W4_Q_FLOATS; }
-int launch_wino4_pack(const float* wpack, float* wino, int ntiles, int nchunks, hipStream_t s) {
-  hipLaunchKernelGGL(wino4_pack_kernel, dim3((unsigned)(ntiles * 4 * nchunks)), dim3(256), 0, s, wpack, wino, ntiles, nchunks);
+int launch_wino4_pack(const float* wpack, float* wino, int coutp, int nchunks, hipStream_t s) {
+  const int ntiles = (coutp + 63) / 64;
+  hipLaunchKernelGGL(wino4_pack_kernel, dim3((unsigned)(ntiles * 4 * nchunks)), dim3(256), 0, s, wpack, wino, ntiles, nchunks, w4_tile_in_halves(coutp, ntiles - 1) ? 1 : 0);
   PH_HIP_CHECK(hipGetLastError());
   return PH_OK;
 }
@@ -164,6 +174,41 @@ __device__ __forceinline__ void p4_vput(float* slot, int vwq, int vwd, const flo
       p4_vput<P + 1, N - 1>(slot, vwq, vwd, v + 1);
     }
   }
+}
+
+// The output stage's lane pair (lanes 2 i, 2 i + 1: channels 0, 1 and 2, 3 of one channel quad) trades half of an output row: in, y[column 0..3] = the lane's own two channels;
+// out, o[c] = all four channels of column c (even lane) or 2 + c (odd lane).  The partner's value comes through DPP (quad_perm [1,0,3,2]: no LDS) as the first operand of the select
+// itself, D = vcc ? src1 : dpp(src0), so a row (two calls) costs eight vector instructions; register moves only, no arithmetic.  The compiler keeps a select's condition in an SGPR pair and so
+// cannot fold the DPP move into it (v_cndmask_b32_e64 has no DPP form on gfx9): written out.  s_nop 1: the two wait states between a VALU write and a DPP read of a register,
+// which the compiler's hazard pass does not see inside an asm.  All 64 lanes must be active.
+__device__ __forceinline__ f32x4 w4_pair_trade(f32x2 lo, f32x2 hi) {  // lo = the lane's channels of column c, hi = of column 2 + c: the whole quad of column c (even lane), 2 + c (odd lane)
+  float o0, o1, o2, o3;
+  asm volatile(
+      "s_nop 1\n\t"
+      "s_mov_b32 vcc_lo, 0x55555555\n\t"
+      "s_mov_b32 vcc_hi, 0x55555555\n\t"  // channels 0, 1: an even lane keeps its own of column c, an odd lane takes the partner's of column 2 + c
+      "v_cndmask_b32_dpp %0, %6, %4, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_cndmask_b32_dpp %1, %7, %5, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "s_mov_b32 vcc_lo, 0xaaaaaaaa\n\t"
+      "s_mov_b32 vcc_hi, 0xaaaaaaaa\n\t"  // channels 2, 3: an odd lane keeps its own of column 2 + c, an even lane takes the partner's of column c
+      "v_cndmask_b32_dpp %2, %4, %6, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_cndmask_b32_dpp %3, %5, %7, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+      : "=&v"(o0), "=&v"(o1), "=&v"(o2), "=&v"(o3)
+      : "v"(lo[0]), "v"(lo[1]), "v"(hi[0]), "v"(hi[1])
+      : "vcc");
+  return f32x4{o0, o1, o2, o3};
+}
+// An output store (dst, dst_pool), 16 bytes per lane, under the file's cache policy
+__device__ __forceinline__ void w4_store16(float* p, f32x4 v) {
+#if W4_ST_POLICY == 1
+  __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
+#elif W4_ST_POLICY == 2
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 0" ::"v"(p), "v"(v) : "memory");  // (s_nop: the wait state before the data registers may be written again)
+#elif W4_ST_POLICY == 3
+  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 0" ::"v"(p), "v"(v) : "memory");
+#else
+  *reinterpret_cast<f32x4*>(p) = v;
+#endif
 }
 
 template <bool LOWRES, bool KS = false>
@@ -619,7 +664,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
         default: run(std::integral_constant<int, 3>{}, mm_tag); break;
       }
     };
-    if (nt == 1 && P.ntile * 64 + 32 >= a.coutp) {  // wave-uniform
+    if (nt == 1 && w4_tile_in_halves(a.coutp, P.ntile)) {  // wave-uniform: the N tile's upper 32 channels, all beyond the layer's last
       run_mm(std::false_type{});
     } else {
       run_mm(std::true_type{});
@@ -670,10 +715,12 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
     // value of the exchange is read exactly once -- the round-4 form, one thread per (tile, slot, row half), read every value twice and formed the shared row differences in both
     // halves) and stores all four rows of the 4 x 4 output tile.
     auto finish = [&](int round) __attribute__((always_inline)) {
-      const int tile = tid >> 4, cq = (tid >> 1) & 7, hc = tid & 1;
+      const int tile = tid >> 4, cq = (tid >> 1) & 7;
+      int hc = tid & 1;
       const int ty = tile >> 3, tx = tile & 7;
       int z0 = ((tile * 8 + (cq ^ (tile & 7))) << 2) + 2 * hc;
       asm volatile("" : "+v"(z0));
+      asm volatile("" : "+v"(hc));  // (as z0: the store addresses made of it are formed here, per tile, not parked in scratch across the K loop)
       const float* zp = exch + z0;
       // row pass (over xi) per nu: Z[a][nu] for the four output rows a
       f32x2 z[4][6];
@@ -691,11 +738,13 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
           z[3][n][e] = fmaf(8.f, d34, d12) + m[5][e];
         }
       }
-      const int co = P.ntile * 64 + (cq >> 2) * 32 + round * 16 + (cq & 3) * 4 + 2 * hc;
-      const f32x2 bias = KS ? f32x2{0.f, 0.f} : *reinterpret_cast<const f32x2*>(a.bias + co);
+      // the slot's channel quad (N half cq >> 2, rows 16 round + 4 (cq & 3) ..): the eight slots of a round are 32 contiguous channels, but in a tile kept in halves; this thread
+      // computes channels co + 2 hc, + 1 of it
+      const int co = P.ntile * 64 + (cq & 3) * 4 + (w4_tile_in_halves(a.coutp, P.ntile) ? (cq >> 2) * 32 + round * 16 : round * 32 + (cq >> 2) * 16);
+      const f32x2 bias = KS ? f32x2{0.f, 0.f} : *reinterpret_cast<const f32x2*>(a.bias + co + 2 * hc);
       const int oy0 = P.y0 + 4 * ty, ox = P.x0 + 4 * tx;
-      const bool live = oy0 < a.H && ox < a.W && co < a.coutp;  // (H and W are multiples of 4: a 4 x 4 tile is inside the image or outside; channel counts are even)
-      f32x2 prow[2];  // fused 2 x 2 / 2 max pool (ConvArgs::dst_pool; even H and W: no padded windows): the column-pair maxima of the window's first row
+      const bool live = oy0 < a.H && ox < a.W && co < a.coutp;  // (H and W are multiples of 4: a 4 x 4 tile is inside the image or outside; padded channel counts are multiples of 16: the two lanes of a quad agree)
+      f32x4 prow;  // fused 2 x 2 / 2 max pool (ConvArgs::dst_pool; even H and W: no padded windows): the column-pair maximum of the window's first row
 #pragma unroll
       for (int aa = 0; aa < 4; ++aa) {
         const f32x2 s12 = z[aa][1] + z[aa][2], d12 = z[aa][1] - z[aa][2], s34 = z[aa][3] + z[aa][4], d34 = z[aa][3] - z[aa][4];
@@ -704,42 +753,41 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
         y[1] = (d12 + 2.f * d34) + bias;
         y[2] = (s12 + 4.f * s34) + bias;
         y[3] = ((d12 + 8.f * d34) + z[aa][5]) + bias;
-        if (live) {
-          float* const dp = a.dst + ((size_t)(P.b * a.H + oy0 + aa) * a.W + ox) * a.coutp + co + (KS ? (size_t)ksl * a.split_stride : (size_t)0);
+        if (a.relu) {
 #pragma unroll
           for (int bb = 0; bb < 4; ++bb) {
-            f32x2 v = y[bb];
-            if (a.relu) {
 #pragma unroll
-              for (int e = 0; e < 2; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
-            if (a.relu_mask_src) {  // backward: this launch completes the gradient of a conv + ReLU output -- that ReLU's mask rides in the (lane-local) store
-              const f32x2 f = *reinterpret_cast<const f32x2*>(a.relu_mask_src + (dp - a.dst) + (size_t)bb * a.coutp);
-#pragma unroll
-              for (int e = 0; e < 2; ++e) v[e] = f[e] > 0.f ? v[e] : 0.f;
-            }
-            y[bb] = v;
-            if ((KS || !a.skip_dst) && !(W4_EXP & 512)) *reinterpret_cast<f32x2*>(dp + (size_t)bb * a.coutp) = v;  // (non-temporal stores: the output stage 2x slower)
+            for (int e = 0; e < 2; ++e) y[bb][e] = fmaxf(y[bb][e], 0.f);
           }
-          if (!KS && a.dst_pool) {
-            f32x2 m0, m1;
+        }
+        // The two lanes of a quad trade half of the row (DPP, neighbouring lanes: no LDS): lane hc = 0 gives its columns 2, 3 and takes the partner's channels 2, 3 of columns 0, 1,
+        // lane hc = 1 the other way round.  Then a lane holds the whole channel quad of the columns 2 hc, 2 hc + 1: two 16-byte stores per row instead of four 8-byte ones
+        // (eight v_cndmask_b32_dpp per row).  Every lane of the workgroup takes part: the exchange stands outside `live`.
+        const f32x4 o0 = w4_pair_trade(y[0], y[2]), o1 = w4_pair_trade(y[1], y[3]);
+        f32x4 o[2] = {o0, o1};
+        if (live) {
+          float* const dp = a.dst + ((size_t)(P.b * a.H + oy0 + aa) * a.W + ox + 2 * hc) * a.coutp + co + (KS ? (size_t)ksl * a.split_stride : (size_t)0);
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {
-              m0[e] = fmaxf(y[0][e], y[1][e]);
-              m1[e] = fmaxf(y[2][e], y[3][e]);
+          for (int c = 0; c < 2; ++c) {
+            f32x4 v = o[c];
+            if (a.relu_mask_src) {  // backward: this launch completes the gradient of a conv + ReLU output -- that ReLU's mask rides in the (lane-local) store
+              const f32x4 f = *reinterpret_cast<const f32x4*>(a.relu_mask_src + (dp - a.dst) + (size_t)c * a.coutp);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[e] = f[e] > 0.f ? v[e] : 0.f;
             }
+            o[c] = v;
+            if ((KS || !a.skip_dst) && !(W4_EXP & 512)) w4_store16(dp + (size_t)c * a.coutp, v);
+          }
+          if (!KS && a.dst_pool) {  // the lane's two columns are one window column
+            f32x4 m;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m[e] = fmaxf(o[0][e], o[1][e]);
             if (aa & 1) {
 #pragma unroll
-              for (int e = 0; e < 2; ++e) {
-                m0[e] = fmaxf(m0[e], prow[0][e]);
-                m1[e] = fmaxf(m1[e], prow[1][e]);
-              }
-              float* const pp = a.dst_pool + ((size_t)(P.b * (a.H >> 1) + ((oy0 + aa) >> 1)) * (a.W >> 1) + (ox >> 1)) * a.coutp + co;
-              *reinterpret_cast<f32x2*>(pp) = m0;
-              *reinterpret_cast<f32x2*>(pp + a.coutp) = m1;
+              for (int e = 0; e < 4; ++e) m[e] = fmaxf(m[e], prow[e]);
+              w4_store16(a.dst_pool + ((size_t)(P.b * (a.H >> 1) + ((oy0 + aa) >> 1)) * (a.W >> 1) + (ox >> 1) + hc) * a.coutp + co, m);
             } else {
-              prow[0] = m0;
-              prow[1] = m1;
+              prow = m;
             }
           }
         }

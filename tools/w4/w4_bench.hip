@@ -45,7 +45,7 @@ int main(int argc, char** argv) {
   hipMalloc(&d0, n0 * 4); hipMalloc(&d1, std::max<size_t>(n1, 1) * 4); hipMalloc(&dwp, nwp * 4); hipMalloc(&dw, nw * 4); hipMalloc(&dout, no * 4); hipMalloc(&dbias, 4096);
   auto fill = [&](float* d, size_t n, float s) { for (size_t i = 0; i < n; ++i) h[i] = s * ((rand() & 0xffff) / 32768.f - 1.f); hipMemcpy(d, h.data(), n * 4, hipMemcpyHostToDevice); };
   fill(d0, n0, 1.f); if (n1) fill(d1, n1, 1.f); fill(dwp, nwp, 0.05f); fill(dbias, 1024, 0.1f);
-  if (launch_wino4_pack(dwp, dw, ntiles, nchunks, 0) != PH_OK) return printf("pack failed\n"), 1;  // random direct weights -> the kernel's order
+  if (launch_wino4_pack(dwp, dw, cout, nchunks, 0) != PH_OK) return printf("pack failed\n"), 1;  // random direct weights -> the kernel's order
   hipDeviceSynchronize();
   ConvArgs a{};
   a.src0 = d0; a.src1 = c1 ? d1 : nullptr; a.c0p = c0; a.c1p = c1; a.coutp = cout; a.B = B; a.H = H; a.W = W; a.relu = 1; a.bn = 64;
