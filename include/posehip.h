@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 125
+#define PH_VERSION 126
 
 /* error codes */
 #define PH_OK 0
@@ -370,7 +370,7 @@ int ph_debug_row_wgrad_bench(int32_t M, int32_t n, int32_t k, int32_t iters, flo
  * conv3x3_sm_kernel on (8 x 8 pixels, 16 channels) units for small maps: 1 inference plans where estimated faster | 2 wherever the shape fits | 0 never),
  * "pool_peephole" (unfused programs: a conv writes the next op's 2x2 max pool), "dw_ln_fuse" (ConvNeXt: LayerNorm inside the
  * depthwise / stem kernels), "wgrad_wino" (3x3 weight gradients in the Winograd domain), "mask_fold" (ReLU masks applied by the kernel
- * that completes a gradient), "conv_f16_rows" (plain fp16: conv3x3_f16_rows_kernel 1 where its plan is estimated faster | 2 wherever the shape fits | 0 never), "upsample_f16math"
+ * that completes a gradient), "conv_f16_rows" (plain fp16: conv3x3_f16_rows_kernel 1 where its plan is estimated faster | 2 wherever the shape fits | 0 never), "conv_f16_rows_pin" (that kernel's tile pinned: see ph_model_last_rows_plans), "upsample_f16math"
  * (plain fp16: the bilinear x2 blended in packed fp16 arithmetic, folded or standalone: same bits), "stem_f16mfma" (plain fp16: stem_f16_kernel), "block_fuse" (plain fp16, inference plans:
  * the two convs of a 32-channel encoder block in one launch), "mlp_fuse" (inference plans: CNBlock's Linear + GELU + Linear + layer scale + residual in one launch at 96 / 192 channels),
  * "grn_fuse" (inference plans: ConvNeXtV2 blocks on the fused GRN plan; only a program whose first Linear carries the GELU can take it, so the unfused training program runs the
@@ -425,6 +425,11 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_GRN_BWD 28 /* grn_bwd_reduce_kernel + grn_bwd_sample_kernel + grn_bwd_param_kernel + grn_bwd_apply_kernel (ph_model_last_backward_kernels): backward of a PH_OP_GRN step, fixed-slice sums, no atomics */
 #define PH_KV_FUSED 11   /* no launch of its own: a 1x1 head computed in the epilogue of the conv that produces its input */
 int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
+/* ... and the tile plan of every op of the LAST ph_model_forward that ran conv3x3_f16_rows_kernel (PH_KV_F16_ROWS): quad[4 i .. 4 i + 3] = {R rows, Wt columns of a tile, MT M tiles
+ * per wave, MG pixel groups} of op i, as f16_rows_plan chose them; zeros for an op on any other kernel.  The kernel instantiation is (Wt % 16 == 0, MT, MG).  Written where the
+ * forward decides; host integers only.  The handle option "conv_f16_rows_pin" (R | Wt << 8 | MG << 16; 0, the default: the planner's search) makes the planner consider that
+ * one tile -- under every constraint of the search; a layer it does not fit gets the search -- so that a test can run each instantiation on purpose. */
+int ph_model_last_rows_plans(const ph_model* m, int32_t* quad, int32_t n_ops);
 /* Per-op times of the LAST ph_model_backward, recorded while profiling is on (ph_model_set_profiling).  op_ms[i]: op i's step of the reverse sweep; op_ms_first[i]: its part up to the
  * first data-gradient GEMM (Linear / 2x2-stride-2 ops: the scaling pass and the weight-gradient GEMM; 0 elsewhere); *loss_ms: losses and head-output gradients. */
 int ph_model_backward_profile_read(ph_model* m, double* op_ms, double* op_ms_first, int32_t n_ops, double* loss_ms);
@@ -491,7 +496,9 @@ int ph_model_last_ranges(const ph_model* m, int64_t* rows, int32_t max_rows, int
 int ph_model_set_clock_probe(ph_model* m, void* buf_dev);
 
 /* Debug/parity helper: copy activation slot `slot` of the last forward (NHWC, padded
- * channels) into an NCHW fp32 device buffer of the logical channel count. */
+ * channels) into an NCHW fp32 device buffer of the logical channel count.  Needs a plan that does not recycle ranges: the handle option
+ * "workspace_reuse" 0 (every activation kept, nothing fused across ops) or 2 (the inference plan of 1 -- its routing, fusions and skipped stores --
+ * with one range per slot: what a fused launch read and what it wrote can be read back; a tensor the fusion keeps out of HBM holds nothing). */
 int ph_model_read_slot(ph_model* m, int32_t slot, float* out_dev, int64_t out_numel, void* stream);
 
 /* ------------------------------------------------------------------------------------

@@ -181,6 +181,7 @@ SIGNATURES = {
     "ph_model_set_profiling": (C.c_int, [_vp, _i32]),
     "ph_model_profile_read": (C.c_int, [_vp, C.POINTER(C.c_double), _i32, C.POINTER(_i32)]),
     "ph_model_last_kernels": (C.c_int, [_vp, C.POINTER(_i32), _i32]),
+    "ph_model_last_rows_plans": (C.c_int, [_vp, C.POINTER(_i32), _i32]),
     "ph_model_last_ranges": (C.c_int, [_vp, C.POINTER(_i64), _i32, C.POINTER(_i32)]),
     "ph_model_set_clock_probe": (C.c_int, [_vp, _vp]),
     "ph_model_read_slot": (C.c_int, [_vp, _i32, _vp, _i64, _vp]),

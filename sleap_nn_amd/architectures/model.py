@@ -96,6 +96,7 @@ class Model:
         self._options: Dict[str, float] = {}
         self.precision = "exact"
         self.keep_activations = False
+        self._last_batch = 0  # batch of the last forward (read_slot)
         # a TrainingModule registers its device parameter arena here; after any recompile the packed weights are
         # re-gathered from it, so eval()/train() round trips never fall back to the host copy in _state
         self._live_params: Optional[torch.Tensor] = None
@@ -544,6 +545,7 @@ class Model:
         x, code = self.adapt_channels(x, code)
         x = x.contiguous()
         B, Cin, H, W = x.shape
+        self._last_batch = int(B)
         self._ensure(device)
         lib = L.lib()
         with torch.cuda.device(device):
@@ -585,6 +587,14 @@ class Model:
         arr = (C.c_int32 * n)()
         L.check(L.lib().ph_model_last_kernels(self._handle, arr, n))
         return list(arr)
+
+    def last_rows_plans(self):
+        """``(R, Wt, MT, MG)`` of each op of the LAST forward that ran ``conv3x3_f16_rows_kernel`` (``ph_model_last_rows_plans``), ``(0, 0, 0, 0)`` for an op on any other
+        kernel.  The kernel instantiation is ``(Wt % 16 == 0, MT, MG)``; the handle option ``conv_f16_rows_pin`` (``R | Wt << 8 | MG << 16``) pins the tile."""
+        n = len(self.ops)
+        arr = (C.c_int32 * (4 * n))()
+        L.check(L.lib().ph_model_last_rows_plans(self._handle, arr, n))
+        return [tuple(arr[4 * i : 4 * i + 4]) for i in range(n)]
 
     def last_ranges(self):
         """Workspace byte ranges every launch of the LAST forward was handed (``ph_model_last_ranges``), as the run-time routing
@@ -667,4 +677,14 @@ class Model:
         h, w = height_width
         out = torch.empty((batch, op.cout, h, w), dtype=torch.float32, device=self._handle_device)
         L.check(L.lib().ph_model_read_slot(self._handle, slot, C.c_void_p(out.data_ptr()), out.numel(), L.current_stream_ptr()))
+        return out
+
+    def read_slot(self, slot: int, channels: int, height_width) -> torch.Tensor:
+        """Debug/parity: NCHW copy of activation slot ``slot`` of the last forward (``ph_model_read_slot``) -- any tensor of a keep-everything plan, pool outputs and
+        up-sampled tensors included, where ``read_activation`` reaches the named convs.  The batch is the last forward's."""
+        if self.ops is self.fused_ops and not self.keep_activations and self._options.get("workspace_reuse", 1.0) == 1.0:
+            raise RuntimeError("activation slots are recycled during an inference forward: call set_keep_activations(True) before the forward")
+        h, w = height_width
+        out = torch.empty((self._last_batch, int(channels), h, w), dtype=torch.float32, device=self._handle_device)
+        L.check(L.lib().ph_model_read_slot(self._handle, int(slot), C.c_void_p(out.data_ptr()), out.numel(), L.current_stream_ptr()))
         return out

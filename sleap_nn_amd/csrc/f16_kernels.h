@@ -59,7 +59,7 @@ int prepare_f16_kernels();
 int launch_conv3x3_f16(const ConvF16Args& a, hipStream_t s);
 double f16_conv_cost(const ConvF16Args& a, int n_cu);   // estimated launch body of conv3x3_f16_persist_kernel, shader cycles
 double f16_upsample_cost(int B, int H, int W, int cp, int n_cu);  // ... of upsample2x_fmt_kernel producing the (2H, 2W) tensor from (B, H, W, cp)
-double f16_rows_plan(ConvF16Args& a, int n_cu);         // fills the rows_* plan; estimated launch body in shader cycles, < 0: the shape is not taken
+double f16_rows_plan(ConvF16Args& a, int n_cu, int pin = 0);  // fills the rows_* plan; estimated launch body in shader cycles, < 0: the shape is not taken.  pin = R | Wt << 8 | MG << 16: only that tile is considered (where no constraint refuses it; else the search)
 int launch_conv3x3_f16_rows(const ConvF16Args& a, hipStream_t s);
 int64_t f16_weight_pack_floats(int n_tiles, int chunks0, int chunks1, int bn, int plain);
 int launch_f16_weight_pack(const float* w_dma_f32, float* dst, int n_tiles, int chunks0, int chunks1, int bn, int plain, hipStream_t s);

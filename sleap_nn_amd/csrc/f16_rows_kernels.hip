@@ -521,7 +521,9 @@ bool inv20_exact(int d, int limit) {
 // Estimated launch body in shader cycles, or a negative number when the kernel does not take the shape.  The choice minimises
 //   rounds of the chip x (chunks x max(MFMA time of a chunk, loader time of a chunk) + prologue + epilogue)
 // over MG in {4 (N tile 64), 2 (N tile 128)}, the tile width (the whole row where it fits seven 16-pixel pieces, else strips) and the rows per tile.
-double f16_rows_plan(ConvF16Args& a, int n_cu) {
+// `pin` (handle option "conv_f16_rows_pin": R | Wt << 8 | MG << 16; 0 none): the one candidate looked at, under every constraint below.
+static double rows_plan_search(ConvF16Args& a, int n_cu, int pin) {
+  const int pin_r = pin & 255, pin_wt = (pin >> 8) & 255, pin_mg = (pin >> 16) & 255;
   if (a.prec != 1 || a.bn != 64 || a.coutp < 64 || (a.coutp & 31) || a.chunks0 <= 0) return -1.0;
   if (a.chunks1 > 0 && !a.src1) return -1.0;
   if (a.src1_lowres && (!a.src1 || (a.H & 1) || (a.W & 1) || a.chunks1 <= 0)) return -1.0;
@@ -533,6 +535,7 @@ double f16_rows_plan(ConvF16Args& a, int n_cu) {
   for (int MG = 4; MG >= 2; MG -= 2) {
     const int BN = 256 / MG;
     if (MG == 2 && (a.coutp % 128)) continue;
+    if (pin && MG != pin_mg) continue;
     if (a.head_w && a.coutp != BN) continue;
     const int ntc = (a.coutp + BN - 1) / BN;
     int widths[8];
@@ -540,6 +543,10 @@ double f16_rows_plan(ConvF16Args& a, int n_cu) {
     if (a.W + 2 <= 7 * 16) widths[nw++] = a.W;
     for (int wt : {96, 64, 48, 32, 16})
       if (wt < a.W) widths[nw++] = wt;
+    if (pin) {  // (a pinned width may be any value up to the map's: the kernel takes every Wt the checks below pass)
+      nw = 0;
+      if (pin_wt >= 1 && pin_wt <= a.W && pin_wt + 2 <= 7 * 16) widths[nw++] = pin_wt;
+    }
     for (int wi = 0; wi < nw; ++wi) {
       const int Wt = widths[wi];
       if (even && (Wt & 1)) continue;
@@ -547,6 +554,8 @@ double f16_rows_plan(ConvF16Args& a, int n_cu) {
       for (int R = even ? 2 : 1; R <= a.H + (even ? 1 : 0) && R <= 64; R += even ? 2 : 1) {
         const int px = R * Wt;
         int MT = (px + 16 * MG - 1) / (16 * MG);
+        if (pin && R < pin_r) continue;
+        if (pin && R > pin_r) break;
         if (MT > ((Wt & 15) ? ROWS_MT_UNALIGNED : 9)) break;
         if (MT < 3) MT = 3;
         const int NP = (R + 2) * HP16;
@@ -595,6 +604,14 @@ double f16_rows_plan(ConvF16Args& a, int n_cu) {
     }
   }
   return best;
+}
+
+double f16_rows_plan(ConvF16Args& a, int n_cu, int pin) {
+  if (pin) {
+    const double c = rows_plan_search(a, n_cu, pin);
+    if (c >= 0) return c;  // (a layer the pinned tile does not fit: the normal search)
+  }
+  return rows_plan_search(a, n_cu, 0);
 }
 
 template <int MT, int MG, bool ALIGNED>

@@ -263,7 +263,7 @@ int fwd_conv_f16(ForwardCtx& c, const PackedOp& op, int up) {
         r.src1_lowres = 1;
         r.rows_blend16 = m->upsample_f16math ? 1 : 0;
       }
-      const double c_rows = f16_rows_plan(r, n_cu);
+      const double c_rows = f16_rows_plan(r, n_cu, m->conv_f16_rows_pin);
       double c_old = f16_conv_cost(f, n_cu);
       if (up >= 0) c_old += f16_upsample_cost(c.batch, s0.h / 2, s0.w / 2, c.slot(d.src1).cp, n_cu);
       if (f.head_w && !(f.bn == 64 && f.coutp == 64))  // a head only the row-tile kernel fuses: the other way costs head1x1_mfma_kernel's launch (its bytes at ~5 TB/s + the boundary)
@@ -286,6 +286,8 @@ int fwd_conv_f16(ForwardCtx& c, const PackedOp& op, int up) {
     }
     if (on_rows) {
       c.ran(PH_KV_F16_ROWS);
+      const int32_t quad[4] = {f.rows_r, f.rows_wt, f.rows_mt, f.rows_mg};
+      std::copy(quad, quad + 4, c.m->last_rows_plan.begin() + 4 * c.op_i());
       return launch_conv3x3_f16_rows(f, c.s);
     }
     if (f.head_w && (f.bn != 64 || f.coutp != 64)) {  // (a head only the row-tile kernel fuses: leave it to its own launch)
@@ -1073,6 +1075,7 @@ extern "C" int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_d
   rc = refresh_stale_weights(m, plan, s);
   if (rc != PH_OK) return rc;
   m->last_variant.assign(m->ops.size(), PH_KV_NONE);
+  m->last_rows_plan.assign(4 * m->ops.size(), 0);
   ForwardCtx c{m, plan, fmt, 4 / plan.bpc, batch, height, width, in_channels, in_dtype, input_dev, ws, out_dev, s, m->last_variant.data(), m->last_ranges};
   c.head_done.assign(m->ops.size(), 0);
   c.conv_done.assign(m->ops.size(), 0);

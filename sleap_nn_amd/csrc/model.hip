@@ -873,6 +873,7 @@ std::vector<OptionRef> option_table(ph_model* m) {
       {"stem_f16mfma", &m->stem_f16mfma, nullptr},      // plain fp16: the fused first block with BOTH convs on the fp16 matrix pipe (stem_f16_kernel) instead of stem_fused_kernel<CIN, 3>
       {"upsample_f16math", &m->upsample_f16math, nullptr},  // a bilinear x2 folded into conv3x3_f16_rows_kernel blends in packed fp16 arithmetic (1) or in fp32 as upsample2x_fmt_kernel does (0)
       {"conv_f16_rows", &m->conv_f16_rows, nullptr},    // plain-fp16 precision: conv3x3_f16_rows_kernel 0 never, 1 where its plan is estimated faster than conv3x3_f16_persist_kernel, 2 wherever the shape fits
+      {"conv_f16_rows_pin", &m->conv_f16_rows_pin, nullptr},  // tests: the one (R, Wt, MG) tile f16_rows_plan considers, packed R | Wt << 8 | MG << 16 (0: the search)
       {"conv_smallmap", &m->conv_smallmap, nullptr},    // conv3x3_sm_kernel for small maps at small batches: 0 never, 1 where estimated faster (inference plans, conv_splitk = 1), 2 wherever the shape fits
       {"conv_splitk", &m->conv_splitk, nullptr},        // split K on the F(2x2,3x3) kernel for layers with fewer work units than CUs: 0 never, 1 where estimated faster, n >= 2 force n slices
       {"upsample_fold", &m->upsample_fold, nullptr},    // bilinear x2 folded into the F(4x4,3x3) input transform of the conv that consumes it
@@ -891,7 +892,7 @@ std::vector<OptionRef> option_table(ph_model* m) {
       {"mask_fold", &m->mask_fold, nullptr},            // ReLU mask applied by the pool backward that completes a conv output's gradient
       {"wgrad_wino", &m->wgrad_wino, nullptr},          // 3x3 weight gradients: 1 Winograd F(2x2,3x3) domain, 0 direct nine-tap kernel
       {"wgrad_rows", &m->wgrad_rows, nullptr},          // 0 32x32-tile wgrad kernel, 1 auto, 2 nine row-wgrad GEMMs
-      {"workspace_reuse", &m->workspace_reuse, nullptr},  // 1: activation slots share memory once their last reader has run (inference programs only)
+      {"workspace_reuse", &m->workspace_reuse, nullptr},  // 1: activation slots share memory once their last reader has run (inference programs only); 2: that plan's routing and fusions, every slot in its own range (tests: ph_model_read_slot across a fused launch)
       {"convt_one_launch", &m->convt_one_launch, nullptr},  // 1: the four output-phase GEMMs of a transposed conv in one launch (grid.y = phase); 0: four launches
       {"convt_phase", &m->convt_phase, nullptr},        // 0: transposed convs by zero-stuffing + 3x3 conv (4x the FLOPs; A/B reference)
       {"convnext_f16", &m->convnext_f16, nullptr},      // 1: under conv_precision 2 a ConvNeXt program runs whole in plain fp16 (0: exact fp32 whatever the precision)
@@ -971,6 +972,13 @@ int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops) {
   return PH_OK;
 }
 
+int ph_model_last_rows_plans(const ph_model* m, int32_t* quad, int32_t n_ops) {
+  PH_REQUIRE(m && quad, "ph_model_last_rows_plans: null argument");
+  PH_REQUIRE(n_ops == (int32_t)m->ops.size(), "ph_model_last_rows_plans: model has %d ops", (int)m->ops.size());
+  for (int i = 0; i < 4 * n_ops; ++i) quad[i] = i < (int)m->last_rows_plan.size() ? m->last_rows_plan[i] : 0;
+  return PH_OK;
+}
+
 int ph_model_last_ranges(const ph_model* m, int64_t* rows, int32_t max_rows, int32_t* n_rows) {
   PH_REQUIRE(m && n_rows && max_rows >= 0 && (rows || max_rows == 0), "ph_model_last_ranges: bad arguments");
   *n_rows = (int32_t)m->last_ranges.size();
@@ -995,7 +1003,7 @@ int ph_model_set_clock_probe(ph_model* m, void* buf_dev) {
 int ph_model_read_slot(ph_model* m, int32_t slot, float* out_dev, int64_t out_numel, void* stream) {
   PH_REQUIRE(m && out_dev && m->last_ws, "ph_model_read_slot: no forward has run");
   PH_REQUIRE(slot >= 0 && slot < m->n_slots && m->last_plan.slots[slot].offset >= 0, "bad slot %d", slot);
-  PH_REQUIRE(!m->last_plan.reuse, "activations are recycled in this plan: set the handle option workspace_reuse to 0 before the forward to read a slot back");
+  PH_REQUIRE(!m->last_plan.recycle, "activations are recycled in this plan: set the handle option workspace_reuse to 0 (or 2) before the forward to read a slot back");
   const SlotShape& s = m->last_plan.slots[slot];
   PH_REQUIRE(out_numel == (int64_t)m->last_batch * s.c * s.h * s.w, "slot %d has %d x %d x %d x %d elements", slot, m->last_batch, s.c, s.h, s.w);
   if (m->last_plan.fmt != FMT_F32)

@@ -106,6 +106,7 @@ struct Plan {
   std::vector<SlotShape> slots;
   int64_t tmp_offset = 0, tmp_bytes = 0, total = 0;
   bool reuse = false;  // slots share memory by lifetime (handle option workspace_reuse)
+  bool recycle = false;  // ... and their ranges really are handed on (workspace_reuse 1).  reuse without recycle (workspace_reuse 2): the inference plan's routing and fusions with every slot in a range of its own, so that ph_model_read_slot can read what the fused launches read and wrote
   std::vector<char> unread;  // reuse plans: slot has no reader in the program (a fused conv+pool's full-resolution output the decoder never taps)
   int fmt = FMT_F32;  // activation format of every slot (act_format.h)
   int bpc = 4;        // bytes per channel in that format
@@ -129,6 +130,7 @@ struct ph_model {
   char* last_ws = nullptr;
   int last_batch = 0;
   std::vector<int> last_variant;  // PH_KV_* code of the kernel each op of the last forward ran (ph_model_last_kernels)
+  std::vector<int32_t> last_rows_plan;    // (R, Wt, MT, MG) of each op of the last forward that ran conv3x3_f16_rows_kernel, zeros elsewhere; written where fwd_conv_f16 decides (ph_model_last_rows_plans)
   std::vector<ph::RangeRec> last_ranges;  // workspace ranges each launch of the last forward read / wrote (ph_model_last_ranges)
   std::vector<hipEvent_t> bwd_ev;         // profiling on: [0] before the losses, [1 + 2 (n - 1 - i)] before op i's step of the reverse sweep, [2 + 2 (n - 1 - i)] between its weight- and data-gradient
                                           // launches (Linear ops; elsewhere recorded at once), [2 n + 1] after the sweep (ph_model_backward_profile_read)
@@ -180,6 +182,7 @@ struct ph_model {
   int stem_f16mfma = 1;                       // "stem_f16mfma"
   int upsample_f16math = 1;                   // "upsample_f16math"
   int conv_f16_rows = 1;                      // "conv_f16_rows" (plain fp16: the row-tile kernel of f16_rows_kernels.hip; 1 where estimated faster, 2 wherever it fits, 0 never)
+  int conv_f16_rows_pin = 0;                  // "conv_f16_rows_pin": R | Wt << 8 | MG << 16 -- f16_rows_plan considers only that tile (still under every constraint of the search; a layer it does not fit gets the normal search); 0 (default): the search
   int conv_smallmap = 1;                      // "conv_smallmap" (1: inference plans with conv_splitk = 1 (the automatic small-batch routing), where estimated faster; 2: every fp32 3x3 conv whose shape fits, any plan; 0: never): conv3x3_sm_kernel
   int conv_splitk = 1;                        // "conv_splitk" (1: where estimated faster, inference plans only; n >= 2: force n slices in every plan; 0: never): F(2x2,3x3) layers with fewer (pixel tile, N tile) units than half the CUs split K over workgroups + a fixed-order second stage (small batches); n >= 2 forces n slices, 0 never
   int upsample_fold = 1;                      // "upsample_fold": a bilinear x2 whose only reader is the next conv's second source is folded into that conv's F(4x4,3x3) input transform (inference plans)
@@ -201,7 +204,7 @@ struct ph_model {
   double gemm_fill_threshold_wino2d = 0.4;    // ... and when it is the F(2x2,3x3) kernel (fill counted on its 16x16-pixel tiles)
   double gemm_fill_threshold_wino = 0.5;      // ... and the (lower) break-even when the halo kernel is the Winograd one
   double gemm_fill_threshold = 0.8;           // 3x3 convs whose maps fill the 16x32 tiles less than this run as row GEMMs
-  int workspace_reuse = 0;                    // "workspace_reuse": 1 = slots of an inference program share memory by lifetime (no read-back, no backward)
+  int workspace_reuse = 0;                    // "workspace_reuse": 1 = slots of an inference program share memory by lifetime (no read-back, no backward); 2 = the same plan (routing, fusions, stores skipped) with a range per slot: the slots a launch really wrote can be read back, a tensor a fusion keeps out of HBM holds nothing
   int convt_one_launch = 1;                   // "convt_one_launch": the four output-phase GEMMs of a transposed conv as ONE launch (grid.y = phase) instead of four (four launch floors at small batches)
   int convt_phase = 1;                        // "convt_phase": transposed convs as four phase GEMMs (0: zero-stuffing + 3x3 conv, 4x the FLOPs; A/B)
   int swint_f16 = 0;                          // "swint_f16": 1 = a Swin program under conv_precision 2 runs whole on fp16 activations (swin_f16_kernels.hip + the fp16 row GEMM / LayerNorm); 0 (default) = exact fp32

@@ -160,6 +160,7 @@ int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
   // written where an older tensor has just left the caches.
   const bool reuse = m->workspace_reuse != 0;
   plan.reuse = reuse;
+  plan.recycle = reuse && m->workspace_reuse != 2;
   const int n_ops = (int)m->ops.size();
   std::vector<int> last_use(m->n_slots, -1);
   std::vector<int64_t> slot_bytes(m->n_slots, 0);
@@ -230,7 +231,7 @@ int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
     // is safe; ph_model_forward refuses the fusion for any other overlap.)
     const bool forwarded = op_i > 0 && (((d.kind == PH_OP_POOL || d.kind == PH_OP_GELU || d.kind == PH_OP_LAYERNORM || d.kind == PH_OP_SCALE_ADD) && d.src0 >= 0 && d.src0 == m->ops[op_i - 1].d.dst) ||
                                         fuses_block2(m, (size_t)op_i - 1, fmt, reuse));
-    if (reuse && !forwarded)  // slots whose last reader ran before this op (a slot nobody reads is released right after the op that wrote it)
+    if (plan.recycle && !forwarded)  // slots whose last reader ran before this op (a slot nobody reads is released right after the op that wrote it)
       for (int sl = 0; sl < m->n_slots; ++sl)
         if (!released[sl] && plan.slots[sl].offset >= 0 && slot_bytes[sl] > 0 && std::max(last_use[sl], plan.slots[sl].def_op) < op_i) release(sl);
     int h, w;
