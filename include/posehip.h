@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 126
+#define PH_VERSION 127
 
 /* error codes */
 #define PH_OK 0
@@ -342,6 +342,12 @@ int ph_render_seg_targets(const uint8_t* masks_dev, const int32_t* n_instances_d
  * under handle option conv_splitk = splitk (padded channel counts; section 4.1d of DESIGN.md).  out[0] = K slices on the F(2x2,3x3) kernel, out[1] = on the
  * F(4x4,3x3) kernel (1 = no split), out[2], out[3] = KiB of partial-sum scratch each would need (0 when it does not split). */
 int ph_debug_split_plan(int32_t B, int32_t H, int32_t W, int32_t cin_padded, int32_t cout_padded, int32_t splitk, int32_t n_cu, int64_t* out4);
+
+/* Diagnostic / test hook: every device allocation the handle owns, in the order it was made (ph_model_create's packed weights, gather maps and derived forms,
+ * then whatever later calls added: the lazy fp16 packs of the first fp16 forward, the tables of the first ph_model_set_params).  *n_rows = the number of
+ * allocations; the first min(max_rows, *n_rows) rows of ptrs[] / bytes[] are filled with the device pointer and the size of the allocation as the runtime
+ * reports it (max_rows = 0 only counts).  The pointers stay the handle's: read them, never free or write them. */
+int ph_model_debug_allocs(const ph_model* m, void** ptrs, int64_t* bytes, int32_t max_rows, int32_t* n_rows);
 
 /* Diagnostic (tools/gemm_bench.py): average milliseconds of one row-GEMM kernel variant on synthetic operands. */
 int ph_debug_gemm_bench(int32_t variant, int32_t M, int32_t K, int32_t N, int32_t mode, int32_t H, int32_t W,

@@ -607,6 +607,28 @@ class Model:
         L.check(L.lib().ph_model_last_ranges(self._handle, arr, n.value, C.byref(n)))
         return [(int(arr[6 * i]), int(arr[6 * i + 1]), bool(arr[6 * i + 2]), int(arr[6 * i + 3]), int(arr[6 * i + 4]), int(arr[6 * i + 5])) for i in range(n.value)]
 
+    def debug_allocs(self, read_first: int = 0):
+        """Every device allocation the handle owns, in the order it was made (``ph_model_debug_allocs``): a list of ``(pointer, bytes)``.  With
+        ``read_first = n`` the list is cut to the first ``n`` allocations and each entry is a host ``uint8`` tensor of the allocation's bytes instead
+        (the device is synchronised first)."""
+        lib = L.lib()
+        n = C.c_int32()
+        L.check(lib.ph_model_debug_allocs(self._handle, None, None, 0, C.byref(n)))
+        ptrs, sizes = (C.c_void_p * max(1, n.value))(), (C.c_int64 * max(1, n.value))()
+        L.check(lib.ph_model_debug_allocs(self._handle, ptrs, sizes, n.value, C.byref(n)))
+        rows = [(int(ptrs[i] or 0), int(sizes[i])) for i in range(n.value)]
+        if not read_first:
+            return rows
+        torch.cuda.synchronize()
+        out = []
+        for ptr, size in rows[:read_first]:
+            host = torch.empty(size, dtype=torch.uint8)
+            rc = lib.hipMemcpy(C.c_void_p(host.data_ptr()), C.c_void_p(ptr), C.c_size_t(size), 2)  # (hipMemcpyDeviceToHost; the runtime libposehip is linked against)
+            if rc != 0:
+                raise RuntimeError(f"hipMemcpy of allocation {len(out)} ({size} bytes) failed with {rc}")
+            out.append(host)
+        return out
+
     def op_table(self, batch: int, height: int, width: int):
         """Per op: label, kind, algorithmic FLOPs (2*Cin*Cout*k*k*Hout*Wout*B for convolutions, SURVEY
         section 8d) and algorithmic HBM bytes (input read once + output written once, logical channels)."""

@@ -50,7 +50,7 @@ struct GemmF16Args {
   int gelu = 0;                     // erf-GELU in fp32 on acc + bias
 };
 int launch_gemm_f16(const GemmF16Args& a, hipStream_t s);
-// fp16 weight image of a Linear (taps 1) / Conv2d k2 s2 (taps 4) from the fp32 row-GEMM pack (model.hip: pack_gemm with N tile bn):
+// fp16 weight image of a Linear (taps 1) / Conv2d k2 s2 (taps 4) from the fp32 row-GEMM pack (weights.hip: pack_gemm with N tile bn):
 // [32-row block of cout][K step of 16][lane][8 halves] = the A fragment of one MFMA, K = taps x cinp
 int64_t gemm_f16_weight_image_halves(int coutp, int cinp, int taps);
 int launch_gemm_f16_weight_image(const float* wpack, void* dst, int cout, int cin, int coutp, int cinp, int taps, int bn, hipStream_t s);

@@ -484,7 +484,7 @@ int launch_gemm_f16(const GemmF16Args& a, hipStream_t s) {
   return PH_OK;
 }
 
-// fp32 row-GEMM pack (model.hip: pack_gemm; [n tile of bn][stage = 32-channel slice x taps, taps innermost][piece = n / 8][slot = channel quad ^
+// fp32 row-GEMM pack (weights.hip: pack_gemm; [n tile of bn][stage = 32-channel slice x taps, taps innermost][piece = n / 8][slot = channel quad ^
 // (piece & 1)][row n % 8][4], zero-padded) -> the fp16 image of gemm_f16_kernel.  One thread = one lane's 8 halves of one K step.
 __global__ __launch_bounds__(256) void gemm_f16_weight_image_kernel(const float* __restrict__ wpack, f16x8* __restrict__ dst, int cout, int cin, int coutp, int cinp, int taps, int bn) {
   const int kpt = cinp >> 4, ksteps = taps * kpt;

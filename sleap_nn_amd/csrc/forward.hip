@@ -1023,27 +1023,6 @@ int fwd_op(ForwardCtx& c, const PackedOp& op) {
   }
 }
 
-// The inference-only weight forms ph_model_set_params left stale on a handle that was training: derive them before the first forward that reads them
-int refresh_stale_weights(ph_model* m, const Plan& plan, hipStream_t s) {
-  if (m->wino4_stale && (m->conv_wino4 >= 2 || (m->conv_wino4 == 1 && plan.reuse) || m->conv_smallmap >= 2 || (m->conv_smallmap == 1 && plan.reuse))) {  // (F(4x4,3x3), small-map)
-    for (const DerivedBuffer& db : m->derived)
-      if (db.kind == DERIVED_WINO4 || db.kind == DERIVED_SMALLMAP) {
-        int rc = db.kind == DERIVED_WINO4 ? launch_wino4_pack(db.src, db.dst, db.panels, db.bn, s) : launch_sm_pack(db.src, db.dst, db.panels, db.bn, db.n_tiles, s);
-        if (rc != PH_OK) return rc;
-      }
-    m->wino4_stale = false;
-  }
-  if (m->cnx_f16_stale && plan.fmt == FMT_F16) {  // (the fp16 row-GEMM images)
-    for (const DerivedBuffer& db : m->derived)
-      if (db.kind == DERIVED_GEMM_F16_IMAGE) {
-        int rc = launch_gemm_f16_weight_image(db.src, db.dst, db.panels, db.n_tiles, fmt_cpad(FMT_F16, db.panels), fmt_cpad(FMT_F16, db.n_tiles), db.chunks0, db.bn, s);
-        if (rc != PH_OK) return rc;
-      }
-    m->cnx_f16_stale = false;
-  }
-  return PH_OK;
-}
-
 }  // namespace
 
 extern "C" int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_dtype, int32_t batch, int32_t in_channels, int32_t height, int32_t width, void* workspace_dev,

@@ -1,4 +1,4 @@
-// Internal structures of the network runtime shared by model.hip (handle, weight forms), plan.hip (workspace plan), forward.hip (forward), backward.hip (backward) and
+// Internal structures of the network runtime shared by model.hip (handle, options, accessors), weights.hip (weight forms, ph_model_create), plan.hip (workspace plan), forward.hip (forward), backward.hip (backward) and
 // train.hip (parameter arena, bucket split, branch scales, head losses).
 #pragma once
 #include <string>
@@ -35,7 +35,7 @@ struct PackedOp {
   float* wdk_gemm_dev[2] = {nullptr, nullptr};  // k x k conv (k != 3): data-gradient weights (flipped taps, in/out swapped) in the row-GEMM layout, per concat source
   int bn_dk[2] = {0, 0};
   int bn_d[2] = {0, 0};
-  float* w_wino_dev = nullptr;             // 3x3 conv, N tile 64: Winograd F(2,3) weights derived on the device from w_dev
+  float* w_wino_dev = nullptr;             // 3x3 conv, N tile 32 or 64 (fused stem: its second conv): Winograd F(2,3) weights derived on the device from w_dev
   float* wd_wino_dev[2] = {nullptr, nullptr};  // ... and from wd_dev (data gradient)
   float* w_stem2_dev = nullptr;            // fused stem: F(2x2,3x3) weights of the second conv
   float* w_w16_dev = nullptr;              // 3x3 conv, Cout 16 / 32, Cin 16 / 32: wave-private F(2x2,3x3) weights derived from w_dev
@@ -45,7 +45,7 @@ struct PackedOp {
   float* w_n64_dev = nullptr;              // 3x3 conv with 32 output channels and >= 64 input channels: the weights packed once more for an N tile of 64 (upper half zeros) ...
   float* b_n64_dev = nullptr;              // ... with a 64-entry bias, so that the layer can run on the F(2x2,3x3) kernel's half-empty-N-tile form (w_wino2_dev is derived from w_n64_dev)
   float* w_sm_dev = nullptr;               // 3x3 conv: small-map F(2x2,3x3) weights derived from w_dev (conv3x3_sm_kernel)
-  float* w_wino4_dev = nullptr;            // 3x3 conv, N tile 64, >= 128 padded input channels: Winograd F(4x4,3x3) weights derived from w_dev
+  float* w_wino4_dev = nullptr;            // 3x3 conv, N tile 64, >= 64 padded input channels: Winograd F(4x4,3x3) weights derived from w_dev (w_n64_dev where that exists)
   float* wd_wino4_dev[2] = {nullptr, nullptr};  // ... and from wd_dev (data gradient: Cout input channels)
   // ConvTranspose2d(k3, s2, p1, op1) as four output-phase row GEMMs (mode 3) + its data gradient (mode 4)
   float* wt_phase_dev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -68,25 +68,35 @@ struct PackedBuffer {
   size_t n = 0;
 };
 
-// What a DerivedBuffer holds, i.e. which launch recomputes it from src (ph_model_set_params; the inference-only forms lazily, in ph_model_forward)
+// The forms derived on the device from a packed buffer (not pure gathers of parameters: Winograd transforms, fp16 images).  What each kind is -- its size, the launch
+// that computes it, the meaning of DerivedBuffer::p[] -- stands once, in the table of weights.hip.
 enum DerivedKind {
-  DERIVED_WINO = 0,            // Winograd F(2,3) transform of src (launch_wino_pack); bn == 0: the fused stem's second conv (launch_stem_wino_pack)
-  DERIVED_F16_PACK = 1,        // fp16 weight pack of the LDS-DMA panels (launch_f16_weight_pack: n_tiles, chunks0, chunks1, plain)
-  DERIVED_WINO2D = 2,          // F(2x2,3x3) transform (launch_wino2d_pack)
-  DERIVED_W16 = 3,             // wave-private F(2x2,3x3) transform (launch_w16_pack: panels = chunks, bn = N blocks of 16)
-  DERIVED_STEM_WINO2D = 4,     // the fused stem's F(2x2,3x3) transform (launch_stem_wino2d_pack)
-  DERIVED_WINO4 = 5,           // F(4x4,3x3) transform (launch_wino4_pack: panels = padded output channels, bn = 16-channel chunks); inference plans only
-  DERIVED_SMALLMAP = 6,        // small-map F(2x2,3x3) transform (launch_sm_pack: panels = N blocks of 16, bn = 16-channel chunks, n_tiles = the source packing's N tile); inference plans only
-  DERIVED_GEMM_F16_IMAGE = 7,  // fp16 row-GEMM weight image of a Linear / 2x2-stride-2 conv (launch_gemm_f16_weight_image: panels = cout, n_tiles = cin, chunks0 = taps, bn = the source packing's N tile)
+  DERIVED_WINO = 0,            // Winograd F(2,3) transform of a 3x3 conv's packing
+  DERIVED_F16_PACK = 1,        // fp16 weight pack of the LDS-DMA panels
+  DERIVED_WINO2D = 2,          // F(2x2,3x3) transform
+  DERIVED_W16 = 3,             // wave-private F(2x2,3x3) transform
+  DERIVED_STEM_WINO2D = 4,     // the fused stem's second conv: F(2x2,3x3) transform
+  DERIVED_WINO4 = 5,           // F(4x4,3x3) transform
+  DERIVED_SMALLMAP = 6,        // small-map F(2x2,3x3) transform
+  DERIVED_GEMM_F16_IMAGE = 7,  // fp16 row-GEMM weight image of a Linear / 2x2-stride-2 conv
+  DERIVED_STEM_WINO = 8,       // the fused stem's second conv: F(2,3) transform
+  DERIVED_KINDS
 };
 
-// A buffer computed on the device from a packed buffer (not a pure gather of parameters): Winograd conv weights.
+// Who reads a derived form, i.e. when ph_model_set_params recomputes it (reads_forms in weights.hip is the rule)
+enum RefreshClass {
+  REFRESH_ALWAYS = 0,  // every ph_model_set_params, a launch of its own
+  REFRESH_BATCHED,     // every ph_model_set_params, as a segment of the kind's one multi-buffer launch
+  REFRESH_INFERENCE,   // only while the handle's options let a plan read it (F(4x4,3x3), small-map: inference plans); else left stale
+  REFRESH_F16_GEMM,    // only on a Linear program's plain-fp16 pipe (convnext_f16 / swint_f16); else left stale
+  REFRESH_CLASSES
+};
+
 struct DerivedBuffer {
   const float* src = nullptr;
   float* dst = nullptr;
-  int panels = 0, bn = 0;
   DerivedKind kind = DERIVED_WINO;
-  int n_tiles = 0, chunks0 = 0, chunks1 = 0, plain = 0;  // DERIVED_F16_PACK (n_tiles, chunks0: also DERIVED_SMALLMAP / DERIVED_GEMM_F16_IMAGE, as listed above)
+  int p[5] = {0, 0, 0, 0, 0};  // the kind's parameters, in the order its table entry names them
 };
 
 struct SlotShape {
@@ -161,8 +171,7 @@ struct ph_model {
   std::vector<int64_t> weight_offset;          // canonical arena offset of weights[i] (ph_model_create order)
   std::vector<int64_t> weight_numel;
   int64_t n_params = 0;
-  bool wino4_stale = false;                    // ph_model_set_params skipped the F(4x4,3x3) weights (training handle): refresh before their next use
-  bool cnx_f16_stale = false;                  // ph_model_set_params skipped the fp16 row-GEMM weight images (conv_precision != 2): refresh before their next use
+  bool forms_stale[ph::REFRESH_CLASSES] = {};  // ph_model_set_params skipped the derived forms of this class (nothing the handle's options allow reads them): refresh_stale_weights derives them before their next use
   std::vector<ph::DerivedBuffer> derived;      // refreshed after the gathers of ph_model_set_params
   std::vector<ph::PackedBuffer> packed;        // every packed weight buffer, for ph_model_set_params
   // ---- per-handle options (ph_model_set_option); the library reads no environment variables
@@ -218,7 +227,7 @@ struct ph_model {
 
 namespace ph {
 int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt = FMT_F32);
-int forward_format(const ph_model* m);
+int forward_format(const ph_model* m);  // format the forward of this program runs in under the handle's conv_precision
 int drain_events(ph_model* m);  // profiling: fold the events of the last forward into op_ms
 bool has_other_reader(const ph_model* m, int slot, size_t except_op);  // an op other than `except_op` reads `slot`
 int bucket_split_op(const ph_model* m, int64_t* offset_out);  // train.hip: the op whose backward step makes the arena tail [*offset_out, n_params) final; -1 = no clean split
@@ -234,10 +243,10 @@ bool fuses_pool(const ph_model* m, size_t i);                         // pool pe
 bool fuses_layernorm(const ph_model* m, size_t i, bool reuse);        // the LayerNorm behind a patch stem / depthwise conv rides in that kernel
 bool defers_upsample_f32(const ph_model* m, size_t i, const Plan& plan);  // a bilinear x2 left to the fp32 conv behind it
 bool defers_upsample_f16(const ph_model* m, size_t i, const Plan& plan);  // ... to the fp16 row-tile conv behind it
-int ensure_f16_weights(ph_model* m, int plain, hipStream_t s);  // format the forward of this program runs in under the handle's conv_precision
-int upload(ph_model* m, const std::vector<float>& host, float** dev);
-int upload_ints(ph_model* m, const std::vector<int>& host, int** dev);
-int choose_bn(int coutp);
+// weights.hip
+int ensure_f16_weights(ph_model* m, int plain, hipStream_t s);                      // the lazy fp16 packs of the 3x3 convs ([plain] = 0 split, 1 plain fp16), derived at the first forward that needs them
+int refresh_stale_weights(ph_model* m, const Plan& plan, hipStream_t s);            // the forms ph_model_set_params left stale, before the first forward that reads them
+int refresh_derived(ph_model* m, const float* params_flat_dev, hipStream_t s);      // the derived-form half of ph_model_set_params (+ the GRN bias fold)
 void apply_conv_options(const ph_model* m, ConvArgs& a);
 // Whether head op `d` applies its sigmoid epilogue in `plan`.  A head whose loss is PH_LOSS_BCE_DICE emits LOGITS in the plans a backward can follow
 // (exact fp32, every activation kept): the loss kernel supervises the logit, as the reference's training_step does (lightning_modules.py:3052-3075).

@@ -235,7 +235,7 @@ int launch_grn_scale_weights(const float* wpack, const float* scale, float* dst,
 // CNBlock's MLP in one launch (cnblock_mlp_kernels.hip): dst = residual + scale * (W2 gelu(W1 x + b1) + b2) over (M, C) rows
 struct MlpArgs {
   const float* x = nullptr;         // (M, C): the LayerNorm output
-  const float* w1img = nullptr;     // Linear(C, 4C) weight as [hidden block][C / 8 pieces of [lane][4]] (model.hip: pack_mlp_w1)
+  const float* w1img = nullptr;     // Linear(C, 4C) weight as [hidden block][C / 8 pieces of [lane][4]] (weights.hip: pack_mlp_w1)
   const float* w2img = nullptr;     // Linear(4C, C) weight as [hidden block][C / 8 pieces of [lane][4]] in the K order of the chained product (pack_mlp_w2)
   const float* b1 = nullptr;        // >= 4C
   const float* b2 = nullptr;        // >= C

@@ -76,74 +76,7 @@ int ph_model_set_params(ph_model* m, const float* params_flat_dev, void* stream)
     int rc = launch_gather_multi(params_flat_dev, static_cast<const GatherSegment*>(m->gather_table_dev), m->gather_segments, m->gather_blocks, static_cast<hipStream_t>(stream));
     if (rc != PH_OK) return rc;
   }
-  // derived buffers: the F(2,3) and F(2x2,3x3) transforms (most of them) each go in ONE table-driven launch, the rest one by one
-  if (!m->pack_tables_built) {
-    for (int kind = 0; kind < 2; ++kind) {
-      std::vector<PackSegment> seg;
-      unsigned blocks = 0;
-      for (const DerivedBuffer& db : m->derived) {
-        const bool mine = kind == 0 ? (db.kind == DERIVED_WINO && db.bn != 0) : db.kind == DERIVED_WINO2D;
-        if (!mine) continue;
-        const unsigned long long total = (unsigned long long)(kind == 0 ? wino_pack_floats(db.panels, db.bn) : wino2d_pack_floats(db.panels, db.bn));
-        if (total == 0) continue;
-        seg.push_back(PackSegment{db.src, db.dst, total, db.bn, blocks});
-        blocks += (unsigned)((total + 1023) / 1024);
-      }
-      void* t = nullptr;
-      if (!seg.empty()) {
-        PH_HIP_CHECK(hipMalloc(&t, seg.size() * sizeof(PackSegment)));
-        m->allocs.push_back(t);
-        PH_HIP_CHECK(hipMemcpy(t, seg.data(), seg.size() * sizeof(PackSegment), hipMemcpyHostToDevice));
-      }
-      m->pack_table_dev[kind] = t;
-      m->pack_segments[kind] = (int)seg.size();
-      m->pack_blocks[kind] = blocks;
-    }
-    m->pack_tables_built = true;
-  }
-  {
-    int rc = launch_wino_pack_multi(static_cast<const PackSegment*>(m->pack_table_dev[0]), m->pack_segments[0], m->pack_blocks[0], static_cast<hipStream_t>(stream));
-    if (rc == PH_OK) rc = launch_wino2d_pack_multi(static_cast<const PackSegment*>(m->pack_table_dev[1]), m->pack_segments[1], m->pack_blocks[1], static_cast<hipStream_t>(stream));
-    if (rc != PH_OK) return rc;
-  }
-  for (const DerivedBuffer& db : m->derived) {
-    if ((db.kind == DERIVED_WINO && db.bn != 0) || db.kind == DERIVED_WINO2D) continue;  // in the two launches above
-    if (db.kind == DERIVED_WINO4 || db.kind == DERIVED_SMALLMAP) {  // F(4x4,3x3) / small-map weights: only inference plans read them (conv_wino4 = conv_smallmap = 1) -- a training step does not pay for the re-derivation,
-      if ((db.kind == DERIVED_WINO4 ? m->conv_wino4 : m->conv_smallmap) < 2 && !m->workspace_reuse) {  // the next forward that wants them refreshes them (ph_model_forward)
-        m->wino4_stale = true;
-        continue;
-      }
-      const int rc5 = db.kind == DERIVED_WINO4 ? launch_wino4_pack(db.src, db.dst, db.panels, db.bn, static_cast<hipStream_t>(stream)) : launch_sm_pack(db.src, db.dst, db.panels, db.bn, db.n_tiles, static_cast<hipStream_t>(stream));
-      if (rc5 != PH_OK) return rc5;
-      continue;
-    }
-    if (db.kind == DERIVED_GEMM_F16_IMAGE) {  // fp16 row-GEMM images: only a plain-fp16 forward reads them -- a training step does not pay for them, the next such forward refreshes them (ph_model_forward)
-      if (m->conv_precision != 2 || !(m->convnext_f16 || m->swint_f16)) {
-        m->cnx_f16_stale = true;
-        continue;
-      }
-      const int rc7 = launch_gemm_f16_weight_image(db.src, db.dst, db.panels, db.n_tiles, fmt_cpad(FMT_F16, db.panels), fmt_cpad(FMT_F16, db.n_tiles), db.chunks0, db.bn, static_cast<hipStream_t>(stream));
-      if (rc7 != PH_OK) return rc7;
-      continue;
-    }
-    int rc = db.kind == DERIVED_F16_PACK ? launch_f16_weight_pack(db.src, db.dst, db.n_tiles, db.chunks0, db.chunks1, db.bn, db.plain, static_cast<hipStream_t>(stream))
-             : db.kind == DERIVED_W16 ? launch_w16_pack(db.src, db.dst, db.panels, db.bn, static_cast<hipStream_t>(stream))
-             : db.kind == DERIVED_STEM_WINO2D ? launch_stem_wino2d_pack(db.src, db.dst, static_cast<hipStream_t>(stream))
-                            : launch_stem_wino_pack(db.src, db.dst, static_cast<hipStream_t>(stream));
-    if (rc != PH_OK) return rc;
-  }
-  // fused GRN plan ("grn_fuse"): the constant term W2 grn.bias + b2 of a residual Linear behind a GRN op follows the parameters.  Only a program whose first Linear
-  // carries the GELU can take that plan (fuses_grn), so an unfused (training) program never pays for this
-  for (size_t i = 2; i < m->ops.size(); ++i) {
-    const PackedOp& op = m->ops[i];
-    const ph_op_desc& g = m->ops[i - 1].d;
-    const ph_op_desc& l1 = m->ops[i - 2].d;
-    if (!op.b_grn_dev || g.kind != PH_OP_GRN || !(l1.kind == PH_OP_LINEAR && l1.flags == PH_FLAG_GELU)) continue;
-    int rc = launch_grn_fold_bias(params_flat_dev + m->weight_offset[op.d.weight], params_flat_dev + m->weight_offset[op.d.bias], params_flat_dev + m->weight_offset[g.bias], op.b_grn_dev,
-                                  op.d.cout, op.d.cin0, static_cast<hipStream_t>(stream));
-    if (rc != PH_OK) return rc;
-  }
-  return PH_OK;
+  return refresh_derived(m, params_flat_dev, static_cast<hipStream_t>(stream));  // (weights.hip: the derived forms follow the packed buffers they are computed from)
 }
 
 int64_t ph_model_grad_bucket_split(const ph_model* m) {
