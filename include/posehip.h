@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 127
+#define PH_VERSION 128
 
 /* error codes */
 #define PH_OK 0
@@ -97,6 +97,7 @@ enum ph_op_kind {
   PH_OP_LINEAR = 11,    /* per-pixel Linear(cin0 -> cout), weight (cout, cin0) + bias; PH_FLAG_GELU: erf-GELU
                            epilogue (block[3..4]); PH_FLAG_SCALE_RESIDUAL: dst = weight2[c] * (acc + bias) +
                            src1 (block[5], layer_scale, residual add); PH_FLAG_RESIDUAL: dst = acc + bias + src1;
+                           PH_FLAG_RESIDUAL | PH_FLAG_RELU: dst = relu(acc + bias + src1) (the tail of a ResNet bottleneck);
                            bias = -1: Linear(bias=False)                                                 */
   PH_OP_PATCH_CONV = 12, /* Conv2d(k2, s2) + bias, weight (cout, cin0, 2, 2)  (convnext.py:101-110)     */
   /* the two epilogues of PH_OP_LINEAR as ops of their own: the training program keeps the
@@ -119,12 +120,20 @@ enum ph_op_kind {
   /* ConvNeXtV2 encoder (HuggingFace ConvNextV2Backbone behind the reference's PretrainedBackbone, architectures/pretrained.py).  Exact fp32.  Its two ops of its own
      (PH_OP_GRN, the PH_FLAG_PAD0_NORM stem) carry PH_FLAG_NO_TRAIN: ph_model_backward runs their steps on a handle whose option pretrained_train is 1
      (convnextv2_train_kernels.hip; the stem's weight gradient is the patch stem's im2col + row-wgrad GEMM over normalised patches) and refuses the program otherwise. */
-  PH_OP_GRN = 18          /* Global Response Normalization over a (B, H, W, C) slot (cin0 = cout = C): G[b,c] = sqrt(sum_hw x^2), N[b,c] = G[b,c] / (mean_c G[b,:] + 1e-6),
+  PH_OP_GRN = 18,         /* Global Response Normalization over a (B, H, W, C) slot (cin0 = cout = C): G[b,c] = sqrt(sum_hw x^2), N[b,c] = G[b,c] / (mean_c G[b,:] + 1e-6),
                              dst = weight[c] * (x * N[b,c]) + bias[c] + x; weight / bias (1,1,1,C).  Two launches (convnextv2_kernels.hip): grn_reduce_kernel writes
                              per-(sample, pixel slice, channel) sums of squares into the scratch region -- fixed slices, no atomics, so two forwards are bit-identical --
                              and grn_apply_kernel adds the slices in order, takes the channel mean over the C true channels and applies; pad channels come out zero.
                              Backward (T = sum_hw g x, D = mean_c G + 1e-6, dG = w T / D - (sum_c w T G) / (C D^2), K = dG / G where G > 0 else 0):
                              dx = g (1 + w N) + x K, dweight[c] = sum_b T N, dbias[c] = sum_{b,hw} g; the same fixed slices, sums added in slice and sample order */
+  /* ResNet encoder (HuggingFace ResNetBackbone behind the reference's PretrainedBackbone).  Exact fp32, inference only: the three ops carry PH_FLAG_NO_TRAIN and
+     ph_model_backward refuses them whatever the handle's options.  BatchNorm (eval) never reaches the library: the host folds it into each conv's weight and bias. */
+  PH_OP_RESNET_STEM = 19, /* image -> (x / 255 - mean[ci]) / std[ci] (ph_model_set_input_norm) -> Conv2d(k7, s2, p3) + bias + ReLU -> NHWC slot dst (H/2 x W/2)
+                             -> MaxPool2d(k3, s2, p1) -> NHWC slot dst2 (H/4 x W/4).  The conv's zero padding applies to the NORMALISED image.  Two launches
+                             (resnet_kernels.hip): the im2col product (K = 49 cin) on v_mfma_f32_32x32x2_f32, then the pool.  weight (cout, cin0, 7, 7), cin0 <= 4 */
+  PH_OP_CONV_S2 = 20,     /* Conv2d(k = ksize in {1, 3}, stride 2, padding ksize / 2) + bias (+ReLU) over an even-sized map, as a row GEMM whose rows gather their
+                             taps at stride 2 (gemm_mfma_dma_tile_kernel mode 4 / mode 6).  weight (cout, cin0, k, k) */
+  PH_OP_ADD_RELU = 21     /* dst = relu(src0 + src1), element-wise over two slots of one shape (cin0 = cout channels): the tail of a ResNet basic block */
 };
 
 #define PH_FLAG_RELU 1
@@ -135,7 +144,8 @@ enum ph_op_kind {
 #define PH_FLAG_SILU 32    /* PH_OP_CONVT: SiLU instead of ReLU (the activation is an epilogue parameter of the phase GEMMs) */
 #define PH_FLAG_NO_TRAIN 64 /* PH_OP_HEAD: a head of the segmentation model types, which neither MSE nor cross entropy trains; the forward ignores it,
                                ph_model_backward refuses the program unless ph_model_set_head_loss chose the head's loss on this handle.
-                               PH_OP_GRN / PH_OP_PATCH_STEM with PH_FLAG_PAD0_NORM: refused unless the handle option pretrained_train is 1 */
+                               PH_OP_GRN / PH_OP_PATCH_STEM with PH_FLAG_PAD0_NORM: refused unless the handle option pretrained_train is 1.
+                               PH_OP_RESNET_STEM / PH_OP_CONV_S2 / PH_OP_ADD_RELU (a ResNet program): always refused, they have no backward step */
 #define PH_FLAG_LN_EPS_1EM5 128 /* PH_OP_LAYERNORM / PH_OP_PATCH_MERGE: eps 1e-5 (nn.LayerNorm's default: the Swin norms) instead of 1e-6 */
 #define PH_FLAG_RESIDUAL 256    /* PH_OP_LINEAR: dst = acc + bias + src1 (a residual add without a layer scale: Swin's attn.proj and mlp.3; ConvNeXtV2's pwconv2) */
 #define PH_FLAG_PAD0_NORM 512   /* PH_OP_PATCH_STEM: padding 0 instead of 1 and the input is (x / 255 - mean[ci]) / std[ci] with the handle's input statistics
@@ -429,6 +439,9 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_GRN_FUSED 26 /* grn_finalize_kernel: the fused GRN plan ("grn_fuse"); the sums of squares come from the Linear in front (gemm_mfma_dma_kernel<.., EPI = 2>), the Linear behind runs per sample on weights scaled by grn_scale_weights_kernel */
 #define PH_KV_PATCH_STEM_NORM 27 /* patch_stem_norm_kernel: the padding-0 patch stem with input statistics (PH_FLAG_PAD0_NORM) */
 #define PH_KV_GRN_BWD 28 /* grn_bwd_reduce_kernel + grn_bwd_sample_kernel + grn_bwd_param_kernel + grn_bwd_apply_kernel (ph_model_last_backward_kernels): backward of a PH_OP_GRN step, fixed-slice sums, no atomics */
+#define PH_KV_RESNET_STEM 29 /* resnet_stem_conv_kernel + maxpool3s2_kernel: normalised 7x7 stride-2 stem as an im2col product on v_mfma_f32_32x32x2_f32, then the 3x3 stride-2 max pool */
+#define PH_KV_CONV_S2 30 /* gemm_mfma_dma_tile_kernel mode 4 (3x3 stride 2 pad 1) / mode 6 (1x1 stride 2) as the forward of a PH_OP_CONV_S2 */
+#define PH_KV_ADD_RELU 31 /* add_relu_kernel: dst = relu(src0 + src1), float4 per thread */
 #define PH_KV_FUSED 11   /* no launch of its own: a 1x1 head computed in the epilogue of the conv that produces its input */
 int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
 /* ... and the tile plan of every op of the LAST ph_model_forward that ran conv3x3_f16_rows_kernel (PH_KV_F16_ROWS): quad[4 i .. 4 i + 3] = {R rows, Wt columns of a tile, MT M tiles

@@ -26,7 +26,8 @@ PRECISIONS = {"exact": 0, "split": 1, "fp16": 2}
 
 
 def get_backbone(backbone: str, backbone_config):
-    """architectures/model.py:36-67.  ``unet``, ``convnext``, ``swint`` and ``pretrained`` (the ConvNeXtV2 family) are built natively; all four train on the device."""
+    """architectures/model.py:36-67.  ``unet``, ``convnext``, ``swint`` and ``pretrained`` (the ConvNeXtV2 family; the ResNet family with the config key
+    ``allow_resnet``, inference only) are built natively; all four train on the device."""
     if backbone == "unet":
         return UNet.from_config(backbone_config)
     if backbone == "convnext":
@@ -56,6 +57,7 @@ class Model:
         # `loaded_buffers` of a pretrained backbone (image_mean / image_std) are read from the checkpoint and handed to the handle (ph_model_set_input_norm)
         self.buffers: Dict[str, torch.Tensor] = dict(getattr(self.backbone, "buffers", {}))
         self._loaded_buffers = tuple(getattr(self.backbone, "loaded_buffers", ()))
+        self._ignored_buffers = tuple(getattr(self.backbone, "ignored_buffers", ()))  # in every checkpoint, accepted, never read (BatchNorm's num_batches_tracked)
         self._head_ops_start = len(self.ops)
         for i, head in enumerate(self.heads):
             if isinstance(head, ClassVectorsHead):
@@ -228,6 +230,8 @@ class Model:
                 if tuple(got.shape) != tuple(want.shape):
                     raise RuntimeError(f"size mismatch for {k}: checkpoint {tuple(got.shape)} vs model {tuple(want.shape)}")
                 self.buffers[k] = got.clone()
+            elif k in sd and k in self._ignored_buffers:
+                continue
             elif k in sd:  # the kernels compute these from coordinates: a checkpoint that disagrees was written by another definition
                 got = torch.as_tensor(sd[k]).detach().to("cpu")
                 if tuple(got.shape) != tuple(want.shape) or not torch.equal(got.to(want.dtype), want):
@@ -256,7 +260,8 @@ class Model:
             if k.endswith(".layer_scale"):
                 sd[k] = torch.full(shape, 1e-6)
             elif len(shape) == 1:
-                ln = k.endswith(".weight") and any(o.kind in (L.OP_LAYERNORM, L.OP_PATCH_MERGE) and o.weight == k for o in self.unfused_ops)
+                ln = k.endswith(".weight") and (any(o.kind in (L.OP_LAYERNORM, L.OP_PATCH_MERGE) and o.weight == k for o in self.unfused_ops) or
+                                                k in getattr(self.backbone, "unit_init_keys", ()))  # (a ResNet backbone's BatchNorm weights: the module default)
                 sd[k] = torch.ones(shape) if ln else torch.zeros(shape)
             else:
                 rf = 1
@@ -283,6 +288,9 @@ class Model:
         backbone (``allow_pretrained=True``; ``TrainingModule(model, pretrained_training=True)``): its GRN and stem ops keep ``FLAG_NO_TRAIN`` and the handle
         option ``pretrained_train`` lifts the refusal of ``ph_model_backward`` (csrc/convnextv2_train_kernels.hip).  The training program is the
         unfused one: it runs the two-launch GRN forward whatever ``grn_fuse`` says."""
+        if mode and self.is_resnet:
+            raise NotImplementedError("a 'pretrained' ResNet backbone is inference only on the MI355X path: its program runs BatchNorm folded into the convs (eval statistics); "
+                                      "training needs BatchNorm with batch statistics, which is not built (sleap_nn_amd/architectures/pretrained.py)")
         if mode and self.backbone_type == "pretrained":
             if not allow_pretrained:
                 raise NotImplementedError("training a 'pretrained' (ConvNeXtV2) backbone is opt-in on the MI355X path (its GRN and padding-0 stem ops carry PH_FLAG_NO_TRAIN): "
@@ -293,6 +301,11 @@ class Model:
             raise NotImplementedError("training a 'swint' backbone is opt-in on the MI355X path: Model.train(True, allow_swint=True), or "
                                       "TrainingModule(model, swint_training=True)")
         return self.set_fusion(not mode)
+
+    @property
+    def is_resnet(self) -> bool:
+        """A ``pretrained`` backbone of the ResNet family (HuggingFace ResNetBackbone): BatchNorm folded at handle creation, exact fp32, inference only."""
+        return self.backbone_type == "pretrained" and getattr(self.backbone, "family", "") == "resnet"
 
     def trainable_ranges(self, freeze_encoder: Optional[bool] = None) -> List[tuple]:
         """``[(start, end), ...]`` of the flat parameter arena (``param_keys`` order) that an optimizer steps: sorted, disjoint, on parameter boundaries, neighbours
@@ -393,7 +406,8 @@ class Model:
         on the fp16 matrix pipe with fp32 logits and softmax statistics, the patch-merge norm, the residual stream stored in
         fp16, then the fp16 decoder.  Without it a Swin program runs exact under every precision
         (tests/test_gpu_swint.py pins that); ``"split"`` is exact for it either way.
-        A ``pretrained`` (ConvNeXtV2) program has no fp16 form: it runs exact under every precision and whatever ``convnext_f16`` says (tests/test_gpu_pretrained.py).
+        A ``pretrained`` (ConvNeXtV2) program has no fp16 form: it runs exact under every precision and whatever ``convnext_f16`` says (tests/test_gpu_pretrained.py);
+        so does a ``pretrained`` ResNet program (tests/test_gpu_pretrained_resnet.py).
         Programs with a class-vector head (global max pool, softmax) and every training program run exact whatever is set."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
@@ -489,7 +503,10 @@ class Model:
             d.dst2, d.cmid = op.dst2, op.cmid
             d.weight2 = index[op.weight2] if op.weight2 else -1
             d.bias2 = index[op.bias2] if op.bias2 else -1
-        tensors = [self._state[k].contiguous() for k in keys]
+        # a ResNet backbone: the conv ops read W * g / sqrt(var + eps) and beta - mean * g / sqrt(var + eps) where the arena has W and beta -- folded here, from the state and
+        # the buffers as they stand (load_state_dict releases the handle, so a fold never outlives what it was made from); _state keeps the unfolded tensors
+        folded = self.backbone.folded_params(self._state, self.buffers) if self.is_resnet else {}
+        tensors = [folded.get(k, self._state[k]).contiguous() for k in keys]
         ptrs = (C.c_void_p * len(keys))(*[t.data_ptr() for t in tensors])
         numel = (C.c_int64 * len(keys))(*[t.numel() for t in tensors])
         with torch.cuda.device(device):
@@ -545,6 +562,9 @@ class Model:
         x, code = self.adapt_channels(x, code)
         x = x.contiguous()
         B, Cin, H, W = x.shape
+        if self.is_resnet and (H % self.backbone.max_stride or W % self.backbone.max_stride):  # every strided conv must see an even map: anything else would be another network's map
+            raise ValueError(f"a 'pretrained' ResNet backbone takes frames whose height and width are multiples of {self.backbone.max_stride}, got {H} x {W} "
+                             "(the inference layers pad to max_stride)")
         self._last_batch = int(B)
         self._ensure(device)
         lib = L.lib()
@@ -647,7 +667,16 @@ class Model:
                     hw[op.dst] = (h, w)
                 hw[op.dst2] = (ph, pw)
                 continue
+            if op.kind == L.OP_RESNET_STEM:
+                fh, fw = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+                hw[op.dst], hw[op.dst2] = (fh, fw), ((fh - 1) // 2 + 1, (fw - 1) // 2 + 1)
+                rows.append({"label": op.label.split(".")[-1], "kind": op.kind, "flops": 2.0 * op.cin0 * op.cout * 49 * fh * fw * batch,
+                             "bytes": float(op.cin0 * h * w * batch + 4 * op.cout * (2 * fh * fw + hw[op.dst2][0] * hw[op.dst2][1]) * batch),
+                             "cin0": op.cin0, "cin1": 0, "cout": op.cout, "ksize": 7, "out_hw": hw[op.dst2]})
+                continue
             oh, ow = h, w
+            if op.kind == L.OP_CONV_S2:
+                oh, ow = h // 2, w // 2
             if op.kind == L.OP_PATCH_STEM:
                 pad2 = 0 if op.flags & L.FLAG_PAD0_NORM else 2
                 oh, ow = (h + pad2 - op.ksize) // op.cmid + 1, (w + pad2 - op.ksize) // op.cmid + 1
@@ -665,10 +694,10 @@ class Model:
                 oh, ow = (h + 1) // 2, (w + 1) // 2
             elif op.kind in (L.OP_UPSAMPLE, L.OP_CONVT):
                 oh, ow = 2 * h, 2 * w
-            cin = op.cin0 + (op.cin1 if op.kind not in (L.OP_LINEAR, L.OP_SCALE_ADD) else 0)
+            cin = op.cin0 + (op.cin1 if op.kind not in (L.OP_LINEAR, L.OP_SCALE_ADD, L.OP_ADD_RELU) else 0)
             cout = op.cout if op.kind not in (L.OP_POOL, L.OP_UPSAMPLE) else op.cin0
             flops = 0.0
-            if op.kind in (L.OP_CONV, L.OP_INPUT_CONV):
+            if op.kind in (L.OP_CONV, L.OP_INPUT_CONV, L.OP_CONV_S2):
                 flops = 2.0 * cin * cout * op.ksize * op.ksize * oh * ow * batch
             elif op.kind == L.OP_CONVT:
                 flops = 2.0 * cin * cout * 9 * h * w * batch

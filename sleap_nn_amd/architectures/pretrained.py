@@ -1,4 +1,4 @@
-"""HuggingFace ConvNeXtV2 encoder + UNet-style decoder -> op program for libposehip.
+"""HuggingFace ConvNeXtV2 (or, opt-in, ResNet) encoder + UNet-style decoder -> op program for libposehip.
 
 Reproduces Case A (``mode="decoder"``) of the reference ``PretrainedBackbone``
 (``sleap_nn/architectures/pretrained.py:111-502``) for the ConvNeXtV2 family, without torch modules and
@@ -18,7 +18,11 @@ has the reference's meaning (``freeze_encoder()``, lightning_modules.py:232-236)
 update (``encoder_ops`` / ``Model.trainable_ranges``).  ``drop_path_rate`` of a local ``config.json`` is read and, where non-zero, refused at the opt-in:
 the published ConvNeXtV2 configs have 0.0.
 
-A block is six ops: depthwise 7x7 -> LayerNorm -> Linear C->4C -> GELU -> GRN -> Linear 4C->C with the residual add
+The ResNet family (HuggingFace ``ResNetBackbone``; basic and bottleneck layers) is opt-in through the backbone-config key ``allow_resnet`` -- existing tests pin its refusal -- and
+inference only: BatchNorm (eval) is folded into each conv on the host (``fold_batchnorm`` / ``folded_params``, float64, at handle creation) while the state dict keeps the
+reference's unfolded names; the stem, the strided convs and the residual tails are ``csrc/resnet_kernels.hip`` and the row GEMM's modes 4 and 6.
+
+A ConvNeXtV2 block is six ops: depthwise 7x7 -> LayerNorm -> Linear C->4C -> GELU -> GRN -> Linear 4C->C with the residual add
 in its epilogue (no layer scale).  ``Model._fuse_cnblocks`` folds the GELU into the first Linear for inference.
 """
 from __future__ import annotations
@@ -52,17 +56,49 @@ CONVNEXTV2_SIZES = {
 IMAGENET_MEAN = [0.485, 0.456, 0.406]  # pretrained.py:48-49: what _resolve_norm_stats falls back to without an image processor
 IMAGENET_STD = [0.229, 0.224, 0.225]
 DEFAULT_MODEL_NAME = "facebook/convnextv2-nano-22k-224"
+# microsoft/resnet-<N>: layer type, depths, hidden sizes (embedding_size 64 throughout).  The resnet-50 row is ResNetConfig()'s defaults (tests/test_pretrained_resnet_cpu.py
+# checks it where transformers is installed); the other rows are the published configs as recalled -- nothing here can reach the hub to check them, a local config.json wins
+RESNET_SIZES = {
+    "18": {"layer_type": "basic", "depths": [2, 2, 2, 2], "hidden_sizes": [64, 128, 256, 512]},
+    "34": {"layer_type": "basic", "depths": [3, 4, 6, 3], "hidden_sizes": [64, 128, 256, 512]},
+    "26": {"layer_type": "bottleneck", "depths": [2, 2, 2, 2], "hidden_sizes": [256, 512, 1024, 2048]},
+    "50": {"layer_type": "bottleneck", "depths": [3, 4, 6, 3], "hidden_sizes": [256, 512, 1024, 2048]},
+    "101": {"layer_type": "bottleneck", "depths": [3, 4, 23, 3], "hidden_sizes": [256, 512, 1024, 2048]},
+    "152": {"layer_type": "bottleneck", "depths": [3, 8, 36, 3], "hidden_sizes": [256, 512, 1024, 2048]},
+}
+RESNET_OPT_IN = ("the ResNet family is opt-in: backbone-config key allow_resnet=True (LoadedAssets.build_model(pretrained_resnet=True), "
+                 "Predictor.from_model_paths(..., pretrained_resnet=True))")
+BN_EPS = 1e-5  # nn.BatchNorm2d's default, which HuggingFace's ResNetConvLayer keeps
 
 
 def _refuse(what: str) -> NotImplementedError:
     return NotImplementedError(f"pretrained backbone: {what} is not built on the MI355X path; only the ConvNeXtV2 family in mode='decoder' with all stages is ({THIS_FILE})")
 
 
-def resolve_architecture(model_name: str, run_dir: Optional[str] = None) -> dict:
-    """``model_name`` -> {"depths", "hidden_sizes", "patch_size", "num_channels"} without touching a network.
+def _resolve_resnet(hf: dict, source: str) -> dict:
+    """The ResNet leaf of ``resolve_architecture``: ``hf`` holds config.json's keys (or a row of ``RESNET_SIZES``); what the program cannot run is refused by name."""
+    d = RESNET_SIZES["50"]
+    arch = {"family": "resnet", "embedding_size": int(hf.get("embedding_size", 64)), "hidden_sizes": [int(v) for v in (hf.get("hidden_sizes") or d["hidden_sizes"])],
+            "depths": [int(v) for v in (hf.get("depths") or d["depths"])], "layer_type": str(hf.get("layer_type", "bottleneck")), "num_channels": int(hf.get("num_channels", 3)),
+            "patch_size": 4, "drop_path_rate": 0.0, "source": source}
+    if hf.get("downsample_in_first_stage", False):
+        raise _refuse(f"downsample_in_first_stage=True of {source}")
+    if hf.get("downsample_in_bottleneck", False):
+        raise _refuse(f"downsample_in_bottleneck=True of {source}")
+    if hf.get("hidden_act", "relu") != "relu":
+        raise _refuse(f"hidden_act {hf.get('hidden_act')!r} of {source}")
+    if arch["layer_type"] not in ("basic", "bottleneck"):
+        raise _refuse(f"layer_type {arch['layer_type']!r} of {source}")
+    if len(arch["hidden_sizes"]) != 4 or len(arch["depths"]) != 4:
+        raise _refuse(f"a ResNet with {len(arch['hidden_sizes'])} stages ({source})")
+    return arch
 
-    (a) a directory holding a ``config.json`` (absolute as given; relative against ``run_dir``, then the working directory);
-    (b) the size word of a ``convnextv2-<size>`` id; (c) anything else is refused."""
+
+def resolve_architecture(model_name: str, run_dir: Optional[str] = None, allow_resnet: bool = False) -> dict:
+    """``model_name`` -> {"family", "depths", "hidden_sizes", "patch_size", "num_channels", ...} without touching a network.
+
+    (a) a directory holding a ``config.json`` (absolute as given; relative against ``run_dir``, then the working directory), dispatched on its ``model_type``;
+    (b) the size word of a ``convnextv2-<size>`` id, or -- with ``allow_resnet`` -- the number of a ``resnet-<N>`` id; (c) anything else is refused."""
     name = str(model_name)
     cands = [name] if os.path.isabs(name) else ([os.path.join(run_dir, name)] if run_dir else []) + [os.path.join(os.getcwd(), name)]
     for d in cands:
@@ -72,21 +108,33 @@ def resolve_architecture(model_name: str, run_dir: Optional[str] = None) -> dict
         with open(path) as f:
             hf = json.load(f)
         mt = hf.get("model_type")
+        if mt == "resnet" and allow_resnet:
+            return _resolve_resnet(hf, path)
         if mt != "convnextv2":
-            raise _refuse(f"model_type {mt!r} of {path}")
+            raise _refuse(f"model_type {mt!r} of {path}" + (f" ({RESNET_OPT_IN})" if mt == "resnet" else ""))
         if hf.get("hidden_act", "gelu") != "gelu":
             raise _refuse(f"hidden_act {hf.get('hidden_act')!r} of {path}")
         eps = float(hf.get("layer_norm_eps", 1e-12))  # (the classifier's pooled norm: no op of the backbone reads it)
         depths = [int(v) for v in (hf.get("depths") or CONVNEXTV2_SIZES["tiny"]["depths"])]
         hidden = [int(v) for v in (hf.get("hidden_sizes") or CONVNEXTV2_SIZES["tiny"]["hidden_sizes"])]
-        return {"depths": depths, "hidden_sizes": hidden, "patch_size": int(hf.get("patch_size", 4)), "num_channels": int(hf.get("num_channels", 3)),
+        return {"family": "convnextv2", "depths": depths, "hidden_sizes": hidden, "patch_size": int(hf.get("patch_size", 4)), "num_channels": int(hf.get("num_channels", 3)),
                 "layer_norm_eps": eps, "drop_path_rate": float(hf.get("drop_path_rate", 0.0)), "source": path}
     m = re.search(r"convnextv2-([a-z]+)", name.lower())
     if m and m.group(1) in CONVNEXTV2_SIZES:
         a = CONVNEXTV2_SIZES[m.group(1)]
-        return {"depths": list(a["depths"]), "hidden_sizes": list(a["hidden_sizes"]), "patch_size": 4, "num_channels": 3, "layer_norm_eps": 1e-12, "drop_path_rate": 0.0,
-                "source": m.group(0)}
-    raise _refuse(f"model_name {name!r} (no local config.json, not a convnextv2-<size> id: ResNet, Swinv2, DINO and the isotropic ViTs are other families)")
+        return {"family": "convnextv2", "depths": list(a["depths"]), "hidden_sizes": list(a["hidden_sizes"]), "patch_size": 4, "num_channels": 3, "layer_norm_eps": 1e-12,
+                "drop_path_rate": 0.0, "source": m.group(0)}
+    r = re.search(r"resnet-(\d+)", name.lower())
+    if r and r.group(1) in RESNET_SIZES and allow_resnet:
+        return _resolve_resnet(RESNET_SIZES[r.group(1)], r.group(0))
+    hint = f"; {RESNET_OPT_IN}" if r and r.group(1) in RESNET_SIZES else ""
+    raise _refuse(f"model_name {name!r} (no local config.json, not a convnextv2-<size> id: ResNet, Swinv2, DINO and the isotropic ViTs are other families{hint})")
+
+
+def fold_batchnorm(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor, var: torch.Tensor, eps: float = BN_EPS) -> Tuple[torch.Tensor, torch.Tensor]:
+    """conv (no bias) -> BatchNorm2d in eval mode as one conv: (W * s[:, None, None, None], beta - mean * s) with s = gamma / sqrt(var + eps), computed in float64."""
+    s = gamma.double() / torch.sqrt(var.double() + eps)
+    return (w.double() * s.view(-1, 1, 1, 1)).float().contiguous(), (beta.double() - mean.double() * s).float().contiguous()
 
 
 @dataclass
@@ -124,6 +172,15 @@ class PretrainedBackbone:
     # trained with override what the config or the ImageNet default would give
     buffers: Dict[str, torch.Tensor] = field(default_factory=dict)
     loaded_buffers: Tuple[str, ...] = ("backbone.image_mean", "backbone.image_std")
+    # ResNet family (HuggingFace ResNetBackbone; opt-in through the config key allow_resnet).  BatchNorm never reaches the program: `bn_convs` lists every conv as
+    # (conv weight key, BatchNorm prefix) and `folded_params` gives the two tensors its op reads in place of <conv>.weight and <bn>.bias.  The running statistics are
+    # loaded_buffers (read from the checkpoint); num_batches_tracked is in every checkpoint, accepted and ignored (ignored_buffers)
+    family: str = "convnextv2"
+    embedding_size: int = 64
+    layer_type: str = "bottleneck"
+    bn_convs: List[Tuple[str, str]] = field(default_factory=list)
+    ignored_buffers: Tuple[str, ...] = ()
+    unit_init_keys: Tuple[str, ...] = ()  # parameters init_xavier_ sets to 1 (BatchNorm weights)
 
     @classmethod
     def from_config(cls, config) -> "PretrainedBackbone":
@@ -134,7 +191,7 @@ class PretrainedBackbone:
         if mode not in ("auto", "decoder"):
             raise _refuse(f"mode={mode!r} (the encoder-only pooled bottleneck)")
         name = cfg_get(config, "model_name", None) or DEFAULT_MODEL_NAME
-        arch = resolve_architecture(name, cfg_get(config, "_run_dir", None))
+        arch = resolve_architecture(name, cfg_get(config, "_run_dir", None), allow_resnet=bool(cfg_get(config, "allow_resnet", False)))
         oi = cfg_get(config, "out_indices", None)
         if oi is not None and [int(i) for i in oi] != [0, 1, 2, 3, 4]:
             raise _refuse(f"out_indices={list(oi)} (a subset of the stages)")
@@ -150,7 +207,8 @@ class PretrainedBackbone:
             filters_rate=cfg_get(config, "filters_rate", 2.0), convs_per_block=int(cfg_get(config, "convs_per_block", 2)),
             kernel_size=int(cfg_get(config, "kernel_size", 3)), up_interpolate=bool(cfg_get(config, "up_interpolate", True)),
             depths=[int(d) for d in arch["depths"]], channels=[int(c) for c in arch["hidden_sizes"]], patch_size=int(arch["patch_size"]),
-            drop_path_rate=float(arch.get("drop_path_rate", 0.0)),
+            drop_path_rate=float(arch.get("drop_path_rate", 0.0)), family=str(arch.get("family", "convnextv2")), embedding_size=int(arch.get("embedding_size", 64)),
+            layer_type=str(arch.get("layer_type", "bottleneck")),
         )
         net._build()
         return net
@@ -170,6 +228,8 @@ class PretrainedBackbone:
 
     def check_trainable(self) -> None:
         """What the opt-in to training refuses by name."""
+        if self.family == "resnet":
+            raise _refuse("training a ResNet backbone (BatchNorm with batch statistics is another op; the program runs the eval fold only)")
         if self.drop_path_rate != 0.0:
             raise _refuse(f"training with drop_path_rate={self.drop_path_rate} (stochastic depth of the ConvNeXtV2 blocks; the published configs have 0.0)")
 
@@ -237,7 +297,84 @@ class PretrainedBackbone:
         mean, std = self.norm_stats()
         self.buffers = {"backbone.image_mean": torch.tensor(mean, dtype=torch.float32).view(1, -1, 1, 1),
                         "backbone.image_std": torch.tensor(std, dtype=torch.float32).view(1, -1, 1, 1)}
-        self._build_encoder()
+        if self.family == "resnet":
+            self._build_resnet_encoder()
+        else:
+            self._build_encoder()
+
+    # -- ResNet (HuggingFace ResNetBackbone): embedder (7x7 s2 conv + BN + ReLU, 3x3 s2 max pool), four stages of basic / bottleneck layers, RAW stage outputs as the pyramid
+    def _bn_conv(self, name: str, cout: int, cin: int, k: int) -> Tuple[str, str]:
+        """Register ``<name>.convolution`` (bias-less) + ``<name>.normalization``; -> the keys the conv's op reads as weight and bias (both folded at handle creation)."""
+        cw, bn = name + ".convolution.weight", name + ".normalization"
+        self.param_shapes[cw] = (cout, cin, k, k)
+        self.param_shapes[bn + ".weight"] = (cout,)
+        self.param_shapes[bn + ".bias"] = (cout,)
+        self.buffers[bn + ".running_mean"] = torch.zeros(cout)
+        self.buffers[bn + ".running_var"] = torch.ones(cout)
+        self.buffers[bn + ".num_batches_tracked"] = torch.zeros((), dtype=torch.int64)
+        self.bn_convs.append((cw, bn))
+        return cw, bn + ".bias"
+
+    def _rn_conv(self, name: str, x: int, cin: int, cout: int, k: int, stride: int, relu: bool, residual: int = -1) -> int:
+        """One ResNetConvLayer / ResNetShortCut as the op that runs it: 1x1 s1 -> Linear (row GEMM), 3x3 s1 -> PH_OP_CONV, anything at stride 2 -> PH_OP_CONV_S2."""
+        w, b = self._bn_conv(name, cout, cin, k)
+        act = L.FLAG_RELU if relu else 0
+        dst = self._new_slot()
+        if stride == 2:
+            op = OpSpec(L.OP_CONV_S2, x, -1, dst, cin, 0, cout, k, act | L.FLAG_NO_TRAIN, w, b, label=name)
+        elif k == 1:
+            op = OpSpec(L.OP_LINEAR, x, residual, dst, cin, 0, cout, 1, act | (L.FLAG_RESIDUAL if residual >= 0 else 0), w, b, label=name)
+        else:
+            op = OpSpec(L.OP_CONV, x, -1, dst, cin, 0, cout, 3, act, w, b, label=name)
+        self.ops.append(op)
+        self.labels[name] = dst
+        return dst
+
+    def _rn_layer(self, name: str, x: int, cin: int, cout: int, stride: int) -> int:
+        res = self._rn_conv(name + ".shortcut", x, cin, cout, 1, stride, relu=False) if (cin != cout or stride != 1) else x
+        if self.layer_type == "bottleneck":
+            r = cout // 4  # (HuggingFace's `out_channels // reduction`: 18 -> 4)
+            y = self._rn_conv(name + ".layer.0", x, cin, r, 1, 1, relu=True)
+            y = self._rn_conv(name + ".layer.1", y, r, r, 3, stride, relu=True)
+            y = self._rn_conv(name + ".layer.2", y, r, cout, 1, 1, relu=True, residual=res)  # relu(conv + bias + shortcut): the row GEMM's residual-then-ReLU epilogue
+        else:
+            y = self._rn_conv(name + ".layer.0", x, cin, cout, 3, stride, relu=True)
+            y = self._rn_conv(name + ".layer.1", y, cout, cout, 3, 1, relu=False)
+            dst = self._new_slot()
+            self.ops.append(OpSpec(L.OP_ADD_RELU, y, res, dst, cout, 0, cout, 1, L.FLAG_NO_TRAIN, label=name))
+            y = dst
+        self.labels[name] = y
+        return y
+
+    def _build_resnet_encoder(self) -> None:
+        enc = "backbone.enc"
+        name = f"{enc}.embedder.embedder"
+        w, b = self._bn_conv(name, self.embedding_size, self.in_channels, 7)
+        full, pooled = self._new_slot(), self._new_slot()
+        self.ops.append(OpSpec(L.OP_RESNET_STEM, -1, -1, full, self.in_channels, 0, self.embedding_size, 7, L.FLAG_RELU | L.FLAG_NO_TRAIN, w, b, label=name, dst2=pooled))
+        self.labels[name] = full
+        self.labels[f"{enc}.embedder"] = pooled  # feature map "stem": stride 4, like stage1, and dropped by the reference's stride dedupe
+        x, cin = pooled, self.embedding_size
+        feats: List[Tuple[int, int]] = []
+        for si, (depth, c) in enumerate(zip(self.depths, self.channels)):
+            for j in range(depth):
+                x = self._rn_layer(f"{enc}.encoder.stages.{si}.layers.{j}", x, cin, c, 2 if (si > 0 and j == 0) else 1)
+                cin = c
+            self.labels[f"{enc}.stage{si + 1}"] = x
+            feats.append((x, c))  # the RAW stage output: no output norms, unlike ConvNeXtV2
+        bn_keys = [k for k in self.buffers if ".normalization." in k]
+        self.loaded_buffers = tuple(self.loaded_buffers) + tuple(k for k in bn_keys if not k.endswith("num_batches_tracked"))
+        self.ignored_buffers = tuple(k for k in bn_keys if k.endswith("num_batches_tracked"))
+        self.unit_init_keys = tuple(bn + ".weight" for _w, bn in self.bn_convs)
+        self._build_decoder(feats)
+
+    def folded_params(self, state: Dict[str, torch.Tensor], buffers: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """BatchNorm (eval) folded into the conv in front of it, per output channel: W' = W * g / sqrt(var + eps) under the conv's weight key and
+        b' = beta - mean * g / sqrt(var + eps) under the BatchNorm's bias key -- the two keys the conv's op reads.  float64 on the host, rounded once to float32."""
+        out: Dict[str, torch.Tensor] = {}
+        for cw, bn in self.bn_convs:
+            out[cw], out[bn + ".bias"] = fold_batchnorm(state[cw], state[bn + ".weight"], state[bn + ".bias"], buffers[bn + ".running_mean"], buffers[bn + ".running_var"])
+        return out
 
     def _build_encoder(self) -> None:
         ch = self.channels

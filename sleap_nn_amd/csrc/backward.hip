@@ -982,6 +982,9 @@ int check_backward_handle(ph_model* m, int batch) {
     PH_REQUIRE(!((op.d.flags & PH_FLAG_NO_TRAIN) && m->head_loss_kind[op.d.out_index] == 0),
                "ph_model_backward: head %d belongs to a segmentation model type, whose losses (BCE + Dice, masked smooth-L1) are not built: inference only", op.d.out_index);
   }
+  for (const auto& op : m->ops)  // a ResNet program (HuggingFace ResNetBackbone behind the 'pretrained' backbone) has no backward step at all: BatchNorm with batch statistics is another op
+    PH_REQUIRE(op.d.kind != PH_OP_RESNET_STEM && op.d.kind != PH_OP_CONV_S2 && op.d.kind != PH_OP_ADD_RELU,
+               "ph_model_backward: op kind %d belongs to a 'pretrained' ResNet backbone, which is inference only", op.d.kind);
   for (const auto& op : m->ops)  // the ConvNeXtV2 ops (GRN, the padding-0 stem with input statistics) carry PH_FLAG_NO_TRAIN: their backward steps run on request only
     PH_REQUIRE(m->pretrained_train || !(op.d.kind != PH_OP_HEAD && (op.d.flags & PH_FLAG_NO_TRAIN)),
                "ph_model_backward: op kind %d is inference only on this handle (a 'pretrained' ConvNeXtV2 backbone trains with the handle option pretrained_train = 1)", op.d.kind);

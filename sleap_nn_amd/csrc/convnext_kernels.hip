@@ -474,6 +474,8 @@ int launch_layernorm(const float* src, const float* gamma, const float* beta, fl
 //     mode 4  Conv2d 3x3 stride 2 pad 1 (the data gradient of that transposed conv): 9 taps gathered from a 2H x 2W map.
 //     mode 5  Conv2d k x k "same", odd k <= 9 (kernel_size 5 / 7 backbones, the 7x7 convs of a UNet stem block,
 //             encoder_decoder.py:144-225): k^2 taps, validity computed per tap from the row's (y, x).
+//     mode 6  Conv2d 1x1 at stride 1 or 2 (a ResNet shortcut; a bottleneck's last conv): 1 tap, row m = output pixel (b, oy, ox) reads input pixel
+//             (stride oy, stride ox); epilogue act(acc + bias + residual) -- the residual goes in BEFORE the activation, unlike the other modes.
 //   512 threads = 8 waves, tile 256 rows x BN columns (BN = 32 * NT_TOTAL); waves are arranged
 //   (8 / WN) x WN and each owns WN 32-row tiles x (NT_TOTAL / WN) 32-column tiles.
 //   Pipeline: a ring of three LDS stages of 16 K-values each (256 x 16 A slice + BN x 16 weight
@@ -497,7 +499,7 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void gemm_mfma_dma_tile_kernel(G
   constexpr int NDMA = A_SLOTS + B_SLOTS;  // DMA instructions per wave per stage
   constexpr int STAGE_FLOATS = (A_PIECES + B_PIECES) * 256;
   static_assert((NSTAGE - 2) * NDMA < 64 && NSTAGE >= 2 && WAVES % 2 == 0, "vmcnt field overflow / odd wave count");
-  constexpr int NTAPS_C = MODE == 0 ? 1 : (MODE == 1 ? 4 : 9);
+  constexpr int NTAPS_C = (MODE == 0 || MODE == 6) ? 1 : (MODE == 1 ? 4 : 9);
   // mode 3 with all_phases: the four output phases of a transposed conv in ONE launch (blockIdx.y = phase: its tap count, weight pack and output offset) -- at small batches
   // the four phase launches were four launch floors (the reference's fixture bottom-up model at 320 x 560 x 4: 76 + 54 us of a 454-us forward)
   const int phase = (MODE == 3 && a.all_phases) ? (int)blockIdx.y : a.out_tap;
@@ -567,6 +569,12 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void gemm_mfma_dma_tile_kernel(G
         const int dy = py ? 1 - ty : 0, dx = px ? 1 - tx : 0;
         mask |= (y + dy < a.H && x + dx < a.W) ? (1u << tap) : 0u;
       }
+    } else if (MODE == 6) {  // one tap at a row stride (1x1 conv, stride 1 or 2): row = (b, oy, ox) on the (a.H / stride) x (a.W / stride) grid
+      const int ow = a.W / a.tap_stride, oh = a.H / a.tap_stride;
+      const int ox = row % ow;
+      const int r2 = row / ow;
+      const int oy = r2 % oh;
+      pix = ((long long)(r2 / oh) * a.H + a.tap_stride * oy) * a.W + a.tap_stride * ox;
     } else if (MODE == 4) {  // 3x3 stride-2 pad-1 gather over an a.H x a.W map; row = (b, oy, ox) on the (a.H / 2) x (a.W / 2) grid
       const int ow = a.W >> 1, oh = a.H >> 1;
       const int ox = row % ow;
@@ -592,7 +600,7 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void gemm_mfma_dma_tile_kernel(G
   auto issue_stage = [&](float* buf) {
     const int cp = f_src ? a.c1p : a.c0p;
     int toff;  // pixel offset of the tap
-    if (MODE == 0) {
+    if (MODE == 0 || MODE == 6) {
       toff = 0;
     } else if (MODE == 5) {
       toff = (f_ty - (a.ksize >> 1)) * a.W + (f_tx - (a.ksize >> 1));
@@ -774,6 +782,21 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void gemm_mfma_dma_tile_kernel(G
       const size_t rofs = opix * a.coutp;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
+        if (MODE == 6) {  // dst = act(acc + bias + residual): the residual goes in BEFORE the activation (the tail of a ResNet bottleneck); no scale / shift
+          const int col6 = cbase + 8 * q;
+          if (interior || (row < a.M && col6 < a.coutp)) {
+            f32x4 v6;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v6[e] = acc[m][n][4 * q + e] + bias4[q][e];
+            if (a.residual) v6 += *reinterpret_cast<const f32x4*>(a.residual + rofs + col6);
+            if (a.act == 1) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v6[e] = fmaxf(v6[e], 0.f);
+            }
+            *reinterpret_cast<f32x4*>(a.dst + rofs + col6) = v6;
+          }
+          continue;
+        }
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -1211,6 +1234,8 @@ int prepare_convnext_kernels() {
                                    (int)GemmCfg<MT, NTW, WM, WN, S, W>::LDS));                                                              \
   PH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mfma_dma_tile_kernel<5, MT, NTW, WM, WN, S, W>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                    (int)GemmCfg<MT, NTW, WM, WN, S, W>::LDS));                                                              \
+  PH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mfma_dma_tile_kernel<6, MT, NTW, WM, WN, S, W>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                   (int)GemmCfg<MT, NTW, WM, WN, S, W>::LDS));                                                              \
   PH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mfma_dma_kernel<2, MT, NTW, WM, WN, S, W>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                    (int)GemmCfg<MT, NTW, WM, WN, S, W>::LDS));                                                              \
   PH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mfma_dma_kernel<0, MT, NTW, WM, WN, S, W, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, \
@@ -1235,12 +1260,15 @@ int gemm_variant_bn(int variant) {
 int launch_gemm_variant(int variant, const GemmArgs& a_in, hipStream_t s) {
   GemmArgs a = a_in;
   const int persist2 = a.persist2;  // handle option: persistent workgroups for the 9-tap mode too (measured 3-4 % slower than one tile per workgroup)
-  PH_REQUIRE(a.M > 0 && a.c0p > 0 && a.c0p % 16 == 0 && a.c1p % 16 == 0 && a.coutp % 16 == 0 && a.mode >= 0 && a.mode <= 5, "launch_gemm: bad shape");
+  PH_REQUIRE(a.M > 0 && a.c0p > 0 && a.c0p % 16 == 0 && a.c1p % 16 == 0 && a.coutp % 16 == 0 && a.mode >= 0 && a.mode <= 6, "launch_gemm: bad shape");
+  PH_REQUIRE(a.mode != 6 || ((a.tap_stride == 1 || a.tap_stride == 2) && a.c1p == 0 && !a.scale && !a.shift && !a.affine_first && !a.out_patch && a.act <= 1 && a.H > 0 && a.W > 0 && a.H % a.tap_stride == 0 &&
+                             a.W % a.tap_stride == 0 && a.M % ((a.H / a.tap_stride) * (a.W / a.tap_stride)) == 0),
+             "launch_gemm: the one-tap mode takes one source, stride 1 or 2 over maps the stride divides, whole images, bias (+ residual) (+ ReLU)");
   PH_REQUIRE(a.mode != 5 || ((a.ksize & 1) && a.ksize >= 1 && a.ksize <= 9 && a.M % (a.H * a.W) == 0 && a.H < 65536 && a.W < 65536), "launch_gemm: k x k conv needs an odd kernel <= 9 and whole images");
   PH_REQUIRE(a.mode != 3 || (((a.all_phases && a.wpack_ph[0] && a.wpack_ph[1] && a.wpack_ph[2] && a.wpack_ph[3]) || ((a.ntaps == 1 || a.ntaps == 2 || a.ntaps == 4) && a.ntaps == (1 + (a.out_tap >> 1)) * (1 + (a.out_tap & 1)))) && a.out_patch && a.M % (a.H * a.W) == 0),
              "launch_gemm: transposed-conv phase needs ntaps matching the phase, out_patch and whole images");
   PH_REQUIRE(a.mode != 4 || (a.H % 2 == 0 && a.W % 2 == 0 && a.M % ((a.H / 2) * (a.W / 2)) == 0), "launch_gemm: stride-2 gather needs even map sizes and whole images");
-  PH_REQUIRE(a.mode >= 3 || (!a.affine_first && a.act != 4 && !a.shift), "launch_gemm: affine-first / SiLU epilogues exist for modes 3 and 4 only");
+  PH_REQUIRE((a.mode >= 3 && a.mode != 6) || (!a.affine_first && a.act != 4 && !a.shift), "launch_gemm: affine-first / SiLU epilogues exist for modes 3 and 4 only");
   PH_REQUIRE(a.c1p == 0 || a.src1, "launch_gemm: second source missing");
   PH_REQUIRE((a.act != 3 && !a.dst_pre) || a.mode == 0, "launch_gemm: the training epilogues exist for the Linear mode only");
   PH_REQUIRE(a.act != 3 || a.aux, "launch_gemm: act 3 needs aux");
@@ -1277,6 +1305,8 @@ int launch_gemm_variant(int variant, const GemmArgs& a_in, hipStream_t s) {
         hipLaunchKernelGGL((gemm_mfma_dma_tile_kernel<3, MT, NTW, WM, WN, S, W>), dim3(full.x, a.all_phases ? 4 : 1), dim3(C::THREADS), C::LDS, s, a); \
       else if (a.mode == 5)                                                                                                    \
         hipLaunchKernelGGL((gemm_mfma_dma_tile_kernel<5, MT, NTW, WM, WN, S, W>), full, dim3(C::THREADS), C::LDS, s, a);       \
+      else if (a.mode == 6)                                                                                                    \
+        hipLaunchKernelGGL((gemm_mfma_dma_tile_kernel<6, MT, NTW, WM, WN, S, W>), full, dim3(C::THREADS), C::LDS, s, a);       \
       else                                                                                                                     \
         hipLaunchKernelGGL((gemm_mfma_dma_tile_kernel<4, MT, NTW, WM, WN, S, W>), full, dim3(C::THREADS), C::LDS, s, a);       \
     }                                                                                                                          \

@@ -900,6 +900,8 @@ int fwd_linear_f32(ForwardCtx& c, const PackedOp& op) {
   return launch_gemm(a, c.s);
 }
 
+int launch_tap1_gemm(ForwardCtx& c, const PackedOp& op, int stride, const float* residual);  // (with the ResNet ops below)
+
 int fwd_linear(ForwardCtx& c, const PackedOp& op) {  // PH_OP_LINEAR and PH_OP_PATCH_CONV
   if (c.skip_next_linear) {  // the second Linear of a CNBlock MLP that cnblock_mlp_kernel computed with the first
     c.skip_next_linear = false;
@@ -907,10 +909,110 @@ int fwd_linear(ForwardCtx& c, const PackedOp& op) {  // PH_OP_LINEAR and PH_OP_P
     return PH_OK;
   }
   PH_REQUIRE(c.slot(op.d.src0).c == op.d.cin0, "GEMM channel mismatch");
+  if (op.d.kind == PH_OP_LINEAR && (op.d.flags & PH_FLAG_RESIDUAL) && (op.d.flags & PH_FLAG_RELU)) {  // dst = relu(acc + bias + src1): a ResNet bottleneck's tail
+    PH_REQUIRE(c.fmt == FMT_F32 && !c.m->branch_scales && c.slot(op.d.src1).cp == c.slot(op.d.dst).cp, "the residual + ReLU epilogue runs in exact fp32 without branch scales");
+    c.ran(PH_KV_ROWGEMM);
+    return launch_tap1_gemm(c, op, 1, c.rd(op.d.src1));
+  }
   if (c.fmt == FMT_F16) return fwd_linear_f16(c, op);
   if (fuses_mlp(c.m, c.op_i(), c.fmt, c.plan.reuse) && mlp_pair_fits(c, op)) return fwd_linear_mlp(c, op);
   if (c.fused_grn == c.op_i() && op.d.kind == PH_OP_LINEAR) return fwd_linear_grn(c, op);
   return fwd_linear_f32(c, op);
+}
+
+// ---- ResNet encoder ops (resnet_kernels.hip, the strided row-GEMM modes)
+
+int fwd_resnet_stem(ForwardCtx& c, const PackedOp& op) {
+  const ph_op_desc& d = op.d;
+  PH_REQUIRE(d.cin0 == c.in_channels, "input has %d channels, network expects %d", c.in_channels, d.cin0);
+  PH_REQUIRE(c.fmt == FMT_F32, "the resnet stem runs in exact fp32 only");
+  const SlotShape& sf = c.slot(d.dst);
+  const SlotShape& sp = c.slot(d.dst2);
+  ResnetStemArgs a{};
+  a.src = c.input_dev;
+  a.wimg = op.w_dev;
+  a.bias = op.b_dev;
+  a.conv_dst = c.wr(d.dst);  // launch 0: image -> the stride-2 map
+  a.dtype = c.in_dtype;
+  a.cin = d.cin0;
+  a.coutp = sf.cp;
+  a.B = c.batch;
+  a.H = c.height;
+  a.W = c.width;
+  a.OH = sf.h;
+  a.OW = sf.w;
+  a.PH = sp.h;
+  a.PW = sp.w;
+  for (int ch = 0; ch < 4; ++ch) {
+    a.mean[ch] = c.m->in_mean[ch];
+    a.std[ch] = c.m->in_std[ch];
+  }
+  c.ran(PH_KV_RESNET_STEM);
+  int rc = launch_resnet_stem(a, c.s);
+  if (rc != PH_OK) return rc;
+  c.next_launch();
+  const float* full = c.rd(d.dst);  // launch 1: the stride-2 map -> the pooled map
+  return launch_maxpool3s2(full, c.wr(d.dst2), c.batch, sf.h, sf.w, sf.cp, c.s);
+}
+
+// one-tap row GEMM (mode 6): a 1x1 conv at stride 1 or 2, bias (+ residual) (+ ReLU) with the residual in front of the activation
+int launch_tap1_gemm(ForwardCtx& c, const PackedOp& op, int stride, const float* residual) {
+  const ph_op_desc& d = op.d;
+  const SlotShape& s0 = c.slot(d.src0);
+  const SlotShape& so = c.slot(d.dst);
+  GemmArgs g{};
+  g.src0 = c.rd(d.src0);
+  g.c0p = s0.cp;
+  g.wpack = op.w_dma_dev;
+  g.bias = op.b_dev;
+  g.residual = residual;
+  g.dst = c.wr(d.dst);
+  g.zeros = c.m->zeros_dev;
+  g.coutp = so.cp;
+  g.bn = op.bn;
+  g.M = c.batch * so.h * so.w;
+  g.mode = 6;
+  g.tap_stride = stride;
+  g.H = s0.h;
+  g.W = s0.w;
+  g.act = c.relu(d);
+  g.late_split = c.m->gemm_late_split;
+  return launch_gemm(g, c.s);
+}
+
+int fwd_conv_s2(ForwardCtx& c, const PackedOp& op) {
+  const ph_op_desc& d = op.d;
+  const SlotShape& s0 = c.slot(d.src0);
+  const SlotShape& so = c.slot(d.dst);
+  PH_REQUIRE(c.fmt == FMT_F32 && s0.c == d.cin0, "stride-2 conv channel mismatch");
+  c.ran(PH_KV_CONV_S2);
+  if (d.ksize == 1) return launch_tap1_gemm(c, op, 2, nullptr);
+  GemmArgs g{};  // 3x3 stride 2 pad 1: nine taps gathered from the 2H x 2W map (the mode the transposed conv's data gradient runs on)
+  g.src0 = c.rd(d.src0);
+  g.c0p = s0.cp;
+  g.wpack = op.w_dma_dev;
+  g.bias = op.b_dev;
+  g.dst = c.wr(d.dst);
+  g.zeros = c.m->zeros_dev;
+  g.coutp = so.cp;
+  g.bn = op.bn;
+  g.M = c.batch * so.h * so.w;
+  g.mode = 4;
+  g.H = s0.h;
+  g.W = s0.w;
+  g.act = c.relu(d);
+  g.late_split = c.m->gemm_late_split;
+  return launch_gemm(g, c.s);
+}
+
+int fwd_add_relu(ForwardCtx& c, const PackedOp& op) {
+  const ph_op_desc& d = op.d;
+  const SlotShape& s0 = c.slot(d.src0);
+  PH_REQUIRE(c.fmt == FMT_F32 && s0.c == d.cin0 && c.slot(d.src1).cp == s0.cp && c.slot(d.dst).cp == s0.cp, "add channel mismatch");
+  const float* x = c.rd(d.src0);
+  const float* y = c.rd(d.src1);
+  c.ran(PH_KV_ADD_RELU);
+  return launch_add_relu(x, y, c.wr(d.dst), (size_t)c.batch * s0.h * s0.w * s0.cp, c.s);
 }
 
 // ---- GRN, element-wise ops, heads
@@ -1013,6 +1115,9 @@ int fwd_op(ForwardCtx& c, const PackedOp& op) {
     case PH_OP_LINEAR:
     case PH_OP_PATCH_CONV: return fwd_linear(c, op);
     case PH_OP_GRN: return fwd_grn(c, op);
+    case PH_OP_RESNET_STEM: return fwd_resnet_stem(c, op);
+    case PH_OP_CONV_S2: return fwd_conv_s2(c, op);
+    case PH_OP_ADD_RELU: return fwd_add_relu(c, op);
     case PH_OP_GLOBAL_MAXPOOL: return fwd_global_maxpool(c, op);
     case PH_OP_GELU: return fwd_gelu(c, op);
     case PH_OP_SCALE_ADD: return fwd_scale_add(c, op);

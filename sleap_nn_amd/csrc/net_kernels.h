@@ -131,7 +131,7 @@ struct GemmArgs {
   const float* zeros = nullptr;     // >= 64 B of zeros in HBM
   int c0p = 0, c1p = 0, coutp = 0, bn = 0;
   int M = 0;                        // output rows
-  int mode = 0;                     // 0: row = pixel (Linear); 1: 2x2/stride-2 patches; 2: 3x3 "same" conv; 3: transposed-conv phase; 4: 3x3 stride-2 gather; 5: k x k "same" conv
+  int mode = 0;                     // 0: row = pixel (Linear); 1: 2x2/stride-2 patches; 2: 3x3 "same" conv; 3: transposed-conv phase; 4: 3x3 stride-2 gather; 5: k x k "same" conv; 6: one tap at a row stride, residual BEFORE the activation
   int H = 0, W = 0;                 // input spatial size (modes 1, 2)
   int act = 0;                      // 0 none, 1 ReLU, 2 GELU, 3 multiply by GELU'(aux) (Linear modes only), 4 SiLU (modes 3, 4)
   float* dst_pre = nullptr;         // optional second output (M, coutp): the value before the activation (training keeps it)
@@ -152,6 +152,7 @@ struct GemmArgs {
   // (rows are samples of sq_hw pixels each; sq_nseg >= 31 / sq_hw + 2 segment places per block; the fused GRN plan, convnextv2_kernels.hip)
   float* sumsq = nullptr;
   int sq_hw = 0, sq_nseg = 0;
+  int tap_stride = 1;               // mode 6: row (b, oy, ox) of the (H / tap_stride) x (W / tap_stride) grid reads input pixel (tap_stride oy, tap_stride ox); 1 or 2
 };
 
 int launch_patch_stem(const PatchStemArgs& a, hipStream_t s);
@@ -209,6 +210,20 @@ struct WindowAttnF16Args {
 int launch_window_attn_f16(const WindowAttnF16Args& a, hipStream_t s);
 int launch_patch_merge_ln_f16(const void* src, const float* gamma, const float* beta, void* dst, int B, int H, int W, int c, float eps, hipStream_t s);
 int launch_gemm(const GemmArgs& a, hipStream_t s);
+// ResNet encoder (resnet_kernels.hip): the normalised 7x7 stride-2 stem conv as an im2col product on the fp32 matrix pipe, its 3x3 stride-2 max pool, add + ReLU
+struct ResnetStemArgs {
+  const void* src = nullptr;     // NCHW uint8 / float image
+  const float* wimg = nullptr;   // [N block of 32][step s < KH][lane]: W[co = 32 nb + (lane & 31)][k = s + KH (lane >> 5)], k = (ci, ky, kx) row-major, KH = ceil(49 cin / 2); zeros past cout / K
+  const float* bias = nullptr;   // >= coutp
+  float* conv_dst = nullptr;     // NHWC coutp, OH x OW
+  int dtype = 0, cin = 0, coutp = 0, B = 0, H = 0, W = 0, OH = 0, OW = 0, PH = 0, PW = 0;
+  float mean[4] = {0.f, 0.f, 0.f, 0.f};
+  float std[4] = {1.f, 1.f, 1.f, 1.f};
+};
+int64_t resnet_stem_weight_floats(int cin, int coutp);
+int launch_resnet_stem(const ResnetStemArgs& a, hipStream_t s);
+int launch_maxpool3s2(const float* src, float* dst, int B, int H, int W, int cp, hipStream_t s);  // MaxPool2d(k3, s2, p1): (B, H, W, cp) -> (B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, cp)
+int launch_add_relu(const float* x, const float* y, float* dst, size_t n, hipStream_t s);         // dst = relu(x + y)
 // ConvNeXtV2 (convnextv2_kernels.hip): the padding-0 patch stem with input statistics, and Global Response Normalization in two launches
 int launch_patch_stem_norm(const PatchStemArgs& a, hipStream_t s);
 struct GrnArgs {

@@ -257,7 +257,27 @@ int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
       p.offset = alloc(d.dst2, (int64_t)B * p.h * p.w * p.cp * bpc);
       continue;
     }
+    if (d.kind == PH_OP_RESNET_STEM) {  // dst: the stride-2 conv map (read by the op's own pool launch only), dst2: the pooled map
+      PH_REQUIRE(d.src0 < 0, "resnet stem must read the network input");
+      PH_REQUIRE(d.dst >= 0 && d.dst < m->n_slots && d.dst2 >= 0 && d.dst2 < m->n_slots && d.dst != d.dst2, "bad resnet stem slots");
+      SlotShape& f = plan.slots[d.dst];
+      f.c = d.cout; f.cp = fmt_cpad(fmt, d.cout); f.h = (h - 1) / 2 + 1; f.w = (w - 1) / 2 + 1; f.def_op = op_i;
+      f.offset = alloc(d.dst, (int64_t)B * f.h * f.w * f.cp * bpc);
+      SlotShape& p = plan.slots[d.dst2];
+      p.c = d.cout; p.cp = f.cp; p.h = (f.h - 1) / 2 + 1; p.w = (f.w - 1) / 2 + 1; p.def_op = op_i;
+      p.offset = alloc(d.dst2, (int64_t)B * p.h * p.w * p.cp * bpc);
+      continue;
+    }
     int oh = h, ow = w;
+    if (d.kind == PH_OP_CONV_S2) {
+      PH_REQUIRE(d.src0 >= 0 && h % 2 == 0 && w % 2 == 0, "a stride-2 conv needs an even map, got %dx%d: input H,W must be multiples of the model max stride", h, w);
+      oh = h / 2;
+      ow = w / 2;
+    } else if (d.kind == PH_OP_ADD_RELU) {
+      PH_REQUIRE(d.src0 >= 0 && d.src1 >= 0 && d.src1 < m->n_slots && plan.slots[d.src1].offset >= 0, "add: slot %d is not written yet", d.src1);
+      const SlotShape& s1 = plan.slots[d.src1];
+      PH_REQUIRE(s1.h == h && s1.w == w && s1.c == d.cout && plan.slots[d.src0].c == d.cout, "add: the two sources differ in shape");
+    }
     if (d.kind == PH_OP_PATCH_STEM) {
       PH_REQUIRE(d.src0 < 0, "patch stem must read the network input");
       const int pad2 = (d.flags & PH_FLAG_PAD0_NORM) ? 0 : 2;

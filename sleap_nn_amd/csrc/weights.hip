@@ -760,12 +760,48 @@ int forms_linear(PackCtx& c, PackedOp& op) {
   return PH_OK;
 }
 
+// ResNet stem, Conv2d(cin0 -> cout, k7, s2, p3) with BatchNorm folded in by the host: the im2col weight image of resnet_stem_conv_kernel,
+// [N block of 32][step s][lane] = W[co = 32 nb + (lane & 31)][k = s + KH (lane >> 5)] over k = (ci, ky, kx) row-major (the OIHW order itself), KH = ceil(49 cin / 2)
+int forms_resnet_stem(PackCtx& c, PackedOp& op) {
+  const ph_op_desc& d = op.d;
+  if (!c.has_weight_and_bias(d)) return c.fail("weight index out of range");
+  if (d.ksize != 7 || d.cin0 < 1 || d.cin0 > 4 || d.src0 >= 0 || d.dst2 < 0) return c.fail("resnet stem is a 7x7 stride-2 conv over the network input (1..4 channels) with a pooled slot");
+  const int K = 49 * d.cin0, KH = (K + 1) / 2, coutp = pad16(d.cout), nblk = (coutp + 31) / 32;
+  if (c.weight_numel[d.weight] != (int64_t)d.cout * K || c.weight_numel[d.bias] != d.cout) return c.fail("weight size mismatch");
+  auto pack_img = [&](const auto* w, auto& out) {
+    out.assign((size_t)resnet_stem_weight_floats(d.cin0, coutp), 0);
+    for (int nb = 0; nb < nblk; ++nb)
+      for (int st = 0; st < KH; ++st)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int co = nb * 32 + (lane & 31), k = st + KH * (lane >> 5);
+          if (co < d.cout && k < K) out[((size_t)nb * KH + st) * 64 + lane] = w[(size_t)co * K + k];
+        }
+  };
+  PH_TRY(c.pack(pack_img, d.weight, &op.w_dev));
+  return c.pack(pad_vec((size_t)nblk * 32, d.cout), d.bias, &op.b_dev);
+}
+
+// Conv2d(k in {1, 3}, stride 2, padding k / 2) as a row GEMM: the pack of the 3x3 stride-2 gather (mode 4, nine taps) or of the one-tap strided mode (mode 6)
+int forms_conv_s2(PackCtx& c, PackedOp& op) {
+  const ph_op_desc& d = op.d;
+  if (!c.has_weight_and_bias(d)) return c.fail("weight index out of range");
+  if ((d.ksize != 1 && d.ksize != 3) || d.src0 < 0 || d.src1 >= 0 || d.cin1 != 0) return c.fail("a stride-2 conv takes one source and kernel 1 or 3");
+  const int taps = d.ksize * d.ksize, coutp = pad16(d.cout);
+  if (c.weight_numel[d.weight] != (int64_t)d.cin0 * d.cout * taps || c.weight_numel[d.bias] != d.cout) return c.fail("weight size mismatch");
+  op.bn = gemm_choose_bn(coutp);
+  PH_TRY(c.pack([&](const auto* w, auto& out) { pack_gemm(w, d.cout, d.cin0, 0, taps, op.bn, out); }, d.weight, &op.w_dma_dev));
+  return c.pack(pad_vec(n_padded(coutp, op.bn), d.cout), d.bias, &op.b_dev);
+}
+
 int forms_op(PackCtx& c, PackedOp& op) {
   switch (op.d.kind) {
     case PH_OP_POOL:
     case PH_OP_UPSAMPLE:
     case PH_OP_GELU:
+    case PH_OP_ADD_RELU:
     case PH_OP_GLOBAL_MAXPOOL: return PH_OK;
+    case PH_OP_RESNET_STEM: return forms_resnet_stem(c, op);
+    case PH_OP_CONV_S2: return forms_conv_s2(c, op);
     case PH_OP_SCALE_ADD: return forms_scale_add(c, op);
     case PH_OP_STEM: return forms_stem(c, op);
     case PH_OP_CONV:

@@ -69,6 +69,8 @@ class TrainingModule:
             raise NotImplementedError(f"training a '{model.model_type}' model is not built here (BCE + Dice, masked smooth-L1 and mask targets): these model types are "
                                       "not trained with the MSE loss of the pose heads; use sleap_nn_amd.training.segmentation.SegmentationTrainingModule")
         self._pretrained = getattr(model, "backbone_type", None) == "pretrained"
+        if getattr(model, "is_resnet", False):
+            raise NotImplementedError("a 'pretrained' ResNet backbone is inference only on the MI355X path (BatchNorm runs folded into the convs; batch statistics are not built)")
         if self._pretrained and not pretrained_training:
             raise NotImplementedError("training a 'pretrained' (ConvNeXtV2) backbone is opt-in: TrainingModule(model, pretrained_training=True)")
         if freeze_encoder is not None and not self._pretrained:
