@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 128
+#define PH_VERSION 129
 
 /* error codes */
 #define PH_OK 0
@@ -362,6 +362,30 @@ int ph_model_debug_allocs(const ph_model* m, void** ptrs, int64_t* bytes, int32_
 /* Diagnostic (tools/gemm_bench.py): average milliseconds of one row-GEMM kernel variant on synthetic operands. */
 int ph_debug_gemm_bench(int32_t variant, int32_t M, int32_t K, int32_t N, int32_t mode, int32_t H, int32_t W,
                         int32_t act, int32_t iters, float* ms_out);
+
+/* Test support (tests/test_gpu_row_gemm.py), not a product path: ONE launch of the row GEMM (gemm_mfma_dma_kernel / gemm_mfma_dma_tile_kernel) on
+ * operands the caller owns, synchronised before it returns.  The host arrays go through the product's own packers; launch checks come back as error codes.
+ *   variant      0..4 = that tile variant (256x128, 256x96, 256x64, 256x32, 128x128; the pack's N tile must be the variant's), -1 = the library's own choice
+ *   mode ...     as the forward / backward routines set them: mode 0 Linear, 1 Conv2d k2 s2, 2 Conv2d 3x3 "same", 3 ConvTranspose2d(k3, s2, p1, op1) phase(s),
+ *                4 Conv2d 3x3 s2 p1, 5 Conv2d k x k "same", 6 Conv2d 1x1 at tap_stride with the residual before the activation.  M = output rows (modes 1, 4, 6:
+ *                pixels of the strided grid; mode 3: input pixels), H x W = the INPUT map.  act: 0 none, 1 ReLU, 2 GELU, 3 times GELU'(aux), 4 SiLU.
+ *   cin0, cin1, cout   true channel counts; every device tensor is NHWC with its channels padded to a multiple of 16 (pad channels of the sources: zeros)
+ *   bn           N tile of the weight pack (128, 96, 64, 32) or 0 = the one the library chooses for pad16(cout)
+ *   variant_used, bn_used   written by the call
+ *   src0, src1, residual, aux, dst, dst_pre, sumsq   device pointers; all but src0 and dst may be NULL where the mode allows
+ *   weight       host, canonical: (cout, cin0 + cin1, taps) -- taps = 1, 4 (ky, kx), 9 or k^2 (ky, kx) -- and for mode 3 the ConvTranspose2d weight (cin0, cout, 3, 3)
+ *                (all_phases: the four phases in one launch; else phase out_tap = 2 (oy & 1) + (ox & 1))
+ *   bias, scale, shift   host, cout floats; scale and shift may be NULL */
+typedef struct ph_gemm_case {
+  int32_t variant, mode, M, H, W, ksize, tap_stride, out_patch, out_tap, out_H, out_W, all_phases, act, affine_first, late_split, persist2, sq_hw, sq_nseg;
+  int32_t cin0, cin1, cout, bn;
+  int32_t variant_used, bn_used;
+  const float *src0, *src1, *residual, *aux;
+  float *dst, *dst_pre, *sumsq;
+  const float *weight, *bias, *scale, *shift;
+} ph_gemm_case;
+int32_t ph_gemm_case_size(void);
+int ph_debug_gemm_run(ph_gemm_case* c);
 
 /* Diagnostic (tools/row_wgrad_bench.py): average milliseconds of the row weight-gradient GEMM dW[n][k] = sum_m dY[m][n] X[m][k]
  * (Linear layers of the training step, train_kernels.h launch_row_wgrad) on synthetic operands, and the largest error of 64

@@ -120,6 +120,14 @@ class AugSample(C.Structure):
                 ("erase_x", C.c_int32), ("erase_h", C.c_int32), ("erase_w", C.c_int32), ("fill", C.c_int32 * 3), ("seed", C.c_uint32), ("pad_", C.c_int32)]
 
 
+class GemmCase(C.Structure):
+    """``struct ph_gemm_case`` (include/posehip.h): one row-GEMM launch of ph_debug_gemm_run (test support)."""
+
+    _fields_ = ([(n, C.c_int32) for n in ("variant", "mode", "M", "H", "W", "ksize", "tap_stride", "out_patch", "out_tap", "out_H", "out_W", "all_phases", "act", "affine_first",
+                                          "late_split", "persist2", "sq_hw", "sq_nseg", "cin0", "cin1", "cout", "bn", "variant_used", "bn_used")]
+                + [(n, C.c_void_p) for n in ("src0", "src1", "residual", "aux", "dst", "dst_pre", "sumsq", "weight", "bias", "scale", "shift")])
+
+
 AUG_FLIP, AUG_WARP, AUG_UNIFORM, AUG_GAUSS, AUG_CONTRAST, AUG_BRIGHTNESS, AUG_ERASE = 1, 2, 4, 8, 16, 32, 64
 
 
@@ -175,6 +183,8 @@ SIGNATURES = {
     "ph_model_debug_allocs": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64), _i32, C.POINTER(_i32)]),
     "ph_debug_gemm_bench": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float)]),
     "ph_debug_row_wgrad_bench": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ph_gemm_case_size": (_i32, []),
+    "ph_debug_gemm_run": (C.c_int, [C.POINTER(GemmCase)]),
     "ph_render_confmaps": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "ph_render_pafs": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "ph_render_class_maps": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp]),

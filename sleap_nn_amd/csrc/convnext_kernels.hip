@@ -1320,8 +1320,7 @@ int launch_gemm_variant(int variant, const GemmArgs& a_in, hipStream_t s) {
   return PH_OK;
 }
 
-int launch_gemm(const GemmArgs& a, hipStream_t s) {
-  int variant;
+int gemm_choose_variant(const GemmArgs& a) {
   switch (a.bn) {
     case 128: {
       // 256-row tiles (variant 0) or 128-row tiles (variant 4, ~5 % less efficient per tile): whichever wastes
@@ -1330,13 +1329,20 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
       const long b0 = (long)((a.M + 255) / 256) * nt, b4 = (long)((a.M + 127) / 128) * nt;
       const double e0 = (double)b0 / (double)((b0 + 255) / 256 * 256);
       const double e4 = 0.95 * (double)b4 / (double)((b4 + 255) / 256 * 256);
-      variant = e4 > e0 ? 4 : 0;
-      break;
+      return e4 > e0 ? 4 : 0;
     }
-    case 96: variant = 1; break;
-    case 64: variant = 2; break;
-    case 32: variant = 3; break;
-    default: set_error("launch_gemm: unsupported N tile %d", a.bn); return PH_E_INVALID;
+    case 96: return 1;
+    case 64: return 2;
+    case 32: return 3;
+    default: return -1;
+  }
+}
+
+int launch_gemm(const GemmArgs& a, hipStream_t s) {
+  const int variant = gemm_choose_variant(a);
+  if (variant < 0) {
+    set_error("launch_gemm: unsupported N tile %d", a.bn);
+    return PH_E_INVALID;
   }
   return launch_gemm_variant(variant, a, s);
 }

@@ -128,7 +128,7 @@ struct GemmArgs {
   const float* scale = nullptr;     // layer_scale (padded) or nullptr
   const float* residual = nullptr;  // (M, coutp) or nullptr
   float* dst = nullptr;             // (M, coutp)
-  const float* zeros = nullptr;     // >= 64 B of zeros in HBM
+  const float* zeros = nullptr;     // >= 128 B of zeros in HBM (a masked lane of the tile kernel reads 16 B at zeros + (lane >> 3) * 4 floats)
   int c0p = 0, c1p = 0, coutp = 0, bn = 0;
   int M = 0;                        // output rows
   int mode = 0;                     // 0: row = pixel (Linear); 1: 2x2/stride-2 patches; 2: 3x3 "same" conv; 3: transposed-conv phase; 4: 3x3 stride-2 gather; 5: k x k "same" conv; 6: one tap at a row stride, residual BEFORE the activation
@@ -210,6 +210,8 @@ struct WindowAttnF16Args {
 int launch_window_attn_f16(const WindowAttnF16Args& a, hipStream_t s);
 int launch_patch_merge_ln_f16(const void* src, const float* gamma, const float* beta, void* dst, int B, int H, int W, int c, float eps, hipStream_t s);
 int launch_gemm(const GemmArgs& a, hipStream_t s);
+int gemm_choose_variant(const GemmArgs& a);                              // the tile variant launch_gemm takes for a.bn / a.M / a.coutp (-1: no kernel for that N tile)
+int launch_gemm_variant(int variant, const GemmArgs& a, hipStream_t s);  // one named variant (PH_GEMM_VARIANTS in convnext_kernels.hip), under launch_gemm's checks
 // ResNet encoder (resnet_kernels.hip): the normalised 7x7 stride-2 stem conv as an im2col product on the fp32 matrix pipe, its 3x3 stride-2 max pool, add + ReLU
 struct ResnetStemArgs {
   const void* src = nullptr;     // NCHW uint8 / float image

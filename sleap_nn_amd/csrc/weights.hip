@@ -521,25 +521,26 @@ int forms_conv_c16(PackCtx& c, PackedOp& op) {
 // (input row y), odd rows ky = 0 (input row y + 1) and ky = 2 (row y) -- likewise in x: four output phases with
 // 1, 2, 2, 4 taps.  Each phase is one row GEMM over the input grid (mode 3) whose tap t reads input pixel
 // (y + dy, x + dx); weights per phase: wp[co][ci][t] = Wt[ci][co][ky(t)][kx(t)].  Then the folded BatchNorm and the data gradient (mode 4).
+template <typename T>
+void pack_convt_phase(const T* w, int cout, int cin, int ph, int bn, std::vector<T>& out) {  // the row-GEMM pack of output phase ph = 2 py + px from the IOHW (cin, cout, 3, 3) weight
+  const int py = ph >> 1, px = ph & 1, nt = (1 + py) * (1 + px);
+  std::vector<T> wp((size_t)cout * cin * nt);
+  for (int t = 0; t < nt; ++t) {
+    const int ty = px ? t >> 1 : t, tx = px ? t & 1 : 0;
+    const int ky = py ? 2 * ty : 1, kx = px ? 2 * tx : 1;  // tap t reads (y + 1 - ty, x + 1 - tx): ky = 0 <-> dy = 1
+    for (int co = 0; co < cout; ++co)
+      for (int ci = 0; ci < cin; ++ci) wp[((size_t)co * cin + ci) * nt + t] = w[(((size_t)ci * cout + co) * 3 + ky) * 3 + kx];
+  }
+  pack_gemm(wp.data(), cout, cin, 0, nt, bn, out);
+}
+
 int forms_convt_phases(PackCtx& c, PackedOp& op) {
   const ph_op_desc& d = op.d;
   const int coutp = pad16(d.cout);
   op.bn_t = gemm_choose_bn(coutp);
   const size_t npad_t = n_padded(coutp, op.bn_t);
-  for (int ph = 0; ph < 4; ++ph) {
-    const int py = ph >> 1, px = ph & 1, nt = (1 + py) * (1 + px);
-    auto pack_p = [&](const auto* w, auto& out) {
-      std::remove_reference_t<decltype(out)> wp((size_t)d.cout * d.cin0 * nt);
-      for (int t = 0; t < nt; ++t) {
-        const int ty = px ? t >> 1 : t, tx = px ? t & 1 : 0;
-        const int ky = py ? 2 * ty : 1, kx = px ? 2 * tx : 1;  // tap t reads (y + 1 - ty, x + 1 - tx): ky = 0 <-> dy = 1
-        for (int co = 0; co < d.cout; ++co)
-          for (int ci = 0; ci < d.cin0; ++ci) wp[((size_t)co * d.cin0 + ci) * nt + t] = w[(((size_t)ci * d.cout + co) * 3 + ky) * 3 + kx];
-      }
-      pack_gemm(wp.data(), d.cout, d.cin0, 0, nt, op.bn_t, out);
-    };
-    PH_TRY(c.pack(pack_p, d.weight, &op.wt_phase_dev[ph]));
-  }
+  for (int ph = 0; ph < 4; ++ph)
+    PH_TRY(c.pack([&](const auto* w, auto& out) { pack_convt_phase(w, d.cout, d.cin0, ph, op.bn_t, out); }, d.weight, &op.wt_phase_dev[ph]));
   PH_TRY(c.pack(pad_vec(npad_t, d.cout), d.bias, &op.bt_dev));
   if (d.weight2 >= 0) {  // folded BatchNorm (eval): y = act(scale * (conv + bias) + shift)
     if (!c.widx_ok(d.weight2) || !c.widx_ok(d.bias2) || c.weight_numel[d.weight2] != d.cout || c.weight_numel[d.bias2] != d.cout) return c.fail("transposed conv: scale / shift must be (cout)");
@@ -866,4 +867,92 @@ extern "C" ph_model* ph_model_create(const ph_op_desc* ops, int32_t n_ops, const
     return give_up();
   }
   return m;
+}
+
+extern "C" int32_t ph_gemm_case_size(void) { return (int32_t)sizeof(ph_gemm_case); }
+
+// Test support (tests/test_gpu_row_gemm.py), not a product path: one row-GEMM launch on operands the caller owns.  The canonical weight, bias, scale and shift go
+// through the product's own packers (pack_gemm, pack_convt_phase, pad_vec over n_padded), the launch through launch_gemm / launch_gemm_variant and their checks.
+extern "C" int ph_debug_gemm_run(ph_gemm_case* c) {
+  PH_REQUIRE(c && c->src0 && c->dst && c->weight && c->bias && c->M > 0 && c->cin0 > 0 && c->cin1 >= 0 && c->cout > 0, "ph_debug_gemm_run: bad arguments");
+  PH_REQUIRE(c->mode >= 0 && c->mode <= 6 && (c->mode != 5 || ((c->ksize & 1) && c->ksize >= 1 && c->ksize <= 9)) && (c->mode != 3 || (c->cin1 == 0 && c->out_tap >= 0 && c->out_tap < 4)),
+             "ph_debug_gemm_run: bad mode / kernel size / phase");
+  PH_REQUIRE(c->cin1 == 0 || c->src1, "ph_debug_gemm_run: second source missing");
+  if (prepare_convnext_kernels() != PH_OK) return PH_E_HIP;
+  const int coutp = pad16(c->cout);
+  const int bn = c->bn ? c->bn : gemm_choose_bn(coutp);
+  PH_REQUIRE(bn == 128 || bn == 96 || bn == 64 || bn == 32, "ph_debug_gemm_run: unsupported N tile %d", bn);
+  const size_t npad = n_padded(coutp, bn);
+  struct Owned {  // what the entry allocates, freed on every way out
+    std::vector<void*> p;
+    ~Owned() {
+      for (void* q : p) (void)hipFree(q);
+    }
+  } owned;
+  auto up = [&](const std::vector<float>& h, const float** dev) -> int {
+    void* p = nullptr;
+    PH_HIP_CHECK(hipMalloc(&p, std::max<size_t>(h.size(), 4) * sizeof(float)));
+    owned.p.push_back(p);
+    PH_HIP_CHECK(hipMemcpy(p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    *dev = static_cast<const float*>(p);
+    return PH_OK;
+  };
+  auto up_vec = [&](const float* src, const float** dev) -> int {
+    std::vector<float> h;
+    pad_vec(npad, c->cout)(src, h);
+    return up(h, dev);
+  };
+  GemmArgs g{};
+  std::vector<float> wp;
+  if (c->mode == 3) {  // the ConvTranspose2d weight (cin, cout, 3, 3): one phase, or the four of a one-launch transposed conv
+    for (int ph = 0; ph < 4; ++ph) {
+      if (!c->all_phases && ph != c->out_tap) continue;
+      pack_convt_phase(c->weight, c->cout, c->cin0, ph, bn, wp);
+      PH_TRY(up(wp, &g.wpack_ph[ph]));
+    }
+    g.wpack = g.wpack_ph[c->all_phases ? 0 : c->out_tap];
+    g.ntaps = (1 + (c->out_tap >> 1)) * (1 + (c->out_tap & 1));
+  } else {
+    const int taps = (c->mode == 0 || c->mode == 6) ? 1 : (c->mode == 1 ? 4 : (c->mode == 5 ? c->ksize * c->ksize : 9));
+    pack_gemm(c->weight, c->cout, c->cin0, c->cin1, taps, bn, wp);
+    PH_TRY(up(wp, &g.wpack));
+  }
+  PH_TRY(up_vec(c->bias, &g.bias));
+  if (c->scale) PH_TRY(up_vec(c->scale, &g.scale));
+  if (c->shift) PH_TRY(up_vec(c->shift, &g.shift));
+  PH_TRY(up(std::vector<float>(32, 0.f), &g.zeros));  // 128 B: the least GemmArgs::zeros allows
+  g.src0 = c->src0;
+  g.src1 = c->src1;
+  g.residual = c->residual;
+  g.aux = c->aux;
+  g.dst = c->dst;
+  g.dst_pre = c->dst_pre;
+  g.sumsq = c->sumsq;
+  g.c0p = pad16(c->cin0);
+  g.c1p = c->cin1 > 0 ? pad16(c->cin1) : 0;
+  g.coutp = coutp;
+  g.bn = bn;
+  g.M = c->M;
+  g.mode = c->mode;
+  g.H = c->H;
+  g.W = c->W;
+  g.act = c->act;
+  g.late_split = c->late_split;
+  g.persist2 = c->persist2;
+  g.all_phases = c->all_phases;
+  g.ksize = c->ksize;
+  g.affine_first = c->affine_first;
+  g.out_patch = c->out_patch;
+  g.out_tap = c->out_tap;
+  g.out_H = c->out_H;
+  g.out_W = c->out_W;
+  g.sq_hw = c->sq_hw;
+  g.sq_nseg = c->sq_nseg;
+  g.tap_stride = c->tap_stride;
+  const int variant = c->variant >= 0 ? c->variant : gemm_choose_variant(g);
+  c->bn_used = bn;
+  c->variant_used = variant;
+  const int rc = c->variant >= 0 ? launch_gemm_variant(variant, g, nullptr) : launch_gemm(g, nullptr);
+  PH_HIP_CHECK(hipDeviceSynchronize());
+  return rc;
 }
