@@ -93,7 +93,7 @@ def train_leg(cfg, B, global_batch, steps, warmup, ctx, scaling="weak"):
     def share(cin_p, cout_p, one_source=True, hw=(0, 0)):
         h, w = hw
         if cout_p >= 64 and cin_p >= 128 and h > 0 and h % 4 == 0 and w % 4 == 0:
-            # conv3x3_wino4_kernel (TrainingModule runs it in the training plan: conv_wino4 = 2) where wino4_fits estimates it faster: rounds of the chip x time per tile
+            # conv3x3_wino4_kernel (TrainingModule runs it in the training plan: conv_wino4 = 2) where the route (csrc/conv3x3_route.hip) estimates it faster: rounds of the chip x time per tile
             ntc, n_cu = -(-cout_p // 64), 256
             t4, t2 = -(-h // 16) * -(-w // 32) * B * ntc, -(-h // 16) * -(-w // 16) * B * ntc
             if -(-t4 // n_cu) * (2.0 / 1.3) <= -(-t2 // n_cu):

@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 129
+#define PH_VERSION 130
 
 /* error codes */
 #define PH_OK 0
@@ -352,6 +352,48 @@ int ph_render_seg_targets(const uint8_t* masks_dev, const int32_t* n_instances_d
  * under handle option conv_splitk = splitk (padded channel counts; section 4.1d of DESIGN.md).  out[0] = K slices on the F(2x2,3x3) kernel, out[1] = on the
  * F(4x4,3x3) kernel (1 = no split), out[2], out[3] = KiB of partial-sum scratch each would need (0 when it does not split). */
 int ph_debug_split_plan(int32_t B, int32_t H, int32_t W, int32_t cin_padded, int32_t cout_padded, int32_t splitk, int32_t n_cu, int64_t* out4);
+
+/* Diagnostic / test hook (pure host arithmetic, no GPU needed): the route of one exact-fp32 3x3 conv launch on a chip of n_cu CUs (csrc/conv3x3_route.h, DESIGN.md
+ * "Routing of the exact-fp32 3x3 conv").  The case is turned into launch arguments with dummy non-null pointers where a bit says the pointer exists; nothing is launched.
+ *   c0p, c1p, coutp, bn, B, H, W   padded channel counts, N tile (32 / 64), map
+ *   forms        PH_CRF_*: the weight forms that exist        flags   PH_CRA_*: the arguments of the launch (head_cout / head_wcp with PH_CRA_HEAD)
+ *   use_dma ... splitk   the option fields of the launch arguments, as the runtime fills them from the handle's options and the kind of plan
+ *   ptr_salt     varies the dummy pointers (the route may not depend on their values)
+ *   split_scratch_bytes   0 = the plan reserved no split-K scratch
+ * out: kernel = the ConvKernel (0 register-staged, 1 9-tap LDS-DMA, 2 F(2,3), 3 conv3x3_c16, 4 wave-private F(2x2,3x3), 5 wave-split F(2x2,3x3), 6 F(4x4,3x3), 7 small-map),
+ * kv = its PH_KV_* code, ksplit = K slices, props = PH_CRP_* bits. */
+#define PH_CRF_DMA 1
+#define PH_CRF_WINO 2
+#define PH_CRF_WINO2 4
+#define PH_CRF_W16 8
+#define PH_CRF_C16 16
+#define PH_CRF_WINO4 32
+#define PH_CRF_SM 64
+#define PH_CRA_SRC1 1
+#define PH_CRA_SRC1_LOWRES 2
+#define PH_CRA_POOL 4
+#define PH_CRA_SKIP_DST 8
+#define PH_CRA_ACCUMULATE 16
+#define PH_CRA_RELU_MASK 32
+#define PH_CRA_HEAD 64
+#define PH_CRP_MASK 1      /* stores plainly: applies a ReLU mask                      */
+#define PH_CRP_POOLS 2     /* writes the fused 2x2 max pool from its Winograd tiles    */
+#define PH_CRP_HEAD_W2D 4  /* may carry a 1x1 head: wave-split form                    */
+#define PH_CRP_HEAD_W16 8  /* ... wave-private form                                    */
+#define PH_CRP_LOWRES 16   /* folds a half-resolution second source                    */
+#define PH_CRP_HEAD_SM 32  /* may carry a 1x1 head: small-map form                     */
+typedef struct ph_conv_route_case {
+  int32_t c0p, c1p, coutp, bn, B, H, W;
+  int32_t forms, flags, head_cout, head_wcp;
+  int32_t use_dma, dma32, use_wino, persist, use_c16, use_w16, use_wino2d, use_wino4, wino4_min_cin, use_sm, splitk;
+  int32_t ptr_salt;
+  int64_t split_scratch_bytes;
+} ph_conv_route_case;
+typedef struct ph_conv_route_out {
+  int32_t kernel, kv, ksplit, props;
+} ph_conv_route_out;
+int32_t ph_conv_route_case_size(void);
+int ph_debug_conv3x3_route(const ph_conv_route_case* c, int32_t n_cu, ph_conv_route_out* out);
 
 /* Diagnostic / test hook: every device allocation the handle owns, in the order it was made (ph_model_create's packed weights, gather maps and derived forms,
  * then whatever later calls added: the lazy fp16 packs of the first fp16 forward, the tables of the first ph_model_set_params).  *n_rows = the number of

@@ -63,11 +63,11 @@ BR_WG_NONE, BR_WG_DIRECT, BR_WG_WINO, BR_WG_WINO16, BR_WG_ROWS9, BR_WG_ROWSKK, B
 BR_WG_NAMES = {BR_WG_NONE: "none", BR_WG_DIRECT: "launch_wgrad (32x32 tiles)", BR_WG_WINO: "launch_wgrad_wino", BR_WG_WINO16: "launch_wgrad16_wino",
                BR_WG_ROWS9: "nine row GEMMs (conv_wgrad_rows on a 3x3 conv)", BR_WG_ROWSKK: "k^2 row GEMMs (k x k conv)", BR_WG_INPUT: "launch_input_wgrad",
                BR_WG_PATCH_STEM: "launch_patch_stem_wgrad", BR_WG_CONVT_TAPS: "transposed-conv taps (nine gathered row GEMMs)", BR_WG_ROW_GEMM: "Linear / 2x2-stride-2 conv row GEMM"}
-# data-gradient route: 0 = none, a KV_* code below 32 = the LDS-DMA family's kernel (conv3x3_dma_variant), else one of
+# data-gradient route: 0 = none, a KV_* code below 32 = the LDS-DMA family's kernel (ConvRoute::kv), else one of
 BR_DG_NONE, BR_DG_REGSTAGED, BR_DG_GEMM5, BR_DG_GEMM4, BR_DG_GEMM0 = 0, 32, 33, 34, 35
 BR_DG_NAMES = {BR_DG_NONE: "none", BR_DG_REGSTAGED: "launch_conv3x3 (register-staged)", BR_DG_GEMM5: "row GEMM mode 5 (k x k taps)", BR_DG_GEMM4: "row GEMM mode 4 (3x3 stride 2)",
                BR_DG_GEMM0: "row GEMM mode 0 (Linear / 2x2-stride-2 conv)"}
-BR_DG_DMA_CODES = (KV_DIRECT, KV_WINO1D, KV_WINO2D, KV_W16, KV_C16, KV_WINO4, KV_WINO2D_KS)  # what conv3x3_dma_variant can return
+BR_DG_DMA_CODES = (KV_DIRECT, KV_WINO1D, KV_WINO2D, KV_W16, KV_C16, KV_WINO4, KV_WINO2D_KS)  # the kv of a ConvRoute in the LDS-DMA family
 BR_MASK_NONE, BR_MASK_OWN, BR_MASK_EARLIER = range(3)
 BR_MASK_NAMES = {BR_MASK_NONE: "none", BR_MASK_OWN: "this step (launch_relu_mask / launch_relu_mask_bias_grad)", BR_MASK_EARLIER: "an earlier step's stores (mask_fold)"}
 BR_BIAS_NONE, BR_BIAS_OWN, BR_BIAS_WITH_MASK, BR_BIAS_CLOSER, BR_BIAS_INPUT_WGRAD, BR_BIAS_ROW_WGRAD = range(6)
@@ -128,6 +128,19 @@ class GemmCase(C.Structure):
                 + [(n, C.c_void_p) for n in ("src0", "src1", "residual", "aux", "dst", "dst_pre", "sumsq", "weight", "bias", "scale", "shift")])
 
 
+class ConvRouteCase(C.Structure):
+    """``struct ph_conv_route_case`` (include/posehip.h): one exact-fp32 3x3 conv launch as ph_debug_conv3x3_route takes it (test support; launches nothing)."""
+
+    _fields_ = ([(n, C.c_int32) for n in ("c0p", "c1p", "coutp", "bn", "B", "H", "W", "forms", "flags", "head_cout", "head_wcp", "use_dma", "dma32", "use_wino", "persist", "use_c16",
+                                          "use_w16", "use_wino2d", "use_wino4", "wino4_min_cin", "use_sm", "splitk", "ptr_salt")] + [("split_scratch_bytes", C.c_int64)])
+
+
+class ConvRouteOut(C.Structure):
+    """``struct ph_conv_route_out``: the ConvKernel, its KV_* code, the K slices and the PH_CRP_* property bits."""
+
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "kv", "ksplit", "props")]
+
+
 AUG_FLIP, AUG_WARP, AUG_UNIFORM, AUG_GAUSS, AUG_CONTRAST, AUG_BRIGHTNESS, AUG_ERASE = 1, 2, 4, 8, 16, 32, 64
 
 
@@ -183,6 +196,8 @@ SIGNATURES = {
     "ph_model_debug_allocs": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64), _i32, C.POINTER(_i32)]),
     "ph_debug_gemm_bench": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float)]),
     "ph_debug_row_wgrad_bench": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ph_conv_route_case_size": (_i32, []),
+    "ph_debug_conv3x3_route": (C.c_int, [C.POINTER(ConvRouteCase), _i32, C.POINTER(ConvRouteOut)]),
     "ph_gemm_case_size": (_i32, []),
     "ph_debug_gemm_run": (C.c_int, [C.POINTER(GemmCase)]),
     "ph_render_confmaps": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),

@@ -50,6 +50,7 @@ struct BackwardCtx {
   // frozen prefix ("bwd_frozen_ops"): ops [0, frozen) get no step.  The program is in topological order, so nothing a frozen op reads is written by a trainable one:
   // the trainable ops still leave their data gradients in the frozen ops' output slots (the skips), and nobody reads them
   const int frozen;
+  const int n_cu;         // CUs of the device, read once per call (the data-gradient convs' routes)
   std::vector<int> branch_of;  // per op: row of the per-sample branch scales (ph_model_set_branch_scales) -- residual Linear i of the program, in program order --, else -1
   // per slot: the first op (program order = last in this sweep) that reads it, and the op that writes it; -1 = none
   std::vector<int> first_consumer, producer;
@@ -397,7 +398,6 @@ int conv3x3_dgrad(BackwardCtx& c, const PackedOp& op, int part, const ConvPart& 
   a.wpack_wino2 = op.wd_wino2_dev[part];
   a.wpack_w16 = op.wd_w16_dev[part];
   a.wpack_wino4 = op.wd_wino4_dev[part];
-  a.use_wino4 = m->conv_wino4 == 3 ? 2 : (m->conv_wino4 == 2 ? 1 : 0);  // (training plans keep every slot: the F(4x4,3x3) kernel runs in them only on request)
   a.w16 = op.wd16_dev;
   a.bias = op.zero_bias_dev;
   a.dst = c.G(p.src);
@@ -411,17 +411,17 @@ int conv3x3_dgrad(BackwardCtx& c, const PackedOp& op, int part, const ConvPart& 
   a.zeros = m->zeros_dev;
   a.dst_pool = nullptr;
   apply_conv_options(m, a);
-  if (!m->dgrad_wino) a.use_wino = 0;
+  apply_conv_plan_options(m, CONV_PLAN_DGRAD, a);  // (training plans keep every slot: the F(4x4,3x3) kernel runs in them only on request)
   a.accumulate = c.init[p.src];
-  const bool dma = m->use_dma && (a.bn == 64 || m->dma32);
   // this launch completes the gradient of a conv + ReLU output and its kernel has a lane-local epilogue: that ReLU's mask rides there
-  if (dma && c.relu_producer_closed_by(p.src, PH_OP_CONV, PH_OP_INPUT_CONV) && d.src0 != d.src1 && conv3x3_dma_honours_mask(a)) {
+  if (c.relu_producer_closed_by(p.src, PH_OP_CONV, PH_OP_INPUT_CONV) && d.src0 != d.src1 && conv3x3_route(a, c.n_cu).takes_mask) {
     a.relu_mask_src = c.A(p.src);
     c.masked[p.src] = 1;
     c.note(PH_BR_FOLDED_MASK);
   }
-  c.note_dgrad(part, dma ? conv3x3_dma_variant(a) : PH_BR_DG_REGSTAGED, a.accumulate != 0);
-  int rc = dma ? launch_conv3x3_dma(a, c.s) : launch_conv3x3(a, c.s);
+  const ConvRoute r = conv3x3_route(a, c.n_cu);
+  c.note_dgrad(part, r.kernel == CONV_REGSTAGED ? PH_BR_DG_REGSTAGED : r.kv, a.accumulate != 0);
+  int rc = launch_conv3x3_routed(a, r, c.s);
   if (rc != PH_OK) return rc;
   c.init[p.src] = 1;
   return PH_OK;
@@ -1026,8 +1026,11 @@ int ph_model_backward(ph_model* m, const void* input_dev, int32_t in_dtype, int3
     return PH_E_WORKSPACE;
   }
   const int n_ops = (int)m->ops.size();
+  int n_cu = 0;
+  rc = device_cu_count(&n_cu);
+  if (rc != PH_OK) return rc;
   BackwardCtx c{m, bp, batch, height, width, in_channels, in_dtype, input_dev, static_cast<const char*>(act_workspace_dev), static_cast<char*>(grad_workspace_dev), head_out_dev,
-                grads_flat_dev, s, m->profiling, std::max(0, std::min(m->bwd_frozen_ops, n_ops))};
+                grads_flat_dev, s, m->profiling, std::max(0, std::min(m->bwd_frozen_ops, n_ops)), n_cu};
   index_program(c);
   if (c.prof) PH_HIP_CHECK(hipEventRecord(m->bwd_ev[0], s));
   rc = bwd_losses(c, LossArgs{target_dev, loss_weights_host, sample_weights_dev, OhkmParams{ohkm_enabled, hard_to_easy_ratio, min_hard_keypoints, max_hard_keypoints, ohkm_loss_scale}, loss_dev});

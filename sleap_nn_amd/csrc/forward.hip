@@ -70,17 +70,10 @@ void conv_f16_common(const ForwardCtx& c, const PackedOp& op, int c0p, int H, in
   f.clock_probe = c.probe_block();
 }
 
-// the LDS-DMA kernel family, or the register-staged kernel where the options or the N tile keep a layer off it
-int launch_conv3x3_any(ForwardCtx& c, const ConvArgs& a) {
-  const bool dma = c.m->use_dma && (a.bn == 64 || c.m->dma32);
-  c.ran(dma ? conv3x3_dma_variant(a) : PH_KV_DIRECT);
-  return dma ? launch_conv3x3_dma(a, c.s) : launch_conv3x3(a, c.s);
-}
-
-int cu_count() {
-  int n_cu = 0;
-  if (device_cu_count(&n_cu) != PH_OK || n_cu <= 0) n_cu = 256;
-  return n_cu;
+// records and launches the kernel the route names
+int launch_routed(ForwardCtx& c, const ConvArgs& a, const ConvRoute& r) {
+  c.ran(r.kv);
+  return launch_conv3x3_routed(a, r, c.s);
 }
 
 // ---- network input
@@ -251,7 +244,7 @@ int fwd_conv_f16(ForwardCtx& c, const PackedOp& op, int up) {
     // conv3x3_f16_rows_kernel (row tiles, loader waves, weights L2 -> registers; f16_rows_kernels.hip) where its plan is estimated faster ("conv_f16_rows" 2: wherever
     // the shape fits).  A bilinear x2 in front of this conv that only feeds its second source was not launched (fwd_upsample): the kernel reads the
     // half-resolution tensor itself; if it does not take the layer, the tensor is produced now.
-    const int n_cu = cu_count();
+    const int n_cu = c.n_cu;
     bool on_rows = false;
     if (fmt == FMT_F16 && m->conv_f16_rows) {
       ConvF16Args r = f;
@@ -350,7 +343,7 @@ int resolve_deferred_up_f32(ForwardCtx& c, const ph_op_desc& d, int up, ConvArgs
   const size_t mark = c.mark();
   f.src1 = c.rd(u.src0);
   f.src1_lowres = 1;
-  if ((c.m->use_dma && conv3x3_dma_is_wino4(f)) || conv3x3_takes_sm(f)) {
+  if (conv3x3_route(f, c.n_cu).folds_lowres) {
     a = f;
     c.unnote(0, d.src1);  // (the half-resolution tensor took the up-sampled one's place)
     return PH_OK;
@@ -377,7 +370,7 @@ bool conv3x3_prefers_rowgemm(const ForwardCtx& c, const PackedOp& op, const Conv
   // the halo kernel runs Winograd F(2,3) (2/3 of the MFMA work) where its weights exist: it wins down to ~0.5 tile fill (measured on the ConvNeXt decoder: 48x48 and 24x24 maps)
   double halo_gain = (op.w_wino_dev && m->use_dma) ? m->gemm_fill_threshold / m->gemm_fill_threshold_wino : 1.0;
   double halo_fill = fill;
-  if (m->use_dma && m->conv_wino && m->conv_wino2d && m->conv_persist && op.w_wino2_dev && a.bn == 64 && a.c0p + a.c1p >= 32 && wino2d_fits(a)) {
+  if (conv3x3_wino2d_sets_rowgemm_fill(a)) {
     // the F(2x2,3x3) kernel: 16x16-pixel tiles and 4/9 of the MFMA work -- it beats the 9-tap row GEMM down to ~0.4 tile fill
     halo_fill = (double)s0.h * s0.w / ((double)((s0.h + 15) / 16 * 16) * ((s0.w + 15) / 16 * 16));
     halo_gain = m->gemm_fill_threshold / m->gemm_fill_threshold_wino2d;
@@ -387,16 +380,17 @@ bool conv3x3_prefers_rowgemm(const ForwardCtx& c, const PackedOp& op, const Conv
 
 // A 1x1 head that reads this conv's output rides in the epilogue of the F(2x2,3x3) kernel (the accumulator layout is the MFMA's B operand: conv3x3_wino2d_kernel), of the
 // wave-private kernel or of the small-map kernel.  (Eligibility is per kernel and on pad16 of the head's input channels: exact fp32 pads to 16, unlike the fp16 form.)
-void try_head_f32(ForwardCtx& c, const ph_op_desc& d, ConvArgs& a, bool on_sm) {
+void try_head_f32(ForwardCtx& c, const ph_op_desc& d, ConvArgs& a, const ConvRoute& rt) {
+  const bool on_sm = rt.kernel == CONV_SMALLMAP;
   if (!(c.m->head_fuse && !a.dst_pool && ((a.coutp == 64 && a.bn == 64) || ((a.coutp == 16 || a.coutp == 32) && a.bn == 32)) && c.m->use_dma)) return;
   const int j = find_head_reader(c, d.dst);
   if (j < 0) return;
   const ph_op_desc& hx = c.m->ops[j].d;
   ConvArgs no4 = a;  // (a fused head beats F(4x4,3x3) + a head launch on the 64-channel layers both could take: ask what runs without that kernel; head_w then keeps it off)
   no4.use_wino4 = 0;
-  const bool on_w2d = a.coutp == 64 && hx.cout <= 32 && pad16(hx.cin0) == 64 && conv3x3_dma_is_wino2d(no4) && wino2d_ksplit(no4) <= 1;
-  const bool on_w16 = a.coutp <= 32 && hx.cout <= 16 && pad16(hx.cin0) == a.coutp && conv3x3_dma_is_w16_head(a);  // (conv3x3_w16_kernel<.., HEAD>)
-  const bool sm_head = on_sm && a.coutp <= 32 && pad16(hx.cin0) == a.coutp;  // (conv3x3_sm_kernel: the workgroup holds every channel of its pixels)
+  const bool on_w2d = a.coutp == 64 && hx.cout <= 32 && pad16(hx.cin0) == 64 && conv3x3_family_route(no4, c.n_cu).head_w2d;
+  const bool on_w16 = a.coutp <= 32 && hx.cout <= 16 && pad16(hx.cin0) == a.coutp && conv3x3_family_route(a, c.n_cu).head_w16;  // (conv3x3_w16_kernel<.., HEAD>)
+  const bool sm_head = rt.head_sm && pad16(hx.cin0) == a.coutp;  // (conv3x3_sm_kernel: the workgroup holds every channel of its pixels)
   if (head_can_ride(c, hx) && (sm_head || (!on_sm && (on_w2d || on_w16)))) attach_head(c, a, j, a.coutp, d.dst);
 }
 
@@ -431,22 +425,20 @@ int fwd_conv3x3_f32(ForwardCtx& c, const PackedOp& op, int up) {
   a.w16 = op.w16_dev;
   a.zeros = m->zeros_dev;
   apply_conv_options(m, a);
+  apply_conv_plan_options(m, plan.reuse ? CONV_PLAN_INFERENCE : CONV_PLAN_TRAIN_FWD, a);
   a.wpack_sm = op.w_sm_dev;
-  a.use_sm = m->conv_smallmap >= 2 ? 2 : ((m->conv_smallmap == 1 && m->conv_splitk == 1 && plan.reuse && m->use_dma) ? 1 : 0);
   a.wpack_wino4 = op.w_wino4_dev;
-  a.use_wino4 = m->conv_wino4 == 3 ? 2 : ((m->conv_wino4 == 2 || (m->conv_wino4 == 1 && plan.reuse)) ? 1 : 0);
   // (the two round-4 routings below -- Cout-32 layers on the N-tile-64 kernels, split K -- apply to inference plans only: a training program's forward keeps the kernels its
   // gradient tests were pinned with.  The wave-private kernel's two-source (16 + 32 -> 16) and fused-head forms are NOT gated that way: they are shapes of conv_w16 itself and
   // run in every plan; tests/test_gpu_training.py's default network (filters 8, output stride 2: concat 16 + 32 -> 16) trains through the two-source form, its gradients are
   // compared with autograd's)
-  if (op.w_n64_dev && op.w_wino2_dev && op.w_wino_dev && (m->conv_n32_wino2d >= 2 || (m->conv_n32_wino2d == 1 && plan.reuse)) && m->use_dma && m->conv_wino && m->conv_wino2d && m->conv_persist && !w16_fits(a) && wino2d_fits(a)) {
+  if (op.w_n64_dev && op.w_wino2_dev && op.w_wino_dev && (m->conv_n32_wino2d >= 2 || (m->conv_n32_wino2d == 1 && plan.reuse)) && conv3x3_n64_swap_ok(a)) {
     // Cout 32, K >= 64 (and not a shape of the wave-private kernel): N tile 64 with its upper half empty -- the F(2x2,3x3) kernel skips the missing half's MFMAs
     a.bn = 64;
     a.wpack = op.w_n64_dev;
     a.bias = op.b_n64_dev;
     a.wpack_dma = nullptr;
   }
-  if (a.splitk == 1 && !plan.reuse) a.splitk = 0;
   if (plan.tmp_bytes > 0) {
     a.split_scratch = c.scratch();
     a.split_scratch_bytes = plan.tmp_bytes;
@@ -455,15 +447,17 @@ int fwd_conv3x3_f32(ForwardCtx& c, const PackedOp& op, int up) {
     int rc = resolve_deferred_up_f32(c, d, up, a);
     if (rc != PH_OK) return rc;
   }
-  const bool on_sm = conv3x3_takes_sm(a);  // small maps at small batches: (8 x 8 pixels, 16 channels) units, one launch, no split K (conv3x3_sm_kernel)
+  // Each answer below changes the arguments the next question is asked with.  The small-map kernel is decided here, once: the head and pool fusions do not move a layer on or off it
+  const ConvRoute rt = conv3x3_route(a, c.n_cu);
+  const bool on_sm = rt.kernel == CONV_SMALLMAP;
   if (!on_sm && conv3x3_prefers_rowgemm(c, op, a)) return launch_conv_rowgemm(c, op, a.src0, a.c0p, a.src1, a.c1p, a.dst, a.coutp, 2);
-  try_head_f32(c, d, a, on_sm);
+  try_head_f32(c, d, a, rt);
   if (!a.head_w && (a.bn == 64 || m->dma32) && fuses_pool(m, c.op_i())) {
     // An UNFUSED program (the training forward: the backward walks one op per activation) still gets the conv kernels' fused
     // 2x2 max pool: when the next op is the pool of this conv's output, the epilogue writes both tensors and the pool op is skipped.
     const ph_op_desc& nx = c.next_op()->d;
     a.dst_pool = c.wr(nx.dst);
-    if (conv3x3_dma_is_f2x2(a)) {  // the F(2x2,3x3) kernels (a Winograd tile is a pool window); other kernels keep the separate pool
+    if (conv3x3_family_route(a, c.n_cu).pools) {  // the F(2x2,3x3) kernels (a Winograd tile is a pool window); other kernels keep the separate pool
       c.pooled_by_conv = d.dst;
     } else {
       a.dst_pool = nullptr;
@@ -471,11 +465,10 @@ int fwd_conv3x3_f32(ForwardCtx& c, const PackedOp& op, int up) {
     }
   }
   if (a.split_scratch) c.note_tmp(1);  // (partial-sum planes of a split-K launch)
-  if (on_sm) {
-    c.ran(PH_KV_SMALLMAP);
-    return launch_conv3x3_sm(a, c.s);
-  }
-  return launch_conv3x3_any(c, a);
+  if (on_sm) return launch_routed(c, a, rt);
+  ConvArgs q = a;  // (the small-map kernel declined the layer above)
+  q.use_sm = 0;
+  return launch_routed(c, a, conv3x3_route(q, c.n_cu));
 }
 
 int fwd_conv(ForwardCtx& c, const PackedOp& op) {
@@ -607,7 +600,7 @@ int fwd_convt_stuffed(ForwardCtx& c, const PackedOp& op) {
   a.wpack_dma = op.w_dma_dev;
   a.zeros = m->zeros_dev;
   apply_conv_options(m, a);
-  return launch_conv3x3_any(c, a);
+  return launch_routed(c, a, conv3x3_route(a, c.n_cu));
 }
 
 int fwd_convt(ForwardCtx& c, const PackedOp& op) {
@@ -1160,7 +1153,10 @@ extern "C" int ph_model_forward(ph_model* m, const void* input_dev, int32_t in_d
   if (rc != PH_OK) return rc;
   m->last_variant.assign(m->ops.size(), PH_KV_NONE);
   m->last_rows_plan.assign(4 * m->ops.size(), 0);
-  ForwardCtx c{m, plan, fmt, 4 / plan.bpc, batch, height, width, in_channels, in_dtype, input_dev, ws, out_dev, s, m->last_variant.data(), m->last_ranges};
+  int n_cu = 0;
+  rc = device_cu_count(&n_cu);
+  if (rc != PH_OK) return rc;
+  ForwardCtx c{m, plan, fmt, 4 / plan.bpc, batch, height, width, in_channels, in_dtype, input_dev, ws, out_dev, s, m->last_variant.data(), n_cu, m->last_ranges};
   c.head_done.assign(m->ops.size(), 0);
   c.conv_done.assign(m->ops.size(), 0);
   for (const PackedOp& op : m->ops) {

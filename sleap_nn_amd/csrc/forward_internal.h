@@ -21,6 +21,7 @@ struct ForwardCtx {
   float* const* const out_dev;
   const hipStream_t s;
   int* const kv;      // PH_KV_* code per op (m->last_variant)
+  const int n_cu;     // CUs of the device, read once per call: what every routing estimate of the call is made with
 
   // ---- the range recorder.  Every slot pointer that goes into a launcher's arguments is taken through rd() (a source) or wr() (a destination), which note the slot's
   // byte range under the current op and launch (ph_model_last_ranges): the record follows the routing, whatever it decides.

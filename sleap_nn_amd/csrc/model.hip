@@ -57,7 +57,22 @@ void apply_conv_options(const ph_model* m, ConvArgs& a) {
   a.split_counters = m->split_counters_dev;
   a.split_counters_n = m->split_counters_dev ? 4096 : 0;  // (units; the buffer holds three words per unit)
   a.splitk_finish = m->conv_splitk_finish;
-  a.use_sm = 0;  // (ph_model_forward: the kind of plan decides)
+  a.use_sm = 0;  // (apply_conv_plan_options: the kind of plan decides)
+  a.use_dma = m->use_dma;
+  a.dma32 = m->dma32;
+}
+
+// The options whose meaning depends on the plan a launch belongs to.  The F(4x4,3x3) kernel, the small-map kernel and the automatic K split are routings of inference
+// plans (they were measured there; a training program's forward keeps the kernels its gradient tests were pinned with) unless the option asks for every plan.
+void apply_conv_plan_options(const ph_model* m, ConvPlanKind kind, ConvArgs& a) {
+  const bool inference = kind == CONV_PLAN_INFERENCE;
+  a.use_wino4 = m->conv_wino4 == 3 ? 2 : ((m->conv_wino4 == 2 || (m->conv_wino4 == 1 && inference)) ? 1 : 0);
+  if (kind == CONV_PLAN_DGRAD) {  // (no small-map kernel: it has no accumulate / mask form; splitk stays as set: a data-gradient conv gets no split scratch)
+    if (!m->dgrad_wino) a.use_wino = 0;
+    return;
+  }
+  a.use_sm = m->conv_smallmap >= 2 ? 2 : ((m->conv_smallmap == 1 && m->conv_splitk == 1 && inference && m->use_dma) ? 1 : 0);
+  if (a.splitk == 1 && !inference) a.splitk = 0;
 }
 
 int drain_events(ph_model* m) {
@@ -127,6 +142,40 @@ int ph_debug_split_plan(int32_t B, int32_t H, int32_t W, int32_t cin_padded, int
   out4[1] = ((H & 3) || (W & 3)) ? 1 : wino4_ksplit_shape(B, H, W, cin_padded, cout_padded, splitk, n_cu);
   out4[2] = wino2d_split_scratch_bytes(B, H, W, cin_padded, cout_padded, splitk, n_cu) / 1024;
   out4[3] = wino4_split_scratch_bytes(B, H, W, cin_padded, cout_padded, splitk, n_cu) / 1024;
+  return PH_OK;
+}
+
+int32_t ph_conv_route_case_size(void) { return (int32_t)sizeof(ph_conv_route_case); }
+
+int ph_debug_conv3x3_route(const ph_conv_route_case* c, int32_t n_cu, ph_conv_route_out* out) {
+  PH_REQUIRE(c && out && n_cu > 0 && c->B > 0 && c->H > 0 && c->W > 0 && c->c0p > 0 && c->c1p >= 0 && c->coutp > 0 && (c->bn == 32 || c->bn == 64), "ph_debug_conv3x3_route: bad arguments");
+  float* const p = reinterpret_cast<float*>((uintptr_t)4096 * (uintptr_t)(1 + (c->ptr_salt & 0xFFFF)));  // never read: the route looks at which pointers are null
+  auto have = [&](int32_t word, int32_t bit) { return (word & bit) ? p : nullptr; };
+  ConvArgs a{};
+  a.src0 = a.wpack = a.bias = a.zeros = p;
+  a.dst = p;
+  a.c0p = c->c0p, a.c1p = c->c1p, a.coutp = c->coutp, a.bn = c->bn, a.B = c->B, a.H = c->H, a.W = c->W;
+  a.relu = 1;
+  a.wpack_dma = have(c->forms, PH_CRF_DMA), a.wpack_wino = have(c->forms, PH_CRF_WINO), a.wpack_wino2 = have(c->forms, PH_CRF_WINO2), a.wpack_w16 = have(c->forms, PH_CRF_W16);
+  a.w16 = have(c->forms, PH_CRF_C16), a.wpack_wino4 = have(c->forms, PH_CRF_WINO4), a.wpack_sm = have(c->forms, PH_CRF_SM);
+  a.src1 = have(c->flags, PH_CRA_SRC1);
+  a.src1_lowres = (c->flags & PH_CRA_SRC1_LOWRES) ? 1 : 0;
+  a.dst_pool = have(c->flags, PH_CRA_POOL);
+  a.skip_dst = (c->flags & PH_CRA_SKIP_DST) ? 1 : 0;
+  a.accumulate = (c->flags & PH_CRA_ACCUMULATE) ? 1 : 0;
+  a.relu_mask_src = have(c->flags, PH_CRA_RELU_MASK);
+  a.head_w = a.head_b = have(c->flags, PH_CRA_HEAD);
+  a.head_dst = have(c->flags, PH_CRA_HEAD);
+  a.head_cout = c->head_cout, a.head_wcp = c->head_wcp;
+  if (c->split_scratch_bytes > 0) a.split_scratch = p, a.split_scratch_bytes = c->split_scratch_bytes;
+  a.use_dma = c->use_dma, a.dma32 = c->dma32, a.use_wino = c->use_wino, a.persist = c->persist, a.use_c16 = c->use_c16, a.use_w16 = c->use_w16, a.use_wino2d = c->use_wino2d;
+  a.use_wino4 = c->use_wino4, a.wino4_min_cin = c->wino4_min_cin, a.use_sm = c->use_sm, a.splitk = c->splitk;
+  const ConvRoute r = conv3x3_route(a, n_cu);
+  out->kernel = (int32_t)r.kernel;
+  out->kv = r.kv;
+  out->ksplit = r.ksplit;
+  out->props = (r.takes_mask ? PH_CRP_MASK : 0) | (r.pools ? PH_CRP_POOLS : 0) | (r.head_w2d ? PH_CRP_HEAD_W2D : 0) | (r.head_w16 ? PH_CRP_HEAD_W16 : 0) |
+               (r.folds_lowres ? PH_CRP_LOWRES : 0) | (r.head_sm ? PH_CRP_HEAD_SM : 0);
   return PH_OK;
 }
 

@@ -9,6 +9,7 @@
 #include "convnext_f16_kernels.h"
 #include "f16_kernels.h"
 #include "net_kernels.h"
+#include "conv3x3_route.h"
 
 namespace ph {
 
@@ -180,7 +181,7 @@ struct ph_model {
   int conv_wino = 1;                          // "conv_wino": Winograd F(2,3) 3x3 kernels (2: N-tile-64 layers only, 0: direct 9-tap kernels)
   int conv_w16 = 1;                           // "conv_w16": Cout-32 / Cin-16-or-32 3x3 convs on the wave-private F(2x2,3x3) kernel
   int conv_wino2d = 1;                        // "conv_wino2d": N-tile-64 3x3 convs on the F(2x2,3x3) kernel (0: the F(2,3)-along-x kernel)
-  int conv_wino4 = 1;                         // "conv_wino4": K-heavy N-tile-64 3x3 convs on the F(4x4,3x3) kernel: 1 in inference plans (workspace_reuse), 2 in every plan -- both where wino4_fits estimates it faster than F(2x2,3x3) --, 3 every plan and wherever the shape fits, 0 never
+  int conv_wino4 = 1;                         // "conv_wino4": K-heavy N-tile-64 3x3 convs on the F(4x4,3x3) kernel: 1 in inference plans (workspace_reuse), 2 in every plan -- both where the route estimates it faster than F(2x2,3x3) (conv3x3_route.hip) --, 3 every plan and wherever the shape fits, 0 never
   int conv_wino4_min_cin = 64;                // "conv_wino4_min_cin": padded input channels (both sources) from which a layer takes that kernel
   int conv_n32_wino2d = 1;                    // "conv_n32_wino2d" (1: inference plans, 2: every plan, 0: never): Cout-32 layers with >= 64 input channels (the last decoder level of an output-stride-2 UNet: 96 -> 32) on the F(2x2,3x3) kernel with a half-empty N tile of 64 instead of the N-tile-32 F(2,3) kernel
   int block_fuse = 1;                         // "block_fuse"
@@ -248,6 +249,8 @@ int ensure_f16_weights(ph_model* m, int plain, hipStream_t s);                  
 int refresh_stale_weights(ph_model* m, const Plan& plan, hipStream_t s);            // the forms ph_model_set_params left stale, before the first forward that reads them
 int refresh_derived(ph_model* m, const float* params_flat_dev, hipStream_t s);      // the derived-form half of ph_model_set_params (+ the GRN bias fold)
 void apply_conv_options(const ph_model* m, ConvArgs& a);
+enum ConvPlanKind { CONV_PLAN_INFERENCE, CONV_PLAN_TRAIN_FWD, CONV_PLAN_DGRAD };  // whose launch: an inference plan's forward (workspace_reuse), a training plan's forward, a data gradient
+void apply_conv_plan_options(const ph_model* m, ConvPlanKind kind, ConvArgs& a);  // after apply_conv_options: conv_wino4 / conv_smallmap / conv_splitk / dgrad_wino as that kind of launch reads them
 // Whether head op `d` applies its sigmoid epilogue in `plan`.  A head whose loss is PH_LOSS_BCE_DICE emits LOGITS in the plans a backward can follow
 // (exact fp32, every activation kept): the loss kernel supervises the logit, as the reference's training_step does (lightning_modules.py:3052-3075).
 inline int head_sigmoid(const ph_model* m, const Plan& plan, const ph_op_desc& d) {

@@ -31,7 +31,7 @@ struct ConvArgs {
   int use_wino2d = 1;  // N-tile-64 layers on the F(2x2,3x3) kernel where wpack_wino2 exists (handle option "conv_wino2d")
   const float* w16 = nullptr;  // [tap][ci 16][co 16] weights for conv3x3_c16_kernel (16 -> 16 channel layers), or nullptr
   int skip_dst = 0;           // the full-resolution output is never read (inference plan, fused pool): only dst_pool is written (Winograd kernels; others ignore it)
-  const float* relu_mask_src = nullptr;  // backward: NHWC tensor shaped like dst (the forward activation this gradient belongs to); the stored value is zeroed where it is <= 0 (the Winograd kernels' plain stores: ask conv3x3_dma_honours_mask)
+  const float* relu_mask_src = nullptr;  // backward: NHWC tensor shaped like dst (the forward activation this gradient belongs to); the stored value is zeroed where it is <= 0 (the Winograd kernels' plain stores: ConvRoute::takes_mask)
   // fused 1x1 head (conv3x3_wino2d_kernel, Cout = one N tile of 64): head_dst[b][o][y][x] = (sigmoid)(sum_c head_w[o][c] * out[y][x][c] + head_b[o]), NCHW fp32
   const float* head_w = nullptr;  // [head_cout][head_wcp] row-major (the head op's own weight layout), or nullptr = no fused head
   const float* head_b = nullptr;  // [head_cout]
@@ -61,6 +61,9 @@ struct ConvArgs {
   float* fin_dst_pool = nullptr;
   const float* fin_bias = nullptr;
   int fin_relu = 0;
+  // which family runs the layer at all (handle options "conv_dma" / "conv_dma32"): the register-staged kernel is a route like the others (conv3x3_route.h)
+  int use_dma = 1;            // 0: the register-staged 3x3 kernel instead of the LDS-DMA family
+  int dma32 = 1;              // 0: ... for the N-tile-32 layers
 };
 
 struct InputConvArgs {
@@ -283,26 +286,19 @@ int launch_wino_pack_multi(const PackSegment* seg_dev, int n_seg, unsigned total
 int launch_wino2d_pack_multi(const PackSegment* seg_dev, int n_seg, unsigned total_blocks, hipStream_t s);  // F(2x2,3x3) buffers
 int launch_stem_wino_pack(const float* w1, float* w1w, hipStream_t s);
 int launch_stem_wino2d_pack(const float* w1, float* w2, hipStream_t s);  // [tap][co][ci] -> [position 16][co][ci]  // [tap][co][ci] -> [kernel row][m index][co][ci]
-int launch_conv3x3_dma(const ConvArgs& a, hipStream_t s);
-bool conv3x3_dma_honours_mask(const ConvArgs& a);  // launch_conv3x3_dma would run a kernel that applies relu_mask_src
-bool conv3x3_dma_is_f2x2(const ConvArgs& a);       // launch_conv3x3_dma would run one of the two F(2x2,3x3) kernels
-bool conv3x3_dma_is_wino2d(const ConvArgs& a);     // ... the wave-split one (takes a fused head on a 64-channel output)
-bool conv3x3_dma_is_w16_head(const ConvArgs& a);   // ... the wave-private one on a shape whose 1x1 head (<= 16 channels) can ride in its epilogue
-int conv3x3_dma_variant(const ConvArgs& a);        // PH_KV_* code (posehip.h) of the kernel launch_conv3x3_dma would run
+// (which kernel runs a 3x3 conv, and the launcher over that decision: conv3x3_route.h.  The *_fits / *_shape_ok predicates below mean only "this kernel can run these arguments")
 // wpack [panel][tap 9][bn][16] -> F(2x2,3x3) weights [panel][g 2][xi 4][nu 4][n tile][lh][lx][4] (see conv3x3_wino2d_kernel)
 int launch_wino2d_pack(const float* wpack, float* wino, int panels, int bn, hipStream_t s);
 int64_t wino2d_pack_floats(int panels, int bn);
-int launch_conv3x3_wino2d(const ConvArgs& a, hipStream_t s);
+int launch_conv3x3_wino2d(const ConvArgs& a, hipStream_t s, int ksplit = 1);  // ksplit: ConvRoute::ksplit
 // wpack [panel][tap 9][64][16] -> F(4x4,3x3) weights [n tile][quarter][wave][fragment slot][lane] (see conv3x3_wino4_kernel)
 // (coutp: the layer's padded output channel count, ConvArgs::coutp of its launches -- the channel order inside the last N tile depends on it)
 int launch_wino4_pack(const float* wpack, float* wino, int coutp, int nchunks, hipStream_t s);
 int64_t wino4_pack_floats(int ntiles, int nchunks);
-int launch_conv3x3_wino4(const ConvArgs& a, hipStream_t s);
-bool wino4_fits(const ConvArgs& a);
-bool conv3x3_dma_is_wino4(const ConvArgs& a);      // launch_conv3x3_dma would run the F(4x4,3x3) kernel (the only one that folds a half-resolution src1)
+int launch_conv3x3_wino4(const ConvArgs& a, hipStream_t s, int ksplit = 1);  // ksplit: ConvRoute::ksplit
+bool wino4_shape_ok(const ConvArgs& a);
 int prepare_wino4_kernels();
 bool wino2d_fits(const ConvArgs& a);  // sources addressable through the kernel's 32-bit buffer descriptors
-int wino2d_ksplit(const ConvArgs& a);  // K slices launch_conv3x3_wino2d would use for this launch (1 = the one-stage kernel)
 int launch_splitk_reduce(const float* part, long long stride, int ks, const float* bias, float* dst, float* dst_pool, int B, int H, int W, int coutp, int relu, hipStream_t s);
 int wino4_ksplit_shape(int B, int H, int W, int cinp, int coutp, int splitk, int n_cu);            // K slices the F(4x4,3x3) kernel would take
 int64_t wino4_split_scratch_bytes(int B, int H, int W, int cinp, int coutp, int splitk, int n_cu);
@@ -314,7 +310,7 @@ int launch_w16_pack(const float* wpack, float* w16, int chunks, int nbs, hipStre
 int64_t w16_pack_floats(int chunks, int nbs);
 int launch_conv3x3_w16(const ConvArgs& a, hipStream_t s);
 bool w16_fits(const ConvArgs& a);
-bool w16_takes_head(const ConvArgs& a);  // the wave-private kernel would run this launch and can carry a fused 1x1 head (<= 16 head channels, head_wcp = coutp)
+bool w16_takes_head(const ConvArgs& a);  // the wave-private kernel can run this launch and carry a fused 1x1 head (<= 16 head channels, head_wcp = coutp)
 bool w16_shape_ok(int c0p, int c1p, int coutp);  // channel counts the wave-private kernel takes (c1p = 0: one source)
 int prepare_w16_kernels();
 // wpack [n tile][chunk][tap 9][bn][16] -> small-map F(2x2,3x3) weights [N block of 16][chunk of 32][pair][wave][half][lane][4] (see conv3x3_sm_kernel)
@@ -323,7 +319,6 @@ int64_t sm_pack_floats(int nblocks, int chunks16);
 int launch_conv3x3_sm(const ConvArgs& a, hipStream_t s);
 bool sm_fits(const ConvArgs& a);
 double sm_cost_us(const ConvArgs& a, int n_cu);
-bool conv3x3_takes_sm(const ConvArgs& a);  // the small-map kernel runs this launch (inference plans: where its estimate beats the kernel launch_conv3x3_dma would pick); it also folds a half-resolution src1
 int launch_input_conv(const InputConvArgs& a, hipStream_t s);
 int launch_pool(const float* src, float* dst, int B, int H, int W, int cp, hipStream_t s);
 int launch_upsample(const float* src, float* dst, int B, int H, int W, int cp, hipStream_t s);

@@ -19,6 +19,7 @@
 #include "act_format.h"
 #include "common.h"
 #include "net_kernels.h"
+#include "conv3x3_route.h"
 #include "f16_kernels.h"
 
 namespace ph {
@@ -1303,85 +1304,23 @@ static int launch_conv3x3_c16(const ConvArgs& a, hipStream_t s) {
 
 static int cu_count(int* out) { return device_cu_count(out); }
 
-// Kernel choice for a 3x3 "same" conv on the LDS-DMA family.  Which variant runs is decided by fields of `a` that the
-// model runtime fills from the handle's options (ph_model_set_option); there is no process-global state here.
-// which kernel launch_conv3x3_dma picks: 4 F(4x4,3x3), 1 wave-private F(2x2,3x3), 0 conv3x3_c16, 2 wave-split F(2x2,3x3), 3 the F(2,3) / direct halo kernels
-static int conv3x3_dma_route(const ConvArgs& a) {
-  const bool wino = a.use_wino && a.wpack_wino && (a.bn == 64 || a.use_wino != 2);  // use_wino 2: Winograd for the N-tile-64 layers only
-  if (wino && a.persist && a.use_wino4 && a.c0p + a.c1p >= a.wino4_min_cin && wino4_fits(a)) return 4;
-  if (wino && a.persist && a.use_w16 && w16_fits(a)) return 1;
-  if (a.use_c16 && a.w16 && a.c0p == 16 && a.coutp == 16 && !a.src1 && !a.dst_pool) return 0;
-  if (wino && a.persist && a.use_wino2d && a.wpack_wino2 && a.bn == 64 && a.c0p + a.c1p >= 32 && wino2d_fits(a)) return 2;
-  return 3;
-}
-// The small-map kernel (conv3x3_sm_kernel) against the kernel launch_conv3x3_dma would run, both priced in microseconds of launch body as in wino4_fits (rounds of the chip x unit time,
-// + ~8 us per extra launch: a split-K second stage, a bilinear x2 the other kernel cannot fold).  use_sm = 2 forces it wherever the shape fits (tests, A/B).
-bool conv3x3_takes_sm(const ConvArgs& a) {
-  if (!a.use_sm || !sm_fits(a)) return false;
-  if (a.use_sm >= 2) return true;
-  int n_cu = 0;
-  if (device_cu_count(&n_cu) != PH_OK || n_cu <= 0) n_cu = 256;
-  ConvArgs hi = a;  // what runs otherwise takes the up-sampled tensor, unless it is the F(4x4,3x3) kernel
-  hi.src1_lowres = 0;
-  const int r = a.src1_lowres && conv3x3_dma_route(a) == 4 ? 4 : conv3x3_dma_route(hi);
-  const double extra = (a.src1_lowres && r != 4) ? 6.0 : 0.0;
-  const double Qn = (a.c0p + a.c1p) / 4.0;
-  const long ntc = (a.coutp + 63) / 64;
-  const bool may_split = a.split_scratch != nullptr;
-  double other;
-  if (r == 4) {
-    const int ks = may_split ? wino4_ksplit_shape(a.B, a.H, a.W, a.c0p + a.c1p, a.coutp, a.splitk, n_cu) : 1;
-    const long t4 = (long)((a.H + 15) / 16) * ((a.W + 31) / 32) * a.B * ntc;
-    other = (double)((t4 * ks + n_cu - 1) / n_cu) * (11.0 + 1.5 * Qn / ks) + (ks > 1 ? 8.0 : 0.0);
-  } else if (r == 2) {
-    const int ks = may_split ? wino2d_ksplit_shape(a.B, a.H, a.W, a.c0p + a.c1p, a.coutp, a.splitk, n_cu) : 1;
-    const long t2 = (long)((a.H + 15) / 16) * ((a.W + 15) / 16) * a.B * ntc;
-    other = (double)((t2 * ks + n_cu - 1) / n_cu) * (8.0 + 1.0 * Qn / ks) + (ks > 1 ? 8.0 : 0.0);
-  } else if (r == 1) {  // the wave-private kernel: 16 x 32-pixel tiles, ~9 us + 3 us per 16 input channels (cfg1's 128 x 128 levels: 32 workgroups, 9 - 15 us)
-    const long t1 = (long)((a.H + 31) / 32) * ((a.W + 15) / 16) * a.B;
-    other = (double)((t1 + n_cu - 1) / n_cu) * (6.0 + 3.0 * (a.c0p + a.c1p) / 16.0);
-  } else {
-    return false;  // the 16 -> 16 / F(2,3) / direct kernels keep their layers
-  }
-  if ((r == 4 || r == 2) && (a.coutp & 63) != 0 && (a.coutp & 63) <= 32) other *= 0.6;  // the half-empty N tile: the waves of the missing half skip their MFMAs (published workload, 96 -> 32 at 160 x 280 x 4: 55 us measured, 94 modelled)
-  return sm_cost_us(a, n_cu) < other + extra;
-}
-bool conv3x3_dma_honours_mask(const ConvArgs& a) {  // the three F(2x2,3x3) / F(4x4,3x3) kernels store lane-locally; the fused pool / head epilogues are forward-only
-  const int r = conv3x3_dma_route(a);
-  return (r == 1 || r == 2 || r == 4) && !a.dst_pool && !a.head_w && !a.skip_dst;
-}
-bool conv3x3_dma_is_f2x2(const ConvArgs& a) { const int r = conv3x3_dma_route(a); return r == 1 || r == 2; }
-bool conv3x3_dma_is_wino2d(const ConvArgs& a) { return conv3x3_dma_route(a) == 2; }
-bool conv3x3_dma_is_wino4(const ConvArgs& a) { return conv3x3_dma_route(a) == 4; }
-bool conv3x3_dma_is_w16_head(const ConvArgs& a) { return conv3x3_dma_route(a) == 1 && w16_takes_head(a); }
-// PH_KV_* code of the kernel launch_conv3x3_dma would run (ph_model_last_kernels)
-int conv3x3_dma_variant(const ConvArgs& a) {
-  switch (conv3x3_dma_route(a)) {
-    case 0: return PH_KV_C16;
-    case 1: return PH_KV_W16;
-    case 2: return wino2d_ksplit(a) > 1 ? PH_KV_WINO2D_KS : PH_KV_WINO2D;
-    case 4: return PH_KV_WINO4;
-    default: break;
-  }
-  const bool wino = a.use_wino && a.wpack_wino && (a.bn == 64 || a.use_wino != 2);
-  return (a.persist && wino) ? PH_KV_WINO1D : PH_KV_DIRECT;
-}
-
-int launch_conv3x3_dma(const ConvArgs& a, hipStream_t s) {
-  const int route = conv3x3_dma_route(a);
-  PH_REQUIRE(!a.relu_mask_src || ((route == 1 || route == 2 || route == 4) && !a.dst_pool && !a.head_w && !a.skip_dst),
-             "relu_mask_src is applied by the F(2x2,3x3) / F(4x4,3x3) kernels' plain stores only (ask conv3x3_dma_honours_mask first)");
-  PH_REQUIRE(!a.head_w || (route == 2 && !a.dst_pool && a.coutp == 64 && a.bn == 64 && a.head_cout >= 1 && a.head_cout <= 32 && a.head_wcp == 64 && a.head_b && a.head_dst) ||
-                 (route == 1 && w16_takes_head(a) && a.head_cout >= 1 && a.head_cout <= 16 && a.head_wcp == a.coutp && a.head_b && a.head_dst),
-             "a fused head needs the F(2x2,3x3) kernel on 64 output channels (<= 32 head channels) or the wave-private kernel on 16 -> 16 / 32 -> 32 channels (<= 16 head channels): ask conv3x3_dma_is_wino2d / _is_w16_head first");
-  if (route == 1) return launch_conv3x3_w16(a, s);
-  if (route == 0) return launch_conv3x3_c16(a, s);
-  if (route == 2) return launch_conv3x3_wino2d(a, s);
-  if (route == 4) return launch_conv3x3_wino4(a, s);
-  PH_REQUIRE(!a.src1_lowres, "a half-resolution second source is only taken by the F(4x4,3x3) kernel (ask conv3x3_dma_is_wino4 first)");
+// Launches the kernel the route names (conv3x3_route.h: conv3x3_route decides, from fields of `a` that the model runtime fills from the handle's options; there is no
+// process-global state here).
+int launch_conv3x3_routed(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
+  if (r.kernel == CONV_SMALLMAP) return launch_conv3x3_sm(a, s);
+  if (r.kernel == CONV_REGSTAGED) return launch_conv3x3(a, s);
+  PH_REQUIRE(!a.relu_mask_src || r.takes_mask, "relu_mask_src is applied by the F(2x2,3x3) / F(4x4,3x3) kernels' plain stores only (ask ConvRoute::takes_mask first)");
+  PH_REQUIRE(!a.head_w || (r.kernel == CONV_WINO2D && !a.dst_pool && a.coutp == 64 && a.bn == 64 && a.head_cout >= 1 && a.head_cout <= 32 && a.head_wcp == 64 && a.head_b && a.head_dst) ||
+                 (r.head_w16 && a.head_cout >= 1 && a.head_cout <= 16 && a.head_wcp == a.coutp && a.head_b && a.head_dst),
+             "a fused head needs the F(2x2,3x3) kernel on 64 output channels (<= 32 head channels) or the wave-private kernel on 16 -> 16 / 32 -> 32 channels (<= 16 head channels): ask ConvRoute::head_w2d / head_w16 first");
+  if (r.kernel == CONV_W16) return launch_conv3x3_w16(a, s);
+  if (r.kernel == CONV_C16) return launch_conv3x3_c16(a, s);
+  if (r.kernel == CONV_WINO2D) return launch_conv3x3_wino2d(a, s, r.ksplit);
+  if (r.kernel == CONV_WINO4) return launch_conv3x3_wino4(a, s, r.ksplit);
+  PH_REQUIRE(!a.src1_lowres, "a half-resolution second source is only taken by the F(4x4,3x3) and small-map kernels (ask ConvRoute::folds_lowres first)");
   const int tiles = ((a.W + TW - 1) / TW) * ((a.H + D_TH - 1) / D_TH) * a.B;
   const int ntc = (a.coutp + a.bn - 1) / a.bn;
-  const bool wino = a.use_wino && a.wpack_wino && (a.bn == 64 || a.use_wino != 2);
+  const bool wino = r.kernel == CONV_WINO1D;
   int n_cu = 0;
   if (a.persist) {
     const int rc = cu_count(&n_cu);

@@ -154,6 +154,7 @@ int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
   plan.bpc = fmt_bytes_per_channel(fmt);
   const int bpc = plan.bpc;
   int64_t off = 0, tmp = 0;
+  int n_cu = 0;  // CUs of the device, read once where a layer's split-K scratch depends on it
   // Slot allocation.  Default: every slot gets its own range (training keeps every activation; ph_model_read_slot can read any of
   // them back).  With the handle option "workspace_reuse" (inference programs) a slot's range returns to a free list after its
   // last reader and later slots take the best-fitting free block: 9.0 -> 3.6 GB at cfg3 x 32 frames, and a layer's output is
@@ -328,8 +329,10 @@ int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
       }
     }
     if (d.kind == PH_OP_CONV && d.ksize == 3 && fmt == FMT_F32 && (m->conv_splitk >= 2 || (m->conv_splitk == 1 && reuse))) {  // (auto: inference plans only, as the kernel choice below)  // partial-sum planes of a split-K launch (conv3x3_wino2d_kernel<.., KS>)
-      int n_cu = 0;
-      if (device_cu_count(&n_cu) != PH_OK || n_cu <= 0) n_cu = 256;
+      if (!n_cu) {
+        const int rc = device_cu_count(&n_cu);
+        if (rc != PH_OK) return rc;
+      }
       tmp = std::max<int64_t>(tmp, wino2d_split_scratch_bytes(B, h, w, pad16(d.cin0) + (d.src1 >= 0 ? pad16(d.cin1) : 0), pad16(d.cout), m->conv_splitk, n_cu));
       if (m->conv_wino4) tmp = std::max<int64_t>(tmp, wino4_split_scratch_bytes(B, h, w, pad16(d.cin0) + (d.src1 >= 0 ? pad16(d.cin1) : 0), pad16(d.cout), m->conv_splitk, n_cu));
     }

@@ -362,13 +362,12 @@ bool sm_fits(const ConvArgs& a) {
   const uint64_t units = (uint64_t)a.B * ((a.H + 7) / 8) * ((a.W + 7) / 8) * (a.coutp / 16);
   return units < 0x7FFFFFFFull;
 }
-// Estimated launch body in microseconds (the dispatch floor excluded, as in wino4_fits): rounds of the chip x (prologue + epilogue ~2.5 us + ~0.8 us per 32-channel chunk)
 static int sm_nb(const ConvArgs& a, int n_cu) {  // N blocks per workgroup
   const long units1 = (long)a.B * ((a.H + 7) / 8) * ((a.W + 7) / 8) * (a.coutp / 16);
   if (a.head_w) return a.coutp / 16;  // (sm_fits: Cout <= 32)
   return ((a.coutp & 31) == 0 && units1 > n_cu) ? 2 : 1;
 }
-// Estimated launch body in microseconds (the dispatch floor excluded, as in wino4_fits): rounds of the chip x (prologue + epilogue ~2.3 us + ~0.95 us per 32-channel chunk, ~1.5 us
+// Estimated launch body in microseconds (the dispatch floor excluded, as the cost models of conv3x3_route.hip): rounds of the chip x (prologue + epilogue ~2.3 us + ~0.95 us per 32-channel chunk, ~1.5 us
 // for a chunk of the half-resolution source; two N blocks: 1.3 / 1.9); calibrated on cfg1's eleven layers (profiles/r5_cfg1_smallmap.txt)
 double sm_cost_us(const ConvArgs& a, int n_cu) {
   const int nb = sm_nb(a, n_cu);
@@ -380,7 +379,8 @@ double sm_cost_us(const ConvArgs& a, int n_cu) {
 int launch_conv3x3_sm(const ConvArgs& a, hipStream_t s) {
   PH_REQUIRE(sm_fits(a), "conv3x3_sm_kernel does not take this shape (ask sm_fits first)");
   int n_cu = 0;
-  if (device_cu_count(&n_cu) != PH_OK || n_cu <= 0) n_cu = 256;
+  const int rc = device_cu_count(&n_cu);
+  if (rc != PH_OK) return rc;
   const int nb = sm_nb(a, n_cu);
   const unsigned units = (unsigned)a.B * ((a.H + 7) / 8) * ((a.W + 7) / 8) * (a.coutp / 16 / nb);
   if (a.src1_lowres && nb == 2)

@@ -979,14 +979,6 @@ int64_t wino2d_split_scratch_bytes(int B, int H, int W, int cinp, int coutp, int
   const int ks = wino2d_ksplit_shape(B, H, W, cinp, coutp, splitk, n_cu);
   return ks > 1 ? (int64_t)ks * B * H * W * coutp * 4 : 0;
 }
-int wino2d_ksplit(const ConvArgs& a) {
-  if (!a.split_scratch || a.accumulate || a.relu_mask_src || a.head_w) return 1;
-  int n_cu = 0;
-  if (device_cu_count(&n_cu) != PH_OK || n_cu <= 0) return 1;
-  const int ks = wino2d_ksplit_shape(a.B, a.H, a.W, a.c0p + a.c1p, a.coutp, a.splitk, n_cu);
-  return (ks > 1 && (int64_t)ks * a.B * a.H * a.W * a.coutp * 4 <= a.split_scratch_bytes) ? ks : 1;
-}
-
 int prepare_wino2d_kernels() {
   const void* ks[5] = {reinterpret_cast<const void*>(conv3x3_wino2d_kernel<64, false, false>), reinterpret_cast<const void*>(conv3x3_wino2d_kernel<64, true, false>),
                        reinterpret_cast<const void*>(conv3x3_wino2d_kernel<64, false, true>), reinterpret_cast<const void*>(conv3x3_wino2d_kernel<64, true, true>),
@@ -1006,9 +998,11 @@ bool wino2d_fits(const ConvArgs& a) {
   const uint64_t px = (uint64_t)a.B * a.H * a.W;
   return px * (uint64_t)a.c0p * 4 < 0xFFFFFF00ull && px * (uint64_t)a.c1p * 4 < 0xFFFFFF00ull && px < 0x7FFFFFFFull;
 }
-// 3x3 conv, N tile 64: the caller (launch_conv3x3_dma) checks the preconditions.
-int launch_conv3x3_wino2d(const ConvArgs& a, hipStream_t s) {
+// 3x3 conv, N tile 64: the caller (launch_conv3x3_routed) checks the preconditions.  ksplit: the route's K slices (conv3x3_route.h; 1 = one stage)
+int launch_conv3x3_wino2d(const ConvArgs& a, hipStream_t s, int ksplit) {
   PH_REQUIRE(a.bn == 64 && a.wpack_wino2 && a.c0p + a.c1p >= 32 && wino2d_fits(a), "wino2d: N tile 64, transformed weights, at least 32 input channels, sources below 4 GiB");
+  PH_REQUIRE(ksplit == 1 || (ksplit > 1 && a.split_scratch && !a.accumulate && !a.relu_mask_src && !a.head_w && (int64_t)ksplit * a.B * a.H * a.W * a.coutp * 4 <= a.split_scratch_bytes),
+             "wino2d: %d K slices need a forward launch without a fused head and a split scratch that holds them", ksplit);
   int n_cu = 0;
   const int rc = w2_cu_count(&n_cu);
   if (rc != PH_OK) return rc;
@@ -1016,7 +1010,6 @@ int launch_conv3x3_wino2d(const ConvArgs& a, hipStream_t s) {
   const int ntc = (a.coutp + 63) / 64;
   const bool ht = (a.coutp & 63) != 0 && (a.coutp & 63) <= 32, bwd = a.accumulate || a.relu_mask_src;
   const size_t lds = (size_t)W2_LDS_FLOATS * sizeof(float);
-  const int ksplit = wino2d_ksplit(a);
   if (ksplit > 1) {  // split K: raw partial sums per slice, then the fixed-order second stage (bias, ReLU, pool)
     ConvArgs k = a;
     k.dst = a.split_scratch;

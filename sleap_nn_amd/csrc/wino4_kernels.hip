@@ -10,7 +10,7 @@
 // 36 multiplications per sixteen outputs instead of 144: the matrix cores execute 1/4 of the direct convolution's FLOPs
 // (F(2x2,3x3): 4/9).  fp32 throughout; the transforms have coefficients up to 8 (A), 5 (B) and 1/24 (G): measured against the fp64
 // convolution the result is ~5x further off than F(2x2,3x3) (1e-5 relative max at K = 768), inside the heads' 1e-4 bar;
-// which layers run here is decided per layer by wino4_fits' time model (a tile costs ~11 us outside its K loop).
+// which layers run here is decided per layer by the route's time model (conv3x3_route.hip: wino4_cost_us) (a tile costs ~11 us outside its K loop).
 //
 //   * GEMM view: per Winograd position p = xi * 6 + nu one GEMM with M = 4x4-pixel tiles, N = output channels, K = input channels.  A workgroup
 //     tile is 8 x 4 Winograd tiles (32 x 16 output pixels) x 64 channels; all 36 positions x (32 tiles x 64 channels) accumulators (288 KiB)
@@ -852,30 +852,13 @@ int prepare_wino4_kernels() {
 
 // Shapes the kernel takes: N tile 64, whole 4x4 Winograd tiles (H and W multiples of 4), channel counts in quarters, every tensor
 // addressable through a 32-bit buffer descriptor; no fused pool / head / accumulate / ReLU mask (those stay on the F(2x2,3x3) kernel).
-bool wino4_fits(const ConvArgs& a) {
+bool wino4_shape_ok(const ConvArgs& a) {
   if (!a.wpack_wino4 || a.bn != 64 || (a.H & 3) || (a.W & 3) || a.head_w || a.accumulate) return false;
   if (a.src1_lowres && (!a.src1 || (a.H & 1) || (a.W & 1))) return false;
   const uint64_t px = (uint64_t)a.B * a.H * a.W;
   if (px * (uint64_t)a.c0p * 4 >= 0xFFFFFF00ull || px * (uint64_t)a.c1p * 4 >= 0xFFFFFF00ull || px >= 0x7FFFFFFFull) return false;
   const uint64_t wbytes = (uint64_t)((a.coutp + 63) / 64) * (uint64_t)((a.c0p + a.c1p) / 4) * W4_Q_FLOATS * 4;
-  if (wbytes >= 0xFFFFFF00ull) return false;
-  // Against the F(2x2,3x3) kernel, which would run the layer otherwise.  Both kernels run one persistent workgroup per CU, so a launch costs rounds-of-the-chip x time per unit;
-  // measured unit times (cfg3 layers, K from 128 to 768 channels): F(2x2,3x3) ~8 us of prologue + epilogue + 2.0 us per half (8 channels) for a 16 x 16-pixel tile, this kernel
-  // ~8 us + 1.6 us per quarter (4 channels) for a 32 x 16 one (768 -> 256 at 64 x 64, 32 frames: 4 rounds x 315 us = 1.26 ms measured 1.24; F(2x2,3x3): 8 x 200 = 1.60, measured 1.62),
-  // a split-K second stage ~8 us.  Each kernel is priced at the K split it would take (wino4_ksplit_shape / wino2d_ksplit_shape); large batches reduce to the old 2 / 1.3 rule.
-  if (a.use_wino4 >= 2) return true;  // forced (handle option conv_wino4 = 3: tests, the timing harness)
-  int n_cu = 0;
-  if (device_cu_count(&n_cu) != PH_OK || n_cu <= 0) n_cu = 256;
-  const bool may_split = a.split_scratch != nullptr;
-  const int ks4 = may_split ? wino4_ksplit_shape(a.B, a.H, a.W, a.c0p + a.c1p, a.coutp, a.splitk, n_cu) : 1;
-  const int ks2 = may_split ? wino2d_ksplit_shape(a.B, a.H, a.W, a.c0p + a.c1p, a.coutp, a.splitk, n_cu) : 1;
-  const long ntc = (a.coutp + 63) / 64;
-  const long t4 = (long)((a.H + W4_PH - 1) / W4_PH) * ((a.W + W4_PW - 1) / W4_PW) * a.B * ntc;
-  const long t2 = (long)((a.H + 15) / 16) * ((a.W + 15) / 16) * a.B * ntc;
-  const double Qn = (a.c0p + a.c1p) / 4.0;
-  const double cost4 = (double)((t4 * ks4 + n_cu - 1) / n_cu) * (11.0 + 1.5 * Qn / ks4) + (ks4 > 1 ? 8.0 : 0.0);  // (the pipelined kernel: 3 200 cycles per quarter, 23 000 per tile outside its loop)
-  const double cost2 = (double)((t2 * ks2 + n_cu - 1) / n_cu) * (8.0 + 1.0 * Qn / ks2) + (ks2 > 1 ? 8.0 : 0.0);
-  return cost4 <= cost2;
+  return wbytes < 0xFFFFFF00ull;
 }
 
 // K slices a layer of this shape takes on this kernel (1 = no split): where its units fill less than half of the CUs; a slice keeps at least 16 quarters (64 channels)
@@ -892,22 +875,15 @@ int64_t wino4_split_scratch_bytes(int B, int H, int W, int cinp, int coutp, int 
   const int ks = wino4_ksplit_shape(B, H, W, cinp, coutp, splitk, n_cu);
   return ks > 1 ? (int64_t)ks * B * H * W * coutp * 4 : 0;
 }
-static int wino4_ksplit(const ConvArgs& a) {
-  if (!a.split_scratch || a.relu_mask_src) return 1;
-  int n_cu = 0;
-  if (device_cu_count(&n_cu) != PH_OK || n_cu <= 0) return 1;
-  const int ks = wino4_ksplit_shape(a.B, a.H, a.W, a.c0p + a.c1p, a.coutp, a.splitk, n_cu);
-  return (ks > 1 && (int64_t)ks * a.B * a.H * a.W * a.coutp * 4 <= a.split_scratch_bytes) ? ks : 1;
-}
-
-int launch_conv3x3_wino4(const ConvArgs& a, hipStream_t s) {
-  PH_REQUIRE(wino4_fits(a), "wino4: N tile 64, H and W multiples of 4, no fused head / accumulate, tensors below 4 GiB");
+// ksplit: the route's K slices (conv3x3_route.h; 1 = one stage)
+int launch_conv3x3_wino4(const ConvArgs& a, hipStream_t s, int ksplit) {
+  PH_REQUIRE(wino4_shape_ok(a), "wino4: N tile 64, H and W multiples of 4, no fused head / accumulate, tensors below 4 GiB");
+  PH_REQUIRE(ksplit == 1 || (ksplit > 1 && a.split_scratch && !a.relu_mask_src && (int64_t)ksplit * a.B * a.H * a.W * a.coutp * 4 <= a.split_scratch_bytes), "wino4: %d K slices do not fit the split scratch", ksplit);
   int n_cu = 0;
   const int rc = device_cu_count(&n_cu);
   if (rc != PH_OK) return rc;
   const int tiles = ((a.W + W4_PW - 1) / W4_PW) * ((a.H + W4_PH - 1) / W4_PH) * a.B;
   const int ntc = (a.coutp + 63) / 64;
-  const int ksplit = wino4_ksplit(a);
   if (ksplit > 1) {  // split K: raw partial sums per slice, then the fixed-order second stage (bias, ReLU)
     ConvArgs k = a;
     k.dst = a.split_scratch;

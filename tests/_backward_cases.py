@@ -122,7 +122,7 @@ CASES = [
                must=[({"kind": CONV, "cin0": 96, "cin1": 0, "cout": 96}, 0, "wgrad", L.BR_WG_WINO), ({"kind": POOL}, None, "folded_mask", 1), ({"kind": POOL}, None, "summed_bias", 0)]),
     _unet_case("wgrad_rows_forced_narrow", F8, 2, (40, 56), 9, {"wgrad_rows": 2}, must=[({"kind": CONV, "cin0": 8, "cout": 8}, 0, "wgrad", L.BR_WG_ROWS9)]),
     # ---- data gradient
-    # (conv3x3_dma_route: 1 = the wave-private kernel, 2 = F(2x2,3x3), 3 = F(2,3) along x or, under dgrad_wino = 0, the direct kernel; 0 = conv3x3_c16 once conv_w16 is off)
+    # (conv3x3_route: the wave-private kernel, F(2x2,3x3), F(2,3) along x or, under dgrad_wino = 0, the direct kernel; conv3x3_c16 once conv_w16 is off)
     _unet_case("dgrad_default_narrow", F8, 3, (40, 56), 12, heads=_bottomup(3, 1), mt="bottomup", must=[({"kind": CONV}, 0, "dgrad", L.KV_W16), ({"kind": CONV}, 0, "accumulate", 0)]),
     _unet_case("dgrad_default_wide", WIDE, 2, (20, 28), 8, must=[({"kind": CONV}, 0, "dgrad", L.KV_W16), ({"kind": CONV}, 0, "dgrad", L.KV_WINO2D), ({"kind": CONV}, 0, "dgrad", L.KV_WINO1D),
                                                                   ({"kind": CONV}, 1, "dgrad", L.KV_WINO2D)]),

@@ -18,7 +18,7 @@ DEV = "cuda:0"
 
 # Values of the record no program of the front end reaches, each with its reason.  Anything else the record can hold must be seen in some case.
 UNREACHED = {
-    ("dgrad", L.KV_WINO2D_KS): "conv3x3_dgrad hands the data-gradient conv no split-K scratch (ConvArgs::split_scratch stays null), so wino2d_ksplit is always 1",
+    ("dgrad", L.KV_WINO2D_KS): "conv3x3_dgrad hands the data-gradient conv no split-K scratch (ConvArgs::split_scratch stays null), so the route never splits K",
 }
 _SEEN = {}  # case name -> route words of its first step (filled by test_case, read by the closure test)
 

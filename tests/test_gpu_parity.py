@@ -526,7 +526,7 @@ def test_cfg3_benched_workload_full_size_vs_oracle_and_batch_invariance(precisio
         ref = _CFG3_REF["ref"] = O.model_forward(sd, bench.CFG3_BB, bench.CFG3_HEADS, "bottomup", frames[:2])
     dev_frames = frames.to(DEV)
     # (1) What bench.py runs: DEFAULT options.  Which kernel takes a layer depends on the number of work units to deal over the CUs, i.e. on the batch
-    # (wino4_fits: F(4x4,3x3) vs F(2x2,3x3) by rounds of the chip; wino2d_ksplit: K split over workgroups when a layer fills less than half of them), so every
+    # (conv3x3_route: F(4x4,3x3) vs F(2x2,3x3) by rounds of the chip; K split over workgroups when a layer fills less than half of them), so every
     # per-rank batch of the bench's scaling runs is put under parity with the routing IT takes: 32 frames (N = 1), 8 (4 GPUs), 4 (8 GPUs), and 2 / 1.
     default_kernels = {}
     for nb in (32, 8, 4, 2, 1):

@@ -50,7 +50,7 @@ int main(int argc, char** argv) {
   ConvArgs a{};
   a.src0 = d0; a.src1 = c1 ? d1 : nullptr; a.c0p = c0; a.c1p = c1; a.coutp = cout; a.B = B; a.H = H; a.W = W; a.relu = 1; a.bn = 64;
   a.bias = dbias; a.dst = dout; a.src1_lowres = c1 ? lowres : 0; a.use_wino4 = 2; a.wpack_wino4 = dw;
-  if (!wino4_fits(a)) return printf("shape does not fit\n"), 1;
+  if (!wino4_shape_ok(a)) return printf("shape does not fit\n"), 1;
 #if defined(W4_STAMP) || defined(W4_CLOCK)
   unsigned long long* probe;
   hipMalloc(&probe, 256 * 12 * 8 * 8);
