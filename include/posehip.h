@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 130
+#define PH_VERSION 131
 
 /* error codes */
 #define PH_OK 0
@@ -428,6 +428,35 @@ typedef struct ph_gemm_case {
 } ph_gemm_case;
 int32_t ph_gemm_case_size(void);
 int ph_debug_gemm_run(ph_gemm_case* c);
+
+/* Test support (tests/test_gpu_conv3x3.py), not a product path: ONE routed launch of the exact-fp32 3x3 conv on tensors the caller owns, synchronised before it returns.
+ * The canonical weight and bias go through the product's own packers and device derivations (the forms named in `forms`, PH_CRF_*, built as ph_model_create builds
+ * them); the kernel is chosen by conv3x3_route on the device's CU count and launched by launch_conv3x3_routed: a case steers the route through the option fields only.
+ * Launch checks come back as error codes; whatever the call allocates is freed on every way out.
+ *   cin0, cin1, cout   true channel counts; every device tensor is NHWC fp32 with its channels padded to a multiple of 16 (pad channels of the sources: zeros)
+ *   bn           N tile of the packing: 64 from 64 padded output channels on, 32 below -- or 64 with 32 padded output channels and K >= 64 (the half-empty-tile packing)
+ *   flags        PH_CRA_*; each pointer bit must agree with its pointer (src1, dst_pool, relu_mask_src, head_w).  PH_CRA_SRC1_LOWRES: src1 is (B, H/2, W/2, c1p)
+ *   use_dma ... splitk, split_scratch_bytes   as ph_conv_route_case; split_scratch_bytes > 0 needs split_scratch
+ *   relu, splitk_finish, head_cout, head_sigmoid   ConvArgs' fields of those names (the head's weight rows are padded to pad16(cout) channels)
+ *   src0, src1, dst, dst_pool, relu_mask_src, head_dst, split_scratch   device pointers; head_dst is NCHW (B, head_cout, H, W)
+ *   weight (cout, cin0 + cin1, 3, 3), bias (cout), head_w (head_cout, cout), head_b (head_cout)   host, canonical
+ * written by the call: kernel, kv, ksplit, props as ph_conv_route_out; n_cu = the CU count the route was asked with; counters_zero = 1 when the split-K counters the
+ * call owns (zeroed, of the size a model handle holds; handed to the launch only where splitk_finish != 0) are all zero again after the launch. */
+typedef struct ph_conv_run_case {
+  int32_t cin0, cin1, cout, bn, B, H, W;
+  int32_t forms, flags, head_cout;
+  int32_t use_dma, dma32, use_wino, persist, use_c16, use_w16, use_wino2d, use_wino4, wino4_min_cin, use_sm, splitk;
+  int32_t relu, splitk_finish, head_sigmoid;
+  int32_t kernel, kv, ksplit, props, n_cu, counters_zero;
+  int64_t split_scratch_bytes;
+  const float *src0, *src1;
+  float *dst, *dst_pool;
+  const float* relu_mask_src;
+  float *head_dst, *split_scratch;
+  const float *weight, *bias, *head_w, *head_b;
+} ph_conv_run_case;
+int32_t ph_conv_run_case_size(void);
+int ph_debug_conv3x3_run(ph_conv_run_case* c);
 
 /* Diagnostic (tools/row_wgrad_bench.py): average milliseconds of the row weight-gradient GEMM dW[n][k] = sum_m dY[m][n] X[m][k]
  * (Linear layers of the training step, train_kernels.h launch_row_wgrad) on synthetic operands, and the largest error of 64

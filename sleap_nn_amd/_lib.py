@@ -135,6 +135,16 @@ class ConvRouteCase(C.Structure):
                                           "use_w16", "use_wino2d", "use_wino4", "wino4_min_cin", "use_sm", "splitk", "ptr_salt")] + [("split_scratch_bytes", C.c_int64)])
 
 
+class ConvRunCase(C.Structure):
+    """``struct ph_conv_run_case`` (include/posehip.h): one routed exact-fp32 3x3 conv launch of ph_debug_conv3x3_run (test support)."""
+
+    _fields_ = ([(n, C.c_int32) for n in ("cin0", "cin1", "cout", "bn", "B", "H", "W", "forms", "flags", "head_cout", "use_dma", "dma32", "use_wino", "persist", "use_c16", "use_w16",
+                                          "use_wino2d", "use_wino4", "wino4_min_cin", "use_sm", "splitk", "relu", "splitk_finish", "head_sigmoid", "kernel", "kv", "ksplit", "props",
+                                          "n_cu", "counters_zero")]
+                + [("split_scratch_bytes", C.c_int64)]
+                + [(n, C.c_void_p) for n in ("src0", "src1", "dst", "dst_pool", "relu_mask_src", "head_dst", "split_scratch", "weight", "bias", "head_w", "head_b")])
+
+
 class ConvRouteOut(C.Structure):
     """``struct ph_conv_route_out``: the ConvKernel, its KV_* code, the K slices and the PH_CRP_* property bits."""
 
@@ -198,6 +208,8 @@ SIGNATURES = {
     "ph_debug_row_wgrad_bench": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ph_conv_route_case_size": (_i32, []),
     "ph_debug_conv3x3_route": (C.c_int, [C.POINTER(ConvRouteCase), _i32, C.POINTER(ConvRouteOut)]),
+    "ph_conv_run_case_size": (_i32, []),
+    "ph_debug_conv3x3_run": (C.c_int, [C.POINTER(ConvRunCase)]),
     "ph_gemm_case_size": (_i32, []),
     "ph_debug_gemm_run": (C.c_int, [C.POINTER(GemmCase)]),
     "ph_render_confmaps": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),

@@ -22,6 +22,7 @@ int upload(ph_model* m, const std::vector<float>& host, float** dev) {
   void* p = nullptr;
   PH_HIP_CHECK(hipMalloc(&p, std::max<size_t>(host.size(), 4) * sizeof(float)));
   m->allocs.push_back(p);
+  if (host.size() < 4) PH_HIP_CHECK(hipMemset(p, 0, 4 * sizeof(float)));  // (the allocation is rounded up to four elements: its tail holds zeros, not what the memory held before)
   PH_HIP_CHECK(hipMemcpy(p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
   *dev = static_cast<float*>(p);
   return PH_OK;
@@ -31,6 +32,7 @@ int upload_ints(ph_model* m, const std::vector<int>& host, int** dev) {
   void* p = nullptr;
   PH_HIP_CHECK(hipMalloc(&p, std::max<size_t>(host.size(), 4) * sizeof(int)));
   m->allocs.push_back(p);
+  if (host.size() < 4) PH_HIP_CHECK(hipMemset(p, 0, 4 * sizeof(int)));
   PH_HIP_CHECK(hipMemcpy(p, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
   *dev = static_cast<int*>(p);
   return PH_OK;
@@ -464,22 +466,47 @@ int forms_conv_kxk(PackCtx& c, PackedOp& op) {
 // (conv3x3_wino2d_kernel, N tile 64), then -- `tail` -- the wave-private F(2x2,3x3) form (conv3x3_w16_kernel: N tile 32, the channel counts of w16_shape_ok) and
 // F(4x4,3x3) (conv3x3_wino4_kernel: N tile 64, derived from 64 padded input channels on -- 4x the direct weights' bytes; which layers take the kernel is
 // conv_wino4_min_cin + the time model).  The forward conv's and the data-gradient convs'.
+// (the parameters of each form, FormParams as FORMS[] reads them, and whether the form exists for that packing: shared with ph_debug_conv3x3_run)
+bool wino_form(int cin_a, int cin_b, int cout_, int bn, FormParams& p) {
+  if (bn != 64 && bn != 32) return false;
+  p = {{((pad16(cout_) + bn - 1) / bn) * chunks16(cin_a, cin_b), bn}};
+  return true;
+}
+bool wino2_form(int cin_a, int cin_b, int cout_, int bn, FormParams& p) {
+  if (bn != 64) return false;
+  p = {{((pad16(cout_) + 63) / 64) * chunks16(cin_a, cin_b), 64}};
+  return true;
+}
+bool wino4_form(int cin_a, int cin_b, int cout_, int bn, FormParams& p) {
+  if (bn != 64 || 16 * chunks16(cin_a, cin_b) < 64) return false;
+  p = {{pad16(cout_), chunks16(cin_a, cin_b)}};
+  return true;
+}
+bool w16_form(int cin_a, int cin_b, int cout_, int bn, FormParams& p) {
+  const int cip = pad16(cin_a), cibp = cin_b > 0 ? pad16(cin_b) : 0, cop = pad16(cout_);
+  if (bn != 32 || !w16_shape_ok(cip, cibp, cop)) return false;
+  p = {{(cip + cibp) / 16, cop / 16}};
+  return true;
+}
+FormParams sm_form(int cin_a, int cin_b, int cout_, int bn) { return {{pad16(cout_) / 16, chunks16(cin_a, cin_b), bn}}; }  // (every 3x3 conv has it)
+// 32 output channels, K >= 64: the layer also gets a packing with an N tile of 64 (rows 32 .. 63 zero) for the half-empty-tile form of the F(2x2,3x3) / F(4x4,3x3) kernels
+bool has_n64_form(int cin_a, int cin_b, int cout_, int bn) { return bn == 32 && pad16(cout_) == 32 && 16 * chunks16(cin_a, cin_b) >= 64; }
+
 int derive_wino(PackCtx& c, const float* src, int cin_a, int cin_b, int cout_, int bn, float** dst) {
-  if (bn != 64 && bn != 32) return PH_OK;
-  return derive(c.m, DERIVED_WINO, src, {{((pad16(cout_) + bn - 1) / bn) * chunks16(cin_a, cin_b), bn}}, dst);
+  FormParams p;
+  return wino_form(cin_a, cin_b, cout_, bn, p) ? derive(c.m, DERIVED_WINO, src, p, dst) : PH_OK;
 }
 int derive_wino2(PackCtx& c, const float* src, int cin_a, int cin_b, int cout_, int bn, float** dst) {
-  if (bn != 64) return PH_OK;
-  return derive(c.m, DERIVED_WINO2D, src, {{((pad16(cout_) + 63) / 64) * chunks16(cin_a, cin_b), 64}}, dst);
+  FormParams p;
+  return wino2_form(cin_a, cin_b, cout_, bn, p) ? derive(c.m, DERIVED_WINO2D, src, p, dst) : PH_OK;
 }
 int derive_wino4(PackCtx& c, const float* src, int cin_a, int cin_b, int cout_, int bn, float** dst) {
-  if (bn != 64 || 16 * chunks16(cin_a, cin_b) < 64) return PH_OK;
-  return derive(c.m, DERIVED_WINO4, src, {{pad16(cout_), chunks16(cin_a, cin_b)}}, dst);
+  FormParams p;
+  return wino4_form(cin_a, cin_b, cout_, bn, p) ? derive(c.m, DERIVED_WINO4, src, p, dst) : PH_OK;
 }
 int derive_w16(PackCtx& c, const float* src, int cin_a, int cin_b, int cout_, int bn, float** dst) {
-  const int cip = pad16(cin_a), cibp = cin_b > 0 ? pad16(cin_b) : 0, cop = pad16(cout_);
-  if (bn != 32 || !w16_shape_ok(cip, cibp, cop)) return PH_OK;
-  return derive(c.m, DERIVED_W16, src, {{(cip + cibp) / 16, cop / 16}}, dst);
+  FormParams p;
+  return w16_form(cin_a, cin_b, cout_, bn, p) ? derive(c.m, DERIVED_W16, src, p, dst) : PH_OK;
 }
 
 // 3x3 conv (not transposed): the forms of the forward
@@ -488,7 +515,7 @@ int forms_conv3x3_forward(PackCtx& c, PackedOp& op) {
   const int coutp = pad16(d.cout);
   PH_TRY(derive_wino(c, op.w_dev, d.cin0, d.cin1, d.cout, op.bn, &op.w_wino_dev));
   PH_TRY(derive_wino2(c, op.w_dev, d.cin0, d.cin1, d.cout, op.bn, &op.w_wino2_dev));
-  if (op.bn == 32 && coutp == 32 && 16 * chunks16(d.cin0, d.cin1) >= 64) {
+  if (has_n64_form(d.cin0, d.cin1, d.cout, op.bn)) {
     // 32 output channels, K >= 64: a second packing with an N tile of 64 (rows 32 .. 63 zero) for the F(2x2,3x3) kernel's half-empty-tile form (conv_n32_wino2d)
     PH_TRY(c.pack([&](const auto* w, auto& out) { pack_conv(w, false, d.cin0, d.cin1, d.cout, 64, out); }, d.weight, &op.w_n64_dev));
     PH_TRY(c.pack(pad_vec(64, d.cout), d.bias, &op.b_n64_dev));
@@ -498,7 +525,7 @@ int forms_conv3x3_forward(PackCtx& c, PackedOp& op) {
   if (op.w_n64_dev) PH_TRY(derive_wino4(c, op.w_n64_dev, d.cin0, d.cin1, d.cout, 64, &op.w_wino4_dev));  // (Cout 32, K >= 64: the kernel's waves of the empty N half skip their MFMAs)
   PH_TRY(derive_w16(c, op.w_dev, d.cin0, d.cin1, d.cout, op.bn, &op.w_w16_dev));
   // small-map F(2x2,3x3) weights (conv3x3_sm_kernel): 16/9 of the direct weights' bytes, every 3x3 conv
-  PH_TRY(derive(c.m, DERIVED_SMALLMAP, op.w_dev, {{coutp / 16, chunks16(d.cin0, d.cin1), op.bn}}, &op.w_sm_dev));
+  PH_TRY(derive(c.m, DERIVED_SMALLMAP, op.w_dev, sm_form(d.cin0, d.cin1, d.cout, op.bn), &op.w_sm_dev));
   // row-GEMM form for feature maps too small for the 16x32-pixel tiles
   op.bn_g = gemm_choose_bn(coutp);
   PH_TRY(c.pack([&](const auto* w, auto& out) { pack_gemm(w, d.cout, d.cin0, d.cin1, 9, op.bn_g, out); }, d.weight, &op.w_gemm_dev));
@@ -630,19 +657,22 @@ int forms_input_conv(PackCtx& c, PackedOp& op) {
   return c.pack(pad_vec(coutp, d.cout), d.bias, &op.b_dev);
 }
 
+// 1x1 head weight (cout, cin) -> [co][Cp], zero-padded channels
+template <typename T>
+void pack_head_w(const T* w, int cout, int cin, std::vector<T>& out) {
+  const int cp = pad16(cin);
+  out.assign((size_t)cout * cp, T(0));
+  for (int co = 0; co < cout; ++co)
+    for (int ci = 0; ci < cin; ++ci) out[(size_t)co * cp + ci] = w[(size_t)co * cin + ci];
+}
+
 int forms_head(PackCtx& c, PackedOp& op) {
   const ph_op_desc& d = op.d;
   if (!c.has_weight_and_bias(d)) return c.fail("weight index out of range");
   if (c.weight_numel[d.bias] != d.cout) return c.fail("bias size mismatch");
   if (c.weight_numel[d.weight] != (int64_t)d.cin0 * d.cout) return c.fail("weight size mismatch");
   if (d.out_index < 0 || d.out_index >= c.n_outputs) return c.fail("bad out_index");
-  const int cp = pad16(d.cin0);
-  auto pack_head_w = [&](const auto* w, auto& out) {  // [co][Cp]
-    out.assign((size_t)d.cout * cp, 0);
-    for (int co = 0; co < d.cout; ++co)
-      for (int ci = 0; ci < d.cin0; ++ci) out[(size_t)co * cp + ci] = w[(size_t)co * d.cin0 + ci];
-  };
-  PH_TRY(c.pack(pack_head_w, d.weight, &op.w_dev));
+  PH_TRY(c.pack([&](const auto* w, auto& out) { pack_head_w(w, d.cout, d.cin0, out); }, d.weight, &op.w_dev));
   return c.pack(pad_vec(d.cout, d.cout), d.bias, &op.b_dev);
 }
 
@@ -955,4 +985,136 @@ extern "C" int ph_debug_gemm_run(ph_gemm_case* c) {
   const int rc = c->variant >= 0 ? launch_gemm_variant(variant, g, nullptr) : launch_gemm(g, nullptr);
   PH_HIP_CHECK(hipDeviceSynchronize());
   return rc;
+}
+
+extern "C" int32_t ph_conv_run_case_size(void) { return (int32_t)sizeof(ph_conv_run_case); }
+
+// Test support (tests/test_gpu_conv3x3.py), not a product path: one routed launch of the exact-fp32 3x3 conv on tensors the caller owns.  The canonical weight and bias go
+// through pack_conv / repack_dma / pack_c16 / pad_vec over n_padded and the FORMS[] launchers with the parameters ph_model_create derives them with; the arguments are
+// filled as fwd_conv3x3_f32 fills them, conv3x3_route chooses the kernel and launch_conv3x3_routed launches it.
+extern "C" int ph_debug_conv3x3_run(ph_conv_run_case* c) {
+  PH_REQUIRE(c && c->src0 && c->dst && c->weight && c->bias && c->B > 0 && c->H > 0 && c->W > 0 && c->cin0 > 0 && c->cin1 >= 0 && c->cout > 0, "ph_debug_conv3x3_run: bad arguments");
+  const int coutp = pad16(c->cout), c0p = pad16(c->cin0), c1p = c->cin1 > 0 ? pad16(c->cin1) : 0, bn = c->bn;
+  const bool n64 = bn == 64 && has_n64_form(c->cin0, c->cin1, c->cout, choose_bn(coutp));
+  PH_REQUIRE(bn == choose_bn(coutp) || n64, "ph_debug_conv3x3_run: N tile %d is no packing of %d output channels", bn, coutp);
+  auto on = [&](int32_t bit) { return (c->flags & bit) != 0; };
+  PH_REQUIRE(on(PH_CRA_SRC1) == (c->src1 != nullptr) && on(PH_CRA_SRC1) == (c->cin1 > 0) && on(PH_CRA_POOL) == (c->dst_pool != nullptr) &&
+                 on(PH_CRA_RELU_MASK) == (c->relu_mask_src != nullptr) && on(PH_CRA_HEAD) == (c->head_w != nullptr) && (!on(PH_CRA_SRC1_LOWRES) || c->src1),
+             "ph_debug_conv3x3_run: flags and pointers disagree");
+  PH_REQUIRE(!c->head_w || (c->head_b && c->head_dst && c->head_cout >= 1), "ph_debug_conv3x3_run: a head needs its bias, its output and a channel count");
+  PH_REQUIRE((c->split_scratch_bytes > 0) == (c->split_scratch != nullptr), "ph_debug_conv3x3_run: split scratch and its size disagree");
+  PH_REQUIRE(c->splitk_finish >= 0 && c->splitk_finish <= 2, "ph_debug_conv3x3_run: splitk_finish is 0, 1 or 2");
+  if (prepare_kernels() != PH_OK) return PH_E_HIP;
+  struct Owned {  // what the entry allocates, freed on every way out
+    std::vector<void*> p;
+    ~Owned() {
+      for (void* q : p) (void)hipFree(q);
+    }
+  } owned;
+  auto up = [&](const std::vector<float>& h, const float** dev) -> int {
+    void* p = nullptr;
+    PH_HIP_CHECK(hipMalloc(&p, std::max<size_t>(h.size(), 4) * sizeof(float)));
+    owned.p.push_back(p);
+    PH_HIP_CHECK(hipMemcpy(p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    *dev = static_cast<const float*>(p);
+    return PH_OK;
+  };
+  auto derived = [&](DerivedKind kind, const float* src, const FormParams& fp, const float** dev) -> int {  // as derive(): FORMS[] sizes and launches it
+    void* p = nullptr;
+    PH_HIP_CHECK(hipMalloc(&p, (size_t)FORMS[kind].bytes(fp.p)));
+    owned.p.push_back(p);
+    PH_TRY(FORMS[kind].launch(src, static_cast<float*>(p), fp.p, nullptr));
+    *dev = static_cast<const float*>(p);
+    return PH_OK;
+  };
+  ConvArgs a{};
+  std::vector<float> wp, tmp;
+  pack_conv(c->weight, false, c->cin0, c->cin1, c->cout, bn, wp);
+  PH_TRY(up(wp, &a.wpack));
+  pad_vec(n_padded(coutp, bn), c->cout)(c->bias, tmp);
+  PH_TRY(up(tmp, &a.bias));
+  PH_TRY(up(std::vector<float>(64, 0.f), &a.zeros));
+  FormParams fp;
+  if (c->forms & PH_CRF_DMA) {
+    PH_REQUIRE(!n64, "ph_debug_conv3x3_run: the half-empty-tile packing has no LDS-DMA form");
+    repack_dma(wp, bn, tmp);
+    PH_TRY(up(tmp, &a.wpack_dma));
+  }
+  if (c->forms & PH_CRF_WINO) {
+    PH_REQUIRE(wino_form(c->cin0, c->cin1, c->cout, bn, fp), "ph_debug_conv3x3_run: no F(2,3) form for this packing");
+    PH_TRY(derived(DERIVED_WINO, a.wpack, fp, &a.wpack_wino));
+  }
+  if (c->forms & PH_CRF_WINO2) {
+    PH_REQUIRE(wino2_form(c->cin0, c->cin1, c->cout, bn, fp), "ph_debug_conv3x3_run: no F(2x2,3x3) form for this packing");
+    PH_TRY(derived(DERIVED_WINO2D, a.wpack, fp, &a.wpack_wino2));
+  }
+  if (c->forms & PH_CRF_WINO4) {
+    PH_REQUIRE(wino4_form(c->cin0, c->cin1, c->cout, bn, fp), "ph_debug_conv3x3_run: no F(4x4,3x3) form for this packing");
+    PH_TRY(derived(DERIVED_WINO4, a.wpack, fp, &a.wpack_wino4));
+  }
+  if (c->forms & PH_CRF_W16) {
+    PH_REQUIRE(w16_form(c->cin0, c->cin1, c->cout, bn, fp), "ph_debug_conv3x3_run: no wave-private form for this packing");
+    PH_TRY(derived(DERIVED_W16, a.wpack, fp, &a.wpack_w16));
+  }
+  if (c->forms & PH_CRF_SM) PH_TRY(derived(DERIVED_SMALLMAP, a.wpack, sm_form(c->cin0, c->cin1, c->cout, bn), &a.wpack_sm));
+  if (c->forms & PH_CRF_C16) {
+    PH_REQUIRE(c->cin1 == 0 && c->cin0 <= 16 && c->cout <= 16, "ph_debug_conv3x3_run: conv3x3_c16's weights exist for 16 -> 16 channels from one source");
+    pack_c16(c->weight, c->cout, c->cin0, tmp);
+    PH_TRY(up(tmp, &a.w16));
+  }
+  if (c->head_w) {
+    pack_head_w(c->head_w, c->head_cout, c->cout, tmp);
+    PH_TRY(up(tmp, &a.head_w));
+    pad_vec((size_t)c->head_cout, c->head_cout)(c->head_b, tmp);
+    PH_TRY(up(tmp, &a.head_b));
+    a.head_dst = c->head_dst;
+    a.head_cout = c->head_cout;
+    a.head_wcp = coutp;
+    a.head_sigmoid = c->head_sigmoid;
+  }
+  const size_t n_counters = 3 * 4096;  // as ph_model_create: arrivals | claimed shares | departures of 4096 split-K units
+  const float* counters = nullptr;
+  PH_TRY(up(std::vector<float>(n_counters, 0.f), &counters));
+  a.src0 = c->src0;
+  a.src1 = c->src1;
+  a.c0p = c0p, a.c1p = c1p, a.coutp = coutp;
+  a.dst = c->dst;
+  a.B = c->B, a.H = c->H, a.W = c->W;
+  a.relu = c->relu;
+  a.bn = bn;
+  a.dst_pool = c->dst_pool;
+  a.skip_dst = on(PH_CRA_SKIP_DST) ? 1 : 0;
+  a.accumulate = on(PH_CRA_ACCUMULATE) ? 1 : 0;
+  a.relu_mask_src = c->relu_mask_src;
+  a.src1_lowres = on(PH_CRA_SRC1_LOWRES) ? 1 : 0;
+  a.use_dma = c->use_dma, a.dma32 = c->dma32, a.use_wino = c->use_wino, a.persist = c->persist, a.use_c16 = c->use_c16, a.use_w16 = c->use_w16, a.use_wino2d = c->use_wino2d;
+  a.use_wino4 = c->use_wino4, a.wino4_min_cin = c->wino4_min_cin, a.use_sm = c->use_sm, a.splitk = c->splitk;
+  a.split_scratch = c->split_scratch;
+  a.split_scratch_bytes = c->split_scratch_bytes;
+  a.splitk_finish = c->splitk_finish;
+  a.split_counters = c->splitk_finish ? reinterpret_cast<unsigned*>(const_cast<float*>(counters)) : nullptr;
+  a.split_counters_n = a.split_counters ? 4096 : 0;
+  int n_cu = 0;
+  PH_TRY(device_cu_count(&n_cu));
+  const ConvRoute r = conv3x3_route(a, n_cu);
+  c->kernel = (int32_t)r.kernel;
+  c->kv = r.kv;
+  c->ksplit = r.ksplit;
+  c->props = (r.takes_mask ? PH_CRP_MASK : 0) | (r.pools ? PH_CRP_POOLS : 0) | (r.head_w2d ? PH_CRP_HEAD_W2D : 0) | (r.head_w16 ? PH_CRP_HEAD_W16 : 0) |
+             (r.folds_lowres ? PH_CRP_LOWRES : 0) | (r.head_sm ? PH_CRP_HEAD_SM : 0);
+  c->n_cu = n_cu;
+  c->counters_zero = 0;
+  // what the forward asks the route before it hands a launch these arguments (fwd_conv3x3_f32, try_head_f32): the launcher does not check them for every kernel
+  PH_REQUIRE(!(r.kernel == CONV_DMA9 && !a.wpack_dma) && !(r.kernel == CONV_C16 && !a.w16), "ph_debug_conv3x3_run: the routed kernel's weight form was not built");
+  PH_REQUIRE(!a.relu_mask_src || r.takes_mask, "ph_debug_conv3x3_run: the routed kernel applies no ReLU mask");  // (the launcher checks this inside the LDS-DMA family only)
+  PH_REQUIRE(!a.head_w || r.head_sm || r.head_w2d || r.head_w16, "ph_debug_conv3x3_run: the routed kernel carries no fused head");
+  PH_REQUIRE(!a.src1_lowres || r.folds_lowres, "ph_debug_conv3x3_run: the routed kernel does not fold a half-resolution second source");
+  PH_REQUIRE(!a.dst_pool || r.kernel != CONV_C16, "ph_debug_conv3x3_run: conv3x3_c16 has no fused pool");
+  const int rc = launch_conv3x3_routed(a, r, nullptr);
+  PH_HIP_CHECK(hipDeviceSynchronize());
+  if (rc != PH_OK) return rc;
+  std::vector<unsigned> back(n_counters);
+  PH_HIP_CHECK(hipMemcpy(back.data(), counters, n_counters * sizeof(unsigned), hipMemcpyDeviceToHost));
+  c->counters_zero = std::all_of(back.begin(), back.end(), [](unsigned v) { return v == 0; }) ? 1 : 0;
+  return PH_OK;
 }
