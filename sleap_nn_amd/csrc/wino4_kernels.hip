@@ -31,6 +31,8 @@
 //         differences), waves 4..7 one of xi 0 / 5, a SIMD one of each; LDS reads are issued one MFMA group ahead of their use;
 //       - the MFMAs of positions 6..8 of a quarter are issued at the top of the NEXT quarter, behind the barrier (their operands wait in
 //         registers), so that the matrix pipe has work while the reads that follow the barrier are in flight.
+//       - nothing is selected or re-addressed per quarter that is fixed for the tile: a load of a quarter beyond the K slice goes through a buffer descriptor without
+//         records (a scalar choice; zeros, no memory access), and a loop over the whole K runs two quarters per trip, the slot parity in the DS immediate offsets.
 //     One s_barrier per quarter.  LDS in the loop: two raw halo slots + two V slots = 60 KiB.
 //   * Second source at half resolution (ConvArgs::src1_lowres): its slot holds the 18 x 10 LOW-resolution halo (index-clamped by the
 //     loader like the bilinear kernel clamps), the row pass applies B^T U (U = the 6 x 4 bilinear matrix of the patch rows, rows
@@ -269,6 +271,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
   };
 
   const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.wpack_wino4, 0, (int)((unsigned)ntc * (unsigned)Q * (unsigned)(W4_Q_FLOATS * 4)), 0x00020000);
+  const __amdgpu_buffer_rsrc_t wnone = __builtin_amdgcn_make_buffer_rsrc((void*)a.wpack_wino4, 0, 0, 0x00020000);  // no records: whatever is loaded through it is zero
   const unsigned w_lane = (unsigned)(pw * P4_WAVE_FLOATS + lane * 4) * 4u;
   const unsigned w_lane9 = (unsigned)(pw * P4_WAVE_FLOATS + 1024 + lane * 2) * 4u;
 
@@ -298,9 +301,8 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
         off1[i] = (hy < W4_PH / 2 + 2 && hx < W4_PW / 2 + 2) ? (unsigned)((P.b * Hl + sy) * Wl + sx) * (unsigned)(a.c1p * 4) : 0xFFFFFF00u;
       }
     }
-    const __amdgpu_buffer_rsrc_t rsrc0 = __builtin_amdgcn_make_buffer_rsrc((void*)a.src0, 0, (int)((unsigned)(a.B * a.H * a.W) * (unsigned)(a.c0p * 4)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc1 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.src1 ? a.src1 : a.src0), 0,
-                                                                           (int)((unsigned)(lowres ? a.B * Hl * Wl : a.B * a.H * a.W) * (unsigned)(a.c1p * 4)), 0x00020000);
+    const int hbytes0 = (int)((unsigned)(a.B * a.H * a.W) * (unsigned)(a.c0p * 4));
+    const int hbytes1 = (int)((unsigned)(lowres ? a.B * Hl * Wl : a.B * a.H * a.W) * (unsigned)(a.c1p * 4));
     // The halo goes through registers (buffer load one quarter, four ds_write_b32 the next, one per channel plane): an LDS-DMA transfer costs its wave ~150 cycles of issue beside MFMAs
     f32x4 hreg[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};  // (initialised: left undefined, the register allocator spills 144 registers of the folded-bilinear instantiation instead of 20)
     const bool has1 = pw < 2;  // (wave-uniform) this wave owns a second piece of the full-resolution layout
@@ -308,18 +310,20 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
       const bool s1 = k >= Q0;
       const int so = k < qend ? ((W4_EXP & 64) ? 0 : (s1 ? (k - Q0) * 16 : k * 16)) : 0;
       if (W4_EXP & 8) return;
+      // "beyond the slice" is a descriptor without records (zeros, no memory access), a scalar choice like the source's: one select per load is left, the lane's offset in the quarter's source
+      const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc((void*)a.src0, 0, k < qend ? hbytes0 : 0, 0x00020000);
+      const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.src1 ? a.src1 : a.src0), 0, k < qend ? hbytes1 : 0, 0x00020000);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         if (i == 1 && !has1) continue;
-        const unsigned off = k < qend ? (s1 ? off1[i] : off0[i]) : 0xFFFFFF00u;
+        const unsigned off = s1 ? off1[i] : off0[i];
         if (s1)
-          hreg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc1, off, so, 0));
+          hreg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r1, off, so, 0));
         else
-          hreg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc0, off, so, 0));
+          hreg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r0, off, so, 0));
       }
     };
-    auto store_raw = [&](int k) {  // ... and from there into raw slot k & 1
-      float* slot = rawbuf + (k & 1) * W4_RAW_FLOATS + lwr;
+    auto store_raw = [&](float* slot) {  // ... and from there into a raw slot (slot = the lane's place in it: + lwr)
       if (W4_EXP & 8) return;
 #pragma unroll
       for (int c = 0; c < 4; ++c) slot[c * W4_RAW_PLANE] = hreg[0][c];
@@ -339,10 +343,13 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
       const bool live = k < qend && !(W4_EXP & 1);
       if ((W4_EXP & 256) && k != qbeg) return;
       const int so = live ? w_tile + ((W4_EXP & 32) ? qbeg : k) * (W4_Q_FLOATS * 4) : 0;
+      // A quarter beyond the slice reads through the empty descriptor (every offset is out of its range: zeros, no memory access).  `live` changes with k, the lane's offset
+      // does not: the choice is a scalar one, of the descriptor, not a v_cndmask_b32 per load and quarter; fragment slot j's 1 KiB rides in the scalar offset (one lane offset for the four)
+      const __amdgpu_buffer_rsrc_t wr = live ? wrsrc : wnone;
       if (j < 4) {
-        wf[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, live ? w_lane + (unsigned)j * 1024u : 0xFFFFFF00u, so, 0));
+        wf[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr, w_lane + (unsigned)j * 1024u, so, 0));
       } else {
-        const f32x2 r = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(wrsrc, live ? w_lane9 : 0xFFFFFF00u, so, 0));  // (bit_cast of the whole vector: of one element it reads element 0)
+        const f32x2 r = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(wr, w_lane9, so, 0));  // (bit_cast of the whole vector: of one element it reads element 0)
         wf9[0] = r[0];
         wf9[1] = r[1];
       }
@@ -380,12 +387,11 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
     // columns: one ds_read_b128 (columns 0..3) + one ds_read_b64 (4, 5) per row; the four low-resolution columns start at an even column: two ds_read_b64
     float dd[6][4];   // raw values: [patch column][row]
     float ta[6], tb[6];
-    auto t_read = [&](auto xg_tag, auto lr_tag, const float* raw, int h) __attribute__((always_inline)) {
+    auto t_read = [&](auto xg_tag, auto lr_tag, const float* p, int h) __attribute__((always_inline)) {  // p = the thread's first patch row in the raw slot (+ pbase_l / pbase_f)
       constexpr int XG = decltype(xg_tag)::value;
       constexpr bool LR = decltype(lr_tag)::value;
       if (W4_EXP & 2) return;
       if constexpr (LR) {  // (columns = the four low-resolution columns; rows = the four low-resolution rows: 2 and 3 first)
-        const float* p = raw + pbase_l;
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           if ((r >= 2) == (h == 0)) {
@@ -396,7 +402,6 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
             dd[3][r] = hi[1];
           }
       } else {  // (rows r = patch rows 1..4 of an xi pair: 1 and 3 first; every second patch row of xi 0 / 5: the last two first)
-        const float* p = raw + pbase_f;
         constexpr int NR = XG < 2 ? 4 : 3, RS = XG < 2 ? 1 : 2;
 #pragma unroll
         for (int r = 0; r < NR; ++r)
@@ -467,7 +472,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
 #pragma unroll
       for (int c = 0; c < 6; ++c) asm volatile("" : "+v"(tt[c]));
     };
-    auto t_cols = [&](auto xg_tag, auto lr_tag, auto which_tag, float* vslot) __attribute__((always_inline)) {  // which = 0: the first (or only) xi of the group, 1: the second
+    auto t_cols = [&](auto xg_tag, auto lr_tag, auto which_tag, float* vslot, int vw0, int vw1) __attribute__((always_inline)) {  // (vw0, vw1: the thread's places in a 16-byte and the 8-byte fragment slot)  // which = 0: the first (or only) xi of the group, 1: the second
       constexpr int XG = decltype(xg_tag)::value;
       constexpr bool LR = decltype(lr_tag)::value;
       constexpr int WH = decltype(which_tag)::value;
@@ -481,12 +486,12 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
         w4_col_pass(WH ? tb : ta, v);
       }
       constexpr int xi = XG == 0 ? 1 + WH : (XG == 1 ? 3 + WH : (XG == 2 ? 0 : 5));
-      p4_vput<xi * 6, 6>(vslot, vwq, vwd, v);
+      p4_vput<xi * 6, 6>(vslot, vw0, vw1, v);
     };
 
     // ---- prologue: raw of the slice's first three quarters, weights of its first; transform the first quarter
     load_raw(qbeg);
-    store_raw(qbeg);
+    store_raw(rawbuf + (qbeg & 1) * W4_RAW_FLOATS + lwr);
     load_raw(qbeg + 1);
 #pragma unroll
     for (int j = 0; j < 3; ++j) load_w(qbeg, j);
@@ -499,19 +504,19 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
       float* vslot = vbuf + (k & 1) * W4_V_FLOATS;
       constexpr int XG = decltype(xg_tag)::value;
       if (lowres && k >= Q0) {
-        t_read(xg_tag, std::true_type{}, raw, 0);
-        t_read(xg_tag, std::true_type{}, raw, 1);
+        t_read(xg_tag, std::true_type{}, raw + pbase_l, 0);
+        t_read(xg_tag, std::true_type{}, raw + pbase_l, 1);
         t_rows(xg_tag, std::true_type{}, 0);
         t_rows(xg_tag, std::true_type{}, 1);
-        t_cols(xg_tag, std::true_type{}, std::integral_constant<int, 0>{}, vslot);
-        if constexpr (XG < 2) t_cols(xg_tag, std::true_type{}, std::integral_constant<int, 1>{}, vslot);
+        t_cols(xg_tag, std::true_type{}, std::integral_constant<int, 0>{}, vslot, vwq, vwd);
+        if constexpr (XG < 2) t_cols(xg_tag, std::true_type{}, std::integral_constant<int, 1>{}, vslot, vwq, vwd);
       } else {
-        t_read(xg_tag, std::false_type{}, raw, 0);
-        t_read(xg_tag, std::false_type{}, raw, 1);
+        t_read(xg_tag, std::false_type{}, raw + pbase_f, 0);
+        t_read(xg_tag, std::false_type{}, raw + pbase_f, 1);
         t_rows(xg_tag, std::false_type{}, 0);
         t_rows(xg_tag, std::false_type{}, 1);
-        t_cols(xg_tag, std::false_type{}, std::integral_constant<int, 0>{}, vslot);
-        if constexpr (XG < 2) t_cols(xg_tag, std::false_type{}, std::integral_constant<int, 1>{}, vslot);
+        t_cols(xg_tag, std::false_type{}, std::integral_constant<int, 0>{}, vslot, vwq, vwd);
+        if constexpr (XG < 2) t_cols(xg_tag, std::false_type{}, std::integral_constant<int, 1>{}, vslot, vwq, vwd);
       }
     };
     switch (xg) {
@@ -525,7 +530,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
     for (int x = 0; x < 9; ++x)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[x][r] = 0.f;
-    store_raw(qbeg + 1);
+    store_raw(rawbuf + ((qbeg + 1) & 1) * W4_RAW_FLOATS + lwr);
     load_raw(qbeg + 2);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // V of the first quarter and the halo of the second are written
     __builtin_amdgcn_s_barrier();
@@ -558,18 +563,28 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
 #endif
     // One quarter: 18 MFMAs of quarter q with the transform of quarter q + 1 (kind LR), the weight loads of q + 1 and the halo transfers of q + 3 between them.
     // MM = false: this wave's 32 output channels do not exist (last N tile of a layer with 32 channels mod 64): producer duties only.
-    auto quarters = [&](auto xg_tag, auto mm_tag, auto lr_tag, int q0, int q1) __attribute__((always_inline)) {
+    // PAIRED: q0 and q1 - q0 are even and the loop runs two quarters per trip, so that a quarter's parity -- which raw and V slot it reads and writes -- is known at compile time
+    // and sits in the immediate offsets of the LDS instructions: the lane's four LDS addresses (halo store, patch read, V write, V read) stay what they are from quarter
+    // to quarter.  Not PAIRED, every quarter forms the four from the parity (four v_add_u32 / v_lshl_add_u32 per wave and quarter).
+    auto quarters = [&](auto xg_tag, auto mm_tag, auto lr_tag, auto paired_tag, int q0, int q1) __attribute__((always_inline)) {
       constexpr int XG = decltype(xg_tag)::value;
       constexpr bool MM = decltype(mm_tag)::value;
       constexpr bool LR = decltype(lr_tag)::value;
+      constexpr bool PAIRED = decltype(paired_tag)::value;
       constexpr bool PAIR = XG < 2;
       const std::integral_constant<int, 0> first{};
       const std::integral_constant<int, 1> second{};
-      for (int q = q0; q < q1; ++q) {
-        const float* raw = rawbuf + ((q + 1) & 1) * W4_RAW_FLOATS;
-        float* vslot = vbuf + ((q + 1) & 1) * W4_V_FLOATS;
-        const float* vq = vbuf + (q & 1) * W4_V_FLOATS + vrq;
-        const float* vd = vbuf + (q & 1) * W4_V_FLOATS + vrd;
+      // the lane's five LDS places of this loop, opaque to the compiler from here on: the addresses it derives from them (a shift, the slot bases) are formed at the head of
+      // THIS loop and die with it -- derived once per tile for all loops they are live across every loop of the tile and the register allocator spills ~100 of them
+      int i_lwr = lwr, i_pb = LR ? pbase_l : pbase_f, i_vwq = vwq, i_vwd = vwd, i_vrq = vrq, i_vrd = vrd;
+      if constexpr (LOWRES && !KS) asm volatile("" : "+v"(i_lwr), "+v"(i_pb), "+v"(i_vwq), "+v"(i_vwd), "+v"(i_vrq), "+v"(i_vrd));  // (the instantiation with four loops per tile)
+      auto one = [&](auto par_tag, int q) __attribute__((always_inline)) {
+        constexpr int PAR = decltype(par_tag)::value;  // q & 1 where the loop knows it, else -1
+        const int s0 = PAR < 0 ? (q & 1) : PAR, s1 = PAR < 0 ? ((q + 1) & 1) : 1 - PAR;
+        const float* raw = rawbuf + s1 * W4_RAW_FLOATS + i_pb;
+        float* vslot = vbuf + s1 * W4_V_FLOATS;
+        const float* vq = vbuf + s0 * W4_V_FLOATS + i_vrq;
+        const float* vd = vbuf + s0 * W4_V_FLOATS + i_vrd;
         f32x4 vf0, vf1, vf2;
         // the previous quarter's last six MFMAs come first (their operands have been in registers since before the barrier), the quarter's memory instructions between them
         P4_ST(0)
@@ -578,7 +593,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
           acc[7] = P4_MFMA(wf[3][1], vf3[1], acc[7]);
         }
         P4_SB
-        store_raw(q + 2);  // (loaded during quarter q - 1; slot q & 1 was transformed during quarter q - 1)
+        store_raw(rawbuf + s0 * W4_RAW_FLOATS + i_lwr);  // quarter q + 2 (loaded during quarter q - 1; slot q & 1 was transformed during quarter q - 1)
         t_read(xg_tag, lr_tag, raw, 0);
         P4_SB
         P4_ST(1)
@@ -619,7 +634,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
           acc[3] = P4_MFMA(wf[1][1], vf1[1], acc[3]);
           vf3 = *reinterpret_cast<const f32x4*>(vq + 768);
         }
-        t_cols(xg_tag, lr_tag, first, vslot);
+        t_cols(xg_tag, lr_tag, first, vslot, i_vwq, i_vwd);
         if constexpr (MM) {
           acc[2] = P4_MFMA(wf[1][2], vf1[2], acc[2]);
           acc[3] = P4_MFMA(wf[1][3], vf1[3], acc[3]);
@@ -632,7 +647,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
           acc[5] = P4_MFMA(wf[2][1], vf2[1], acc[5]);
           vf9 = *reinterpret_cast<const float2*>(vd);
         }
-        if constexpr (PAIR) t_cols(xg_tag, lr_tag, second, vslot);
+        if constexpr (PAIR) t_cols(xg_tag, lr_tag, second, vslot, i_vwq, i_vwd);
         if constexpr (MM) {
           acc[4] = P4_MFMA(wf[2][2], vf2[2], acc[4]);
           acc[5] = P4_MFMA(wf[2][3], vf2[3], acc[5]);
@@ -644,16 +659,38 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(ConvArgs a) {
         if (!(W4_EXP & 4)) __builtin_amdgcn_s_barrier();
         P4_SB
         P4_ST_END
+      };
+      if constexpr (PAIRED) {
+        for (int q = q0; q < q1; q += 2) {
+          one(std::integral_constant<int, 0>{}, q);
+          one(std::integral_constant<int, 1>{}, q + 1);
+        }
+      } else {
+        for (int q = q0; q < q1; ++q) one(std::integral_constant<int, -1>{}, q);
       }
     };
     // (the transform of quarter q + 1 is the low-resolution one from q = Q0 - 1 on)
+    // A K slice starts and ends at any quarter: one quarter per trip.  The whole K (quarters 0 .. Q, Q even: wino4_shape_ok) runs in pairs; around the odd quarter at
+    // which the transform changes, the two quarters Q0 - 2 and Q0 - 1 run singly.
     auto run = [&](auto xg_tag, auto mm_tag) __attribute__((always_inline)) {
+      const std::false_type single{};
+      const std::true_type paired{};
       if constexpr (LOWRES) {
         const int qs = min(max(Q0 - 1, qbeg), qend);
-        quarters(xg_tag, mm_tag, std::false_type{}, qbeg, qs);
-        quarters(xg_tag, mm_tag, std::true_type{}, qs, qend);
+        if constexpr (KS) {
+          quarters(xg_tag, mm_tag, std::false_type{}, single, qbeg, qs);
+          quarters(xg_tag, mm_tag, std::true_type{}, single, qs, qend);
+        } else {
+          const int qa = qs & ~1, qb = (qs + 1) & ~1;  // (qbeg = 0, qend = Q is even: qa <= qs <= qb <= qend)
+          quarters(xg_tag, mm_tag, std::false_type{}, paired, qbeg, qa);
+          quarters(xg_tag, mm_tag, std::false_type{}, single, qa, qs);
+          quarters(xg_tag, mm_tag, std::true_type{}, single, qs, qb);
+          quarters(xg_tag, mm_tag, std::true_type{}, paired, qb, qend);
+        }
+      } else if constexpr (KS) {
+        quarters(xg_tag, mm_tag, std::false_type{}, single, qbeg, qend);
       } else {
-        quarters(xg_tag, mm_tag, std::false_type{}, qbeg, qend);
+        quarters(xg_tag, mm_tag, std::false_type{}, paired, qbeg, qend);
       }
     };
     auto run_mm = [&](auto mm_tag) __attribute__((always_inline)) {
@@ -854,6 +891,7 @@ int prepare_wino4_kernels() {
 // addressable through a 32-bit buffer descriptor; no fused pool / head / accumulate / ReLU mask (those stay on the F(2x2,3x3) kernel).
 bool wino4_shape_ok(const ConvArgs& a) {
   if (!a.wpack_wino4 || a.bn != 64 || (a.H & 3) || (a.W & 3) || a.head_w || a.accumulate) return false;
+  if ((a.c0p & 3) || (a.c1p & 3) || ((a.c0p + a.c1p) & 7)) return false;  // whole quarters per source, an even number in all (the K loop runs them in pairs; padded channel counts are multiples of 16)
   if (a.src1_lowres && (!a.src1 || (a.H & 1) || (a.W & 1))) return false;
   const uint64_t px = (uint64_t)a.B * a.H * a.W;
   if (px * (uint64_t)a.c0p * 4 >= 0xFFFFFF00ull || px * (uint64_t)a.c1p * 4 >= 0xFFFFFF00ull || px >= 0x7FFFFFFFull) return false;
