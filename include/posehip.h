@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 131
+#define PH_VERSION 132
 
 /* error codes */
 #define PH_OK 0
@@ -133,7 +133,16 @@ enum ph_op_kind {
                              (resnet_kernels.hip): the im2col product (K = 49 cin) on v_mfma_f32_32x32x2_f32, then the pool.  weight (cout, cin0, 7, 7), cin0 <= 4 */
   PH_OP_CONV_S2 = 20,     /* Conv2d(k = ksize in {1, 3}, stride 2, padding ksize / 2) + bias (+ReLU) over an even-sized map, as a row GEMM whose rows gather their
                              taps at stride 2 (gemm_mfma_dma_tile_kernel mode 4 / mode 6).  weight (cout, cin0, k, k) */
-  PH_OP_ADD_RELU = 21     /* dst = relu(src0 + src1), element-wise over two slots of one shape (cin0 = cout channels): the tail of a ResNet basic block */
+  PH_OP_ADD_RELU = 21,    /* dst = relu(src0 + src1), element-wise over two slots of one shape (cin0 = cout channels): the tail of a ResNet basic block */
+  /* Swin Transformer V2 encoder (HuggingFace Swinv2Backbone behind the reference's PretrainedBackbone).  Exact fp32, inference only: its ops of its own -- this one,
+     PH_OP_LAYERNORM with PH_FLAG_RESIDUAL, PH_OP_PATCH_MERGE with PH_FLAG_NO_NORM -- carry PH_FLAG_NO_TRAIN and ph_model_backward refuses the program whatever the
+     handle's options.  The host hands the library DERIVED tensors for this op and the qkv Linear in front of it (computed in float64 from the checkpoint's parameters). */
+  PH_OP_WINDOW_ATTN_V2 = 22 /* cosine window attention core (swinv2_kernels.hip): src0 = qkv slot (B, H, W, 3C) as PH_OP_WINDOW_ATTN, weight = 16 sigmoid(continuous
+                             position bias) HEAD-MAJOR (heads, (2 ksize - 1)^2), bias = (3C) query.bias | zeros | value.bias (the q, k, v of a padded token: hidden state
+                             0, key has no bias), weight2 = (heads) exp(min(logit_scale, log 100)), ksize = window side (2..8), cin1 = heads (cout = 32 heads), cmid = the
+                             layer's shift, applied on both axes whatever the map (HuggingFace rolls and masks a shifted layer even where one window covers the axis).
+                             dst = softmax(scale (q / max(|q|, 1e-12)) . (k / max(|k|, 1e-12)) + bias [- 200 across the shift's bands: the installed
+                             Swinv2SelfAttention adds its -100 mask twice]) v at each token's own pixel */
 };
 
 #define PH_FLAG_RELU 1
@@ -145,11 +154,14 @@ enum ph_op_kind {
 #define PH_FLAG_NO_TRAIN 64 /* PH_OP_HEAD: a head of the segmentation model types, which neither MSE nor cross entropy trains; the forward ignores it,
                                ph_model_backward refuses the program unless ph_model_set_head_loss chose the head's loss on this handle.
                                PH_OP_GRN / PH_OP_PATCH_STEM with PH_FLAG_PAD0_NORM: refused unless the handle option pretrained_train is 1.
-                               PH_OP_RESNET_STEM / PH_OP_CONV_S2 / PH_OP_ADD_RELU (a ResNet program): always refused, they have no backward step */
+                               PH_OP_RESNET_STEM / PH_OP_CONV_S2 / PH_OP_ADD_RELU (a ResNet program): always refused, they have no backward step.
+                               PH_OP_WINDOW_ATTN_V2, PH_OP_LAYERNORM with PH_FLAG_RESIDUAL, PH_OP_PATCH_MERGE with PH_FLAG_NO_NORM (a Swinv2 program): always refused */
 #define PH_FLAG_LN_EPS_1EM5 128 /* PH_OP_LAYERNORM / PH_OP_PATCH_MERGE: eps 1e-5 (nn.LayerNorm's default: the Swin norms) instead of 1e-6 */
-#define PH_FLAG_RESIDUAL 256    /* PH_OP_LINEAR: dst = acc + bias + src1 (a residual add without a layer scale: Swin's attn.proj and mlp.3; ConvNeXtV2's pwconv2) */
+#define PH_FLAG_RESIDUAL 256    /* PH_OP_LINEAR: dst = acc + bias + src1 (a residual add without a layer scale: Swin's attn.proj and mlp.3; ConvNeXtV2's pwconv2).
+                                   PH_OP_LAYERNORM: dst = src1 + LayerNorm(src0) (Swinv2 norms after each branch; src1 and dst are distinct slots; exact fp32 only) */
 #define PH_FLAG_PAD0_NORM 512   /* PH_OP_PATCH_STEM: padding 0 instead of 1 and the input is (x / 255 - mean[ci]) / std[ci] with the handle's input statistics
                                    (ph_model_set_input_norm; 0 and 1 until set): HuggingFace's ConvNextV2Embeddings behind PretrainedBackbone._normalize */
+#define PH_FLAG_NO_NORM 1024    /* PH_OP_PATCH_MERGE: the four-phase gather alone, no LayerNorm and no weight / bias (Swinv2 norms behind the reduction); exact fp32 only */
 
 typedef struct ph_op_desc {
   int32_t kind;      /* enum ph_op_kind                                              */
@@ -458,6 +470,12 @@ typedef struct ph_conv_run_case {
 int32_t ph_conv_run_case_size(void);
 int ph_debug_conv3x3_run(ph_conv_run_case* c);
 
+/* Test support (tests/test_gpu_window_attn_v2.py), not a product path: ONE launch of the cosine window attention (window_attn_v2_kernel) on tensors the caller owns,
+ * synchronised before it returns.  All pointers are device pointers: qkv (B, H, W, 96 heads) = query | key | value of the map, qkv_bias (96 heads) = what a padded token's
+ * q, k, v are (its key section is zeros in the product), scale (heads), table (heads, (2 w - 1)^2), dst (B, H, W, 32 heads).  shift applies on both axes. */
+int ph_debug_window_attn_v2_run(const float* qkv, const float* qkv_bias, const float* scale, const float* table, float* dst, int32_t B, int32_t H, int32_t W, int32_t heads,
+                                int32_t w, int32_t shift);
+
 /* Diagnostic (tools/row_wgrad_bench.py): average milliseconds of the row weight-gradient GEMM dW[n][k] = sum_m dY[m][n] X[m][k]
  * (Linear layers of the training step, train_kernels.h launch_row_wgrad) on synthetic operands, and the largest error of 64
  * sampled entries against a float64 sum on the host, relative to the largest of them. */
@@ -537,6 +555,9 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_RESNET_STEM 29 /* resnet_stem_conv_kernel + maxpool3s2_kernel: normalised 7x7 stride-2 stem as an im2col product on v_mfma_f32_32x32x2_f32, then the 3x3 stride-2 max pool */
 #define PH_KV_CONV_S2 30 /* gemm_mfma_dma_tile_kernel mode 4 (3x3 stride 2 pad 1) / mode 6 (1x1 stride 2) as the forward of a PH_OP_CONV_S2 */
 #define PH_KV_ADD_RELU 31 /* add_relu_kernel: dst = relu(src0 + src1), float4 per thread */
+#define PH_KV_WINDOW_ATTN_V2 32 /* window_attn_v2_kernel: cosine window attention, one wave per (window, head) on v_mfma_f32_32x32x2_f32 */
+#define PH_KV_LAYERNORM_ADD 33 /* layernorm_add_kernel: dst = src1 + LayerNorm(src0) */
+#define PH_KV_PATCH_MERGE_GATHER 34 /* patch_merge_gather_kernel as the forward of a PH_OP_PATCH_MERGE with PH_FLAG_NO_NORM */
 #define PH_KV_FUSED 11   /* no launch of its own: a 1x1 head computed in the epilogue of the conv that produces its input */
 int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
 /* ... and the tile plan of every op of the LAST ph_model_forward that ran conv3x3_f16_rows_kernel (PH_KV_F16_ROWS): quad[4 i .. 4 i + 3] = {R rows, Wt columns of a tile, MT M tiles

@@ -27,7 +27,7 @@ PRECISIONS = {"exact": 0, "split": 1, "fp16": 2}
 
 def get_backbone(backbone: str, backbone_config):
     """architectures/model.py:36-67.  ``unet``, ``convnext``, ``swint`` and ``pretrained`` (the ConvNeXtV2 family; the ResNet family with the config key
-    ``allow_resnet``, inference only) are built natively; all four train on the device."""
+    ``allow_resnet`` and the Swinv2 family with ``allow_swinv2``, both inference only) are built natively; all four train on the device."""
     if backbone == "unet":
         return UNet.from_config(backbone_config)
     if backbone == "convnext":
@@ -291,6 +291,9 @@ class Model:
         if mode and self.is_resnet:
             raise NotImplementedError("a 'pretrained' ResNet backbone is inference only on the MI355X path: its program runs BatchNorm folded into the convs (eval statistics); "
                                       "training needs BatchNorm with batch statistics, which is not built (sleap_nn_amd/architectures/pretrained.py)")
+        if mode and self.is_swinv2:
+            raise NotImplementedError("a 'pretrained' Swinv2 backbone is inference only on the MI355X path: its cosine window attention, residual-after-norm LayerNorm and "
+                                      "norm-less patch merge have no backward step (sleap_nn_amd/architectures/pretrained.py)")
         if mode and self.backbone_type == "pretrained":
             if not allow_pretrained:
                 raise NotImplementedError("training a 'pretrained' (ConvNeXtV2) backbone is opt-in on the MI355X path (its GRN and padding-0 stem ops carry PH_FLAG_NO_TRAIN): "
@@ -306,6 +309,11 @@ class Model:
     def is_resnet(self) -> bool:
         """A ``pretrained`` backbone of the ResNet family (HuggingFace ResNetBackbone): BatchNorm folded at handle creation, exact fp32, inference only."""
         return self.backbone_type == "pretrained" and getattr(self.backbone, "family", "") == "resnet"
+
+    @property
+    def is_swinv2(self) -> bool:
+        """A ``pretrained`` backbone of the Swinv2 family (HuggingFace Swinv2Backbone): qkv, bias table and logit scales derived at handle creation, exact fp32, inference only."""
+        return self.backbone_type == "pretrained" and getattr(self.backbone, "family", "") == "swinv2"
 
     def trainable_ranges(self, freeze_encoder: Optional[bool] = None) -> List[tuple]:
         """``[(start, end), ...]`` of the flat parameter arena (``param_keys`` order) that an optimizer steps: sorted, disjoint, on parameter boundaries, neighbours
@@ -407,7 +415,8 @@ class Model:
         fp16, then the fp16 decoder.  Without it a Swin program runs exact under every precision
         (tests/test_gpu_swint.py pins that); ``"split"`` is exact for it either way.
         A ``pretrained`` (ConvNeXtV2) program has no fp16 form: it runs exact under every precision and whatever ``convnext_f16`` says (tests/test_gpu_pretrained.py);
-        so does a ``pretrained`` ResNet program (tests/test_gpu_pretrained_resnet.py).
+        so does a ``pretrained`` ResNet program (tests/test_gpu_pretrained_resnet.py) and a ``pretrained`` Swinv2 program, whatever ``swint_f16`` says
+        (tests/test_gpu_pretrained_swinv2.py).
         Programs with a class-vector head (global max pool, softmax) and every training program run exact whatever is set."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
@@ -505,7 +514,9 @@ class Model:
             d.bias2 = index[op.bias2] if op.bias2 else -1
         # a ResNet backbone: the conv ops read W * g / sqrt(var + eps) and beta - mean * g / sqrt(var + eps) where the arena has W and beta -- folded here, from the state and
         # the buffers as they stand (load_state_dict releases the handle, so a fold never outlives what it was made from); _state keeps the unfolded tensors
-        folded = self.backbone.folded_params(self._state, self.buffers) if self.is_resnet else {}
+        # a Swinv2 backbone: the qkv Linear and the attention op read the concatenated query | key | value, the padded token's q | 0 | v, the 16 sigmoid(MLP) bias table and the
+        # clamped, exponentiated logit scales under four of each block's keys (derived_params), by the same mechanism
+        folded = self.backbone.folded_params(self._state, self.buffers) if self.is_resnet else self.backbone.derived_params(self._state, self.buffers) if self.is_swinv2 else {}
         tensors = [folded.get(k, self._state[k]).contiguous() for k in keys]
         ptrs = (C.c_void_p * len(keys))(*[t.data_ptr() for t in tensors])
         numel = (C.c_int64 * len(keys))(*[t.numel() for t in tensors])
@@ -562,8 +573,8 @@ class Model:
         x, code = self.adapt_channels(x, code)
         x = x.contiguous()
         B, Cin, H, W = x.shape
-        if self.is_resnet and (H % self.backbone.max_stride or W % self.backbone.max_stride):  # every strided conv must see an even map: anything else would be another network's map
-            raise ValueError(f"a 'pretrained' ResNet backbone takes frames whose height and width are multiples of {self.backbone.max_stride}, got {H} x {W} "
+        if (self.is_resnet or self.is_swinv2) and (H % self.backbone.max_stride or W % self.backbone.max_stride):  # every strided conv / patch merge must see an even map: anything else would be another network's map
+            raise ValueError(f"a 'pretrained' {'ResNet' if self.is_resnet else 'Swinv2'} backbone takes frames whose height and width are multiples of {self.backbone.max_stride}, got {H} x {W} "
                              "(the inference layers pad to max_stride)")
         self._last_batch = int(B)
         self._ensure(device)
@@ -684,7 +695,7 @@ class Model:
                 oh, ow = h // 2, w // 2
             elif op.kind == L.OP_PATCH_MERGE:
                 oh, ow = (h + 1) // 2, (w + 1) // 2
-            if op.kind == L.OP_WINDOW_ATTN:
+            if op.kind in (L.OP_WINDOW_ATTN, L.OP_WINDOW_ATTN_V2):
                 # q k^T and p v: 2 * N * d multiply-adds each per token and head (cin1 = heads, ksize = window side, head dimension cout / heads)
                 rows.append({"label": op.label.split(".")[-1], "kind": op.kind, "flops": 4.0 * op.ksize * op.ksize * op.cout * h * w * batch,
                              "bytes": float(4 * (op.cin0 + op.cout) * h * w * batch), "cin0": op.cin0, "cin1": 0, "cout": op.cout, "ksize": op.ksize, "out_hw": (h, w)})

@@ -1,4 +1,4 @@
-"""HuggingFace ConvNeXtV2 (or, opt-in, ResNet) encoder + UNet-style decoder -> op program for libposehip.
+"""HuggingFace ConvNeXtV2 (or, opt-in, ResNet or Swinv2) encoder + UNet-style decoder -> op program for libposehip.
 
 Reproduces Case A (``mode="decoder"``) of the reference ``PretrainedBackbone``
 (``sleap_nn/architectures/pretrained.py:111-502``) for the ConvNeXtV2 family, without torch modules and
@@ -21,6 +21,11 @@ the published ConvNeXtV2 configs have 0.0.
 The ResNet family (HuggingFace ``ResNetBackbone``; basic and bottleneck layers) is opt-in through the backbone-config key ``allow_resnet`` -- existing tests pin its refusal -- and
 inference only: BatchNorm (eval) is folded into each conv on the host (``fold_batchnorm`` / ``folded_params``, float64, at handle creation) while the state dict keeps the
 reference's unfolded names; the stem, the strided convs and the residual tails are ``csrc/resnet_kernels.hip`` and the row GEMM's modes 4 and 6.
+
+The Swinv2 family (HuggingFace ``Swinv2Backbone``; effective windows of 2..8, head dimension 32) is opt-in through the backbone-config key ``allow_swinv2`` for the same reason, and
+inference only: per-stage window and shift follow the config's ``image_size`` (``swinv2_windows``); the qkv concatenation, the padded token's q | 0 | v, the ``16 sigmoid(MLP(coords))`` bias
+table and the clamped, exponentiated logit scales are derived on the host (``derived_params``, float64, at handle creation) while the state dict keeps the reference's names; the cosine window
+attention and the residual-after-norm LayerNorm are ``csrc/swinv2_kernels.hip``.
 
 A ConvNeXtV2 block is six ops: depthwise 7x7 -> LayerNorm -> Linear C->4C -> GELU -> GRN -> Linear 4C->C with the residual add
 in its epilogue (no layer scale).  ``Model._fuse_cnblocks`` folds the GELU into the first Linear for inference.
@@ -69,6 +74,18 @@ RESNET_SIZES = {
 RESNET_OPT_IN = ("the ResNet family is opt-in: backbone-config key allow_resnet=True (LoadedAssets.build_model(pretrained_resnet=True), "
                  "Predictor.from_model_paths(..., pretrained_resnet=True))")
 BN_EPS = 1e-5  # nn.BatchNorm2d's default, which HuggingFace's ResNetConvLayer keeps
+# microsoft/swinv2-<size>-patch4-window<w>-<img>: embed_dim, depths, heads (head dimension 32 throughout).  The tiny row is Swinv2Config()'s defaults
+# (tests/test_pretrained_swinv2_cpu.py checks it where transformers is installed); the other rows are the published configs as recalled -- nothing here can reach the hub to
+# check them, a local config.json wins.  window_size and image_size come from the id; pretrained_window_sizes is all zero (the 12to16 / 12to24 ids have windows above 8 anyway)
+SWINV2_SIZES = {
+    "tiny": {"embed_dim": 96, "depths": [2, 2, 6, 2], "num_heads": [3, 6, 12, 24]},
+    "small": {"embed_dim": 96, "depths": [2, 2, 18, 2], "num_heads": [3, 6, 12, 24]},
+    "base": {"embed_dim": 128, "depths": [2, 2, 18, 2], "num_heads": [4, 8, 16, 32]},
+}
+SWINV2_OPT_IN = ("the Swinv2 family is opt-in: backbone-config key allow_swinv2=True (LoadedAssets.build_model(pretrained_swinv2=True), "
+                 "Predictor.from_model_paths(..., pretrained_swinv2=True))")
+SWINV2_HEAD_DIM = 32  # what window_attn_v2_kernel is built for
+SWINV2_MAX_LOGIT = math.log(1.0 / 0.01)  # Swinv2SelfAttention clamps logit_scale here before the exp: scale <= 100
 
 
 def _refuse(what: str) -> NotImplementedError:
@@ -94,11 +111,92 @@ def _resolve_resnet(hf: dict, source: str) -> dict:
     return arch
 
 
-def resolve_architecture(model_name: str, run_dir: Optional[str] = None, allow_resnet: bool = False) -> dict:
+def swinv2_windows(image_size, patch_size: int, window_size: int, n_stages: int = 4) -> List[Tuple[int, int]]:
+    """Per stage ``(window, shift of the odd blocks)`` as HuggingFace's ``Swinv2Layer._compute_window_shift`` derives them -- from the CONFIG's ``image_size``, not from the
+    frame: stage i has ``input_resolution = image_size // patch_size // 2^i``, ``window = min(resolution, window_size)`` and no shift where the resolution is no larger than
+    that window.  (HuggingFace computes both per axis and keeps the height axis' values: ``window_size[0]``, ``shift_size[0]``.)"""
+    ih = int(image_size[0] if isinstance(image_size, (list, tuple)) else image_size)
+    out = []
+    for i in range(n_stages):
+        res = ih // int(patch_size) // 2 ** i
+        w = min(res, int(window_size))
+        out.append((w, 0 if res <= w else int(window_size) // 2))
+    return out
+
+
+def swinv2_coords_table(window: int, pretrained_window: int = 0) -> torch.Tensor:
+    """``Swinv2SelfAttention.create_coords_table_and_index``'s table for a square window, ((2w - 1)^2, 2) float32, by the same float32 operations (so the same bits):
+    offsets -(w - 1) .. w - 1 over (pretrained_window - 1 if pretrained_window > 0 else w - 1), times 8, then sign(x) log2(|x| + 1) / log2(8).  Row (dy + w - 1)(2w - 1) +
+    (dx + w - 1): the index ``relative_position_index`` gives the pair (query - key) = (dy, dx), which is how the attention kernels address their table."""
+    r = torch.arange(-(window - 1), window, dtype=torch.int64).float()
+    t = torch.stack(torch.meshgrid([r, r], indexing="ij")).permute(1, 2, 0).contiguous().unsqueeze(0)
+    if pretrained_window > 0:
+        t /= pretrained_window - 1
+    elif window > 1:
+        t /= window - 1
+    t *= 8
+    t = torch.sign(t) * torch.log2(torch.abs(t) + 1.0) / math.log2(8)
+    return t.view(-1, 2)
+
+
+def swinv2_bias_table(coords: torch.Tensor, w0: torch.Tensor, b0: torch.Tensor, w2: torch.Tensor) -> torch.Tensor:
+    """``16 sigmoid(Linear(512 -> heads, no bias)(relu(Linear(2 -> 512)(coords))))`` in float64, rounded once: (heads, (2w - 1)^2) float32, head-major as the kernel reads it."""
+    h = torch.relu(coords.double() @ w0.double().t() + b0.double())
+    return (16.0 * torch.sigmoid(h @ w2.double().t())).t().contiguous().float()
+
+
+def swinv2_logit_scale(logit_scale: torch.Tensor) -> torch.Tensor:
+    """``exp(min(logit_scale, log 100))`` per head, float64 rounded once: (heads,) float32."""
+    return torch.exp(torch.clamp(logit_scale.double().reshape(-1), max=SWINV2_MAX_LOGIT)).float().contiguous()
+
+
+def _resolve_swinv2(hf: dict, source: str) -> dict:
+    """The Swinv2 leaf of ``resolve_architecture``: ``hf`` holds config.json's keys (or a row of ``SWINV2_SIZES`` with the id's window and image size); what the program
+    cannot run is refused by name."""
+    d = SWINV2_SIZES["tiny"]
+    embed = int(hf.get("embed_dim", d["embed_dim"]))
+    depths = [int(v) for v in (hf.get("depths") or d["depths"])]
+    heads = [int(v) for v in (hf.get("num_heads") or d["num_heads"])]
+    img = hf.get("image_size", 224)
+    img = [int(v) for v in img] if isinstance(img, (list, tuple)) else [int(img), int(img)]
+    ps = hf.get("patch_size", 4)
+    ps = int(ps[0] if isinstance(ps, (list, tuple)) else ps)
+    ws = int(hf.get("window_size", 7))
+    if len(depths) != 4 or len(heads) != 4:
+        raise _refuse(f"a Swinv2 with {len(depths)} stages ({source})")
+    pws = [int(v) for v in (hf.get("pretrained_window_sizes") or [0, 0, 0, 0])]
+    if len(pws) != 4:
+        raise _refuse(f"pretrained_window_sizes={pws} of {source} (one per stage)")
+    eps = float(hf.get("layer_norm_eps", 1e-5))
+    arch = {"family": "swinv2", "embed_dim": embed, "hidden_sizes": [embed * 2 ** i for i in range(4)], "depths": depths, "num_heads": heads, "image_size": img, "patch_size": ps,
+            "window_size": ws, "pretrained_window_sizes": pws, "mlp_ratio": float(hf.get("mlp_ratio", 4.0)), "qkv_bias": bool(hf.get("qkv_bias", True)), "layer_norm_eps": eps,
+            "num_channels": int(hf.get("num_channels", 3)), "drop_path_rate": float(hf.get("drop_path_rate", 0.1)), "source": source}
+    for c, h in zip(arch["hidden_sizes"], heads):
+        if h < 1 or c != h * SWINV2_HEAD_DIM:
+            raise _refuse(f"a head dimension of {c}/{h} ({source}; the cosine window attention kernel is built for {SWINV2_HEAD_DIM})")
+    for i, (w, _s) in enumerate(swinv2_windows(img, ps, ws)):
+        if not (2 <= w <= 8):
+            raise _refuse(f"an effective window of {w} in stage {i + 1} of {source} (window_size {ws}, image_size {img[0]}; the kernel holds windows of 2..8, at most 64 tokens: "
+                          "the window16 and 12to16 / 12to24 checkpoints need another one)")
+    if hf.get("use_absolute_embeddings", False):
+        raise _refuse(f"use_absolute_embeddings=True of {source}")
+    if hf.get("hidden_act", "gelu") != "gelu":
+        raise _refuse(f"hidden_act {hf.get('hidden_act')!r} of {source}")
+    if eps not in (1e-5, 1e-6):
+        raise _refuse(f"layer_norm_eps={eps} of {source} (the LayerNorm ops have 1e-5 and 1e-6)")
+    if not arch["qkv_bias"]:
+        raise _refuse(f"qkv_bias=False of {source} (the padded tokens of a window read their q and v from the biases)")
+    if arch["mlp_ratio"] <= 0 or int(arch["mlp_ratio"] * embed) != arch["mlp_ratio"] * embed:
+        raise _refuse(f"mlp_ratio={arch['mlp_ratio']} of {source}")
+    return arch
+
+
+def resolve_architecture(model_name: str, run_dir: Optional[str] = None, allow_resnet: bool = False, allow_swinv2: bool = False) -> dict:
     """``model_name`` -> {"family", "depths", "hidden_sizes", "patch_size", "num_channels", ...} without touching a network.
 
     (a) a directory holding a ``config.json`` (absolute as given; relative against ``run_dir``, then the working directory), dispatched on its ``model_type``;
-    (b) the size word of a ``convnextv2-<size>`` id, or -- with ``allow_resnet`` -- the number of a ``resnet-<N>`` id; (c) anything else is refused."""
+    (b) the size word of a ``convnextv2-<size>`` id, or -- with ``allow_resnet`` -- the number of a ``resnet-<N>`` id, or -- with ``allow_swinv2`` -- size, window and image
+    size of a ``swinv2-<size>-patch4-window<w>-<img>`` id; (c) anything else is refused."""
     name = str(model_name)
     cands = [name] if os.path.isabs(name) else ([os.path.join(run_dir, name)] if run_dir else []) + [os.path.join(os.getcwd(), name)]
     for d in cands:
@@ -110,8 +208,10 @@ def resolve_architecture(model_name: str, run_dir: Optional[str] = None, allow_r
         mt = hf.get("model_type")
         if mt == "resnet" and allow_resnet:
             return _resolve_resnet(hf, path)
+        if mt == "swinv2" and allow_swinv2:
+            return _resolve_swinv2(hf, path)
         if mt != "convnextv2":
-            raise _refuse(f"model_type {mt!r} of {path}" + (f" ({RESNET_OPT_IN})" if mt == "resnet" else ""))
+            raise _refuse(f"model_type {mt!r} of {path}" + (f" ({RESNET_OPT_IN})" if mt == "resnet" else f" ({SWINV2_OPT_IN})" if mt == "swinv2" else ""))
         if hf.get("hidden_act", "gelu") != "gelu":
             raise _refuse(f"hidden_act {hf.get('hidden_act')!r} of {path}")
         eps = float(hf.get("layer_norm_eps", 1e-12))  # (the classifier's pooled norm: no op of the backbone reads it)
@@ -127,7 +227,11 @@ def resolve_architecture(model_name: str, run_dir: Optional[str] = None, allow_r
     r = re.search(r"resnet-(\d+)", name.lower())
     if r and r.group(1) in RESNET_SIZES and allow_resnet:
         return _resolve_resnet(RESNET_SIZES[r.group(1)], r.group(0))
-    hint = f"; {RESNET_OPT_IN}" if r and r.group(1) in RESNET_SIZES else ""
+    s = re.search(r"swinv2-(tiny|small|base)-patch4-window(?:\d+to)?(\d+)-(?:\d+to)?(\d+)", name.lower())  # (window12to16-192to256: the fine-tuned window and image size)
+    if s and allow_swinv2:
+        return _resolve_swinv2({**SWINV2_SIZES[s.group(1)], "window_size": int(s.group(2)), "image_size": int(s.group(3)), "patch_size": 4,
+                                "pretrained_window_sizes": [0, 0, 0, 0]}, s.group(0))
+    hint = f"; {RESNET_OPT_IN}" if r and r.group(1) in RESNET_SIZES else f"; {SWINV2_OPT_IN}" if s else ""
     raise _refuse(f"model_name {name!r} (no local config.json, not a convnextv2-<size> id: ResNet, Swinv2, DINO and the isotropic ViTs are other families{hint})")
 
 
@@ -181,6 +285,16 @@ class PretrainedBackbone:
     bn_convs: List[Tuple[str, str]] = field(default_factory=list)
     ignored_buffers: Tuple[str, ...] = ()
     unit_init_keys: Tuple[str, ...] = ()  # parameters init_xavier_ sets to 1 (BatchNorm weights)
+    # Swinv2 family (HuggingFace Swinv2Backbone; opt-in through the config key allow_swinv2).  `swinv2_blocks` lists every block as (name, heads, window, pretrained window):
+    # `derived_params` gives the tensors its qkv Linear and its attention op read in place of query.weight / query.bias / continuous_position_bias_mlp.2.weight / logit_scale
+    embed_dim: int = 96
+    num_heads: List[int] = field(default_factory=list)
+    window_size: int = 7
+    image_size: List[int] = field(default_factory=lambda: [224, 224])
+    pretrained_window_sizes: List[int] = field(default_factory=lambda: [0, 0, 0, 0])
+    mlp_ratio: float = 4.0
+    layer_norm_eps: float = 1e-5
+    swinv2_blocks: List[Tuple[str, int, int, int]] = field(default_factory=list)
 
     @classmethod
     def from_config(cls, config) -> "PretrainedBackbone":
@@ -191,7 +305,8 @@ class PretrainedBackbone:
         if mode not in ("auto", "decoder"):
             raise _refuse(f"mode={mode!r} (the encoder-only pooled bottleneck)")
         name = cfg_get(config, "model_name", None) or DEFAULT_MODEL_NAME
-        arch = resolve_architecture(name, cfg_get(config, "_run_dir", None), allow_resnet=bool(cfg_get(config, "allow_resnet", False)))
+        arch = resolve_architecture(name, cfg_get(config, "_run_dir", None), allow_resnet=bool(cfg_get(config, "allow_resnet", False)),
+                                    allow_swinv2=bool(cfg_get(config, "allow_swinv2", False)))
         oi = cfg_get(config, "out_indices", None)
         if oi is not None and [int(i) for i in oi] != [0, 1, 2, 3, 4]:
             raise _refuse(f"out_indices={list(oi)} (a subset of the stages)")
@@ -208,7 +323,10 @@ class PretrainedBackbone:
             kernel_size=int(cfg_get(config, "kernel_size", 3)), up_interpolate=bool(cfg_get(config, "up_interpolate", True)),
             depths=[int(d) for d in arch["depths"]], channels=[int(c) for c in arch["hidden_sizes"]], patch_size=int(arch["patch_size"]),
             drop_path_rate=float(arch.get("drop_path_rate", 0.0)), family=str(arch.get("family", "convnextv2")), embedding_size=int(arch.get("embedding_size", 64)),
-            layer_type=str(arch.get("layer_type", "bottleneck")),
+            layer_type=str(arch.get("layer_type", "bottleneck")), embed_dim=int(arch.get("embed_dim", 96)), num_heads=[int(h) for h in arch.get("num_heads", [])],
+            window_size=int(arch.get("window_size", 7)), image_size=[int(v) for v in arch.get("image_size", [224, 224])],
+            pretrained_window_sizes=[int(v) for v in arch.get("pretrained_window_sizes", [0, 0, 0, 0])], mlp_ratio=float(arch.get("mlp_ratio", 4.0)),
+            layer_norm_eps=float(arch.get("layer_norm_eps", 1e-5)),
         )
         net._build()
         return net
@@ -230,6 +348,9 @@ class PretrainedBackbone:
         """What the opt-in to training refuses by name."""
         if self.family == "resnet":
             raise _refuse("training a ResNet backbone (BatchNorm with batch statistics is another op; the program runs the eval fold only)")
+        if self.family == "swinv2":
+            raise _refuse("training a Swinv2 backbone (the cosine window attention, the residual-after-norm LayerNorm and the norm-less patch merge have no backward step; "
+                          "the program is the eval forward only)")
         if self.drop_path_rate != 0.0:
             raise _refuse(f"training with drop_path_rate={self.drop_path_rate} (stochastic depth of the ConvNeXtV2 blocks; the published configs have 0.0)")
 
@@ -299,6 +420,8 @@ class PretrainedBackbone:
                         "backbone.image_std": torch.tensor(std, dtype=torch.float32).view(1, -1, 1, 1)}
         if self.family == "resnet":
             self._build_resnet_encoder()
+        elif self.family == "swinv2":
+            self._build_swinv2_encoder()
         else:
             self._build_encoder()
 
@@ -374,6 +497,103 @@ class PretrainedBackbone:
         out: Dict[str, torch.Tensor] = {}
         for cw, bn in self.bn_convs:
             out[cw], out[bn + ".bias"] = fold_batchnorm(state[cw], state[bn + ".weight"], state[bn + ".bias"], buffers[bn + ".running_mean"], buffers[bn + ".running_var"])
+        return out
+
+    # -- Swinv2 (HuggingFace Swinv2Backbone): padding-0 patch stem + LayerNorm, four stages of cosine-attention blocks that norm AFTER each branch, patch merging between
+    # them (gather -> bias-less reduction -> LayerNorm), RAW stage outputs (before the downsampling) as the pyramid
+    def _sv2_linear(self, name: str, src: int, cin: int, cout: int, weight: Optional[str] = None, bias: Optional[str] = None) -> int:
+        return self._emit(OpSpec(L.OP_LINEAR, src, -1, self._new_slot(), cin, 0, cout, 1, 0, weight or name + ".weight", bias, label=name))
+
+    def _sv2_norm(self, name: str, src: int, c: int, eps: float, residual: int = -1) -> int:
+        flags = (L.FLAG_LN_EPS_1EM5 if eps == 1e-5 else 0) | ((L.FLAG_RESIDUAL | L.FLAG_NO_TRAIN) if residual >= 0 else 0)
+        return self._emit(OpSpec(L.OP_LAYERNORM, src, residual, self._new_slot(), c, 0, c, 1, flags, name + ".weight", name + ".bias", label=name))
+
+    def _swinv2_block(self, name: str, x: int, c: int, heads: int, window: int, shift: int, pretrained_window: int) -> int:
+        p = self.param_shapes
+        a = name + ".attention.self"
+        hid = int(self.mlp_ratio * c)
+        # registered in the order of Swinv2Layer.__init__ (parameter arena = state_dict order), whatever the order the ops read them in
+        p[a + ".logit_scale"] = (heads, 1, 1)
+        p[a + ".continuous_position_bias_mlp.0.weight"] = (512, 2)
+        p[a + ".continuous_position_bias_mlp.0.bias"] = (512,)
+        p[a + ".continuous_position_bias_mlp.2.weight"] = (heads, 512)
+        p[a + ".query.weight"] = (c, c)
+        p[a + ".query.bias"] = (c,)
+        p[a + ".key.weight"] = (c, c)
+        p[a + ".value.weight"] = (c, c)
+        p[a + ".value.bias"] = (c,)
+        for n, (co, ci) in ((name + ".attention.output.dense", (c, c)), (name + ".layernorm_before", (c, 0)), (name + ".intermediate.dense", (hid, c)),
+                            (name + ".output.dense", (c, hid)), (name + ".layernorm_after", (c, 0))):
+            p[n + ".weight"] = (co, ci) if ci else (co,)
+            p[n + ".bias"] = (co,)
+        self.swinv2_blocks.append((name, heads, window, pretrained_window))
+        # the qkv Linear and the attention op read DERIVED tensors under four of these keys (derived_params): query.weight -> (3C, C) query | key | value,
+        # query.bias -> (3C) query.bias | 0 | value.bias, continuous_position_bias_mlp.2.weight -> the (heads, (2w - 1)^2) bias table, logit_scale -> the (heads) scales
+        qkv = self._sv2_linear(a + ".qkv", x, c, 3 * c, weight=a + ".query.weight", bias=a + ".query.bias")
+        y = self._emit(OpSpec(L.OP_WINDOW_ATTN_V2, qkv, -1, self._new_slot(), 3 * c, heads, c, window, L.FLAG_NO_TRAIN, a + ".continuous_position_bias_mlp.2.weight",
+                              a + ".query.bias", label=a, cmid=shift, weight2=a + ".logit_scale"))
+        self.labels[a] = y
+        y = self._sv2_linear(name + ".attention.output.dense", y, c, c, bias=name + ".attention.output.dense.bias")
+        self.labels[name + ".attention"] = y
+        x1 = self._sv2_norm(name + ".layernorm_before", y, c, self.layer_norm_eps, residual=x)  # x + LayerNorm(attention(x)): drop path is the identity in eval
+        self.labels[name + ".layernorm_before"] = x1
+        y = self._sv2_linear(name + ".intermediate.dense", x1, c, hid, bias=name + ".intermediate.dense.bias")
+        y = self._emit(OpSpec(L.OP_GELU, y, -1, self._new_slot(), hid, 0, hid, 1, 0, label=name + ".intermediate"))  # (Model folds it into the GEMM's epilogue)
+        self.labels[name + ".intermediate"] = y
+        y = self._sv2_linear(name + ".output.dense", y, hid, c, bias=name + ".output.dense.bias")
+        self.labels[name + ".output"] = y
+        x2 = self._sv2_norm(name + ".layernorm_after", y, c, self.layer_norm_eps, residual=x1)
+        self.labels[name] = x2
+        return x2
+
+    def _build_swinv2_encoder(self) -> None:
+        ch = self.channels
+        enc = "backbone.enc"
+        pe = f"{enc}.embeddings.patch_embeddings.projection"
+        self.param_shapes[pe + ".weight"] = (ch[0], self.in_channels, self.patch_size, self.patch_size)
+        self.param_shapes[pe + ".bias"] = (ch[0],)
+        x = self._emit(OpSpec(L.OP_PATCH_STEM, -1, -1, self._new_slot(), self.in_channels, 0, ch[0], self.patch_size, L.FLAG_PAD0_NORM, pe + ".weight", pe + ".bias",
+                              label=pe, cmid=self.patch_size))
+        self.labels[pe] = x
+        self.param_shapes[f"{enc}.embeddings.norm.weight"] = (ch[0],)
+        self.param_shapes[f"{enc}.embeddings.norm.bias"] = (ch[0],)
+        x = self._sv2_norm(f"{enc}.embeddings.norm", x, ch[0], 1e-5)  # nn.LayerNorm(embed_dim): the module default, whatever layer_norm_eps says
+        self.labels[f"{enc}.embeddings"] = x  # feature map "stem": stride 4, like stage1, and dropped by the reference's stride dedupe
+        windows = swinv2_windows(self.image_size, self.patch_size, self.window_size)
+        feats: List[Tuple[int, int]] = []
+        for si, (depth, c) in enumerate(zip(self.depths, ch)):
+            w, shift = windows[si]
+            for j in range(depth):
+                x = self._swinv2_block(f"{enc}.encoder.layers.{si}.blocks.{j}", x, c, self.num_heads[si], w, 0 if j % 2 == 0 else shift, self.pretrained_window_sizes[si])
+            self.labels[f"{enc}.stage{si + 1}"] = x
+            feats.append((x, c))  # the RAW stage output, before the downsampling: no output norms
+            if si + 1 < len(ch):
+                name = f"{enc}.encoder.layers.{si}.downsample"
+                self.param_shapes[name + ".reduction.weight"] = (2 * c, 4 * c)
+                self.param_shapes[name + ".norm.weight"] = (2 * c,)
+                self.param_shapes[name + ".norm.bias"] = (2 * c,)
+                # the phase order is HuggingFace's = torchvision's: (even, even), (odd, even), (even, odd), (odd, odd) in (row, column); no norm in front of the reduction
+                y = self._emit(OpSpec(L.OP_PATCH_MERGE, x, -1, self._new_slot(), c, 0, 4 * c, 2, L.FLAG_NO_NORM | L.FLAG_NO_TRAIN, label=name + ".gather"))
+                y = self._sv2_linear(name + ".reduction", y, 4 * c, 2 * c)
+                self.labels[name + ".reduction"] = y
+                x = self._sv2_norm(name + ".norm", y, 2 * c, 1e-5)  # norm_layer(2 * dim) = nn.LayerNorm's default eps
+                self.labels[name] = x
+        self._build_decoder(feats)
+
+    def derived_params(self, state: Dict[str, torch.Tensor], buffers: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """The tensors a Swinv2 block's qkv Linear and attention op read in place of four of its parameters, computed in float64 at handle creation and rounded once:
+        ``query.weight`` -> (3C, C) query | key | value; ``query.bias`` -> (3C) query.bias | zeros | value.bias (``key`` has no bias; also the q, k, v of a padded token);
+        ``continuous_position_bias_mlp.2.weight`` -> ``16 sigmoid(MLP(coords))`` as (heads, (2w - 1)^2); ``logit_scale`` -> ``exp(min(logit_scale, log 100))`` as (heads,).
+        The state dict keeps the reference's tensors; ``load_state_dict`` releases the handle, so a derived form never outlives what it was made from."""
+        out: Dict[str, torch.Tensor] = {}
+        for name, _heads, window, pretrained_window in self.swinv2_blocks:
+            a = name + ".attention.self"
+            out[a + ".query.weight"] = torch.cat([state[a + ".query.weight"], state[a + ".key.weight"], state[a + ".value.weight"]], dim=0).float().contiguous()
+            qb, vb = state[a + ".query.bias"], state[a + ".value.bias"]
+            out[a + ".query.bias"] = torch.cat([qb, torch.zeros_like(qb), vb]).float().contiguous()
+            m = a + ".continuous_position_bias_mlp"
+            out[m + ".2.weight"] = swinv2_bias_table(swinv2_coords_table(window, pretrained_window), state[m + ".0.weight"], state[m + ".0.bias"], state[m + ".2.weight"])
+            out[a + ".logit_scale"] = swinv2_logit_scale(state[a + ".logit_scale"])
         return out
 
     def _build_encoder(self) -> None:

@@ -985,6 +985,9 @@ int check_backward_handle(ph_model* m, int batch) {
   for (const auto& op : m->ops)  // a ResNet program (HuggingFace ResNetBackbone behind the 'pretrained' backbone) has no backward step at all: BatchNorm with batch statistics is another op
     PH_REQUIRE(op.d.kind != PH_OP_RESNET_STEM && op.d.kind != PH_OP_CONV_S2 && op.d.kind != PH_OP_ADD_RELU,
                "ph_model_backward: op kind %d belongs to a 'pretrained' ResNet backbone, which is inference only", op.d.kind);
+  for (const auto& op : m->ops)  // nor has a Swinv2 program (HuggingFace Swinv2Backbone): the cosine attention, the residual-after-norm LayerNorm and the norm-less patch merge are forward only
+    PH_REQUIRE(op.d.kind != PH_OP_WINDOW_ATTN_V2 && !(op.d.kind == PH_OP_LAYERNORM && (op.d.flags & PH_FLAG_RESIDUAL)) && !(op.d.kind == PH_OP_PATCH_MERGE && (op.d.flags & PH_FLAG_NO_NORM)),
+               "ph_model_backward: op kind %d belongs to a 'pretrained' Swinv2 backbone, which is inference only", op.d.kind);
   for (const auto& op : m->ops)  // the ConvNeXtV2 ops (GRN, the padding-0 stem with input statistics) carry PH_FLAG_NO_TRAIN: their backward steps run on request only
     PH_REQUIRE(m->pretrained_train || !(op.d.kind != PH_OP_HEAD && (op.d.flags & PH_FLAG_NO_TRAIN)),
                "ph_model_backward: op kind %d is inference only on this handle (a 'pretrained' ConvNeXtV2 backbone trains with the handle option pretrained_train = 1)", op.d.kind);

@@ -654,6 +654,14 @@ int fwd_layernorm(ForwardCtx& c, const PackedOp& op) {
   const SlotShape& s0 = c.slot(d.src0);
   PH_REQUIRE(s0.c == d.cin0, "LayerNorm channel mismatch");
   const float eps = (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f;
+  if (d.flags & PH_FLAG_RESIDUAL) {  // dst = src1 + LayerNorm(src0): Swinv2's layernorm_before / layernorm_after
+    const SlotShape& s1 = c.slot(d.src1);
+    PH_REQUIRE(c.fmt == FMT_F32 && s1.cp == s0.cp && c.slot(d.dst).cp == s0.cp && d.src1 != d.dst && d.src0 != d.dst, "the residual LayerNorm runs in exact fp32 on distinct slots of one shape");
+    const float* x = c.rd(d.src0);
+    const float* res = c.rd(d.src1);
+    c.ran(PH_KV_LAYERNORM_ADD);
+    return launch_layernorm_add(x, res, op.w_dev, op.b_dev, c.wr(d.dst), s0.c, s0.cp, (size_t)c.batch * s0.h * s0.w, c.s, eps);
+  }
   if (c.fmt == FMT_F16) {
     c.ran(PH_KV_CNX_F16_LN);
     return launch_layernorm_f16(c.rd(d.src0), op.w_dev, op.b_dev, c.wr(d.dst), s0.c, pad16(s0.c), s0.cp, (size_t)c.batch * s0.h * s0.w, c.s, eps);
@@ -666,6 +674,12 @@ int fwd_patch_merge(ForwardCtx& c, const PackedOp& op) {
   const SlotShape& s0 = c.slot(d.src0);
   const SlotShape& so = c.slot(d.dst);
   PH_REQUIRE((c.fmt == FMT_F32 || c.fmt == FMT_F16) && s0.c == d.cin0 && s0.cp == d.cin0 && so.cp == d.cout, "patch merge channel mismatch");
+  if (d.flags & PH_FLAG_NO_NORM) {  // Swinv2: the gather alone (its norm sits behind the reduction)
+    PH_REQUIRE(c.fmt == FMT_F32, "the patch-merge gather without a norm runs in exact fp32 only");
+    const float* x = c.rd(d.src0);
+    c.ran(PH_KV_PATCH_MERGE_GATHER);
+    return launch_patch_merge_gather(x, c.wr(d.dst), c.batch, s0.h, s0.w, d.cin0, c.s);
+  }
   const float eps = (d.flags & PH_FLAG_LN_EPS_1EM5) ? 1e-5f : 1e-6f;
   if (c.fmt == FMT_F16) {
     c.ran(PH_KV_SWIN_F16_MERGE_LN);
@@ -708,6 +722,28 @@ int fwd_window_attn(ForwardCtx& c, const PackedOp& op) {
   window_attn_args(c, op, a);
   c.ran(PH_KV_WINDOW_ATTN);
   return launch_window_attn(a, c.s);
+}
+
+// cosine window attention of a Swinv2 block (swinv2_kernels.hip): the table, the padded token's q | 0 | v and the head scales are the host's derived tensors
+int fwd_window_attn_v2(ForwardCtx& c, const PackedOp& op) {
+  const ph_op_desc& d = op.d;
+  const SlotShape& s0 = c.slot(d.src0);
+  PH_REQUIRE(c.fmt == FMT_F32 && s0.c == d.cin0 && s0.cp == d.cin0 && c.slot(d.dst).cp == d.cout, "cosine window attention channel mismatch");
+  WindowAttnV2Args a{};
+  a.qkv = c.rd(d.src0);
+  a.qkv_bias = op.b_dev;
+  a.scale = op.w2_dev;
+  a.table = op.w_dev;
+  a.dst = c.wr(d.dst);
+  a.B = c.batch;
+  a.H = s0.h;
+  a.W = s0.w;
+  a.C = d.cout;
+  a.heads = d.cin1;
+  a.w = d.ksize;
+  a.shift = d.cmid;
+  c.ran(PH_KV_WINDOW_ATTN_V2);
+  return launch_window_attn_v2(a, c.s);
 }
 
 // ---- Linear / 2x2-stride-2 conv (row GEMMs)
@@ -1105,6 +1141,7 @@ int fwd_op(ForwardCtx& c, const PackedOp& op) {
     case PH_OP_LAYERNORM: return fwd_layernorm(c, op);
     case PH_OP_PATCH_MERGE: return fwd_patch_merge(c, op);
     case PH_OP_WINDOW_ATTN: return fwd_window_attn(c, op);
+    case PH_OP_WINDOW_ATTN_V2: return fwd_window_attn_v2(c, op);
     case PH_OP_LINEAR:
     case PH_OP_PATCH_CONV: return fwd_linear(c, op);
     case PH_OP_GRN: return fwd_grn(c, op);

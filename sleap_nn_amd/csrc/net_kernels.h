@@ -212,6 +212,19 @@ struct WindowAttnF16Args {
 };
 int launch_window_attn_f16(const WindowAttnF16Args& a, hipStream_t s);
 int launch_patch_merge_ln_f16(const void* src, const float* gamma, const float* beta, void* dst, int B, int H, int W, int c, float eps, hipStream_t s);
+// Swin Transformer V2 encoder (swinv2_kernels.hip): cosine window attention and the residual-after-norm LayerNorm
+struct WindowAttnV2Args {
+  const float* qkv = nullptr;       // (B, H, W, 3C): query | key | value of the un-padded, un-rolled map; head a owns channels 32 a .. 32 a + 31 of each
+  const float* qkv_bias = nullptr;  // (3C): query.bias | zeros | value.bias -- the q, k, v of a padded token (hidden state 0; key has no bias)
+  const float* scale = nullptr;     // (heads): exp(min(logit_scale, log 100))
+  const float* table = nullptr;     // 16 sigmoid(continuous position bias), head-major: [heads][(2w - 1)^2]
+  float* dst = nullptr;             // (B, H, W, C)
+  int B = 0, H = 0, W = 0, C = 0, heads = 0;
+  int w = 0;                        // window side, 2..8
+  int shift = 0;                    // the layer's shift on both axes, whatever the map
+};
+int launch_window_attn_v2(const WindowAttnV2Args& a, hipStream_t s);
+int launch_layernorm_add(const float* src, const float* res, const float* gamma, const float* beta, float* dst, int c, int cp, size_t npix, hipStream_t s, float eps);  // dst = res + LayerNorm(src)
 int launch_gemm(const GemmArgs& a, hipStream_t s);
 int gemm_choose_variant(const GemmArgs& a);                              // the tile variant launch_gemm takes for a.bn / a.M / a.coutp (-1: no kernel for that N tile)
 int launch_gemm_variant(int variant, const GemmArgs& a, hipStream_t s);  // one named variant (PH_GEMM_VARIANTS in convnext_kernels.hip), under launch_gemm's checks

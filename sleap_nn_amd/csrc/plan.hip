@@ -16,6 +16,8 @@ int forward_format(const ph_model* m) {
   if (m->conv_precision != 1 && m->conv_precision != 2) return FMT_F32;
   bool swin = false;
   for (const PackedOp& op : m->ops) swin = swin || op.d.kind == PH_OP_WINDOW_ATTN || op.d.kind == PH_OP_PATCH_MERGE;
+  for (const PackedOp& op : m->ops)  // a Swinv2 program has no fp16 form: exact whatever the precision and whatever "swint_f16" says
+    if (op.d.kind == PH_OP_WINDOW_ATTN_V2) return FMT_F32;
   const bool enc_f16 = m->conv_precision == 2 && (swin ? m->swint_f16 : m->convnext_f16) != 0;  // the encoder ops have an fp16 form and may use it
   for (const PackedOp& op : m->ops) {
     const ph_op_desc& d = op.d;
@@ -38,8 +40,7 @@ int forward_format(const ph_model* m) {
         if (!enc_f16) return FMT_F32;
         break;
       case PH_OP_GRN:  // a ConvNeXtV2 program has no fp16 form: exact whatever the precision and whatever "convnext_f16" says
-        return FMT_F32;
-      case PH_OP_LINEAR:  // (a Linear with a ReLU is a class-vector head's: exact; PH_FLAG_RESIDUAL is a Swin block's, with or without a bias)
+        return FMT_F32;      case PH_OP_LINEAR:  // (a Linear with a ReLU is a class-vector head's: exact; PH_FLAG_RESIDUAL is a Swin block's, with or without a bias)
         if (!enc_f16 || (d.flags & ~(PH_FLAG_GELU | PH_FLAG_SCALE_RESIDUAL | (swin ? PH_FLAG_RESIDUAL : 0))) || !op.w_cnx_f16_dev) return FMT_F32;
         break;
       case PH_OP_CONV:
@@ -145,7 +146,7 @@ bool fuses_layernorm(const ph_model* m, size_t i, bool reuse) {
   if (!m->dw_ln_fuse || !reuse || i + 1 >= m->ops.size()) return false;
   const ph_op_desc& d = m->ops[i].d;
   const ph_op_desc& nx = m->ops[i + 1].d;
-  return nx.kind == PH_OP_LAYERNORM && nx.src0 == d.dst && nx.cin0 == d.cout && only_reader_is_next(m, i);
+  return nx.kind == PH_OP_LAYERNORM && !(nx.flags & PH_FLAG_RESIDUAL) && nx.src0 == d.dst && nx.cin0 == d.cout && only_reader_is_next(m, i);
 }
 
 int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
@@ -293,9 +294,10 @@ int build_plan(const ph_model* m, int B, int H, int W, Plan& plan, int fmt) {
       oh = (h + 1) / 2;
       ow = (w + 1) / 2;
       PH_REQUIRE(plan.slots[d.src0].c == d.cin0 && d.cout == 4 * d.cin0, "patch merge channel mismatch");
-    } else if (d.kind == PH_OP_WINDOW_ATTN) {
+    } else if (d.kind == PH_OP_WINDOW_ATTN || d.kind == PH_OP_WINDOW_ATTN_V2) {
       PH_REQUIRE(d.src0 >= 0 && plan.slots[d.src0].c == d.cin0 && d.cin0 == 3 * d.cout, "window attention reads a (3C)-channel qkv slot");
-    } else if ((d.kind == PH_OP_LINEAR && (d.flags & (PH_FLAG_SCALE_RESIDUAL | PH_FLAG_RESIDUAL))) || d.kind == PH_OP_SCALE_ADD) {
+    } else if ((d.kind == PH_OP_LINEAR && (d.flags & (PH_FLAG_SCALE_RESIDUAL | PH_FLAG_RESIDUAL))) || d.kind == PH_OP_SCALE_ADD ||
+               (d.kind == PH_OP_LAYERNORM && (d.flags & PH_FLAG_RESIDUAL))) {
       PH_REQUIRE(d.src1 >= 0 && d.src1 < m->n_slots && plan.slots[d.src1].offset >= 0, "residual slot %d is not written yet", d.src1);
       const SlotShape& s1 = plan.slots[d.src1];
       PH_REQUIRE(s1.h == h && s1.w == w && s1.c == d.cout, "residual shape mismatch");

@@ -698,9 +698,14 @@ int forms_dwconv(PackCtx& c, PackedOp& op) {
 // LayerNorm, GRN, patch merge: a per-channel weight and bias, padded alike; only what makes the op valid differs
 int forms_affine(PackCtx& c, PackedOp& op) {
   const ph_op_desc& d = op.d;
+  if (d.kind == PH_OP_PATCH_MERGE && (d.flags & PH_FLAG_NO_NORM)) {  // the gather alone: nothing to pack
+    if (d.cout != 4 * d.cin0 || (d.cin0 & 15) || d.src0 < 0 || d.weight >= 0 || d.bias >= 0) return c.fail("a patch merge without a norm needs a channel count that is a multiple of 16 and no parameters");
+    return PH_OK;
+  }
   if (!c.has_weight_and_bias(d)) return c.fail("weight index out of range");
   const bool sized = c.weight_numel[d.weight] == d.cout && c.weight_numel[d.bias] == d.cout;
   if (d.kind == PH_OP_LAYERNORM && (d.cin0 != d.cout || !sized)) return c.fail("LayerNorm affine size mismatch");
+  if (d.kind == PH_OP_LAYERNORM && (d.flags & PH_FLAG_RESIDUAL) && (d.src0 < 0 || d.src1 < 0 || d.src1 == d.dst || d.src0 == d.dst)) return c.fail("a residual LayerNorm needs two sources and a slot of its own");
   if (d.kind == PH_OP_GRN && (d.cin0 != d.cout || d.src0 < 0 || !sized)) return c.fail("GRN needs a (C) weight and bias");
   if (d.kind == PH_OP_PATCH_MERGE && (d.cout != 4 * d.cin0 || (d.cin0 & 15) || !sized)) return c.fail("patch merge needs a channel count that is a multiple of 16 and a (4C) LayerNorm affine");
   const size_t cp = d.kind == PH_OP_PATCH_MERGE ? d.cout : pad16(d.cout);
@@ -724,6 +729,21 @@ int forms_window_attn(PackCtx& c, PackedOp& op) {
   };
   PH_TRY(c.pack(pack_tbl, d.weight, &op.w_dev));
   return c.pack(pad_vec(d.cin0, d.cin0), d.bias, &op.b_dev);
+}
+
+// Swinv2's cosine attention.  All three tensors are DERIVED by the host (float64, from logit_scale, the continuous-position-bias MLP and the query / value biases):
+// weight = 16 sigmoid(bias table), already head-major (heads, (2w - 1)^2); bias = (3C) query.bias | zeros | value.bias; weight2 = (heads) exp(min(logit_scale, log 100))
+int forms_window_attn_v2(PackCtx& c, PackedOp& op) {
+  const ph_op_desc& d = op.d;
+  if (!c.has_weight_and_bias(d) || !c.widx_ok(d.weight2)) return c.fail("weight index out of range");
+  const int heads = d.cin1, rel = (2 * d.ksize - 1) * (2 * d.ksize - 1);
+  if (d.ksize < 2 || d.ksize > 8) return c.fail("cosine window attention needs 2 <= window_size <= 8");
+  if (heads < 1 || d.cout != heads * 32 || d.cin0 != 3 * d.cout || d.src0 < 0) return c.fail("cosine window attention needs head dimension 32 and a (3C) qkv source");
+  if (d.cmid < 0 || d.cmid >= d.ksize) return c.fail("cosine window attention shift must be smaller than the window");
+  if (c.weight_numel[d.weight] != (int64_t)rel * heads || c.weight_numel[d.bias] != d.cin0 || c.weight_numel[d.weight2] != heads) return c.fail("weight size mismatch");
+  PH_TRY(c.pack(pad_vec((size_t)rel * heads, rel * heads), d.weight, &op.w_dev));
+  PH_TRY(c.pack(pad_vec(d.cin0, d.cin0), d.bias, &op.b_dev));
+  return c.pack(pad_vec(std::max(heads, 4), heads), d.weight2, &op.w2_dev);
 }
 
 // Linear / 2x2-stride-2 conv: data-gradient weights (training): dX = dY * W, one transposed matrix per tap, + a zero bias
@@ -845,6 +865,7 @@ int forms_op(PackCtx& c, PackedOp& op) {
     case PH_OP_GRN:
     case PH_OP_PATCH_MERGE: return forms_affine(c, op);
     case PH_OP_WINDOW_ATTN: return forms_window_attn(c, op);
+    case PH_OP_WINDOW_ATTN_V2: return forms_window_attn_v2(c, op);
     case PH_OP_LINEAR:
     case PH_OP_PATCH_CONV: return forms_linear(c, op);
     default: return c.fail("unknown op kind");

@@ -71,6 +71,8 @@ class TrainingModule:
         self._pretrained = getattr(model, "backbone_type", None) == "pretrained"
         if getattr(model, "is_resnet", False):
             raise NotImplementedError("a 'pretrained' ResNet backbone is inference only on the MI355X path (BatchNorm runs folded into the convs; batch statistics are not built)")
+        if getattr(model, "is_swinv2", False):
+            raise NotImplementedError("a 'pretrained' Swinv2 backbone is inference only on the MI355X path (its cosine window attention and residual-after-norm LayerNorm have no backward step)")
         if self._pretrained and not pretrained_training:
             raise NotImplementedError("training a 'pretrained' (ConvNeXtV2) backbone is opt-in: TrainingModule(model, pretrained_training=True)")
         if freeze_encoder is not None and not self._pretrained:
