@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 132
+#define PH_VERSION 133
 
 /* error codes */
 #define PH_OK 0
@@ -139,7 +139,7 @@ enum ph_op_kind {
      handle's options.  The host hands the library DERIVED tensors for this op and the qkv Linear in front of it (computed in float64 from the checkpoint's parameters). */
   PH_OP_WINDOW_ATTN_V2 = 22 /* cosine window attention core (swinv2_kernels.hip): src0 = qkv slot (B, H, W, 3C) as PH_OP_WINDOW_ATTN, weight = 16 sigmoid(continuous
                              position bias) HEAD-MAJOR (heads, (2 ksize - 1)^2), bias = (3C) query.bias | zeros | value.bias (the q, k, v of a padded token: hidden state
-                             0, key has no bias), weight2 = (heads) exp(min(logit_scale, log 100)), ksize = window side (2..8), cin1 = heads (cout = 32 heads), cmid = the
+                             0, key has no bias), weight2 = (heads) exp(min(logit_scale, log 100)), ksize = window side (2..24; 9..24 run the key-tiled kernel), cin1 = heads (cout = 32 heads), cmid = the
                              layer's shift, applied on both axes whatever the map (HuggingFace rolls and masks a shifted layer even where one window covers the axis).
                              dst = softmax(scale (q / max(|q|, 1e-12)) . (k / max(|k|, 1e-12)) + bias [- 200 across the shift's bands: the installed
                              Swinv2SelfAttention adds its -100 mask twice]) v at each token's own pixel */
@@ -475,6 +475,10 @@ int ph_debug_conv3x3_run(ph_conv_run_case* c);
  * q, k, v are (its key section is zeros in the product), scale (heads), table (heads, (2 w - 1)^2), dst (B, H, W, 32 heads).  shift applies on both axes. */
 int ph_debug_window_attn_v2_run(const float* qkv, const float* qkv_bias, const float* scale, const float* table, float* dst, int32_t B, int32_t H, int32_t W, int32_t heads,
                                 int32_t w, int32_t shift);
+/* Test support (tests/test_gpu_window_attn_v2_wide.py): the same on the key-tiled kernel (window_attn_v2_wide_kernel), for windows of 2..24.  The product path sends that
+ * kernel windows of 9..24 only; here 2..8 run on it too. */
+int ph_debug_window_attn_v2_wide_run(const float* qkv, const float* qkv_bias, const float* scale, const float* table, float* dst, int32_t B, int32_t H, int32_t W,
+                                     int32_t heads, int32_t w, int32_t shift);
 
 /* Diagnostic (tools/row_wgrad_bench.py): average milliseconds of the row weight-gradient GEMM dW[n][k] = sum_m dY[m][n] X[m][k]
  * (Linear layers of the training step, train_kernels.h launch_row_wgrad) on synthetic operands, and the largest error of 64
@@ -558,6 +562,7 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_WINDOW_ATTN_V2 32 /* window_attn_v2_kernel: cosine window attention, one wave per (window, head) on v_mfma_f32_32x32x2_f32 */
 #define PH_KV_LAYERNORM_ADD 33 /* layernorm_add_kernel: dst = src1 + LayerNorm(src0) */
 #define PH_KV_PATCH_MERGE_GATHER 34 /* patch_merge_gather_kernel as the forward of a PH_OP_PATCH_MERGE with PH_FLAG_NO_NORM */
+#define PH_KV_WINDOW_ATTN_V2_WIDE 35 /* window_attn_v2_wide_kernel: cosine window attention of windows 9..24, one workgroup per (window, head), keys tiled, online softmax */
 #define PH_KV_FUSED 11   /* no launch of its own: a 1x1 head computed in the epilogue of the conv that produces its input */
 int ph_model_last_kernels(const ph_model* m, int32_t* codes, int32_t n_ops);
 /* ... and the tile plan of every op of the LAST ph_model_forward that ran conv3x3_f16_rows_kernel (PH_KV_F16_ROWS): quad[4 i .. 4 i + 3] = {R rows, Wt columns of a tile, MT M tiles

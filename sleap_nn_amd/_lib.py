@@ -34,6 +34,7 @@ SWIN_KV_WINDOW_ATTN_F16, SWIN_KV_F16_MERGE_LN = 22, 23  # PH_KV_WINDOW_ATTN_F16 
 CNX2_KV_GRN, CNX2_KV_GRN_FUSED, CNX2_KV_PATCH_STEM_NORM = 25, 26, 27  # PH_KV_GRN / PH_KV_GRN_FUSED / PH_KV_PATCH_STEM_NORM (convnextv2_kernels.hip)
 RESNET_KV_STEM, RESNET_KV_CONV_S2, RESNET_KV_ADD_RELU = 29, 30, 31  # PH_KV_RESNET_STEM / PH_KV_CONV_S2 / PH_KV_ADD_RELU (resnet_kernels.hip, the strided row-GEMM modes)
 SWINV2_KV_WINDOW_ATTN, SWINV2_KV_LAYERNORM_ADD, SWINV2_KV_MERGE_GATHER = 32, 33, 34  # PH_KV_WINDOW_ATTN_V2 / PH_KV_LAYERNORM_ADD / PH_KV_PATCH_MERGE_GATHER (swinv2_kernels.hip, swin_train_kernels.hip's gather)
+SWINV2_KV_WINDOW_ATTN_WIDE = 35  # PH_KV_WINDOW_ATTN_V2_WIDE (swinv2_kernels.hip): the key-tiled kernel of windows 9..24
 CNX2_KV_GRN_BWD = 28  # PH_KV_GRN_BWD (convnextv2_train_kernels.hip): reported by ph_model_last_backward_kernels
 CNX_KV_F16_STEM, CNX_KV_F16_DW, CNX_KV_F16_LN, CNX_KV_F16_GEMM, CNX_KV_F16_ELTWISE = 16, 17, 18, 19, 20  # PH_KV_CNX_F16_*: the ConvNeXt encoder ops on fp16 activations (convnext_f16_kernels.hip); not named KV_*: that prefix lists the families a 3x3 conv can come back with (benchlegs.common.conv_kernel_short_names)
 KV_NAMES = {KV_NONE: "none", KV_DIRECT: "conv3x3_mfma_dma_persist_kernel (direct)", KV_WINO1D: "conv3x3_wino_persist_kernel (Winograd F(2,3) along x)",
@@ -216,6 +217,7 @@ SIGNATURES = {
     "ph_gemm_case_size": (_i32, []),
     "ph_debug_gemm_run": (C.c_int, [C.POINTER(GemmCase)]),
     "ph_debug_window_attn_v2_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "ph_debug_window_attn_v2_wide_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32]),
     "ph_render_confmaps": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "ph_render_pafs": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "ph_render_class_maps": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp]),

@@ -22,7 +22,7 @@ The ResNet family (HuggingFace ``ResNetBackbone``; basic and bottleneck layers) 
 inference only: BatchNorm (eval) is folded into each conv on the host (``fold_batchnorm`` / ``folded_params``, float64, at handle creation) while the state dict keeps the
 reference's unfolded names; the stem, the strided convs and the residual tails are ``csrc/resnet_kernels.hip`` and the row GEMM's modes 4 and 6.
 
-The Swinv2 family (HuggingFace ``Swinv2Backbone``; effective windows of 2..8, head dimension 32) is opt-in through the backbone-config key ``allow_swinv2`` for the same reason, and
+The Swinv2 family (HuggingFace ``Swinv2Backbone``; effective windows of 2..8, and of 9..24 with ``allow_swinv2_wide`` on top; head dimension 32) is opt-in through the backbone-config key ``allow_swinv2`` for the same reason, and
 inference only: per-stage window and shift follow the config's ``image_size`` (``swinv2_windows``); the qkv concatenation, the padded token's q | 0 | v, the ``16 sigmoid(MLP(coords))`` bias
 table and the clamped, exponentiated logit scales are derived on the host (``derived_params``, float64, at handle creation) while the state dict keeps the reference's names; the cosine window
 attention and the residual-after-norm LayerNorm are ``csrc/swinv2_kernels.hip``.
@@ -76,14 +76,21 @@ RESNET_OPT_IN = ("the ResNet family is opt-in: backbone-config key allow_resnet=
 BN_EPS = 1e-5  # nn.BatchNorm2d's default, which HuggingFace's ResNetConvLayer keeps
 # microsoft/swinv2-<size>-patch4-window<w>-<img>: embed_dim, depths, heads (head dimension 32 throughout).  The tiny row is Swinv2Config()'s defaults
 # (tests/test_pretrained_swinv2_cpu.py checks it where transformers is installed); the other rows are the published configs as recalled -- nothing here can reach the hub to
-# check them, a local config.json wins.  window_size and image_size come from the id; pretrained_window_sizes is all zero (the 12to16 / 12to24 ids have windows above 8 anyway)
+# check them, a local config.json wins.  window_size and image_size come from the id.  pretrained_window_sizes is all zero for a plain id; an id of the form
+# window<X>to<Y> (fine-tuned from window X) gets [X, X, X, X // 2] -- the published 12toN configs have [12, 12, 12, 6].  The large row and the <X>to<Y> rule are AS RECALLED
+# from HuggingFace's conversion script (convert_swinv2_timm_to_pytorch.py), like the rows above: unconfirmed here, and a local config.json wins over both
 SWINV2_SIZES = {
     "tiny": {"embed_dim": 96, "depths": [2, 2, 6, 2], "num_heads": [3, 6, 12, 24]},
     "small": {"embed_dim": 96, "depths": [2, 2, 18, 2], "num_heads": [3, 6, 12, 24]},
     "base": {"embed_dim": 128, "depths": [2, 2, 18, 2], "num_heads": [4, 8, 16, 32]},
+    "large": {"embed_dim": 192, "depths": [2, 2, 18, 2], "num_heads": [6, 12, 24, 48]},
 }
 SWINV2_OPT_IN = ("the Swinv2 family is opt-in: backbone-config key allow_swinv2=True (LoadedAssets.build_model(pretrained_swinv2=True), "
                  "Predictor.from_model_paths(..., pretrained_swinv2=True))")
+# effective windows of 9..24 (81..576 tokens: the window16, window12-192, 12to16 and 12to24 checkpoints) run the key-tiled kernel and need a second opt-in on top of that one
+SWINV2_WIDE_OPT_IN = ("windows above 8 are opt-in on top of allow_swinv2: backbone-config key allow_swinv2_wide=True (LoadedAssets.build_model(..., swinv2_wide=True), "
+                      "Predictor.from_model_paths(..., swinv2_wide=True))")
+SWINV2_MAX_WINDOW, SWINV2_MAX_WINDOW_WIDE = 8, 24  # window_attn_v2_kernel holds 64 tokens in one wave; window_attn_v2_wide_kernel tiles the keys of up to 576
 SWINV2_HEAD_DIM = 32  # what window_attn_v2_kernel is built for
 SWINV2_MAX_LOGIT = math.log(1.0 / 0.01)  # Swinv2SelfAttention clamps logit_scale here before the exp: scale <= 100
 
@@ -150,7 +157,7 @@ def swinv2_logit_scale(logit_scale: torch.Tensor) -> torch.Tensor:
     return torch.exp(torch.clamp(logit_scale.double().reshape(-1), max=SWINV2_MAX_LOGIT)).float().contiguous()
 
 
-def _resolve_swinv2(hf: dict, source: str) -> dict:
+def _resolve_swinv2(hf: dict, source: str, allow_wide: bool = False) -> dict:
     """The Swinv2 leaf of ``resolve_architecture``: ``hf`` holds config.json's keys (or a row of ``SWINV2_SIZES`` with the id's window and image size); what the program
     cannot run is refused by name."""
     d = SWINV2_SIZES["tiny"]
@@ -175,9 +182,11 @@ def _resolve_swinv2(hf: dict, source: str) -> dict:
         if h < 1 or c != h * SWINV2_HEAD_DIM:
             raise _refuse(f"a head dimension of {c}/{h} ({source}; the cosine window attention kernel is built for {SWINV2_HEAD_DIM})")
     for i, (w, _s) in enumerate(swinv2_windows(img, ps, ws)):
-        if not (2 <= w <= 8):
-            raise _refuse(f"an effective window of {w} in stage {i + 1} of {source} (window_size {ws}, image_size {img[0]}; the kernel holds windows of 2..8, at most 64 tokens: "
-                          "the window16 and 12to16 / 12to24 checkpoints need another one)")
+        if SWINV2_MAX_WINDOW < w <= SWINV2_MAX_WINDOW_WIDE and not allow_wide:
+            raise _refuse(f"an effective window of {w} in stage {i + 1} of {source} (window_size {ws}, image_size {img[0]}; {SWINV2_WIDE_OPT_IN}; without it a window above {SWINV2_MAX_WINDOW})")
+        if not (2 <= w <= SWINV2_MAX_WINDOW_WIDE):
+            raise _refuse(f"an effective window of {w} in stage {i + 1} of {source} (window_size {ws}, image_size {img[0]}; the kernels hold windows of 2..{SWINV2_MAX_WINDOW_WIDE}, "
+                          f"at most {SWINV2_MAX_WINDOW_WIDE ** 2} tokens)")
     if hf.get("use_absolute_embeddings", False):
         raise _refuse(f"use_absolute_embeddings=True of {source}")
     if hf.get("hidden_act", "gelu") != "gelu":
@@ -191,12 +200,13 @@ def _resolve_swinv2(hf: dict, source: str) -> dict:
     return arch
 
 
-def resolve_architecture(model_name: str, run_dir: Optional[str] = None, allow_resnet: bool = False, allow_swinv2: bool = False) -> dict:
+def resolve_architecture(model_name: str, run_dir: Optional[str] = None, allow_resnet: bool = False, allow_swinv2: bool = False, allow_swinv2_wide: bool = False) -> dict:
     """``model_name`` -> {"family", "depths", "hidden_sizes", "patch_size", "num_channels", ...} without touching a network.
 
     (a) a directory holding a ``config.json`` (absolute as given; relative against ``run_dir``, then the working directory), dispatched on its ``model_type``;
     (b) the size word of a ``convnextv2-<size>`` id, or -- with ``allow_resnet`` -- the number of a ``resnet-<N>`` id, or -- with ``allow_swinv2`` -- size, window and image
-    size of a ``swinv2-<size>-patch4-window<w>-<img>`` id; (c) anything else is refused."""
+    size of a ``swinv2-<size>-patch4-window<w>-<img>`` id (effective windows above 8 with ``allow_swinv2_wide`` on top, which alone opens nothing); (c) anything else is
+    refused."""
     name = str(model_name)
     cands = [name] if os.path.isabs(name) else ([os.path.join(run_dir, name)] if run_dir else []) + [os.path.join(os.getcwd(), name)]
     for d in cands:
@@ -209,7 +219,7 @@ def resolve_architecture(model_name: str, run_dir: Optional[str] = None, allow_r
         if mt == "resnet" and allow_resnet:
             return _resolve_resnet(hf, path)
         if mt == "swinv2" and allow_swinv2:
-            return _resolve_swinv2(hf, path)
+            return _resolve_swinv2(hf, path, allow_swinv2_wide)
         if mt != "convnextv2":
             raise _refuse(f"model_type {mt!r} of {path}" + (f" ({RESNET_OPT_IN})" if mt == "resnet" else f" ({SWINV2_OPT_IN})" if mt == "swinv2" else ""))
         if hf.get("hidden_act", "gelu") != "gelu":
@@ -227,10 +237,12 @@ def resolve_architecture(model_name: str, run_dir: Optional[str] = None, allow_r
     r = re.search(r"resnet-(\d+)", name.lower())
     if r and r.group(1) in RESNET_SIZES and allow_resnet:
         return _resolve_resnet(RESNET_SIZES[r.group(1)], r.group(0))
-    s = re.search(r"swinv2-(tiny|small|base)-patch4-window(?:\d+to)?(\d+)-(?:\d+to)?(\d+)", name.lower())  # (window12to16-192to256: the fine-tuned window and image size)
+    # (window12to16-192to256: the fine-tuned window and image size; the window it was pre-trained at normalises the coordinate table)
+    s = re.search(r"swinv2-(tiny|small|base|large)-patch4-window(?:(\d+)to)?(\d+)-(?:\d+to)?(\d+)", name.lower())
     if s and allow_swinv2:
-        return _resolve_swinv2({**SWINV2_SIZES[s.group(1)], "window_size": int(s.group(2)), "image_size": int(s.group(3)), "patch_size": 4,
-                                "pretrained_window_sizes": [0, 0, 0, 0]}, s.group(0))
+        pre = int(s.group(2)) if s.group(2) else 0
+        return _resolve_swinv2({**SWINV2_SIZES[s.group(1)], "window_size": int(s.group(3)), "image_size": int(s.group(4)), "patch_size": 4,
+                                "pretrained_window_sizes": [pre, pre, pre, pre // 2]}, s.group(0), allow_swinv2_wide)
     hint = f"; {RESNET_OPT_IN}" if r and r.group(1) in RESNET_SIZES else f"; {SWINV2_OPT_IN}" if s else ""
     raise _refuse(f"model_name {name!r} (no local config.json, not a convnextv2-<size> id: ResNet, Swinv2, DINO and the isotropic ViTs are other families{hint})")
 
@@ -306,7 +318,7 @@ class PretrainedBackbone:
             raise _refuse(f"mode={mode!r} (the encoder-only pooled bottleneck)")
         name = cfg_get(config, "model_name", None) or DEFAULT_MODEL_NAME
         arch = resolve_architecture(name, cfg_get(config, "_run_dir", None), allow_resnet=bool(cfg_get(config, "allow_resnet", False)),
-                                    allow_swinv2=bool(cfg_get(config, "allow_swinv2", False)))
+                                    allow_swinv2=bool(cfg_get(config, "allow_swinv2", False)), allow_swinv2_wide=bool(cfg_get(config, "allow_swinv2_wide", False)))
         oi = cfg_get(config, "out_indices", None)
         if oi is not None and [int(i) for i in oi] != [0, 1, 2, 3, 4]:
             raise _refuse(f"out_indices={list(oi)} (a subset of the stages)")

@@ -742,6 +742,10 @@ int fwd_window_attn_v2(ForwardCtx& c, const PackedOp& op) {
   a.heads = d.cin1;
   a.w = d.ksize;
   a.shift = d.cmid;
+  if (d.ksize > 8) {  // more than 64 tokens per window: the key-tiled kernel
+    c.ran(PH_KV_WINDOW_ATTN_V2_WIDE);
+    return launch_window_attn_v2_wide(a, c.s);
+  }
   c.ran(PH_KV_WINDOW_ATTN_V2);
   return launch_window_attn_v2(a, c.s);
 }

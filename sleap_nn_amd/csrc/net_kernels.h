@@ -220,10 +220,11 @@ struct WindowAttnV2Args {
   const float* table = nullptr;     // 16 sigmoid(continuous position bias), head-major: [heads][(2w - 1)^2]
   float* dst = nullptr;             // (B, H, W, C)
   int B = 0, H = 0, W = 0, C = 0, heads = 0;
-  int w = 0;                        // window side, 2..8
+  int w = 0;                        // window side: 2..8 (launch_window_attn_v2) or 2..24 (launch_window_attn_v2_wide)
   int shift = 0;                    // the layer's shift on both axes, whatever the map
 };
 int launch_window_attn_v2(const WindowAttnV2Args& a, hipStream_t s);
+int launch_window_attn_v2_wide(const WindowAttnV2Args& a, hipStream_t s);  // the key-tiled kernel: any window of 2..24 (the forward sends it 9..24)
 int launch_layernorm_add(const float* src, const float* res, const float* gamma, const float* beta, float* dst, int c, int cp, size_t npix, hipStream_t s, float eps);  // dst = res + LayerNorm(src)
 int launch_gemm(const GemmArgs& a, hipStream_t s);
 int gemm_choose_variant(const GemmArgs& a);                              // the tile variant launch_gemm takes for a.bn / a.M / a.coutp (-1: no kernel for that N tile)

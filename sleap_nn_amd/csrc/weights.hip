@@ -737,7 +737,7 @@ int forms_window_attn_v2(PackCtx& c, PackedOp& op) {
   const ph_op_desc& d = op.d;
   if (!c.has_weight_and_bias(d) || !c.widx_ok(d.weight2)) return c.fail("weight index out of range");
   const int heads = d.cin1, rel = (2 * d.ksize - 1) * (2 * d.ksize - 1);
-  if (d.ksize < 2 || d.ksize > 8) return c.fail("cosine window attention needs 2 <= window_size <= 8");
+  if (d.ksize < 2 || d.ksize > 24) return c.fail("cosine window attention needs 2 <= window_size <= 24");
   if (heads < 1 || d.cout != heads * 32 || d.cin0 != 3 * d.cout || d.src0 < 0) return c.fail("cosine window attention needs head dimension 32 and a (3C) qkv source");
   if (d.cmid < 0 || d.cmid >= d.ksize) return c.fail("cosine window attention shift must be smaller than the window");
   if (c.weight_numel[d.weight] != (int64_t)rel * heads || c.weight_numel[d.bias] != d.cin0 || c.weight_numel[d.weight2] != heads) return c.fail("weight size mismatch");

@@ -67,9 +67,10 @@ class LoadedAssets:
     node_names: List[str]
     edges: List[Tuple[str, str]]
 
-    def build_model(self, pretrained_resnet: bool = False, pretrained_swinv2: bool = False):
+    def build_model(self, pretrained_resnet: bool = False, pretrained_swinv2: bool = False, swinv2_wide: bool = False):
         """``pretrained_resnet=True`` (opt-in): a ``pretrained`` run directory of the ResNet family builds (the backbone-config key ``allow_resnet``); without it such a
-        directory is refused by name, as before.  ``pretrained_swinv2=True``: the same for the Swinv2 family (``allow_swinv2``)."""
+        directory is refused by name, as before.  ``pretrained_swinv2=True``: the same for the Swinv2 family (``allow_swinv2``);
+        ``swinv2_wide=True`` on top of it: effective windows of 9..24 build too (``allow_swinv2_wide``; alone it opens nothing)."""
         from sleap_nn_amd.architectures.model import Model
 
         bb_cfg = self.backbone_config
@@ -79,6 +80,8 @@ class LoadedAssets:
                 bb_cfg["allow_resnet"] = True
             if pretrained_swinv2:
                 bb_cfg["allow_swinv2"] = True
+            if swinv2_wide:
+                bb_cfg["allow_swinv2_wide"] = True
         if self.model_type == "centered_instance_segmentation":
             # a lone SegmentationHead with the sigmoid in its epilogue: the semantic type's program, built from the same `segmentation` leaf (whose
             # anchor_part / crop_size are data-pipeline entries, not head arguments); `model_type` here keeps the real name

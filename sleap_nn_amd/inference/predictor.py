@@ -90,14 +90,14 @@ _SEG_KW = ("fg_threshold", "min_mask_area", "center_nms_kernel", "distance_gate_
 
 def _select_layer(assets: Sequence[LoadedAssets], device: str, post: PostprocessConfig, max_instances: Optional[int], tile_size: Optional[int] = None,
                   overlap: Optional[int] = None, seg_kw: Optional[dict] = None, tiled_segmentation: bool = False, pretrained_resnet: bool = False, pretrained_swinv2: bool = False,
-                  **paf_kw):
+                  swinv2_wide: bool = False, **paf_kw):
     """predictor.py:600 (``_select_layer``) for the model types of the hot path.  A single-instance run directory trained with tiling
     (``data_config.preprocessing.tiling.enabled``) gets a ``TiledLayer`` around its ``SingleInstanceLayer`` (predictor.py:191-246, 600-610);
     ``tile_size`` / ``overlap`` are checked against the trained geometry, not applied.  ``seg_kw``: the segmentation layers' knobs (``_SEG_KW``; the semantic
     layer takes the subset it has).  ``tiled_segmentation=True`` (opt-in): a ``bottomup_segmentation`` / ``semantic_segmentation`` run directory trained with
     tiling gets a ``TiledSegmentationLayer`` / ``TiledSemanticSegmentationLayer`` around the layer it would have got, with the same geometry checks; no
     effect on a directory without tiling.  ``pretrained_resnet=True`` (opt-in): ``pretrained`` run directories of the ResNet family build
-    (``LoadedAssets.build_model(pretrained_resnet=True)``); ``pretrained_swinv2=True``: the same for the Swinv2 family."""
+    (``LoadedAssets.build_model(pretrained_resnet=True)``); ``pretrained_swinv2=True``: the same for the Swinv2 family; ``swinv2_wide=True`` on top: its windows of 9..24."""
     by_type = {a.model_type: a for a in assets}
     tiled_seg_types = ("bottomup_segmentation", "semantic_segmentation") if tiled_segmentation else ()
     for a in assets:  # there is no tiled wrapper for the other model types: running them whole-frame at a geometry they were not trained for would be a silent wrong answer
@@ -107,7 +107,8 @@ def _select_layer(assets: Sequence[LoadedAssets], device: str, post: Postprocess
                                       f"is only built for single_instance models, not {a.model_type}{hint}")
 
     def backend(a):
-        kw = {**({"pretrained_resnet": True} if pretrained_resnet else {}), **({"pretrained_swinv2": True} if pretrained_swinv2 else {})}
+        kw = {**({"pretrained_resnet": True} if pretrained_resnet else {}), **({"pretrained_swinv2": True} if pretrained_swinv2 else {}),
+              **({"swinv2_wide": True} if swinv2_wide else {})}
         return HipBackend(a.build_model(**kw), device)
 
     def pre(a):
@@ -220,7 +221,7 @@ class Predictor:
                          mask_cleanup: bool = False, mask_cleanup_radius: int = 0, merge_fragments: bool = False, merge_method: str = "greedy",
                          merge_thresholds: tuple = (0.85, 0.6, 0.4), merge_w_valley: float = 1.0, merge_w_offset: float = 0.25, merge_dilate: int = 1,
                          mask_output: str = "mask", tracker_config=None, tiled_segmentation: bool = False, pretrained_resnet: bool = False, pretrained_swinv2: bool = False,
-                         **paf_kw) -> "Predictor":
+                         swinv2_wide: bool = False, **paf_kw) -> "Predictor":
         """``tracker_config``: a ``sleap_nn_amd.tracking.TrackerConfig``; ``predict`` then assigns track ids across its frames (``Outputs.instance_track_ids`` /
         ``instance_tracking_scores``, or ``"track_id"`` / ``"tracking_score"`` in the ``pred_masks`` entries); a bottom-up segmentation layer is told to keep its
         device label map for the tracker's tables.  ``None``: no tracking, every output as without this argument.
@@ -239,6 +240,8 @@ class Predictor:
         ``pretrained_resnet=True``: a ``pretrained`` run directory whose backbone is a HuggingFace ResNet is built (inference only, exact fp32); without it such a
         directory raises ``NotImplementedError`` naming this keyword.
         ``pretrained_swinv2=True``: the same for a ``pretrained`` run directory whose backbone is a HuggingFace Swinv2 (windows of 2..8, inference only, exact fp32).
+        ``swinv2_wide=True``, in addition to ``pretrained_swinv2=True``: effective windows of 9..24 build too (the window16, window12-192, 12to16 and 12to24 checkpoints; the key-tiled
+        kernel); without it such a directory raises ``NotImplementedError`` naming this keyword.
         ``streams``: bottom-up and top-down run directories of small networks (<= 16 M parameters) are loaded ``streams`` times; the pipelined ``predict`` keeps that many batches in flight
         on streams of their own (see ``replicas``).  Measured on the reference's fixture models at batch 4 (``tools/streams_n_probe.py``, frames/s end to end with 1 / 2 / 3 / 4 lanes):
         bottom-up 8 000 / 12 700 / 13 300 / 14 700, top-down 7 100 / 10 700 / 12 800 / 11 300, single instance 32 900 / 43 500 / 42 400 / 47 000 -- three is the default (the runtime has
@@ -251,12 +254,12 @@ class Predictor:
                       merge_method=merge_method, merge_thresholds=merge_thresholds, merge_w_valley=merge_w_valley, merge_w_offset=merge_w_offset,
                       merge_dilate=merge_dilate, mask_output=mask_output)
         layer = _select_layer(assets, device, post, max_instances, tile_size=tile_size, overlap=overlap, seg_kw=seg_kw, tiled_segmentation=tiled_segmentation,
-                              pretrained_resnet=pretrained_resnet, pretrained_swinv2=pretrained_swinv2, **paf_kw)
+                              pretrained_resnet=pretrained_resnet, pretrained_swinv2=pretrained_swinv2, swinv2_wide=swinv2_wide, **paf_kw)
         replicas = []
         small = lambda l: l.backend.model.num_parameters() <= _REPLICA_MAX_PARAMS
         if streams > 1 and ((isinstance(layer, (BottomUpLayer, SingleInstanceLayer)) and small(layer)) or
                             (isinstance(layer, TopDownLayer) and getattr(layer, "_PIPELINED", True) and small(layer.centroid_layer) and small(layer.centered_instance_layer))):
-            replicas = [_select_layer(assets, device, post, max_instances, pretrained_resnet=pretrained_resnet, pretrained_swinv2=pretrained_swinv2, **paf_kw)
+            replicas = [_select_layer(assets, device, post, max_instances, pretrained_resnet=pretrained_resnet, pretrained_swinv2=pretrained_swinv2, swinv2_wide=swinv2_wide, **paf_kw)
                         for _ in range(streams - 1)]
         if tracker_config is not None and isinstance(layer, SegmentationLayer):
             layer.keep_label_map = True
