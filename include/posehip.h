@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define PH_VERSION 133
+#define PH_VERSION 134
 
 /* error codes */
 #define PH_OK 0
@@ -137,7 +137,7 @@ enum ph_op_kind {
   /* Swin Transformer V2 encoder (HuggingFace Swinv2Backbone behind the reference's PretrainedBackbone).  Exact fp32, inference only: its ops of its own -- this one,
      PH_OP_LAYERNORM with PH_FLAG_RESIDUAL, PH_OP_PATCH_MERGE with PH_FLAG_NO_NORM -- carry PH_FLAG_NO_TRAIN and ph_model_backward refuses the program whatever the
      handle's options.  The host hands the library DERIVED tensors for this op and the qkv Linear in front of it (computed in float64 from the checkpoint's parameters). */
-  PH_OP_WINDOW_ATTN_V2 = 22 /* cosine window attention core (swinv2_kernels.hip): src0 = qkv slot (B, H, W, 3C) as PH_OP_WINDOW_ATTN, weight = 16 sigmoid(continuous
+  PH_OP_WINDOW_ATTN_V2 = 22 /* cosine window attention core (swin_kernels.hip's cosine variant; swinv2_kernels.hip above window 8): src0 = qkv slot (B, H, W, 3C) as PH_OP_WINDOW_ATTN, weight = 16 sigmoid(continuous
                              position bias) HEAD-MAJOR (heads, (2 ksize - 1)^2), bias = (3C) query.bias | zeros | value.bias (the q, k, v of a padded token: hidden state
                              0, key has no bias), weight2 = (heads) exp(min(logit_scale, log 100)), ksize = window side (2..24; 9..24 run the key-tiled kernel), cin1 = heads (cout = 32 heads), cmid = the
                              layer's shift, applied on both axes whatever the map (HuggingFace rolls and masks a shifted layer even where one window covers the axis).
@@ -470,7 +470,7 @@ typedef struct ph_conv_run_case {
 int32_t ph_conv_run_case_size(void);
 int ph_debug_conv3x3_run(ph_conv_run_case* c);
 
-/* Test support (tests/test_gpu_window_attn_v2.py), not a product path: ONE launch of the cosine window attention (window_attn_v2_kernel) on tensors the caller owns,
+/* Test support (tests/test_gpu_window_attn_v2.py), not a product path: ONE launch of the cosine window attention (window_attn_kernel, cosine variant) on tensors the caller owns,
  * synchronised before it returns.  All pointers are device pointers: qkv (B, H, W, 96 heads) = query | key | value of the map, qkv_bias (96 heads) = what a padded token's
  * q, k, v are (its key section is zeros in the product), scale (heads), table (heads, (2 w - 1)^2), dst (B, H, W, 32 heads).  shift applies on both axes. */
 int ph_debug_window_attn_v2_run(const float* qkv, const float* qkv_bias, const float* scale, const float* table, float* dst, int32_t B, int32_t H, int32_t W, int32_t heads,
@@ -479,6 +479,13 @@ int ph_debug_window_attn_v2_run(const float* qkv, const float* qkv_bias, const f
  * kernel windows of 9..24 only; here 2..8 run on it too. */
 int ph_debug_window_attn_v2_wide_run(const float* qkv, const float* qkv_bias, const float* scale, const float* table, float* dst, int32_t B, int32_t H, int32_t W,
                                      int32_t heads, int32_t w, int32_t shift);
+
+/* Test support (tests/test_window_geometry_cpu.py), host code only (no GPU needed): the token map of a window-attention launch on a (B, H, W) map with windows of side w
+ * (2..24) and shifts sh, sw < w, computed by the functions the kernels call (csrc/window_attn.h).  pix_out / code_out: host arrays of `capacity` int32 each, filled as
+ * [window][w * w] with the windows in the kernels' order (b, wy, wx): pix = (b H + y) W + x of the token's pixel or -1 for a padded token,
+ * code = ty | tx << code_bits | band << 2 code_bits (code_bits 4: w <= 16, the one-wave kernels' form; 5: the key-tiled kernel's); two tokens of a window are masked
+ * against each other where their bands differ. */
+int ph_debug_window_tokens(int32_t B, int32_t H, int32_t W, int32_t w, int32_t sh, int32_t sw, int32_t code_bits, int32_t* pix_out, int32_t* code_out, int64_t capacity);
 
 /* Diagnostic (tools/row_wgrad_bench.py): average milliseconds of the row weight-gradient GEMM dW[n][k] = sum_m dY[m][n] X[m][k]
  * (Linear layers of the training step, train_kernels.h launch_row_wgrad) on synthetic operands, and the largest error of 64
@@ -548,7 +555,7 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_CNX_F16_LN 18   /* layernorm_f16_kernel: LayerNorm over the channels of an fp16 tensor, fp32 moments                                  */
 #define PH_KV_CNX_F16_GEMM 19 /* gemm_f16_kernel: Linear / 2x2-stride-2 conv as a row GEMM on v_mfma_f32_32x32x16_f16 (bias, GELU, layer scale + residual epilogues) */
 #define PH_KV_CNX_F16_ELTWISE 20 /* gelu_fmt_kernel / scale_add_fmt_kernel on fp16 activations (unfused programs)                                    */
-#define PH_KV_WINDOW_ATTN 21 /* window_attn_kernel: one wave per (window, head), q k^T and p v on v_mfma_f32_32x32x2_f32, softmax in registers */
+#define PH_KV_WINDOW_ATTN 21 /* window_attn_kernel (plain variant): one wave per (window, head), q k^T and p v on v_mfma_f32_32x32x2_f32, softmax in registers */
 #define PH_KV_WINDOW_ATTN_F16 22 /* window_attn_f16_kernel: the same plan on v_mfma_f32_32x32x16_f16, fp16 q / k / v / p, fp32 logits and softmax statistics ("swint_f16") */
 #define PH_KV_SWIN_F16_MERGE_LN 23 /* patch_merge_ln_f16_kernel: four-phase gather + LayerNorm(4C) on fp16 activations, fp32 moments ("swint_f16") */
 #define PH_KV_WINDOW_ATTN_BWD 24 /* window_attn_bwd_kernel (ph_model_last_backward_kernels): backward of the attention core, one wave per (window, head), fixed-order slices */
@@ -559,7 +566,7 @@ int ph_model_profile_read(ph_model* m, double* op_ms, int32_t n_ops, int32_t* n_
 #define PH_KV_RESNET_STEM 29 /* resnet_stem_conv_kernel + maxpool3s2_kernel: normalised 7x7 stride-2 stem as an im2col product on v_mfma_f32_32x32x2_f32, then the 3x3 stride-2 max pool */
 #define PH_KV_CONV_S2 30 /* gemm_mfma_dma_tile_kernel mode 4 (3x3 stride 2 pad 1) / mode 6 (1x1 stride 2) as the forward of a PH_OP_CONV_S2 */
 #define PH_KV_ADD_RELU 31 /* add_relu_kernel: dst = relu(src0 + src1), float4 per thread */
-#define PH_KV_WINDOW_ATTN_V2 32 /* window_attn_v2_kernel: cosine window attention, one wave per (window, head) on v_mfma_f32_32x32x2_f32 */
+#define PH_KV_WINDOW_ATTN_V2 32 /* window_attn_kernel (cosine variant, swin_kernels.hip): cosine window attention, one wave per (window, head) on v_mfma_f32_32x32x2_f32 */
 #define PH_KV_LAYERNORM_ADD 33 /* layernorm_add_kernel: dst = src1 + LayerNorm(src0) */
 #define PH_KV_PATCH_MERGE_GATHER 34 /* patch_merge_gather_kernel as the forward of a PH_OP_PATCH_MERGE with PH_FLAG_NO_NORM */
 #define PH_KV_WINDOW_ATTN_V2_WIDE 35 /* window_attn_v2_wide_kernel: cosine window attention of windows 9..24, one workgroup per (window, head), keys tiled, online softmax */

@@ -18,7 +18,7 @@ OP_INPUT_CONV, OP_CONV, OP_POOL, OP_UPSAMPLE, OP_CONVT, OP_HEAD, OP_STEM = 1, 2,
 OP_PATCH_STEM, OP_DWCONV, OP_LAYERNORM, OP_LINEAR, OP_PATCH_CONV, OP_GELU, OP_SCALE_ADD, OP_GLOBAL_MAXPOOL = 8, 9, 10, 11, 12, 13, 14, 15
 OP_PATCH_MERGE, OP_WINDOW_ATTN = 16, 17  # Swin Transformer encoder (swin_kernels.hip)
 OP_GRN = 18  # ConvNeXtV2's Global Response Normalization (convnextv2_kernels.hip)
-OP_WINDOW_ATTN_V2 = 22  # Swinv2's cosine window attention (swinv2_kernels.hip); its table, padded-token q | 0 | v and head scales are derived on the host
+OP_WINDOW_ATTN_V2 = 22  # Swinv2's cosine window attention (swin_kernels.hip's cosine variant, swinv2_kernels.hip above window 8); its table, padded-token q | 0 | v and head scales are derived on the host
 OP_RESNET_STEM, OP_CONV_S2, OP_ADD_RELU = 19, 20, 21  # ResNet encoder: normalised 7x7 stride-2 stem + 3x3 stride-2 max pool, strided 1x1 / 3x3 conv, relu(a + b) (resnet_kernels.hip)
 FLAG_RELU, FLAG_SIGMOID, FLAG_GELU, FLAG_SCALE_RESIDUAL, FLAG_SOFTMAX, FLAG_SILU, FLAG_NO_TRAIN = 1, 2, 4, 8, 16, 32, 64
 FLAG_LN_EPS_1EM5, FLAG_RESIDUAL = 128, 256
@@ -33,7 +33,7 @@ SWIN_KV_WINDOW_ATTN_BWD = 24  # PH_KV_WINDOW_ATTN_BWD (swin_train_kernels.hip): 
 SWIN_KV_WINDOW_ATTN_F16, SWIN_KV_F16_MERGE_LN = 22, 23  # PH_KV_WINDOW_ATTN_F16 / PH_KV_SWIN_F16_MERGE_LN: the Swin ops on fp16 activations (swin_f16_kernels.hip, handle option swint_f16)
 CNX2_KV_GRN, CNX2_KV_GRN_FUSED, CNX2_KV_PATCH_STEM_NORM = 25, 26, 27  # PH_KV_GRN / PH_KV_GRN_FUSED / PH_KV_PATCH_STEM_NORM (convnextv2_kernels.hip)
 RESNET_KV_STEM, RESNET_KV_CONV_S2, RESNET_KV_ADD_RELU = 29, 30, 31  # PH_KV_RESNET_STEM / PH_KV_CONV_S2 / PH_KV_ADD_RELU (resnet_kernels.hip, the strided row-GEMM modes)
-SWINV2_KV_WINDOW_ATTN, SWINV2_KV_LAYERNORM_ADD, SWINV2_KV_MERGE_GATHER = 32, 33, 34  # PH_KV_WINDOW_ATTN_V2 / PH_KV_LAYERNORM_ADD / PH_KV_PATCH_MERGE_GATHER (swinv2_kernels.hip, swin_train_kernels.hip's gather)
+SWINV2_KV_WINDOW_ATTN, SWINV2_KV_LAYERNORM_ADD, SWINV2_KV_MERGE_GATHER = 32, 33, 34  # PH_KV_WINDOW_ATTN_V2 / PH_KV_LAYERNORM_ADD / PH_KV_PATCH_MERGE_GATHER (swin_kernels.hip's cosine variant, swinv2_kernels.hip, swin_train_kernels.hip's gather)
 SWINV2_KV_WINDOW_ATTN_WIDE = 35  # PH_KV_WINDOW_ATTN_V2_WIDE (swinv2_kernels.hip): the key-tiled kernel of windows 9..24
 CNX2_KV_GRN_BWD = 28  # PH_KV_GRN_BWD (convnextv2_train_kernels.hip): reported by ph_model_last_backward_kernels
 CNX_KV_F16_STEM, CNX_KV_F16_DW, CNX_KV_F16_LN, CNX_KV_F16_GEMM, CNX_KV_F16_ELTWISE = 16, 17, 18, 19, 20  # PH_KV_CNX_F16_*: the ConvNeXt encoder ops on fp16 activations (convnext_f16_kernels.hip); not named KV_*: that prefix lists the families a 3x3 conv can come back with (benchlegs.common.conv_kernel_short_names)
@@ -218,6 +218,7 @@ SIGNATURES = {
     "ph_debug_gemm_run": (C.c_int, [C.POINTER(GemmCase)]),
     "ph_debug_window_attn_v2_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32]),
     "ph_debug_window_attn_v2_wide_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "ph_debug_window_tokens": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64]),
     "ph_render_confmaps": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "ph_render_pafs": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "ph_render_class_maps": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp]),

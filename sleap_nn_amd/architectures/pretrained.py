@@ -25,7 +25,7 @@ reference's unfolded names; the stem, the strided convs and the residual tails a
 The Swinv2 family (HuggingFace ``Swinv2Backbone``; effective windows of 2..8, and of 9..24 with ``allow_swinv2_wide`` on top; head dimension 32) is opt-in through the backbone-config key ``allow_swinv2`` for the same reason, and
 inference only: per-stage window and shift follow the config's ``image_size`` (``swinv2_windows``); the qkv concatenation, the padded token's q | 0 | v, the ``16 sigmoid(MLP(coords))`` bias
 table and the clamped, exponentiated logit scales are derived on the host (``derived_params``, float64, at handle creation) while the state dict keeps the reference's names; the cosine window
-attention and the residual-after-norm LayerNorm are ``csrc/swinv2_kernels.hip``.
+attention runs the cosine variant of ``csrc/swin_kernels.hip``'s kernel (key-tiled above window 8: ``csrc/swinv2_kernels.hip``, with the residual-after-norm LayerNorm).
 
 A ConvNeXtV2 block is six ops: depthwise 7x7 -> LayerNorm -> Linear C->4C -> GELU -> GRN -> Linear 4C->C with the residual add
 in its epilogue (no layer scale).  ``Model._fuse_cnblocks`` folds the GELU into the first Linear for inference.
@@ -90,8 +90,8 @@ SWINV2_OPT_IN = ("the Swinv2 family is opt-in: backbone-config key allow_swinv2=
 # effective windows of 9..24 (81..576 tokens: the window16, window12-192, 12to16 and 12to24 checkpoints) run the key-tiled kernel and need a second opt-in on top of that one
 SWINV2_WIDE_OPT_IN = ("windows above 8 are opt-in on top of allow_swinv2: backbone-config key allow_swinv2_wide=True (LoadedAssets.build_model(..., swinv2_wide=True), "
                       "Predictor.from_model_paths(..., swinv2_wide=True))")
-SWINV2_MAX_WINDOW, SWINV2_MAX_WINDOW_WIDE = 8, 24  # window_attn_v2_kernel holds 64 tokens in one wave; window_attn_v2_wide_kernel tiles the keys of up to 576
-SWINV2_HEAD_DIM = 32  # what window_attn_v2_kernel is built for
+SWINV2_MAX_WINDOW, SWINV2_MAX_WINDOW_WIDE = 8, 24  # window_attn_kernel's cosine variant holds 64 tokens in one wave; window_attn_v2_wide_kernel tiles the keys of up to 576
+SWINV2_HEAD_DIM = 32  # what the cosine attention kernels are built for
 SWINV2_MAX_LOGIT = math.log(1.0 / 0.01)  # Swinv2SelfAttention clamps logit_scale here before the exp: scale <= 100
 
 

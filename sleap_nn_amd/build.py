@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libposehip.so")
 SOURCES = ["net_kernels.hip", "wino2d_kernels.hip", "wino4_kernels.hip", "w16_kernels.hip", "smallmap_kernels.hip", "conv3x3_route.hip", "f16_kernels.hip", "f16_rows_kernels.hip", "convnext_kernels.hip", "convnext_f16_kernels.hip", "cnblock_mlp_kernels.hip", "convnextv2_kernels.hip", "convnextv2_train_kernels.hip", "resnet_kernels.hip", "swin_kernels.hip", "swin_f16_kernels.hip", "swin_train_kernels.hip", "swinv2_kernels.hip", "model.hip", "weights.hip", "plan.hip", "forward.hip", "train_kernels.hip", "convnext_train_kernels.hip", "train.hip", "backward.hip", "post_kernels.hip", "resize_kernels.hip", "augment_kernels.hip", "tile_kernels.hip", "seg_kernels.hip", "seg_cleanup_kernels.hip", "seg_merge_kernels.hip", "target_kernels.hip", "seg_loss_kernels.hip", "seg_target_kernels.hip", "eval_kernels.hip", "track_kernels.hip", "flow_kernels.hip", "group_host.cpp", "track_host.cpp", "comm_rccl.cpp"]
-HEADERS = ["common.h", "device_math.h", "act_format.h", "f16_kernels.h", "convnext_f16_kernels.h", "net_kernels.h", "conv3x3_route.h", "train_kernels.h", "model_internal.h", "forward_internal.h", os.path.join("..", "..", "include", "posehip.h")]
+HEADERS = ["common.h", "device_math.h", "act_format.h", "f16_kernels.h", "convnext_f16_kernels.h", "net_kernels.h", "window_attn.h", "conv3x3_route.h", "train_kernels.h", "model_internal.h", "forward_internal.h", os.path.join("..", "..", "include", "posehip.h")]
 ARCH = "gfx950"
 
 

@@ -720,8 +720,8 @@ int bwd_window_attn(BackwardCtx& c, const PackedOp& op) {
   w.C = d.cout;
   w.heads = d.cin1;
   w.w = d.ksize;
-  w.sh = d.ksize >= (si.h + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;  // per axis, as the forward
-  w.sw = d.ksize >= (si.w + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;
+  w.sh = window_axis_shift(si.h, d.ksize, d.cmid);  // per axis, as the forward
+  w.sw = window_axis_shift(si.w, d.ksize, d.cmid);
   int rc = launch_window_attn_bwd(w, c.s);
   c.m->last_bwd_variant[c.oi] = PH_KV_WINDOW_ATTN_BWD;
   c.init[d.src0] = 1;

@@ -23,6 +23,14 @@ __device__ __forceinline__ float erf_as(float x) {
 
 // exp on the hardware v_exp_f32 (1 ulp on 2^y; the rounding of y = x log2(e) adds |x| * 6e-8 relative): softmax arguments are <= 0 after the row maximum is subtracted
 __device__ __forceinline__ float exp_hw(float x) { return __builtin_amdgcn_exp2f(1.4426950408889634f * x); }
+// exp(x) for x <= 0 through the hardware exp2, with the rounding of x log2(e) compensated: the cosine window attention's scores reach +-100 before the bias, so x goes far
+// enough from 0 for the plain product's rounding (|x| 2^-24 relative in the result) to show
+__device__ __forceinline__ float exp_comp(float x) {
+  const float l2e = 1.4426950408889634f, l2e_lo = 1.92596299e-8f;  // log2(e) = l2e + l2e_lo
+  const float t = x * l2e;
+  const float lo = fmaf(x, l2e, -t) + x * l2e_lo;
+  return __builtin_amdgcn_exp2f(t) * fmaf(lo, 0.6931471805599453f, 1.0f);
+}
 
 // GELU (erf form, nn.GELU default) and its derivative  d/dx [x * Phi(x)] = Phi(x) + x * phi(x).
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erf_as(x * 0.70710678118654752440f)); }

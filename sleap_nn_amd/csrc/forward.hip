@@ -688,11 +688,11 @@ int fwd_patch_merge(ForwardCtx& c, const PackedOp& op) {
   return launch_patch_merge_ln(c.rd(d.src0), op.w_dev, op.b_dev, c.wr(d.dst), c.batch, s0.h, s0.w, d.cin0, eps, c.s);
 }
 
-// WindowAttnArgs / WindowAttnF16Args: the same fields
-template <typename Args>
-void window_attn_args(ForwardCtx& c, const PackedOp& op, Args& a) {
+// what the plain and the cosine op fill alike; the shift is the caller's
+WindowAttnArgs window_attn_args(ForwardCtx& c, const PackedOp& op) {
   const ph_op_desc& d = op.d;
   const SlotShape& s0 = c.slot(d.src0);
+  WindowAttnArgs a{};
   a.qkv = c.rd(d.src0);
   a.table = op.w_dev;
   a.qkv_bias = op.b_dev;
@@ -703,45 +703,32 @@ void window_attn_args(ForwardCtx& c, const PackedOp& op, Args& a) {
   a.C = d.cout;
   a.heads = d.cin1;
   a.w = d.ksize;
-  // an axis the window covers whole (window >= padded size) is not shifted: decided per axis, from this launch's map
-  a.sh = d.ksize >= (s0.h + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;
-  a.sw = d.ksize >= (s0.w + d.ksize - 1) / d.ksize * d.ksize ? 0 : d.cmid;
+  return a;
 }
 
 int fwd_window_attn(ForwardCtx& c, const PackedOp& op) {
   const ph_op_desc& d = op.d;
   const SlotShape& s0 = c.slot(d.src0);
   PH_REQUIRE((c.fmt == FMT_F32 || c.fmt == FMT_F16) && s0.c == d.cin0 && s0.cp == d.cin0 && c.slot(d.dst).cp == d.cout, "window attention channel mismatch");
+  WindowAttnArgs a = window_attn_args(c, op);
+  a.sh = window_axis_shift(s0.h, d.ksize, d.cmid);
+  a.sw = window_axis_shift(s0.w, d.ksize, d.cmid);
   if (c.fmt == FMT_F16) {
-    WindowAttnF16Args f{};
-    window_attn_args(c, op, f);
     c.ran(PH_KV_WINDOW_ATTN_F16);
-    return launch_window_attn_f16(f, c.s);
+    return launch_window_attn_f16(a, c.s);
   }
-  WindowAttnArgs a{};
-  window_attn_args(c, op, a);
   c.ran(PH_KV_WINDOW_ATTN);
   return launch_window_attn(a, c.s);
 }
 
-// cosine window attention of a Swinv2 block (swinv2_kernels.hip): the table, the padded token's q | 0 | v and the head scales are the host's derived tensors
+// cosine window attention of a Swinv2 block (swin_kernels.hip, swinv2_kernels.hip): the table, the padded token's q | 0 | v and the head scales are the host's derived tensors
 int fwd_window_attn_v2(ForwardCtx& c, const PackedOp& op) {
   const ph_op_desc& d = op.d;
   const SlotShape& s0 = c.slot(d.src0);
   PH_REQUIRE(c.fmt == FMT_F32 && s0.c == d.cin0 && s0.cp == d.cin0 && c.slot(d.dst).cp == d.cout, "cosine window attention channel mismatch");
-  WindowAttnV2Args a{};
-  a.qkv = c.rd(d.src0);
-  a.qkv_bias = op.b_dev;
+  WindowAttnArgs a = window_attn_args(c, op);
   a.scale = op.w2_dev;
-  a.table = op.w_dev;
-  a.dst = c.wr(d.dst);
-  a.B = c.batch;
-  a.H = s0.h;
-  a.W = s0.w;
-  a.C = d.cout;
-  a.heads = d.cin1;
-  a.w = d.ksize;
-  a.shift = d.cmid;
+  a.sh = a.sw = d.cmid;  // the layer's shift on both axes, whatever the map
   if (d.ksize > 8) {  // more than 64 tokens per window: the key-tiled kernel
     c.ran(PH_KV_WINDOW_ATTN_V2_WIDE);
     return launch_window_attn_v2_wide(a, c.s);

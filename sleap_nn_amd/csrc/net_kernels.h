@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "window_attn.h"
+
 namespace ph {
 
 struct ConvArgs {
@@ -161,19 +163,12 @@ struct GemmArgs {
 int launch_patch_stem(const PatchStemArgs& a, hipStream_t s);
 int launch_dwconv7(const DwConvArgs& a, hipStream_t s);
 int launch_layernorm(const float* src, const float* gamma, const float* beta, float* dst, int c, int cp, size_t npix, hipStream_t s, float eps = 1e-6f);
-// Swin Transformer encoder (swin_kernels.hip)
-struct WindowAttnArgs {
-  const float* qkv = nullptr;       // (B, H, W, 3C): q | k | v of the un-padded, un-rolled map; head a owns channels 32 a .. 32 a + 31 of each
-  const float* table = nullptr;     // relative-position bias table, head-major: [heads][(2w - 1)^2]
-  const float* qkv_bias = nullptr;  // (3C): what a padded token's q, k, v are
-  float* dst = nullptr;             // (B, H, W, C)
-  int B = 0, H = 0, W = 0, C = 0, heads = 0;
-  int w = 0;                        // window side, 2..8
-  int sh = 0, sw = 0;               // per-axis shift (0 where the window covers the padded axis)
-};
+// Swin Transformer encoder (swin_kernels.hip).  WindowAttnArgs, its geometry fields (WindowGeom) and the token map: window_attn.h
 int launch_window_attn(const WindowAttnArgs& a, hipStream_t s);
+// ... the cosine variant of the same kernel (Swinv2, windows of 2..8): a.scale set, sh = sw = the layer's shift
+int launch_window_attn_v2(const WindowAttnArgs& a, hipStream_t s);
 // Backward of the attention core (swin_train_kernels.hip): S and P are recomputed from q and k, nothing but the qkv slot is kept by the forward
-struct WindowAttnBwdArgs {
+struct WindowAttnBwdArgs : WindowGeom {
   const float* qkv = nullptr;       // the forward's qkv slot (B, H, W, 3C)
   const float* table = nullptr;     // head-major bias table, as WindowAttnArgs
   const float* qkv_bias = nullptr;  // (3C)
@@ -182,9 +177,6 @@ struct WindowAttnBwdArgs {
   float* gtable = nullptr;          // gradient of relative_position_bias_table, canonical ((2w - 1)^2, heads)
   float* gpad = nullptr;            // (3C): sum of dq | dk | dv over the padded tokens (belongs to qkv.bias)
   float* scratch = nullptr;         // window_attn_bwd_scratch_floats(...) floats: the slice partials of gtable and gpad
-  int B = 0, H = 0, W = 0, C = 0, heads = 0;
-  int w = 0;
-  int sh = 0, sw = 0;
 };
 int64_t window_attn_bwd_scratch_floats(int B, int H, int W, int C, int heads, int w);
 int launch_window_attn_bwd(const WindowAttnBwdArgs& a, hipStream_t s);
@@ -201,30 +193,10 @@ int launch_vec_add(float* dst, const float* src, int n, hipStream_t s);
 // 2x2 phase gather (zero fill past an odd edge) + LayerNorm over the 4C gathered channels: (B, H, W, C) -> (B, ceil(H/2), ceil(W/2), 4C)
 int launch_patch_merge_ln(const float* src, const float* gamma, const float* beta, float* dst, int B, int H, int W, int c, float eps, hipStream_t s);
 // ... on plain-fp16 activations (swin_f16_kernels.hip; FMT_F16, C a multiple of 32: no pad channels)
-struct WindowAttnF16Args {
-  const void* qkv = nullptr;        // FMT_F16 (B, H, W, 3C)
-  const float* table = nullptr;     // as WindowAttnArgs: fp32
-  const float* qkv_bias = nullptr;  // (3C) fp32: converted where a padded token reads it
-  void* dst = nullptr;              // FMT_F16 (B, H, W, C)
-  int B = 0, H = 0, W = 0, C = 0, heads = 0;
-  int w = 0;
-  int sh = 0, sw = 0;
-};
-int launch_window_attn_f16(const WindowAttnF16Args& a, hipStream_t s);
+int launch_window_attn_f16(const WindowAttnArgs& a, hipStream_t s);  // qkv and dst FMT_F16; table and qkv_bias fp32 (converted where a padded token reads it)
 int launch_patch_merge_ln_f16(const void* src, const float* gamma, const float* beta, void* dst, int B, int H, int W, int c, float eps, hipStream_t s);
-// Swin Transformer V2 encoder (swinv2_kernels.hip): cosine window attention and the residual-after-norm LayerNorm
-struct WindowAttnV2Args {
-  const float* qkv = nullptr;       // (B, H, W, 3C): query | key | value of the un-padded, un-rolled map; head a owns channels 32 a .. 32 a + 31 of each
-  const float* qkv_bias = nullptr;  // (3C): query.bias | zeros | value.bias -- the q, k, v of a padded token (hidden state 0; key has no bias)
-  const float* scale = nullptr;     // (heads): exp(min(logit_scale, log 100))
-  const float* table = nullptr;     // 16 sigmoid(continuous position bias), head-major: [heads][(2w - 1)^2]
-  float* dst = nullptr;             // (B, H, W, C)
-  int B = 0, H = 0, W = 0, C = 0, heads = 0;
-  int w = 0;                        // window side: 2..8 (launch_window_attn_v2) or 2..24 (launch_window_attn_v2_wide)
-  int shift = 0;                    // the layer's shift on both axes, whatever the map
-};
-int launch_window_attn_v2(const WindowAttnV2Args& a, hipStream_t s);
-int launch_window_attn_v2_wide(const WindowAttnV2Args& a, hipStream_t s);  // the key-tiled kernel: any window of 2..24 (the forward sends it 9..24)
+// Swin Transformer V2 encoder (swinv2_kernels.hip): key-tiled cosine window attention and the residual-after-norm LayerNorm
+int launch_window_attn_v2_wide(const WindowAttnArgs& a, hipStream_t s);  // any window of 2..24 (the forward sends it 9..24); a.scale set, sh = sw = the layer's shift
 int launch_layernorm_add(const float* src, const float* res, const float* gamma, const float* beta, float* dst, int c, int cp, size_t npix, hipStream_t s, float eps);  // dst = res + LayerNorm(src)
 int launch_gemm(const GemmArgs& a, hipStream_t s);
 int gemm_choose_variant(const GemmArgs& a);                              // the tile variant launch_gemm takes for a.bn / a.M / a.coutp (-1: no kernel for that N tile)

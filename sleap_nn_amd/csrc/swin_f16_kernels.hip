@@ -15,54 +15,40 @@
 
 namespace ph {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // ---------------------------------------------------------------------------------------
 // One wave = one (window, head); four waves (consecutive heads, then the next window) per workgroup, as window_attn_kernel.
 // N = w^2 <= 64 tokens, head dimension 32, T = ceil(N / 32) 32-token tiles, everything in registers:
 //   S^T = K Q^T: two v_mfma_f32_32x32x16_f16 per tile pair (A = K, B = Q).  Lane half h holds channels 16 h .. 16 h + 15 of its
 //   token (two 16-byte loads); K step s takes elements 8 s .. 8 s + 7 of them on BOTH operands -- the same permutation of the
 //   K index, so the product is q . k.  The 32^-0.5 scale goes on the fp32 accumulator.  Query i is the lane (column l & 31), the
-//   keys j = 8 (r >> 2) + 4 h + (r & 3) its accumulator registers: bias, mask, row maximum and row sum are lane-local plus one
+//   keys window_key(tj, r, h) its accumulator registers: bias, mask, row maximum and row sum are lane-local plus one
 //   exchange with lane l ^ 32.  p = fp16(exp(s - max)); the row sum is taken over the ROUNDED p.
 //   O^T = V^T P^T: registers 8 s .. 8 s + 7 of a P^T tile, converted, are the B operand of K step s as they stand (K index
 //   8 h + e <-> key 16 s + 8 (e >> 2) + 4 h + (e & 3)); V is loaded in that key order as the A operand (row = channel l & 31:
 //   2-byte loads, 64 contiguous bytes per wave half-row).  O^T has the query in the lane and four consecutive channels in each
 //   register quad: 8-byte stores at the token's ORIGINAL pixel.
-// Token geometry, padded tokens (q, k, v = fp16(qkv.bias), read from the fp32 vector) and the band mask: window_attn_kernel.
+// Token geometry, padded tokens (q, k, v = fp16(qkv.bias), read from the fp32 vector) and the band mask: window_attn.h.
 // ---------------------------------------------------------------------------------------
 template <int T>
-__global__ __launch_bounds__(256) void window_attn_f16_kernel(WindowAttnF16Args a) {
+__global__ __launch_bounds__(256) void window_attn_f16_kernel(WindowAttnArgs a) {
   __shared__ float tbl[4][232];
   __shared__ int tok_pix[4][64];
   __shared__ int tok_code[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int half = lane >> 5, l31 = lane & 31;
-  const int w = a.w, N = w * w;
-  const int pH = (a.H + w - 1) / w * w, pW = (a.W + w - 1) / w * w;
-  const int nwh = pH / w, nww = pW / w;
-  const long long total = (long long)a.B * nwh * nww * a.heads;
+  const WindowGrid grid = window_grid(a.B, a.H, a.W, a.w);
+  const int w = grid.w, N = grid.N, rel = grid.rel;
+  const long long total = grid.nwin * a.heads;
   long long item = (long long)blockIdx.x * 4 + wave;
   const bool live = item < total;
   if (!live) item = total - 1;
-  const int head = (int)(item % a.heads);
-  long long win = item / a.heads;
-  const int wx = (int)(win % nww);
-  win /= nww;
-  const int wy = (int)(win % nwh);
-  const int b = (int)(win / nwh);
-  const int rel = (2 * w - 1) * (2 * w - 1);
+  const WindowItem it = window_decode(grid, item, a.heads);
+  const int head = it.head;
   for (int i = lane; i < rel; i += 64) tbl[wave][i] = a.table[(size_t)head * rel + i];
   {
-    const int t = lane < N ? lane : 0;  // (dead lanes mirror token 0: their table index stays in range)
-    const int ty = t / w, tx = t - ty * w;
-    int y = wy * w + ty + a.sh, x = wx * w + tx + a.sw;
-    if (y >= pH) y -= pH;
-    if (x >= pW) x -= pW;
-    const int band = ((a.sh > 0 && wy == nwh - 1 && ty >= w - a.sh) ? 2 : 0) | ((a.sw > 0 && wx == nww - 1 && tx >= w - a.sw) ? 1 : 0);
-    tok_pix[wave][lane] = (y < a.H && x < a.W) ? (b * a.H + y) * a.W + x : -1;
-    tok_code[wave][lane] = ty | (tx << 4) | (band << 8);
+    const TokenInfo tk = window_token<4>(grid, it, lane < N ? lane : 0, a.sh, a.sw);  // (dead lanes mirror token 0: their table index stays in range)
+    tok_pix[wave][lane] = tk.pix;
+    tok_code[wave][lane] = tk.code;
   }
   __syncthreads();
   const int C3 = 3 * a.C;
@@ -105,7 +91,7 @@ __global__ __launch_bounds__(256) void window_attn_f16_kernel(WindowAttnF16Args 
       }
     }
   }
-  // V: [tj][K step s][e] = key tj * 32 + 16 s + 8 (e >> 2) + 4 half + (e & 3), channel l & 31 of the head
+  // V: [tj][K step s][e] = key window_key(tj, 8 s + e, half), channel l & 31 of the head
   f16x8 v[T][2];
 #pragma unroll
   for (int tj = 0; tj < T; ++tj)
@@ -113,7 +99,7 @@ __global__ __launch_bounds__(256) void window_attn_f16_kernel(WindowAttnF16Args 
     for (int s = 0; s < 2; ++s)
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const int j = tj * 32 + 16 * s + 8 * (e >> 2) + 4 * half + (e & 3);
+        const int j = window_key(tj, 8 * s + e, half);
         _Float16 val = (_Float16)0.f;
         if (j < N) {
           const int pix = tok_pix[wave][j];
@@ -139,17 +125,15 @@ __global__ __launch_bounds__(256) void window_attn_f16_kernel(WindowAttnF16Args 
 #pragma unroll
   for (int ti = 0; ti < T; ++ti) {
     const int ci = tok_code[wave][ti * 32 + l31];
-    const int tyi = ci & 15, txi = (ci >> 4) & 15, bi = ci >> 8;
     float mx = -INFINITY;
 #pragma unroll
     for (int tj = 0; tj < T; ++tj)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int j = tj * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
+        const int j = window_key(tj, r, half);
         const int cj = tok_code[wave][j];
-        const int tyj = cj & 15, txj = (cj >> 4) & 15, bj = cj >> 8;
-        float val = st[tj][ti][r] * qscale + tbl[wave][(tyi - tyj + w - 1) * (2 * w - 1) + (txi - txj + w - 1)];
-        if (bi != bj) val += -100.0f;
+        float val = st[tj][ti][r] * qscale + tbl[wave][window_bias_index<4>(ci, cj, w)];
+        if (token_band<4>(ci) != token_band<4>(cj)) val += -100.0f;
         if (j >= N) val = -INFINITY;  // dead key columns take no part in the softmax
         st[tj][ti][r] = val;
         mx = fmaxf(mx, val);
@@ -188,19 +172,15 @@ __global__ __launch_bounds__(256) void window_attn_f16_kernel(WindowAttnF16Args 
   }
 }
 
-int launch_window_attn_f16(const WindowAttnF16Args& a, hipStream_t s) {
-  PH_REQUIRE(a.qkv && a.table && a.qkv_bias && a.dst, "window attention (fp16): null pointer");
-  PH_REQUIRE(a.w >= 2 && a.w <= 8, "window attention (fp16): window_size %d is outside 2..8", a.w);
-  PH_REQUIRE(a.heads > 0 && a.C == a.heads * 32, "window attention (fp16): head dimension must be 32 (C %d, heads %d)", a.C, a.heads);
-  PH_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && (long long)a.B * a.H * a.W < (1ll << 31) / 4, "window attention (fp16): bad map size");
-  PH_REQUIRE(a.sh >= 0 && a.sh < a.w && a.sw >= 0 && a.sw < a.w, "window attention (fp16): shift must be smaller than the window");
-  const long long nwin = (long long)a.B * ((a.H + a.w - 1) / a.w) * ((a.W + a.w - 1) / a.w);
-  const long long blocks = (nwin * a.heads + 3) / 4;
-  PH_REQUIRE(blocks < (1ll << 31), "window attention (fp16): too many windows");
-  if (a.w * a.w <= 32)
-    hipLaunchKernelGGL(window_attn_f16_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+int launch_window_attn_f16(const WindowAttnArgs& a, hipStream_t s) {
+  WindowGrid g;
+  unsigned blocks;
+  const int rc = window_attn_check("window attention (fp16)", 8, a.qkv && a.table && a.qkv_bias && a.dst, a, &g, 4, &blocks);
+  if (rc != PH_OK) return rc;
+  if (g.N <= 32)
+    hipLaunchKernelGGL(window_attn_f16_kernel<1>, dim3(blocks), dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL(window_attn_f16_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(window_attn_f16_kernel<2>, dim3(blocks), dim3(256), 0, s, a);
   PH_HIP_CHECK(hipGetLastError());
   return PH_OK;
 }

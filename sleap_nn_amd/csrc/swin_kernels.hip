@@ -6,7 +6,8 @@
 //
 //   window_attn_kernel ..... pad to window multiples, roll by (-sh, -sw), cut into w x w windows, per head
 //                            softmax(q k^T / sqrt(32) + bias [+ band mask]) v, un-window, roll back, crop --
-//                            all of it index arithmetic on the loads and stores of one launch.
+//                            all of it index arithmetic on the loads and stores of one launch.  Its cosine variant is
+//                            the Swinv2 attention of windows up to 8 (launch_window_attn_v2).
 //   patch_merge_ln_kernel .. gather of the four 2x2 phases to 4C channels + LayerNorm over them.
 #include <algorithm>
 
@@ -16,71 +17,79 @@
 
 namespace ph {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// The one argument check of the five launchers (window_attn.h)
+int window_attn_check(const char* label, int max_w, bool pointers, const WindowGeom& a, WindowGrid* g, int per_block, unsigned* blocks) {
+  PH_REQUIRE(pointers, "%s: null pointer", label);
+  PH_REQUIRE(a.w >= 2 && a.w <= max_w, "%s: window_size %d is outside 2..%d", label, a.w, max_w);
+  PH_REQUIRE(a.heads > 0 && a.C == a.heads * 32, "%s: head dimension must be 32 (C %d, heads %d)", label, a.C, a.heads);
+  PH_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && (long long)a.B * a.H * a.W < (1ll << 31) / 4, "%s: bad map size", label);
+  PH_REQUIRE(a.sh >= 0 && a.sh < a.w && a.sw >= 0 && a.sw < a.w, "%s: shift must be smaller than the window", label);
+  *g = window_grid(a.B, a.H, a.W, a.w);
+  if (blocks) {
+    const long long n = (g->nwin * a.heads + per_block - 1) / per_block;
+    PH_REQUIRE(n < (1ll << 31), "%s: too many windows", label);
+    *blocks = (unsigned)n;
+  }
+  return PH_OK;
+}
 
 // ---------------------------------------------------------------------------------------
 // One wave = one (window, head); four waves (consecutive heads, then the next window) per workgroup.  N = w^2 <= 64
 // tokens, head dimension 32, T = ceil(N / 32) 32-token tiles.  Everything lives in registers:
 //   S^T = K Q^T on v_mfma_f32_32x32x2_f32 (A = K, B = Q; the two lane halves hold channels 0..15 / 16..31 of their
 //   token, the same permutation of the K index on both operands, so the loads are four dwordx4 per token).  The
-//   transposed product puts query i in the lane (column l & 31) and the keys j = 8 (r >> 2) + 4 (l >> 5) + (r & 3) in its
+//   transposed product puts query i in the lane (column l & 31) and the keys window_key(tj, r, l >> 5) in its
 //   accumulator registers: bias, mask, row maximum and row sum are lane-local plus one exchange with lane l ^ 32.
 //   O^T = V^T P^T takes those registers as its B operand unchanged (K index = key j in the accumulator order), with V
 //   loaded in the same key order as its A operand; O^T again has the query in the lane, four consecutive channels in
 //   each register quad: the stores are dwordx4 at the token's ORIGINAL pixel.
-// A token's rolled, padded grid position (ry, rx) = (wy w + ty, wx w + tx) comes from pixel ((ry + sh) mod pH,
-// (rx + sw) mod pW); past the map it is a padded token: q, k, v = qkv.bias, a key like any other, never stored.
-// Band mask of the shifted block: only the last window row / column holds two bands, split at w - shift.
+// Token geometry, padded tokens and the band mask: window_attn.h.
+// COSINE (Swinv2; exact fp32 as the plain variant, same registers, lanes and accumulator order) changes four things:
+//   * q and k are divided by max(||.||_2, 1e-12) over the head's 32 channels (F.normalize): a lane holds 16 of them, the
+//     sum of squares takes one exchange with lane l ^ 32.  The head's scale exp(min(logit_scale, log 100)) (a.scale,
+//     computed by the host) is folded into q behind the normalisation.  A padded token has hidden state 0: q =
+//     query.bias, k = 0 exactly (the key section of a.qkv_bias is zero, its normalised k is 0 / 1e-12 = 0), v = value.bias.
+//   * the band mask adds -200, not -100: Swinv2SelfAttention.forward adds the (-100) mask TWICE.  With |q.k| scale <= 100
+//     and a bias in (0, 16) a masked score can stay above an unmasked one: the constant is part of the arithmetic, not
+//     a stand-in for minus infinity.
+//   * exp_comp instead of exp_hw: the scores go far enough from the maximum for the argument's rounding to show.
+//   * a dead key column (j >= N) is skipped by a guard; the plain variant gives it a score of -inf and lets exp_hw
+//     return 0.  Both give p = 0; each variant keeps the form it was compiled with (code objects).
 // ---------------------------------------------------------------------------------------
-struct TokenInfo {
-  int pix;   // pixel index (b H + y) W + x, -1 = padded token
-  int code;  // ty | tx << 4 | band << 8
-};
-
-template <int T>
+template <int T, bool COSINE>
 __global__ __launch_bounds__(256) void window_attn_kernel(WindowAttnArgs a) {
   __shared__ float tbl[4][232];
   __shared__ int tok_pix[4][64];
   __shared__ int tok_code[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int half = lane >> 5, l31 = lane & 31;
-  const int w = a.w, N = w * w;
-  const int pH = (a.H + w - 1) / w * w, pW = (a.W + w - 1) / w * w;
-  const int nwh = pH / w, nww = pW / w;
-  const long long total = (long long)a.B * nwh * nww * a.heads;
+  const WindowGrid grid = window_grid(a.B, a.H, a.W, a.w);
+  const int w = grid.w, N = grid.N, rel = grid.rel;
+  const long long total = grid.nwin * a.heads;
   long long item = (long long)blockIdx.x * 4 + wave;
   const bool live = item < total;
   if (!live) item = total - 1;
-  const int head = (int)(item % a.heads);
-  long long win = item / a.heads;
-  const int wx = (int)(win % nww);
-  win /= nww;
-  const int wy = (int)(win % nwh);
-  const int b = (int)(win / nwh);
-  const int rel = (2 * w - 1) * (2 * w - 1);
+  const WindowItem it = window_decode(grid, item, a.heads);
+  const int head = it.head;
   for (int i = lane; i < rel; i += 64) tbl[wave][i] = a.table[(size_t)head * rel + i];
   {
-    const int t = lane < N ? lane : 0;  // (dead lanes mirror token 0: their table index stays in range)
-    const int ty = t / w, tx = t - ty * w;
-    int y = wy * w + ty + a.sh, x = wx * w + tx + a.sw;
-    if (y >= pH) y -= pH;
-    if (x >= pW) x -= pW;
-    const int band = ((a.sh > 0 && wy == nwh - 1 && ty >= w - a.sh) ? 2 : 0) | ((a.sw > 0 && wx == nww - 1 && tx >= w - a.sw) ? 1 : 0);
-    tok_pix[wave][lane] = (y < a.H && x < a.W) ? (b * a.H + y) * a.W + x : -1;
-    tok_code[wave][lane] = ty | (tx << 4) | (band << 8);
+    const TokenInfo tk = window_token<4>(grid, it, lane < N ? lane : 0, a.sh, a.sw);  // (dead lanes mirror token 0: their table index stays in range)
+    tok_pix[wave][lane] = tk.pix;
+    tok_code[wave][lane] = tk.code;
   }
   __syncthreads();
   const int C3 = 3 * a.C;
-  const float qscale = 0.17677669529663688f;  // 32^-0.5
-  // Q and K: token ti * 32 + (l & 31), channels 16 half .. 16 half + 15 of the head
+  const float* qkv = static_cast<const float*>(a.qkv);
+  const float qscale = COSINE ? a.scale[head] : 0.17677669529663688f;  // the head's scale, applied behind the normalisation : 32^-0.5
+  // Q and K: token ti * 32 + (l & 31), channels 16 half .. 16 half + 15 of the head (cosine: each divided by its token's norm over all 32)
   float q[T][16], k[T][16];
 #pragma unroll
   for (int ti = 0; ti < T; ++ti) {
     const int t = ti * 32 + l31;
     const int pix = tok_pix[wave][t];
-    const float* base = (pix >= 0 ? a.qkv + (size_t)pix * C3 : a.qkv_bias) + head * 32 + half * 16;
+    const float* base = (pix >= 0 ? qkv + (size_t)pix * C3 : a.qkv_bias) + head * 32 + half * 16;
     const bool on = t < N;
+    float qss = 0.f, kss = 0.f;
 #pragma unroll
     for (int v4 = 0; v4 < 4; ++v4) {
       f32x4 qv = {0.f, 0.f, 0.f, 0.f}, kv = {0.f, 0.f, 0.f, 0.f};
@@ -90,8 +99,24 @@ __global__ __launch_bounds__(256) void window_attn_kernel(WindowAttnArgs a) {
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        q[ti][v4 * 4 + e] = qv[e] * qscale;
+        if constexpr (COSINE) {
+          q[ti][v4 * 4 + e] = qv[e];
+          qss = fmaf(qv[e], qv[e], qss);
+          kss = fmaf(kv[e], kv[e], kss);
+        } else {
+          q[ti][v4 * 4 + e] = qv[e] * qscale;
+        }
         k[ti][v4 * 4 + e] = kv[e];
+      }
+    }
+    if constexpr (COSINE) {
+      qss += __shfl_xor(qss, 32, 64);
+      kss += __shfl_xor(kss, 32, 64);
+      const float qn = qscale / fmaxf(sqrtf(qss), 1e-12f), kn = 1.0f / fmaxf(sqrtf(kss), 1e-12f);
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        q[ti][e] *= qn;
+        k[ti][e] *= kn;
       }
     }
   }
@@ -101,11 +126,11 @@ __global__ __launch_bounds__(256) void window_attn_kernel(WindowAttnArgs a) {
   for (int tj = 0; tj < T; ++tj)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int j = tj * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
+      const int j = window_key(tj, r, half);
       float val = 0.f;
       if (j < N) {
         const int pix = tok_pix[wave][j];
-        val = (pix >= 0 ? a.qkv + (size_t)pix * C3 : a.qkv_bias)[2 * a.C + head * 32 + l31];
+        val = (pix >= 0 ? qkv + (size_t)pix * C3 : a.qkv_bias)[2 * a.C + head * 32 + l31];
       }
       v[tj][r] = val;
     }
@@ -128,20 +153,31 @@ __global__ __launch_bounds__(256) void window_attn_kernel(WindowAttnArgs a) {
 #pragma unroll
   for (int ti = 0; ti < T; ++ti) {
     const int ci = tok_code[wave][ti * 32 + l31];
-    const int tyi = ci & 15, txi = (ci >> 4) & 15, bi = ci >> 8;
     float mx = -INFINITY;
 #pragma unroll
     for (int tj = 0; tj < T; ++tj)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int j = tj * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
-        const int cj = tok_code[wave][j];
-        const int tyj = cj & 15, txj = (cj >> 4) & 15, bj = cj >> 8;
-        float val = s[tj][ti][r] + tbl[wave][(tyi - tyj + w - 1) * (2 * w - 1) + (txi - txj + w - 1)];
-        if (bi != bj) val += -100.0f;
-        if (j >= N) val = -INFINITY;  // dead key columns take no part in the softmax
-        s[tj][ti][r] = val;
-        mx = fmaxf(mx, val);
+        const int j = window_key(tj, r, half);
+        auto score = [&] {
+          const int cj = tok_code[wave][j];
+          float val = s[tj][ti][r] + tbl[wave][window_bias_index<4>(ci, cj, w)];
+          if (token_band<4>(ci) != token_band<4>(cj)) val += COSINE ? -200.0f : -100.0f;
+          return val;
+        };
+        // dead key columns take no part in the softmax
+        if constexpr (COSINE) {
+          if (j < N) {
+            const float val = score();
+            s[tj][ti][r] = val;
+            mx = fmaxf(mx, val);
+          }
+        } else {
+          float val = score();
+          if (j >= N) val = -INFINITY;
+          s[tj][ti][r] = val;
+          mx = fmaxf(mx, val);
+        }
       }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     float sum = 0.f;
@@ -149,7 +185,11 @@ __global__ __launch_bounds__(256) void window_attn_kernel(WindowAttnArgs a) {
     for (int tj = 0; tj < T; ++tj)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float p = exp_hw(s[tj][ti][r] - mx);
+        float p;
+        if constexpr (COSINE)
+          p = window_key(tj, r, half) < N ? exp_comp(s[tj][ti][r] - mx) : 0.f;
+        else
+          p = exp_hw(s[tj][ti][r] - mx);
         s[tj][ti][r] = p;
         sum += p;
       }
@@ -171,7 +211,7 @@ __global__ __launch_bounds__(256) void window_attn_kernel(WindowAttnArgs a) {
     const int t = ti * 32 + l31;
     const int pix = tok_pix[wave][t];
     if (live && t < N && pix >= 0) {
-      float* out = a.dst + (size_t)pix * a.C + head * 32 + 4 * half;
+      float* out = static_cast<float*>(a.dst) + (size_t)pix * a.C + head * 32 + 4 * half;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         f32x4 r4;
@@ -183,22 +223,21 @@ __global__ __launch_bounds__(256) void window_attn_kernel(WindowAttnArgs a) {
   }
 }
 
-int launch_window_attn(const WindowAttnArgs& a, hipStream_t s) {
-  PH_REQUIRE(a.qkv && a.table && a.qkv_bias && a.dst, "window attention: null pointer");
-  PH_REQUIRE(a.w >= 2 && a.w <= 8, "window attention: window_size %d is outside 2..8", a.w);
-  PH_REQUIRE(a.heads > 0 && a.C == a.heads * 32, "window attention: head dimension must be 32 (C %d, heads %d)", a.C, a.heads);
-  PH_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && (long long)a.B * a.H * a.W < (1ll << 31) / 4, "window attention: bad map size");
-  PH_REQUIRE(a.sh >= 0 && a.sh < a.w && a.sw >= 0 && a.sw < a.w, "window attention: shift must be smaller than the window");
-  const long long nwin = (long long)a.B * ((a.H + a.w - 1) / a.w) * ((a.W + a.w - 1) / a.w);
-  const long long blocks = (nwin * a.heads + 3) / 4;
-  PH_REQUIRE(blocks < (1ll << 31), "window attention: too many windows");
-  if (a.w * a.w <= 32)
-    hipLaunchKernelGGL(window_attn_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+template <bool COSINE>
+static int launch_window_attn_variant(const char* label, const WindowAttnArgs& a, hipStream_t s) {
+  WindowGrid g;
+  unsigned blocks;
+  const int rc = window_attn_check(label, 8, a.qkv && a.table && a.qkv_bias && a.dst && (a.scale || !COSINE), a, &g, 4, &blocks);
+  if (rc != PH_OK) return rc;
+  if (g.N <= 32)
+    hipLaunchKernelGGL((window_attn_kernel<1, COSINE>), dim3(blocks), dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL(window_attn_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((window_attn_kernel<2, COSINE>), dim3(blocks), dim3(256), 0, s, a);
   PH_HIP_CHECK(hipGetLastError());
   return PH_OK;
 }
+int launch_window_attn(const WindowAttnArgs& a, hipStream_t s) { return launch_window_attn_variant<false>("window attention", a, s); }
+int launch_window_attn_v2(const WindowAttnArgs& a, hipStream_t s) { return launch_window_attn_variant<true>("cosine window attention", a, s); }
 
 // ---------------------------------------------------------------------------------------
 // Patch merging up to its Linear: out pixel (oy, ox) = LayerNorm(concat(x[2oy][2ox], x[2oy+1][2ox], x[2oy][2ox+1],
@@ -265,4 +304,35 @@ int launch_patch_merge_ln(const float* src, const float* gamma, const float* bet
   return PH_OK;
 }
 
+template <int BITS>
+static void fill_window_tokens(const WindowGrid& g, int sh, int sw, int32_t* pix, int32_t* code) {
+  for (long long win = 0; win < g.nwin; ++win) {
+    const WindowItem it = window_decode(g, win, 1);
+    for (int t = 0; t < g.N; ++t) {
+      const TokenInfo tk = window_token<BITS>(g, it, t, sh, sw);
+      pix[win * g.N + t] = tk.pix;
+      code[win * g.N + t] = tk.code;
+    }
+  }
+}
+
 }  // namespace ph
+
+// Test support (tests/test_window_geometry_cpu.py), not a product path: the token map of a launch, [window][N] in the kernels' window order (b, wy, wx), from the
+// functions the kernels call (window_attn.h).  Host code only: no HIP call.
+extern "C" int ph_debug_window_tokens(int32_t B, int32_t H, int32_t W, int32_t w, int32_t sh, int32_t sw, int32_t code_bits, int32_t* pix_out, int32_t* code_out,
+                                      int64_t capacity) {
+  using namespace ph;
+  PH_REQUIRE(pix_out && code_out, "ph_debug_window_tokens: null pointer");
+  PH_REQUIRE(w >= 2 && w <= 24, "ph_debug_window_tokens: window_size %d is outside 2..24", w);
+  PH_REQUIRE(code_bits == 5 || (code_bits == 4 && w <= 16), "ph_debug_window_tokens: code_bits %d cannot hold the coordinates of window %d (4: up to 16, 5: up to 24)", code_bits, w);
+  PH_REQUIRE(B > 0 && H > 0 && W > 0 && (long long)B * H * W < (1ll << 31) / 4, "ph_debug_window_tokens: bad map size");
+  PH_REQUIRE(sh >= 0 && sh < w && sw >= 0 && sw < w, "ph_debug_window_tokens: shift must be smaller than the window");
+  const WindowGrid g = window_grid(B, H, W, w);
+  PH_REQUIRE(capacity >= g.nwin * g.N, "ph_debug_window_tokens: capacity %lld is below the %lld tokens of the launch", (long long)capacity, g.nwin * g.N);
+  if (code_bits == 4)
+    fill_window_tokens<4>(g, sh, sw, pix_out, code_out);
+  else
+    fill_window_tokens<5>(g, sh, sw, pix_out, code_out);
+  return PH_OK;
+}

@@ -13,9 +13,6 @@
 
 namespace ph {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int WAB_SLICES = 256;  // workgroups of the attention backward = slices of its two fixed-order reductions
 
 // ---------------------------------------------------------------------------------------
@@ -25,7 +22,7 @@ constexpr int WAB_SLICES = 256;  // workgroups of the attention backward = slice
 // (S = Qs K^T + bias + mask, Qs = q / sqrt(32), P = softmax(S), O = P V) and D_i = sum_j P_ij dP_ij:
 //   dP = dO V^T,  dS = P * (dP - D),  dV = P^T dO,  dK = dS^T Qs,  dq = dS K / sqrt(32),  dtable[rel(i, j)] += dS_ij.
 // Pass 1 (query in the lane): S^T = K Qs^T and dP^T = V dO^T on v_mfma_f32_32x32x2_f32 put query i in the lane and the
-//   keys j = 8 (r >> 2) + 4 (l >> 5) + (r & 3) in the accumulator registers, exactly the forward's layout: row maximum,
+//   keys window_key(tj, r, l >> 5) in the accumulator registers, exactly the forward's layout: row maximum,
 //   row sum and D_i are lane-local plus one exchange with lane l ^ 32; they go to a 64-float LDS row each.  dS^T is the
 //   B operand of dq^T = K^T dS^T as it stands (K loaded key-major, as the forward loads V).  The dS tile also goes to
 //   LDS (32 x 65 floats) for the table gradient: lane e owns table entry e + 64 n, walks the tile's queries i and reads
@@ -48,15 +45,13 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(WindowAttnBwdArgs 
   __shared__ float dsl[4][32 * 65];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int half = lane >> 5, l31 = lane & 31;
-  const int w = a.w, N = w * w, w2 = 2 * w - 1;
-  const int pH = (a.H + w - 1) / w * w, pW = (a.W + w - 1) / w * w;
-  const int nwh = pH / w, nww = pW / w;
-  const long long nwin = (long long)a.B * nwh * nww;
+  const WindowGrid grid = window_grid(a.B, a.H, a.W, a.w);
+  const int w = grid.w, N = grid.N, rel = grid.rel, w2 = 2 * w - 1;
+  const long long nwin = grid.nwin;
   const long long lo = (long long)blockIdx.x * per;
   const long long hi = lo + per < nwin ? lo + per : nwin;
   const long long n_items = hi > lo ? (hi - lo) * a.heads : 0;
   const long long iters = (n_items + 3) / 4;
-  const int rel = w2 * w2;
   const int C3 = 3 * a.C;
   const float qscale = 0.17677669529663688f;  // 32^-0.5
   float* pt = a.scratch + ((size_t)blockIdx.x * 4 + wave) * (size_t)part_stride;  // this wave's partial row: table part ...
@@ -65,23 +60,14 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(WindowAttnBwdArgs 
     long long item = it * 4 + wave;
     const bool live = item < n_items;
     if (!live) item = n_items - 1;
-    const int head = (int)(item % a.heads);
-    long long win = lo + item / a.heads;
-    const int wx = (int)(win % nww);
-    win /= nww;
-    const int wy = (int)(win % nwh);
-    const int b = (int)(win / nwh);
+    const WindowItem wi = window_decode(grid, item, a.heads, lo);
+    const int head = wi.head;
     __syncthreads();  // the previous item's readers of the LDS rows are done
     for (int i = lane; i < rel; i += 64) tbl[wave][i] = a.table[(size_t)head * rel + i];
     {
-      const int t = lane < N ? lane : 0;  // (dead lanes mirror token 0: their table index stays in range)
-      const int ty = t / w, tx = t - ty * w;
-      int y = wy * w + ty + a.sh, x = wx * w + tx + a.sw;
-      if (y >= pH) y -= pH;
-      if (x >= pW) x -= pW;
-      const int band = ((a.sh > 0 && wy == nwh - 1 && ty >= w - a.sh) ? 2 : 0) | ((a.sw > 0 && wx == nww - 1 && tx >= w - a.sw) ? 1 : 0);
-      tok_pix[wave][lane] = (y < a.H && x < a.W) ? (b * a.H + y) * a.W + x : -1;
-      tok_code[wave][lane] = ty | (tx << 4) | (band << 8);
+      const TokenInfo tk = window_token<4>(grid, wi, lane < N ? lane : 0, a.sh, a.sw);  // (dead lanes mirror token 0: their table index stays in range)
+      tok_pix[wave][lane] = tk.pix;
+      tok_code[wave][lane] = tk.code;
     }
     __syncthreads();
     const bool any_pad = __any(lane < N && tok_pix[wave][lane] < 0) != 0;
@@ -131,17 +117,15 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(WindowAttnBwdArgs 
         dp[tj] = acc2;
       }
       const int ci = tok_code[wave][ti * 32 + l31];
-      const int tyi = ci & 15, txi = (ci >> 4) & 15, bi = ci >> 8;
       float mx = -INFINITY;
 #pragma unroll
       for (int tj = 0; tj < T; ++tj)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int j = tj * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
+          const int j = window_key(tj, r, half);
           const int cj = tok_code[wave][j];
-          const int tyj = cj & 15, txj = (cj >> 4) & 15, bj = cj >> 8;
-          float val = s[tj][r] + tbl[wave][(tyi - tyj + w - 1) * w2 + (txi - txj + w - 1)];
-          if (bi != bj) val += -100.0f;
+          float val = s[tj][r] + tbl[wave][window_bias_index<4>(ci, cj, w)];
+          if (token_band<4>(ci) != token_band<4>(cj)) val += -100.0f;
           if (j >= N) val = -INFINITY;
           s[tj][r] = val;
           mx = fmaxf(mx, val);
@@ -178,7 +162,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(WindowAttnBwdArgs 
       for (int tj = 0; tj < T; ++tj)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int j = tj * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
+          const int j = window_key(tj, r, half);
           const float d = s[tj][r] * (dp[tj][r] - dsum);
           s[tj][r] = d;
           dsl[wave][l31 * 65 + j] = d;
@@ -192,7 +176,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(WindowAttnBwdArgs 
         float kv[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int j = tj * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
+          const int j = window_key(tj, r, half);
           float val = 0.f;
           if (j < N) {
             const int pix = tok_pix[wave][j];
@@ -228,7 +212,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(WindowAttnBwdArgs 
             float acc = 0.f;
             for (int ii = 0; ii < ni; ++ii) {
               const int c = tok_code[wave][ti * 32 + ii];
-              const int tyj = (c & 15) - dy, txj = ((c >> 4) & 15) - dx;
+              const int tyj = token_ty<4>(c) - dy, txj = token_tx<4>(c) - dx;
               if (tyj >= 0 && tyj < w && txj >= 0 && txj < w) acc += dsl[wave][ii * 65 + tyj * w + txj];
             }
             tacc[n] += acc;
@@ -249,7 +233,6 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(WindowAttnBwdArgs 
     for (int tj = 0; tj < T; ++tj) {
       const int tk = tj * 32 + l31;
       const int cj = tok_code[wave][tk];
-      const int tyj = cj & 15, txj = (cj >> 4) & 15, bj = cj >> 8;
       f32x16 acck, accv;
 #pragma unroll
       for (int e = 0; e < 16; ++e) acck[e] = 0.f, accv[e] = 0.f;
@@ -266,11 +249,10 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(WindowAttnBwdArgs 
         float gov[16], qv[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int i = ti * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
+          const int i = window_key(ti, r, half);
           const int ci = tok_code[wave][i];
-          const int tyi = ci & 15, txi = (ci >> 4) & 15, bi = ci >> 8;
-          float val = s2[r] + tbl[wave][(tyi - tyj + w - 1) * w2 + (txi - txj + w - 1)];
-          if (bi != bj) val += -100.0f;
+          float val = s2[r] + tbl[wave][window_bias_index<4>(ci, cj, w)];
+          if (token_band<4>(ci) != token_band<4>(cj)) val += -100.0f;
           float p = exp_hw(val - st_m[wave][i]) * st_il[wave][i];
           if (tk >= N) p = 0.f;
           s2[r] = p;
@@ -344,23 +326,20 @@ __global__ __launch_bounds__(256) void window_attn_bwd_final_kernel(const float*
 static int wab_slices(long long nwin) { return (int)std::min<long long>(WAB_SLICES, nwin); }
 
 int64_t window_attn_bwd_scratch_floats(int B, int H, int W, int C, int heads, int w) {
-  const long long nwin = (long long)B * ((H + w - 1) / w) * ((W + w - 1) / w);
-  return (int64_t)wab_slices(nwin) * 4 * ((int64_t)heads * (2 * w - 1) * (2 * w - 1) + 2 * C);
+  const WindowGrid g = window_grid(B, H, W, w);
+  return (int64_t)wab_slices(g.nwin) * 4 * ((int64_t)heads * g.rel + 2 * C);
 }
 
 int launch_window_attn_bwd(const WindowAttnBwdArgs& a, hipStream_t s) {
-  PH_REQUIRE(a.qkv && a.table && a.qkv_bias && a.gout && a.gqkv && a.gtable && a.gpad && a.scratch, "window attention backward: null pointer");
-  PH_REQUIRE(a.w >= 2 && a.w <= 8, "window attention backward: window_size %d is outside 2..8", a.w);
-  PH_REQUIRE(a.heads > 0 && a.C == a.heads * 32, "window attention backward: head dimension must be 32 (C %d, heads %d)", a.C, a.heads);
-  PH_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && (long long)a.B * a.H * a.W < (1ll << 31) / 4, "window attention backward: bad map size");
-  PH_REQUIRE(a.sh >= 0 && a.sh < a.w && a.sw >= 0 && a.sw < a.w, "window attention backward: shift must be smaller than the window");
-  const long long nwin = (long long)a.B * ((a.H + a.w - 1) / a.w) * ((a.W + a.w - 1) / a.w);
-  const int slices = wab_slices(nwin);
-  const int per = (int)((nwin + slices - 1) / slices);
-  const int rel = (2 * a.w - 1) * (2 * a.w - 1);
+  WindowGrid g;
+  const int rc = window_attn_check("window attention backward", 8, a.qkv && a.table && a.qkv_bias && a.gout && a.gqkv && a.gtable && a.gpad && a.scratch, a, &g);
+  if (rc != PH_OK) return rc;
+  const int slices = wab_slices(g.nwin);
+  const int per = (int)((g.nwin + slices - 1) / slices);
+  const int rel = g.rel;
   const int stride = a.heads * rel + 2 * a.C;
   PH_HIP_CHECK(hipMemsetAsync(a.scratch, 0, (size_t)slices * 4 * stride * sizeof(float), s));
-  if (a.w * a.w <= 32)
+  if (g.N <= 32)
     hipLaunchKernelGGL(window_attn_bwd_kernel<1>, dim3(slices), dim3(256), 0, s, a, per, stride);
   else
     hipLaunchKernelGGL(window_attn_bwd_kernel<2>, dim3(slices), dim3(256), 0, s, a, per, stride);

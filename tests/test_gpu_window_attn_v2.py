@@ -1,4 +1,4 @@
-"""The cosine window attention kernel (csrc/swinv2_kernels.hip: window_attn_v2_kernel) alone: one launch through ``ph_debug_window_attn_v2_run`` on tensors the test
+"""The cosine window attention kernel (csrc/swin_kernels.hip: window_attn_kernel, cosine variant) alone: one launch through ``ph_debug_window_attn_v2_run`` on tensors the test
 owns, against the float64 NumPy statement of tests/_swinv2_cases.py (which tests/test_pretrained_swinv2_cpu.py ties to HuggingFace's layer through tests/swinv2_ref.py).
 
 The bound is the margin tests/test_gpu_conv3x3.py gives the Winograd kernels: per case, FOUR times the error of the reference's own fp32 evaluation of the same operation
